@@ -1,6 +1,14 @@
 """GE2E loss+backward throughput on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2] [--impl auto] [--mode loss|train-step]
+                    [--full] [--dump-outputs DIR]
+
+A plain run does only what its headline figure needs: set-up, W warm-up steps, K timed steps and the JSON line
+(ms_per_step = the time of one timed step).  --full adds everything else the line reports: the post-timing oracle check of
+sampled batches (verify), the forward-only, B = 1 latency and exact-fp32 legs, the CPU baseline, and in train-step mode
+the step without the all-reduce, the all-reduce alone and the encoder tail.  --no-verify, --no-extras and
+--no-cpu-baseline leave parts of --full out.  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy
+(rank 0's; see dump_outputs).
 
 --mode loss (default).  One *step* = one launch of the hot path (ge2e_loss_fwd_bwd through the C ABI)
 over B independent synthetic (N,M,D) batches that are already resident in HBM.  The metric is (N x M)
@@ -192,6 +200,29 @@ def measured_traffic(cfg_name, impl, B):
     return None
 
 
+DUMP_SAMPLE_BYTES = 32 << 20   # --dump-outputs: per-element outputs (dE, per) larger than this are sampled
+
+
+def dump_outputs(dirname, arrays, B):
+    """--dump-outputs: the arrays the timed path gave its caller in its last step, as float32 DIR/<name>.npy.  Per-batch
+    scalars (loss, dw, db) and the bucket are written whole.  Per-element outputs of more than DUMP_SAMPLE_BYTES (dE at
+    every config's default B, per in forward-only runs) are written as a sample of whole batches: a seeded draw that
+    depends only on B and the batch size, so that two builds run with the same arguments write the same elements.  The
+    sampled batch indices go to batches.npy (float64)."""
+    os.makedirs(dirname, exist_ok=True)
+    big = [n for n, t in arrays.items() if t.dim() > 1 and t.shape[0] == B and t.numel() * 4 > DUMP_SAMPLE_BYTES]
+    idx = None
+    if big:
+        per_batch = max(arrays[n][0].numel() * 4 for n in big)
+        k = min(B, max(1, DUMP_SAMPLE_BYTES // per_batch))
+        idx = np.sort(np.random.default_rng(0).choice(B, size=k, replace=False))
+        np.save(os.path.join(dirname, "batches.npy"), idx.astype(np.float64))
+    for name, t in arrays.items():
+        if name in big:
+            t = t.index_select(0, torch.as_tensor(idx, device=t.device))
+        np.save(os.path.join(dirname, name + ".npy"), t.detach().float().cpu().numpy())
+
+
 def time_launches(fn, steps):
     """HIP events on the stream the kernels are launched on (torch's current stream) -> per-step ms."""
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(steps + 1)]
@@ -213,16 +244,23 @@ def main():
     ap.add_argument("--mode", default="loss", choices=["loss", "train-step"])
     ap.add_argument("--batches", type=int, default=0,
                     help="B per launch per GPU (0 = config default; train-step default 1 = one (N,M) batch per rank per step, as s4)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements and checks beyond the headline figure (verify, extras, CPU baseline, "
+                         "train-step breakdown)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32; dE sampled by whole batches)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the B=1 latency legs and the exact-fp32 comparison (profiling runs: only the benched kernel)")
-    ap.add_argument("--no-verify", action="store_true", help="skip the post-timing oracle check of sampled batches")
+                    help="with --full: skip the forward-only and B=1 latency legs and the exact-fp32 comparison")
+    ap.add_argument("--no-verify", action="store_true", help="with --full: skip the post-timing oracle check of sampled batches")
     ap.add_argument("--forward-only", action="store_true",
                     help="profiling runs: the timed step is the forward-only launch (dE = NULL: similarity + loss, the "
                          "workload of s4:61-110 / s5:42-44); the JSON line then carries only the forward_only object's numbers")
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU: ranks, rendezvous (gloo), the bucket all-reduce and the JSON line only; value is null")
     args = ap.parse_args()
+    if args.dump_outputs and args.dry_run:
+        ap.error("--dump-outputs needs a GPU run (a dry run launches no kernel)")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))
@@ -354,9 +392,20 @@ def main():
         if dist and world > 1:
             dist.all_reduce(red, op=dist.ReduceOp.SUM)
         loss_mean = float(red[0].item()) / (B * world)
+    if rank == 0 and args.dump_outputs:
+        # before anything below launches again into the same outputs
+        arrays = ({"loss": out_f.loss, "per": out_f.per} if args.forward_only
+                  else {"loss": out.loss, "dE": out.dE, "dw": out.dw, "db": out.db})
+        if bucket is not None:
+            arrays["bucket"] = bucket
+        dump_outputs(args.dump_outputs, arrays, B)
 
     train = None
     if args.mode == "train-step":
+        train = {"bucket_floats": BUCKET_FLOATS, "bucket_bytes": BUCKET_FLOATS * 4,
+                 "backend": "gloo (dry run)" if dry else "nccl (RCCL)",
+                 "ms_with_allreduce": tmax / args.steps * 1e3}
+    if args.mode == "train-step" and args.full:
         for _ in range(max(2, args.warmup // 2)):
             step_without()
         el_wo, _ = timed(step_without, args.steps)
@@ -369,16 +418,14 @@ def main():
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         el_wo, el_ar = float(tt[0]), float(tt[1])
         nbytes = BUCKET_FLOATS * 4
-        train = {"bucket_floats": BUCKET_FLOATS, "bucket_bytes": nbytes,
-                 "backend": "gloo (dry run)" if dry else "nccl (RCCL)",
-                 "ms_with_allreduce": tmax / args.steps * 1e3,
-                 "ms_without_allreduce": el_wo / args.steps * 1e3,
-                 "allreduce_alone_ms": el_ar / args.steps * 1e3,
-                 # ring all-reduce moves 2 (n-1)/n of the message over every link
-                 "allreduce_busbw_GBs": (2 * (world - 1) / world * nbytes / (el_ar / args.steps) / 1e9) if world > 1 else None}
+        train.update({"ms_without_allreduce": el_wo / args.steps * 1e3,
+                      "allreduce_alone_ms": el_ar / args.steps * 1e3,
+                      # ring all-reduce moves 2 (n-1)/n of the message over every link
+                      "allreduce_busbw_GBs": (2 * (world - 1) / world * nbytes / (el_ar / args.steps) / 1e9) if world > 1 else None})
 
+    extras = args.full and not args.no_extras
     extra = {}
-    if rank == 0 and not dry and args.mode == "loss" and not args.no_extras and not args.forward_only:
+    if rank == 0 and not dry and args.mode == "loss" and extras and not args.forward_only:
         # similarity + loss only (dE = NULL): north_star's "GE2E similarity+loss" sentence and the reference's evaluation
         # paths.  Algorithmic bytes = N M D 4 per batch (E read once, nothing of that size written), flops = 2 N^2 M D.
         for _ in range(3):
@@ -399,7 +446,7 @@ def main():
             "traffic": (measured_traffic(args.config, impl + "_fwd", B) or {}).get("bytes"),
             "traffic_from_profile": measured_traffic(args.config, impl + "_fwd", B),
             "verify": None if args.no_verify else verify_forward(E, out_f.loss, out_f.per, N, M, D, variant)}
-    if rank == 0 and not dry and args.mode == "loss" and not args.no_extras and not args.forward_only:
+    if rank == 0 and not dry and args.mode == "loss" and extras and not args.forward_only:
         # B = 1 latency, raw C-ABI call (not the metric; launch-bound single batches)
         e1 = E[:1].contiguous()
         o1 = GF.LossOutputs(loss=out.loss[:1], per=None, dE=out.dE[:1], dw=out.dw[:1], db=out.db[:1])
@@ -480,7 +527,7 @@ def main():
                 except Exception as ex:  # unsupported shape for this kernel
                     extra["exact_f32"] = {"impl": cand, "value": None, "note": str(ex)[:120]}
 
-    if rank == 0 and not dry and args.mode == "train-step":
+    if rank == 0 and not dry and args.mode == "train-step" and args.full:
         # the encoder tail (normalise s2:34 + un-permute s4:186 + (N,M,D) view s4:189) in front of the loss.
         # Separate: normalize_unperm launch + loss launch(es) + normalize_unperm backward launch; raw: ONE launch that
         # normalises and gathers in its load stage and scatters dL/dy from its store stage (ge2e_loss_fwd_bwd_raw).
@@ -518,7 +565,7 @@ def main():
         extra["encoder_tail"] = tails
 
     verify = None
-    if rank == 0 and not dry and args.mode == "loss" and not args.no_verify:
+    if rank == 0 and not dry and args.mode == "loss" and args.full and not args.no_verify:
         step()   # the benched implementation's outputs (the exact-fp32 leg may have run since)
         torch.cuda.synchronize()
         verify = (verify_forward(E, out_f.loss, out_f.per, N, M, D, variant) if args.forward_only
@@ -593,7 +640,7 @@ def main():
             line["train_step"] = train
         if dry:
             line["dry_run"] = True
-        if world == 1 and not args.no_cpu_baseline and not dry and args.mode == "loss":
+        if world == 1 and args.full and not args.no_cpu_baseline and not dry and args.mode == "loss":
             line["cpu_baseline"] = cpu_baseline(N, M, D, variant)
         print(json.dumps(line), flush=True)
     if dist:

@@ -21,7 +21,7 @@ def run(*extra):
 
 
 def test_gpus_2_spawns_two_ranks_train_step():
-    j = run("--gpus", "2", "--mode", "train-step", "--config", "cfg4")
+    j = run("--gpus", "2", "--mode", "train-step", "--config", "cfg4", "--full")
     assert j["n_gpus"] == 2 and j["dry_run"] is True and j["value"] is None
     assert j["config"]["N"] == 256 and j["config"]["mode"] == "train-step" and j["config"]["batches_per_launch"] == 1
     t = j["train_step"]
@@ -33,7 +33,7 @@ def test_gpus_2_spawns_two_ranks_train_step():
 def test_gpus_8_cfg4_train_step_dry_run():
     """The configuration BASELINE names for the 8-GPU run (cfg4, data parallel, one flat-bucket all-reduce per step) with
     eight ranks on CPU: the backend counts eight ranks in a real collective and every rank's clock reaches the line."""
-    j = run("--gpus", "8", "--mode", "train-step", "--config", "cfg4")
+    j = run("--gpus", "8", "--mode", "train-step", "--config", "cfg4", "--full")
     assert j["n_gpus"] == 8 and j["rccl_ranks"] == 8 and len(j["per_rank_value"]) == 8
     assert j["config"]["N"] == 256 and "dp8" in j["config"]["parallelism"]
     assert j["train_step"]["allreduce_busbw_GBs"] > 0

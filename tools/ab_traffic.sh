@@ -8,7 +8,7 @@ cfg=${CFG:-cfg2}; impl=${IMPL:-auto}
 cd $root
 for rep in 1 2 3; do
   for lib in "$@"; do
-    v=$(GE2E_HIP_LIB=$pk/$lib python3 bench.py --config $cfg --impl $impl --steps 20 --warmup 5 --no-extras --no-cpu-baseline $EXTRA 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['config']['impl'], round(d['value']), round(d['roofline']['frac'],4), (d.get('verify') or {}).get('ok'), (d.get('verify') or {}).get('max_dE_relfro'))")
+    v=$(GE2E_HIP_LIB=$pk/$lib python3 bench.py --full --config $cfg --impl $impl --steps 20 --warmup 5 --no-extras --no-cpu-baseline $EXTRA 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['config']['impl'], round(d['value']), round(d['roofline']['frac'],4), (d.get('verify') or {}).get('ok'), (d.get('verify') or {}).get('max_dE_relfro'))")
     echo "$cfg $lib $v"
   done
 done

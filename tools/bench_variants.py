@@ -20,7 +20,7 @@ for k, defs in enumerate(sys.argv[1:] or [""]):
     bad = [ln[:40] for ln in probe.stdout.splitlines() if ln.startswith("rep")]
     vals = []
     for _ in range(2):
-        b = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--impl", impl, "--no-cpu-baseline", "--steps", "15"],
+        b = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--impl", impl, "--no-cpu-baseline", "--steps", "15"],
                            env=env, capture_output=True, text=True, timeout=300)
         try:
             d = json.loads(b.stdout.strip().splitlines()[-1])

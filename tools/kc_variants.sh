@@ -5,7 +5,7 @@ root=${GRAFT_REPO_ROOT:-/root/repo}
 pk=$root/speaker_embedding_ge2e_loss_amd
 cd /tmp && export TMPDIR=/tmp
 for lib in "$@"; do
-  v=$(GE2E_HIP_LIB=$pk/$lib python3 $root/bench.py --config cfg5 --steps 20 --warmup 5 --no-extras --no-cpu-baseline 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(round(d['value']), round(d['roofline']['frac'],4), (d.get('verify') or {}).get('ok'))")
+  v=$(GE2E_HIP_LIB=$pk/$lib python3 $root/bench.py --full --config cfg5 --steps 20 --warmup 5 --no-extras --no-cpu-baseline 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(round(d['value']), round(d['roofline']['frac'],4), (d.get('verify') or {}).get('ok'))")
   out=$root/gpurun_out/kc_$lib
   rm -rf $out
   GE2E_HIP_LIB=$pk/$lib rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS --output-format csv -d $out -- python3 $root/bench.py --config cfg5 --steps 2 --warmup 1 --no-cpu-baseline --no-extras --no-verify > /dev/null 2> $out.log
