@@ -154,11 +154,11 @@ __global__ __launch_bounds__(512, 2) void ge2e_team_kernel(Problem p, TeamKWs L,
 
     TeamCtl* const ctl = reinterpret_cast<TeamCtl*>(p.ws);
     TeamKFlags* const flags = reinterpret_cast<TeamKFlags*>(ctl + 1);
-    const TeamId id = team_form(ctl, SH, p.launch_seq);
+    const TeamId id = team_form(ctl, SH, team_launch_id(p.launch_seq));
     if (id.team == -2) {    // a control block that cannot be trusted: no counters at all -- static redo, workgroup 0 leaves a clean block
         team_redo<NCH>(p, L, F, smem_f, (int)gridDim.x, (int)blockIdx.x);
         __syncthreads();
-        if (blockIdx.x == 0 && tid < 64) team_head_rewrite(reinterpret_cast<unsigned*>(ctl), (int)(L.head_bytes / 16), 1u, p.launch_seq);
+        if (blockIdx.x == 0 && tid < 64) team_untrusted_done(ctl, (int)(L.head_bytes / 16), team_launch_id(p.launch_seq));
         return;
     }
     if (id.nct == 0 && blockIdx.x == 0 && tid == 0)   // no eight workgroups share an XCD: the call is redone at the end of this launch
@@ -1002,8 +1002,8 @@ static hipError_t launch_variant(Problem& p, TeamKWs& L, const FusedWs& F, hipSt
 
 hipError_t launch_team(const Problem& p_in, hipStream_t stream) {
     Problem p = p_in;
-    {   // TeamCtl::gen: a number per launch, never 0 (a HIP graph replays the number it captured: a replay that finds an
-        // untrusted block redoes itself without counters every time until another launch or ge2e_workspace_init cleans it)
+    {   // the host's half of TeamCtl::gen (team_launch_id): a number per launch, never 0.  A HIP graph replays the number it
+        // captured; the dispatch id the kernel mixes in is what tells two replays apart
         static std::atomic<unsigned> seq{0};
         unsigned s = seq.fetch_add(1u, std::memory_order_relaxed) + 1u;
         p.launch_seq = s ? s : seq.fetch_add(1u, std::memory_order_relaxed) + 1u;

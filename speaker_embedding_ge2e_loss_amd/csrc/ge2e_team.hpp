@@ -56,12 +56,14 @@ struct TeamCtl {
                                                         // arrival are one atomic, so the add that completes the low half returns
                                                         // the final number of stayers)
     unsigned magic;                                     // TEAM_MAGIC <=> the rest of the block (and the team flags) is zero
-    unsigned gen;       unsigned pad4[30];              // != 0: the launch (Problem::launch_seq) whose workgroup 0 wrote this block
+    unsigned gen;       unsigned pad4[30];              // != 0: the launch (team_launch_id) whose workgroup 0 wrote this block
                                                         // after a redo WITHOUT counters; that launch's own late workgroups must
                                                         // not take the block for a clean one (team_form).  Same 8 bytes as the
                                                         // magic: written by one store, read by one load
     unsigned fallbacks; unsigned pad5[31];              // diagnostic, survives the clean-up: calls on this workspace whose abort
-                                                        // word was up (no team formed, a hand-off timed out, unclean block)
+                                                        // word was up (no team formed, a hand-off timed out, unclean block).
+                                                        // Every redo ADDS one (team_redo_done, team_untrusted_done); only memory
+                                                        // that never held a block of ours starts again from 0
     unsigned go;        unsigned pad7[31];              // the redo's size, decided ONCE: 0 = not yet, TEAM_GO_LONE = every stayer by
                                                         // itself, else n = the number of stayers (stored by the last finisher)
     unsigned redo_done; unsigned pad8[31];              // workgroups of the redo that have finished it (team_redo_done)
@@ -69,6 +71,9 @@ struct TeamCtl {
 static_assert(offsetof(TeamCtl, fallbacks) == 1664, "functional.workspace_fallback_count reads byte 1664");
 static_assert(offsetof(TeamCtl, gen) == offsetof(TeamCtl, magic) + 4 && offsetof(TeamCtl, magic) % 16 == 0, "magic | gen: one 8-byte word");
 constexpr unsigned TEAM_GO_LONE = 0xFFFFFFFFu;
+// The magic word of a block a LONE redo gave up on (team_finish): untrusted like any block without TEAM_MAGIC, but its
+// `fallbacks` count is still ours and the next call counts on top of it.
+constexpr unsigned TEAM_MAGIC_LONE = 0x6E2E7EA4u;
 constexpr unsigned long long TEAM_FINISH_TICKS = 5000000ull;    // 50 ms: the whole grid has finished (every inner wait is bounded
                                                                 // by 4 ms and gives up as soon as the abort word rises)
 // bytes of the control block + 64 per-team flag records (shape-independent; TeamKFlags = 3 lines, TeamFlags = 2)
@@ -122,17 +127,32 @@ __device__ __forceinline__ bool spin_until(const unsigned* p, unsigned target, T
     return false;
 }
 
+// The identity of a launch (TeamCtl::gen): a number every workgroup of ONE launch computes alike and the next launch on the
+// same workspace does not.  The host's launch number alone is not that: a HIP graph replays the kernel arguments it
+// captured, so every replay carried the same number, and a replay that found the mark of its predecessor's redo took it for
+// its own and redid itself without counters again -- on every replay from then on.  The dispatch id -- the index of the AQL
+// packet in its queue, which the command processor hands to every wave of the dispatch in two SGPRs -- moves with every
+// packet, replays included, and is the same for all workgroups of one dispatch.  The host number is mixed in because two
+// queues have packet indices of their own.  Should two consecutive launches on one workspace still compute the same number,
+// the second one takes a clean mark for an untrusted block: one redo more (same results, counted in `fallbacks`), after
+// which the next launch differs again; a team is never formed on a block that cannot be trusted.
+extern "C" __device__ __attribute__((const)) unsigned long long ge2e_llvm_dispatch_id() __asm("llvm.amdgcn.dispatch.id");
+__device__ __forceinline__ unsigned team_launch_id(unsigned host_seq) {
+    const unsigned id = host_seq + 0x9E3779B9u * (unsigned)ge2e_llvm_dispatch_id();
+    return id ? id : 1u;
+}
+
 // Called by all threads of the workgroup; `sh` is 4 ints of LDS.  Contains workgroup barriers.
-// `launch_seq`: the host's number of this launch (0 = none): a block whose `gen` carries it was written by workgroup 0 of THIS
+// `launch_id`: team_launch_id of this launch (0 = none): a block whose `gen` carries it was written by workgroup 0 of THIS
 // launch at the end of a redo without counters -- to a workgroup of the same launch that starts late it is as untrusted as
 // the block workgroup 0 found (it would otherwise form a team by itself, wait 2 ms, raise the abort word and wait 50 ms).
-__device__ __forceinline__ TeamId team_form(TeamCtl* ctl, int* sh, unsigned launch_seq = 0u) {
+__device__ __forceinline__ TeamId team_form(TeamCtl* ctl, int* sh, unsigned launch_id = 0u) {
     bool trusted = false;
     if (threadIdx.x == 0) {
         const unsigned long long mg = __hip_atomic_load(
             reinterpret_cast<const unsigned long long*>(__builtin_assume_aligned(&ctl->magic, 8)), __ATOMIC_RELAXED,
             __HIP_MEMORY_SCOPE_AGENT);      // magic | gen << 32, one load (the control block is 256-byte aligned, magic at 1536)
-        trusted = (unsigned)mg == TEAM_MAGIC && (launch_seq == 0u || (unsigned)(mg >> 32) != launch_seq);
+        trusted = (unsigned)mg == TEAM_MAGIC && (launch_id == 0u || (unsigned)(mg >> 32) != launch_id);
     }
     if (threadIdx.x == 0 && !trusted) {
         // not a clean control block (fresh or overwritten memory): no counter in it can be trusted, so no teams and no
@@ -219,8 +239,9 @@ __device__ __forceinline__ TeamRedo team_finish(TeamCtl* ctl, int* sh, int n16, 
         }
         if (up && g == TEAM_GO_LONE) {
             // a workgroup of this grid has not finished within 50 ms: nothing about the block holds any more.  Take the
-            // magic away (the next call redoes itself without counters and writes a fresh block) and redo ALONE.
-            __hip_atomic_store(&ctl->magic, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            // magic away (the next call redoes itself without counters, counts on top of `fallbacks` and writes a fresh
+            // block) and redo ALONE.
+            __hip_atomic_store(&ctl->magic, TEAM_MAGIC_LONE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             n = -1;
         } else if (up) {
             n = (int)g;
@@ -244,6 +265,16 @@ __device__ __forceinline__ void team_redo_done(TeamCtl* ctl, int* sh, int n16, i
     }
     __syncthreads();
     if (sh[0] && threadIdx.x < 64) team_head_rewrite(reinterpret_cast<unsigned*>(ctl), n16, ctl->fallbacks + 1u);
+}
+// End of the redo WITHOUT counters (team_form found an untrusted block): one wave of workgroup 0, once its share is out.  The
+// redo counts on top of the block's own count when the block is one of ours -- an earlier redo's mark (TEAM_MAGIC with
+// another launch's gen) or a block a LONE redo gave up on -- and from 1 on memory that never held one.  Nobody else writes
+// the block during such a launch (no counters, no team_finish), so the magic word still holds what team_form read; the
+// wave's loads complete before its first store.
+__device__ __forceinline__ void team_untrusted_done(TeamCtl* ctl, int n16, unsigned launch_id) {
+    const unsigned mg = ld_poll(&ctl->magic), fb = ld_poll(&ctl->fallbacks);
+    const unsigned base = (mg == TEAM_MAGIC || mg == TEAM_MAGIC_LONE) ? fb : 0u;
+    team_head_rewrite(reinterpret_cast<unsigned*>(ctl), n16, base + 1u, launch_id);
 }
 
 // Producer side of a hand-off: call from ALL threads after the payload stores were issued.

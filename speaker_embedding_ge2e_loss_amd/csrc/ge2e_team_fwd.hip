@@ -71,11 +71,11 @@ __global__ __launch_bounds__(512, 2) void ge2e_team_fwd_kernel(Problem p, TeamKW
 
     TeamCtl* const ctl = reinterpret_cast<TeamCtl*>(p.ws);
     TeamKFlags* const flags = reinterpret_cast<TeamKFlags*>(ctl + 1);
-    const TeamId id = team_form(ctl, SH, p.launch_seq);
+    const TeamId id = team_form(ctl, SH, team_launch_id(p.launch_seq));
     if (id.team == -2) {    // a control block that cannot be trusted: no counters at all -- static redo, workgroup 0 leaves a clean block
         team_redo<NCH>(p, L, F, smem_f, (int)gridDim.x, (int)blockIdx.x);
         __syncthreads();
-        if (blockIdx.x == 0 && tid < 64) team_head_rewrite(reinterpret_cast<unsigned*>(ctl), (int)(L.head_bytes / 16), 1u, p.launch_seq);
+        if (blockIdx.x == 0 && tid < 64) team_untrusted_done(ctl, (int)(L.head_bytes / 16), team_launch_id(p.launch_seq));
         return;
     }
     if (id.nct == 0 && blockIdx.x == 0 && tid == 0)   // no eight workgroups share an XCD: the call is redone at the end of this launch

@@ -13,6 +13,27 @@ from typing import Optional
 import torch
 
 
+def _warmup_input(shape, dev: torch.device) -> torch.Tensor:
+    """Unit rows to warm up on and to check the capture with, drawn from a generator of their own: the default generator's
+    sequence -- dropout masks, sampled batches -- is the same whether or not the step is captured."""
+    g = torch.Generator(device=dev)
+    g.manual_seed(0x6E2E)
+    return torch.nn.functional.normalize(torch.randn(*shape, device=dev, generator=g), dim=-1)
+
+
+def _check_replay(graph, outs, refs, what: str) -> None:
+    """A capture that recorded nothing -- the launch went to a stream the capture was not on, e.g. another device's -- replays
+    as a no-op and leaves stale outputs behind; torch only warns.  Poison the outputs, replay once on the warm-up input (the
+    current stream is the device's own) and compare with the warm-up launch.  One host sync, at capture time only."""
+    with torch.no_grad():
+        for o in outs:
+            o.fill_(float("nan"))
+    graph.replay()
+    for o, r in zip(outs, refs):
+        if not (bool(torch.isfinite(o).all()) and torch.allclose(o, r, rtol=1e-4, atol=1e-6)):
+            raise RuntimeError(f"{what}: the captured graph does not reproduce the warm-up launch (nothing was captured?)")
+
+
 class GraphedLossStep:
     """``step = GraphedLossStep(loss_module, (N, M, D))``; then per training step::
 
@@ -29,17 +50,21 @@ class GraphedLossStep:
         fill and the scaling kernel -- and the same bits.  For a ``GE2ELoss`` of this package (it needs the module's
         ``w``, ``b``, ``variant``, ``impl``)."""
         params = list(loss_module.parameters())
-        dev = device or params[0].device
+        dev = torch.device(device) if device is not None else params[0].device
         self.module = loss_module
+        with torch.cuda.device(dev):   # everything below on dev, whichever device is current (the capture included)
+            self._build(tuple(int(x) for x in shape), dev, warmup, direct)
+
+    def _build(self, shape, dev, warmup, direct):
         self.input = torch.zeros(*shape, dtype=torch.float32, device=dev).requires_grad_(True)
         with torch.no_grad():   # something finite to warm up on
-            self.input.copy_(torch.nn.functional.normalize(torch.randn(*shape, device=dev), dim=-1))
+            self.input.copy_(_warmup_input(shape, dev))
         # the step's workspace: allocated and initialised HERE, outside the capture, owned by this object (the library's
         # control block cleans itself after every call, so the captured step needs no initialisation node)
         from . import functional as GF
-        n_, m_, d_ = (int(x) for x in shape)
+        n_, m_, d_ = shape
         self.workspace = GF.alloc_workspace(
-            GF.workspace_bytes(1, n_, m_, d_, getattr(loss_module, "variant", "softmax"), getattr(loss_module, "impl", "auto")), dev)
+            GF.workspace_bytes(1, n_, m_, d_, getattr(self.module, "variant", "softmax"), getattr(self.module, "impl", "auto")), dev)
         if direct:
             self._capture_direct(dev, warmup)
             return
@@ -48,15 +73,18 @@ class GraphedLossStep:
         with torch.cuda.stream(side), GF.workspace_override(self.workspace):       # torch's capture recipe: warm up on a side stream
             for _ in range(max(1, warmup)):
                 self._zero()
-                self.module(self.input).backward()
+                loss = self.module(self.input)
+                loss.backward()
+            ref = (loss.detach().clone(), self.input.grad.clone())
         torch.cuda.current_stream(dev).wait_stream(side)
         self._zero()
         self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph), GF.workspace_override(self.workspace):
+        with torch.cuda.graph(self.graph, stream=side), GF.workspace_override(self.workspace):
             self.loss = self.module(self.input)
             self.loss.backward()
         self.input_grad = self.input.grad
         self.loss = self.loss.detach()
+        _check_replay(self.graph, (self.loss, self.input_grad), ref, "GraphedLossStep")
 
     def _capture_direct(self, dev, warmup):
         from . import functional as GF
@@ -75,10 +103,12 @@ class GraphedLossStep:
         with torch.cuda.stream(side):
             for _ in range(max(1, warmup)):
                 launch()
+            ref = (out.loss.clone(), out.dE.clone())
         torch.cuda.current_stream(dev).wait_stream(side)
         self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
+        with torch.cuda.graph(self.graph, stream=side):
             launch()
+        _check_replay(self.graph, (out.loss, out.dE), ref, "GraphedLossStep(direct=True)")
         self.loss = out.loss[0]
         self.input_grad = out.dE[0]
         self.input.grad = self.input_grad
@@ -108,11 +138,14 @@ class StaticLossStep:
     are then already in ``dE3`` / ``dw0`` / ``db0`` for an incoming gradient of 1."""
 
     def __init__(self, loss_module: torch.nn.Module, shape, dev: torch.device, warmup: int = 2):
+        with torch.cuda.device(dev):   # everything below on dev, whichever device is current (the capture included)
+            self._build(loss_module, shape, dev, warmup)
+
+    def _build(self, m, shape, dev, warmup):
         from . import functional as GF
         n_, m_, d_ = (int(x) for x in shape)
-        m = loss_module
         self.shape = (n_, m_, d_)
-        self.e4 = torch.nn.functional.normalize(torch.randn(1, n_, m_, d_, device=dev), dim=-1)   # finite values to warm up on
+        self.e4 = _warmup_input((1, n_, m_, d_), dev)                      # finite values to warm up on
         self.e3 = self.e4[0]
         self.dE = torch.empty_like(self.e4)
         self.sc = torch.empty(3, 1, dtype=torch.float32, device=dev)          # loss | dw | db
@@ -134,10 +167,12 @@ class StaticLossStep:
         with torch.cuda.stream(side):
             for _ in range(max(1, warmup)):
                 launch()
+            ref = (self.sc.clone(), self.dE.clone())
         torch.cuda.current_stream(dev).wait_stream(side)
         self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
+        with torch.cuda.graph(self.graph, stream=side):
             launch()
+        _check_replay(self.graph, (self.sc, self.dE), ref, "GE2ELoss(graph=True)")
 
     @staticmethod
     def key_of(m, shape):

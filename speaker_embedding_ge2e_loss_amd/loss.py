@@ -9,6 +9,8 @@ the same static helpers.  The arithmetic runs in libge2e_hip.so.
 """
 from __future__ import annotations
 
+import sys
+
 import torch
 import torch.nn as nn
 
@@ -75,6 +77,29 @@ def _has_hooks(t) -> bool:
     return bool(getattr(t, "_backward_hooks", None)) or bool(getattr(t, "_post_accumulate_grad_hooks", None))
 
 
+def _py_refs(fns, i: int) -> int:
+    return sys.getrefcount(fns[i][0])
+
+
+_free_refs: list = []
+
+
+def _accumulator_held(loss) -> bool:
+    """Whether the Python object of an AccumulateGrad node among the loss's inputs is referenced from anywhere else.  Python
+    cannot list a node's hooks, but a hook registered on a tensor's accumulator (``node.register_hook`` /
+    ``register_prehook``) lives only as long as that node, and a tensor holds its accumulator weakly: whoever hooks it keeps
+    the node object.  (Counted against a fresh accumulator that nobody holds, through the same call.)"""
+    if not _free_refs:
+        t = torch.zeros((), requires_grad=True)
+        _free_refs.append(_py_refs(t.view_as(t).grad_fn.next_functions, 0))
+    fns = loss.grad_fn.next_functions
+    return any(type(fns[i][0]).__name__ == "AccumulateGrad" and _py_refs(fns, i) > _free_refs[0] for i in range(len(fns)))
+
+
+def _distributed() -> bool:
+    return torch.distributed.is_available() and torch.distributed.is_initialized()
+
+
 class GE2ELoss(nn.Module):
 
     def __init__(self, hp, variant: str = "softmax", impl: str = "auto", graph: bool = False):
@@ -83,9 +108,14 @@ class GE2ELoss(nn.Module):
         embeddings in and replays the fused launch, and a plain ``loss.backward()`` publishes the launch's own dE / dw / db
         as the gradients without going through the autograd engine (same bits: the engine would multiply them by 1.0).
         The ``.grad`` tensors the shortcut sets are STATIC -- overwritten by the next forward (a ``.grad`` that is still attached
-        then is cloned first, so accumulating over several steps stays correct); the returned loss is a copy.  Anything else -- another
-        shape, a (B, N, M, D) stack, no-grad mode, a stream that is capturing, hooks on the tensors, ``backward`` with
-        arguments -- takes the eager node."""
+        then is cloned first, so accumulating over several steps stays correct); the returned loss is a copy.  The shortcut keeps
+        the eager node's contract: a second ``loss.backward()`` raises unless the first one passed ``retain_graph=True``, and a
+        loss that nothing requires grad for raises.  Under ``torch.distributed`` (DistributedDataParallel hooks the parameters'
+        AccumulateGrad nodes from C++, where Python cannot see it), or when somebody holds an AccumulateGrad node of ``e``,
+        ``w`` or ``b`` at the forward (a hook registered on it), the gradients are published through ONE
+        ``torch.autograd.backward`` call on the leaves, which runs every hook.  Still the eager node: another shape, a (B, N, M, D) stack, no-grad mode, a stream
+        that is capturing, tensor hooks on ``e`` / ``w`` / ``b`` / the loss, ``backward`` with a gradient / ``inputs`` /
+        ``create_graph``, and any gradient that flows THROUGH the loss (``torch.autograd.grad``, ``(2 * loss).backward()``)."""
         super().__init__()
         self.device = hp.general.device  # s3:11
         self.hp = hp  # s3:12
@@ -148,24 +178,41 @@ class GE2ELoss(nn.Module):
         serial = step.serial
         import weakref
         wloss = weakref.ref(loss)
+        consumed = [False]                       # like the eager node's saved tensors: freed by a backward without retain_graph
+        # (decided here: a temporary loss -- mod(e).backward() -- is gone by the time its backward runs)
+        req = loss.requires_grad
+        engine = req and (_distributed() or _accumulator_held(loss))
 
         def backward(gradient=None, retain_graph=None, create_graph=False, inputs=None):
+            lt = wloss()
+            if consumed[0]:
+                raise RuntimeError("Trying to backward through the graph a second time: GE2ELoss(graph=True) has already "
+                                   "published this loss's gradients (pass retain_graph=True to the first backward)")
+            if retain_graph is None:
+                retain_graph = create_graph
+            if not req:
+                raise RuntimeError("element 0 of tensors does not require grad and does not have a grad_fn")
             if (gradient is not None or create_graph or inputs is not None or step.serial != serial
-                    or _has_hooks(e) or _has_hooks(w) or _has_hooks(b) or _has_hooks(wloss())):
-                return torch.Tensor.backward(wloss(), gradient, retain_graph, create_graph, inputs)
-            for t, g in ((w, step.dw0), (b, step.db0)):
-                if t.requires_grad:
-                    if t.grad is None:
-                        t.grad = g
-                    else:
-                        t.grad.add_(g)
-            if e.requires_grad:
-                if not e.is_leaf:                # the encoder's graph continues behind the embeddings
-                    torch.autograd.backward(e, step.dE3, retain_graph=retain_graph)
-                elif e.grad is None:
-                    e.grad = step.dE3
+                    or _has_hooks(e) or _has_hooks(w) or _has_hooks(b) or (lt is not None and _has_hooks(lt))):
+                torch.Tensor.backward(lt, gradient, retain_graph, create_graph, inputs)
+                consumed[0] = not retain_graph
+                return
+            consumed[0] = not retain_graph
+            pub = [(t, g) for t, g in ((w, step.dw0), (b, step.db0), (e, step.dE3)) if t.requires_grad]
+            if engine:
+                # somebody may have hooked an accumulator -- DistributedDataParallel's reducer does, from C++, where Python cannot
+                # see it: the gradients go through the engine, which runs every hook (one call, the encoder's part included)
+                torch.autograd.backward([t for t, _ in pub], [g for _, g in pub], retain_graph=retain_graph)
+                return
+            for t, g in pub:
+                if t is e and not e.is_leaf:     # the encoder's graph continues behind the embeddings
+                    torch.autograd.backward(e, g, retain_graph=retain_graph)
+                elif t.grad is None:
+                    t.grad = g
+                elif t.grad.data_ptr() == g.data_ptr():
+                    t.grad = t.grad + g          # .grad IS the static buffer (retain_graph): keep the buffer's value intact
                 else:
-                    e.grad.add_(step.dE3)
+                    t.grad.add_(g)
 
         loss.backward = backward                 # instance attribute: shadows Tensor.backward for this loss only
         return loss
