@@ -107,6 +107,19 @@ int ge2e_loss_fwd_bwd(const float* E, int B, int N, int M, int D,
                       void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * The same in DOUBLE precision (the reference's forward is dtype-generic, s3:19-30: float64 embeddings are computed in
+ * float64): every tensor, w, b and every result is float64, every operation of the kernel is fp64 (contractions on
+ * v_mfma_f64_16x16x4_f64).  Any shape ge2e_loss_fwd_bwd takes, both variants, forward only with dE = NULL.  One kernel,
+ * no implementation choice; deterministic.  The workspace is this entry point's own (ge2e_workspace_bytes_f64, 256-byte
+ * aligned, no control block, no initialisation).  Same error codes, checked on the host before anything is launched.
+ */
+size_t ge2e_workspace_bytes_f64(int B, int N, int M, int D, int variant);
+int ge2e_loss_fwd_bwd_f64(const double* E, int B, int N, int M, int D,
+                          const double* w, const double* b, double eps_cos, double eps, int variant,
+                          double* loss, double* per_emb_loss, double* dE, double* dw, double* db,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * The same, fed with the encoder's RAW output (s2_model_GE2E_loss_speach_embed.py:34 +
  * s4_train_embed_model.py:186-192 folded into the loss kernel's load and store stages):
  *   Y   [B][N*M][D]  the encoder's projection BEFORE its L2-normalisation, rows in the encoder's own (permuted) order

@@ -7,6 +7,7 @@
 
 #include "ge2e_common.hpp"
 #include "ge2e_generic.hpp"
+#include "ge2e_f64.hpp"
 #include "ge2e_helpers.hpp"
 #include "ge2e_fused.hpp"
 #include "ge2e_selftest.hpp"
@@ -154,6 +155,30 @@ int ge2e_loss_fwd_bwd(const float* E, int B, int N, int M, int D, const float* w
     p.dE = dE; p.dw = dw; p.db = db; p.cos_out = nullptr;
     p.B = B; p.N = N; p.M = M; p.D = D; p.variant = variant; p.eps_cos = eps_cos; p.eps = eps;
     return run(p, impl, workspace, workspace_bytes, stream);
+}
+
+// The double-precision loss: a kernel of its own (ge2e_f64.hip), a workspace of its own (no team control block: nothing
+// else runs on it).  Same checks, in the same order, as ge2e_loss_fwd_bwd.
+size_t ge2e_workspace_bytes_f64(int B, int N, int M, int D, int variant) {
+    (void)variant;
+    return shape_ok(B, N, M, D) ? f64_workspace_bytes(B, N, M, D) : 0;
+}
+
+int ge2e_loss_fwd_bwd_f64(const double* E, int B, int N, int M, int D, const double* w, const double* b, double eps_cos,
+                          double eps, int variant, double* loss, double* per_emb_loss, double* dE, double* dw, double* db,
+                          void* workspace, size_t workspace_bytes, void* stream) {
+    if (!E || !w || !b || !loss) return GE2E_ERR_NULL;
+    if (dE && (!dw || !db)) return GE2E_ERR_NULL;
+    if (!shape_ok(B, N, M, D)) return GE2E_ERR_SHAPE;
+    if (variant != GE2E_VARIANT_SOFTMAX && variant != GE2E_VARIANT_CONTRAST) return GE2E_ERR_VARIANT;
+    if (!workspace || workspace_bytes < f64_workspace_bytes(B, N, M, D) || ((uintptr_t)workspace & 255)) return GE2E_ERR_WORKSPACE;
+    if (((uintptr_t)E & 15) || ((uintptr_t)dE & 15)) return GE2E_ERR_ALIGN;
+    ProblemF64 p{};
+    p.E = E; p.w = w; p.b = b; p.loss = loss; p.per = per_emb_loss;
+    p.dE = dE; p.dw = dw; p.db = db; p.ws = (double*)workspace;
+    p.B = B; p.N = N; p.M = M; p.D = D; p.variant = variant; p.eps_cos = eps_cos; p.eps = eps;
+    p.log_eps = eps > 0.0 ? log(eps) : -INFINITY;
+    return (int)launch_f64(p, (hipStream_t)stream);
 }
 
 int ge2e_raw_supported(int N, int M, int D) { return (N >= 1 && M >= 2 && D >= 1 && wave_supports_raw(N, M, D)) ? 1 : 0; }

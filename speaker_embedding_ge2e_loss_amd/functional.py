@@ -24,7 +24,7 @@ def _require_cuda(t: torch.Tensor, name: str):
             "(no CPU fallback exists in speaker_embedding_ge2e_loss_amd)")
 
 
-def _as_batched(e: torch.Tensor):
+def _as_batched(e: torch.Tensor, dtype: torch.dtype = torch.float32):
     """(N,M,D) -> view (1,N,M,D); (B,N,M,D) unchanged.  Mirrors s3:49-52: must be contiguous."""
     if e.dim() == 3:
         squeeze = True
@@ -35,8 +35,8 @@ def _as_batched(e: torch.Tensor):
     if not e.is_contiguous():
         # the reference calls .view() on the input (s3:49,52), which raises for non-contiguous
         raise RuntimeError("embeddings must be contiguous (the reference uses .view(), s3:49-52)")
-    if e.dtype != torch.float32:
-        raise TypeError(f"embeddings must be float32 at this boundary, got {e.dtype}")
+    if e.dtype != dtype:
+        raise TypeError(f"embeddings must be {str(dtype)[6:]} at this boundary, got {e.dtype}")
     return (e.unsqueeze(0) if squeeze else e), squeeze
 
 
@@ -153,12 +153,13 @@ def alloc_workspace(nbytes: int, device) -> torch.Tensor:
     return ws
 
 
-def _check_scalar_params(w: torch.Tensor, b: torch.Tensor, dev: torch.device):
-    """w and b cross the C ABI as raw device pointers to one fp32 each: anything else would be a wild device read."""
+def _check_scalar_params(w: torch.Tensor, b: torch.Tensor, dev: torch.device, dtype: torch.dtype = torch.float32):
+    """w and b cross the C ABI as raw device pointers to one fp32 (fp64 on the double-precision entry point) each:
+    anything else would be a wild device read."""
     for name, t in (("w", w), ("b", b)):
         _require_cuda(t, name)
-        if t.dtype != torch.float32 or t.numel() != 1:
-            raise TypeError(f"{name} must be a float32 scalar tensor")
+        if t.dtype != dtype or t.numel() != 1:
+            raise TypeError(f"{name} must be a {str(dtype)[6:]} scalar tensor")
         if t.device != dev:
             raise RuntimeError(f"{name} is on {t.device}, embeddings on {dev}: raw pointers cross the C ABI, all on one device")
 
@@ -188,9 +189,14 @@ def loss_fwd_bwd(embeddings: torch.Tensor, w: torch.Tensor, b: torch.Tensor, *,
 
     ``out`` / ``workspace`` let a caller (the benchmark, a CUDA-graph capture) reuse
     buffers; otherwise they come from torch's caching allocator.
+
+    float64 embeddings (with float64 ``w`` / ``b``) go to ge2e_loss_fwd_bwd_f64: computed in double precision, float64
+    outputs.  That entry point has one kernel, so ``impl`` must be "auto".
     """
     lib = _lib.load()
     _require_cuda(embeddings, "embeddings")
+    if embeddings.dtype == torch.float64:
+        return _loss_fwd_bwd_f64(lib, embeddings, w, b, eps, eps_cos, variant, impl, need_grad, need_per, out, workspace)
     e4, _ = _as_batched(embeddings)
     B, N, M, D = e4.shape
     dev = e4.device
@@ -215,6 +221,62 @@ def loss_fwd_bwd(embeddings: torch.Tensor, w: torch.Tensor, b: torch.Tensor, *,
             out.loss.data_ptr(), ptr(out.per), ptr(out.dE), ptr(out.dw), ptr(out.db),
             workspace.data_ptr(), workspace.numel(), stream)
     _lib.check(code, "ge2e_loss_fwd_bwd")
+    return out
+
+
+def _workspace_for_f64(lib, dev: torch.device, stream: int, shape: tuple, v: int, dev_idx: int) -> torch.Tensor:
+    """The double-precision kernel's workspace: its own entry of the per-(device, stream) cache (it has no control block,
+    so it is never shared with the fp32 kernels' workspace), from the allocator while the stream is being captured."""
+    key = shape + (v, "f64", dev_idx)
+    need = _ws_bytes_cache.get(key)
+    if need is None:
+        need = _ws_bytes_cache[key] = int(lib.ge2e_workspace_bytes_f64(*shape, v))
+    if _capturing is not None and _capturing():
+        return torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+    k = (dev_idx, stream, "f64")
+    ws = _ws_cache.pop(k, None)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+        while len(_ws_cache) >= _WS_CACHE_MAX:
+            _ws_cache.pop(next(iter(_ws_cache)))
+    _ws_cache[k] = ws
+    return ws
+
+
+def _loss_fwd_bwd_f64(lib, embeddings, w, b, eps, eps_cos, variant, impl, need_grad, need_per, out, workspace) -> LossOutputs:
+    if impl != "auto":
+        raise ValueError(f'impl="{impl}" names a float32 kernel; float64 embeddings have one kernel (impl="auto")')
+    e4, _ = _as_batched(embeddings, torch.float64)
+    B, N, M, D = e4.shape
+    dev = e4.device
+    _check_scalar_params(w, b, dev, torch.float64)
+    if e4.data_ptr() % 16:         # a contiguous view at an odd storage offset
+        e4 = e4.clone()
+    if out is None:
+        f64 = dict(dtype=torch.float64, device=dev)
+        sc = torch.empty(3 if need_grad else 1, B, **f64)  # loss | dw | db in one allocation
+        out = LossOutputs(
+            loss=sc[0],
+            per=torch.empty(B, N, M, **f64) if need_per else None,
+            dE=torch.empty(B, N, M, D, **f64) if need_grad else None,
+            dw=sc[1] if need_grad else None,
+            db=sc[2] if need_grad else None)
+    else:
+        for name in ("loss", "per", "dE", "dw", "db"):
+            t = getattr(out, name)
+            if t is not None and (t.dtype != torch.float64 or not t.is_contiguous() or t.device != dev):
+                raise TypeError(f"out.{name} must be a contiguous float64 tensor on {dev}")
+    v = _lib.VARIANTS[variant]
+    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    with _on_device(dev) as guard:
+        stream = _stream_ptr(e4)
+        if workspace is None:
+            workspace = _workspace_for_f64(lib, dev, stream, (B, N, M, D), v, guard.idx)
+        code = lib.ge2e_loss_fwd_bwd_f64(
+            e4.data_ptr(), B, N, M, D, w.data_ptr(), b.data_ptr(), eps_cos, eps, v,
+            out.loss.data_ptr(), ptr(out.per), ptr(out.dE), ptr(out.dw), ptr(out.db),
+            workspace.data_ptr(), workspace.numel(), stream)
+    _lib.check(code, "ge2e_loss_fwd_bwd_f64")
     return out
 
 
@@ -704,7 +766,40 @@ class _GE2ELossFunction(torch.autograd.Function):
         return gE, gw, gb, None, None, None, None
 
 
-# The autograd node in C++ (libge2e_torch.so, csrc_torch/ge2e_autograd.cpp: torch.ops.ge2e_amd.loss): the same two C-ABI
+class _GE2ELossF64Function(torch.autograd.Function):
+    """The same node over ge2e_loss_fwd_bwd_f64: float64 embeddings, w, b in, float64 loss and gradients out.  The
+    upstream gradient is applied in float64 (a handful of elementwise torch ops on the launch's own dE / dw / db)."""
+
+    @staticmethod
+    def forward(ctx, embeddings, w, b, eps, eps_cos, variant):
+        need = any(ctx.needs_input_grad[:3])
+        squeeze = embeddings.dim() == 3
+        o = loss_fwd_bwd(embeddings, w, b, eps=eps, eps_cos=eps_cos, variant=variant, need_grad=need)
+        ctx.squeeze = squeeze
+        ctx.w_shape, ctx.b_shape = w.shape, b.shape
+        if need:
+            ctx.save_for_backward(o.dE, o.dw, o.db)
+        return o.loss[0] if squeeze else o.loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        dE, dw, db = ctx.saved_tensors
+        g = grad_out.to(torch.float64).reshape(-1)               # (1,) for a 0-dim loss, (B,) for a stack
+        need_e, need_w, need_b = ctx.needs_input_grad[:3]
+        gE = gw = gb = None
+        if need_e:
+            gE = dE * g.view(-1, 1, 1, 1)
+            if ctx.squeeze:
+                gE = gE[0]
+        if need_w:
+            gw = (dw * g).sum().reshape(ctx.w_shape)
+        if need_b:
+            gb = (db * g).sum().reshape(ctx.b_shape)
+        return gE, gw, gb, None, None, None
+
+
+# The autograd node in C++ (libge2e_torch.so,csrc_torch/ge2e_autograd.cpp: torch.ops.ge2e_amd.loss): the same two C-ABI
 # calls as _GE2ELossFunction without the Python dispatch around them -- the eager module step at B = 1 is host-bound.
 # Used when the library has been built (build.build() does); _GE2ELossFunction is the same node in Python.
 _cpp_node = {"tried": False, "op": None, "enabled": True}
@@ -748,9 +843,19 @@ def ge2e_loss(embeddings: torch.Tensor, w: torch.Tensor, b: torch.Tensor, *, eps
     """Differentiable GE2E loss: 0-dim for (N,M,D) input, (B,) for (B,N,M,D)."""
     _require_cuda(embeddings, "embeddings")
     in_dtype = embeddings.dtype
+    # The dtype contract.  The reference is dtype-generic (s3:19-30 computes in whatever dtype the embeddings have and
+    # returns it, SURVEY 8a/a2).  Here:
+    #   float32           native: the fp32 kernels;
+    #   float64           native with impl="auto": the double-precision kernel (ge2e_loss_fwd_bwd_f64), float64 loss and
+    #                     gradients.  w and b may be float32 (the module's parameters: the reference's `self.w * cos`
+    #                     promotes) or float64; the cast is a differentiable torch op, so each leaf's gradient comes
+    #                     back in the leaf's own dtype.  An explicit impl names an fp32 kernel and takes the cast route;
+    #   float16/bfloat16  computed in fp32, the casts either side are differentiable torch ops.
+    # (The static helpers -- cos_sim, calc_loss, centroids, ... -- compute in fp32 whatever they are given.)
+    if in_dtype == torch.float64 and impl == "auto":
+        return _GE2ELossF64Function.apply(embeddings, w.to(torch.float64), b.to(torch.float64), float(eps),
+                                          float(eps_cos), variant)
     if in_dtype != torch.float32:
-        # the reference is dtype-generic (s3:19-30 accepts fp16 / fp64 and returns that dtype, SURVEY 8a/a2); the kernels
-        # compute in fp32, the casts either side are differentiable torch ops
         embeddings = embeddings.float()
     op = None if _ws_override else _cpp_loss_op()         # (a caller-owned workspace -- a graph capture -- goes through Python)
     if op is not None:

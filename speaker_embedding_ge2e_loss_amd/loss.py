@@ -113,7 +113,8 @@ class GE2ELoss(nn.Module):
         loss that nothing requires grad for raises.  Under ``torch.distributed`` (DistributedDataParallel hooks the parameters'
         AccumulateGrad nodes from C++, where Python cannot see it), or when somebody holds an AccumulateGrad node of ``e``,
         ``w`` or ``b`` at the forward (a hook registered on it), the gradients are published through ONE
-        ``torch.autograd.backward`` call on the leaves, which runs every hook.  Still the eager node: another shape, a (B, N, M, D) stack, no-grad mode, a stream
+        ``torch.autograd.backward`` call on the leaves, which runs every hook.  Still the eager node: another shape, a (B, N, M, D) stack, an input that is not
+        float32 (float64 embeddings run the double-precision kernel, eagerly; float16 / bfloat16 the cast route), no-grad mode, a stream
         that is capturing, tensor hooks on ``e`` / ``w`` / ``b`` / the loss, ``backward`` with a gradient / ``inputs`` /
         ``create_graph``, and any gradient that flows THROUGH the loss (``torch.autograd.grad``, ``(2 * loss).backward()``)."""
         super().__init__()
@@ -133,7 +134,9 @@ class GE2ELoss(nn.Module):
 
         Like the reference, w is NOT clamped (s3:22 discards torch.clamp's result), the
         loss is a sum over all (speaker, utterance) rows (s3:126), and the gradient flows
-        through both cosine norms.
+        through both cosine norms.  Like the reference, the loss and the embeddings' gradient come back in the
+        embeddings' dtype: float32 and float64 are computed natively (float64 with ``impl="auto"``; ``w.grad`` /
+        ``b.grad`` stay fp32 like the parameters), float16 / bfloat16 are computed in fp32.
         """
         if self.graph:
             loss = self._forward_graphed(embeddings)
