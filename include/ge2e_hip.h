@@ -201,7 +201,8 @@ int ge2e_calc_loss_rows_bwd(const float* sim, int B, int n, int N, int j0, int M
 
 /* What `loss.backward()` (s4:200) does with the results of ge2e_loss_fwd_bwd: scale by the incoming gradient g (device;
  * g_count = 1 for a scalar loss or B for a per-batch loss vector) in ONE launch:
- *   gE [B][N][M][D] = g[b] dE[b]   (NULL: skip);   gw [1] = sum_b g[b] dw[b];   gb [1] = sum_b g[b] db[b]   (NULL: skip) */
+ *   gE [B][N][M][D] = g[b] dE[b]   (NULL: skip);   gw [1] = sum_b g[b] dw[b];   gb [1] = sum_b g[b] db[b]   (NULL: skip)
+ * dE and gE need only float alignment: 16-byte loads are used when N*M*D % 4 == 0 and both are 16-byte aligned. */
 int ge2e_scale_grads(const float* dE, const float* dw, const float* db, const float* g, int g_count, int B, int N, int M,
                      int D, float* gE, float* gw, float* gb, void* stream);
 

@@ -187,7 +187,9 @@ __global__ __launch_bounds__(256) void scale_grads_kernel(const float* __restric
                                                           float* __restrict__ gw, float* __restrict__ gb) {
     if (gE) {
         const size_t total = (size_t)B * per_batch;
-        if ((per_batch & 3) == 0) {
+        // float4 path: whole batches of float4 AND both pointers 16-byte aligned (a contiguous view at an odd storage
+        // offset is not); anything else takes the scalar loop -- the same products, element by element
+        if ((per_batch & 3) == 0 && (((uintptr_t)dE | (uintptr_t)gE) & 15) == 0) {
             const size_t n4 = total / 4, p4 = per_batch / 4;
             for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
                 const float s = g[gB == 1 ? 0 : i / p4];
