@@ -1,0 +1,180 @@
+"""Case tables of tests/test_gpu_bounds.py (a plain module: tests/test_bounds_cases.py checks it without a GPU).
+
+Every shape sits on a padding edge of the kernel it names.  The edges are those the library reports (ge2e_resolve_impl,
+ge2e_raw_supported); test_bounds_cases.py scans those predicates and fails if a table misses one, so nothing here is
+taken on trust.  Inputs and (w, b) are those of test_gpu_parity.test_ragged_shapes ("raw" rows, w = 7.5, b = -2).
+B*N*M*D <= 6e6 keeps the fp64 closed form quick (the bound of test_gpu_fuzz.py).
+"""
+import functools
+
+import numpy as np
+
+from oracle import ge2e_oracle as orc
+
+W, BIAS = 7.5, -2.0
+MAX_ELEMS = 6e6
+S, C = "softmax", "contrast"
+
+# (impl, B, N, M, D, variant)
+LOSS_CASES = [
+    # generic: any shape.  D % 4 != 0 (rows of E not 16-byte aligned), N = 1, M = 2, N = 65 (more speakers than a wave)
+    ("generic", 2, 1, 2, 1, S), ("generic", 1, 2, 2, 7, S), ("generic", 3, 5, 3, 7, C), ("generic", 1, 65, 2, 33, S),
+    ("generic", 1, 65, 2, 33, C), ("generic", 2, 7, 4, 65, C), ("generic", 1, 1, 9, 33, S), ("generic", 2, 4, 5, 64, S),
+    # fused_f32: N 1..64, M 2..64, D a multiple of 64 up to 256 (it takes none of 4, 36, 100, 200, 252); B = 300 > its grid
+    ("fused_f32", 3, 1, 2, 64, S), ("fused_f32", 2, 64, 2, 256, C), ("fused_f32", 1, 64, 64, 64, S),
+    ("fused_f32", 2, 1, 64, 128, S), ("fused_f32", 300, 2, 3, 64, C), ("fused_f32", 1, 64, 64, 256, C),
+    ("fused_f32", 2, 33, 9, 192, C),
+    # fused_split: the same N and M, D any multiple of 4 (padded to 64 inside the load / store stages)
+    ("fused_split", 3, 1, 2, 4, S), ("fused_split", 2, 64, 2, 36, C), ("fused_split", 1, 64, 64, 100, S),
+    ("fused_split", 2, 1, 64, 200, S), ("fused_split", 300, 2, 3, 252, C), ("fused_split", 1, 64, 64, 256, C),
+    ("fused_split", 2, 33, 9, 200, S),
+    # team: eight members share N speakers unevenly; (N + 7) / 8 * M = 80 is its largest image; B over and under the teams
+    ("team", 1, 16, 16, 4, S), ("team", 2, 23, 7, 80, C), ("team", 9, 40, 16, 132, S), ("team", 70, 57, 5, 200, C),
+    ("team", 1, 64, 10, 252, S), ("team", 9, 64, 10, 256, C), ("team", 2, 64, 10, 256, S), ("team", 70, 16, 2, 256, S),
+    ("team", 1, 57, 10, 200, C),
+    # tiled: npad = 64 ceil(N / 64) no multiple of N; N M no multiple of 64, 128, 256 (one with: 256); M > 64; D % 32 either way
+    ("tiled", 3, 1, 2, 8, S), ("tiled", 1, 15, 70, 72, C), ("tiled", 3, 65, 3, 200, S), ("tiled", 1, 130, 5, 264, C),
+    ("tiled", 1, 300, 3, 776, S), ("tiled", 1, 65, 7, 1024, C), ("tiled", 3, 130, 4, 1024, S), ("tiled", 1, 64, 4, 264, S),
+    ("tiled", 3, 15, 3, 72, C),
+    # ... and launches big enough for its 256-row tiles (>= 192 of them): similarity + row pass in one kernel (N = 256 has an
+    # instantiation of its own), the 256 x 256 similarity and dE contractions fed by registers (D or N % 32 != 0) and by LDS-DMA.
+    # Limits: the 256 x 256 centroid-gradient contraction (and its row split) needs >= 192 tiles with N, D >= 256, which does
+    # not fit in MAX_ELEMS, so it never runs here; of the large launches only the fused similarity + row pass runs as contrast
+    # (tens of thousands of contrast rows tie on most draws: SEEDS names draws that do not).
+    ("tiled", 64, 130, 4, 32, S), ("tiled", 64, 256, 3, 32, S), ("tiled", 32, 257, 2, 8, S), ("tiled", 32, 257, 2, 32, S),
+    ("tiled", 32, 130, 4, 264, S), ("tiled", 32, 128, 5, 264, S), ("tiled", 64, 130, 4, 32, C), ("tiled", 64, 256, 3, 32, C),
+    # wave: every instantiated M at its largest register-only N and at its largest N; B = 2100 > the grid's 2048 waves
+    ("wave", 5, 6, 2, 256, S), ("wave", 1, 12, 2, 4, C), ("wave", 2100, 5, 3, 36, S), ("wave", 5, 10, 3, 252, C),
+    ("wave", 1, 4, 4, 256, S), ("wave", 5, 10, 4, 36, C), ("wave", 2100, 4, 5, 36, S), ("wave", 1, 8, 5, 256, C),
+    ("wave", 5, 3, 6, 4, C), ("wave", 2100, 8, 6, 4, S), ("wave", 1, 3, 8, 252, S), ("wave", 5, 8, 8, 256, C),
+    ("wave", 5, 2, 10, 256, S), ("wave", 1, 6, 10, 252, C), ("wave", 2100, 2, 16, 4, S), ("wave", 5, 3, 16, 36, C),
+    ("wave", 2100, 2, 2, 256, S),
+    # auto / auto_no_team: one case per implementation they resolve to
+    ("auto", 1, 4, 5, 256, S), ("auto", 3, 64, 10, 256, C), ("auto", 210, 16, 2, 8, S), ("auto", 1, 130, 3, 72, C),
+    ("auto", 1, 65, 2, 33, S),
+    ("auto_no_team", 5, 2, 16, 36, C), ("auto_no_team", 3, 64, 10, 256, S), ("auto_no_team", 2, 100, 5, 40, S),
+    ("auto_no_team", 2, 7, 4, 65, S),
+]
+AUTO_REACHES = {"auto": {"wave", "team", "fused_split", "tiled", "generic"},
+                "auto_no_team": {"wave", "fused_split", "tiled", "generic"}}
+
+# the edges the issue lists, per implementation: (field, values that must each appear in a case of that implementation)
+REQUIRED = {
+    "generic": {"D": {1, 7, 33, 65}, "N": {1, 65}, "M": {2}},
+    "fused_f32": {"D": {64, 256}, "M": {2}},
+    "fused_split": {"D": {4, 36, 100, 200, 252, 256}, "M": {2}},
+    "team": {"N": {16, 23, 40, 57, 64}, "D": {4, 80, 132, 200, 252, 256}, "B": {1, 2, 9, 70}},
+    "tiled": {"N": {1, 15, 65, 130, 300}, "D": {8, 72, 200, 264, 776, 1024}, "B": {1, 3}},
+    "wave": {"D": {4, 36, 252, 256}, "B": {1, 5, 2100}},
+}
+
+# output combinations: (name, per, grads, misaligned)
+COMBOS = [("all", True, True, False), ("no_per", False, True, False), ("fwd_per", True, False, False),
+          ("fwd", False, False, False), ("misaligned", True, True, True)]
+
+# ge2e_cos_sim: (B, N, M, D).  N = 16 with D % 64 == 0 is the header's edge of the matrix-core route; N M = 48, 195, 1050
+# are no multiples of 64; (2, 15, 4, 64) stays on the VALU kernel whatever the workspace (N < 16).
+# At (1, 16, 3, 64) and (1, 16, 3, 72) the generic size (control block included) is the LARGER of the two, so both
+# workspaces are the same, the matrix-core route runs with slack behind its last region and the workspace guard cannot bite
+# there: those two check the outputs' guards and the values only.  The exact-size property, and "the smaller workspace
+# takes the VALU kernel", are carried by the cases where ge2e_cos_sim_workspace_bytes is the tiled size: (1, 16, 64, 256) --
+# the header's edge again, with enough rows for that --, (3, 16, 16, 256), (2, 65, 3, 128), (1, 300, 3, 768).
+COS_CASES = [(1, 16, 3, 64), (1, 16, 64, 256), (3, 16, 16, 256), (2, 65, 3, 128), (1, 15, 70, 64), (1, 300, 3, 768), (2, 15, 4, 64), (1, 16, 3, 72)]
+
+# ge2e_loss_fwd_bwd_raw: (B, N or "max", M, D, variant); "max" = the largest N ge2e_raw_supported takes for that M.
+# Every instantiated M, at its largest N and at N = 1, with B = 1, 3 and 2100 (more than the grid's 2048 waves): each
+# <M, NX, RAW> is a kernel of its own.  D cycles through RAW_DS; where B rows D would pass MAX_ELEMS the next D that fits is
+# taken (a wave holds at most 64 rows, the header's limit, so B = 2100 at the largest N runs at D = 4 and 36 only).
+# Contrast wherever there is another speaker and B < 2100 (tens of thousands of contrast rows would tie, see above).
+RAW_MS = (2, 3, 4, 5, 6, 8, 10, 16)
+RAW_DS = (4, 36, 252, 256)
+RAW_BS = (1, 3, 2100)
+
+
+def _raw_cases():
+    out = []
+    for mi, M in enumerate(RAW_MS):
+        for ni, N in enumerate(("max", 1)):
+            for bi, B in enumerate(RAW_BS):
+                rows = 64 if N == "max" else M
+                k = mi + bi + 2 * ni
+                D = next(RAW_DS[(k + i) % 4] for i in range(4) if B * rows * RAW_DS[(k + i) % 4] <= MAX_ELEMS)
+                out.append((B, N, M, D, C if (N == "max" and B < 2100) else S))
+    return out
+
+
+RAW_CASES = _raw_cases()
+
+
+def case_id(c):
+    return "{}_B{}_N{}_M{}_D{}_{}".format(*c[:5], c[5][0])
+
+
+def raw_id(c):
+    return "B{}_N{}_M{}_D{}_{}".format(*c[:4], c[4][0])
+
+
+def raw_max_n(lib, M, D):
+    """The largest N ge2e_raw_supported accepts for (M, D); 0 if none."""
+    n = 0
+    while lib.ge2e_raw_supported(n + 1, M, D):
+        n += 1
+    return n
+
+
+def resolve_raw(lib, case):
+    B, N, M, D, variant = case
+    return (B, raw_max_n(lib, M, D) if N == "max" else N, M, D, variant)
+
+
+# draws chosen on the CPU (test_bounds_cases.py) because the default one ties two other-speaker similarities of a row
+SEEDS = {("tiled", 64, 130, 4, 32, C): 2, ("tiled", 64, 256, 3, 32, C): 2}
+
+
+def loss_inputs(case):
+    _, B, N, M, D, _ = case
+    return orc.synth_embeddings((B, N, M, D), "raw", seed=SEEDS.get(case, B + N + M + D))
+
+
+@functools.lru_cache(maxsize=None)
+def loss_reference(case):
+    return orc.closed_form(loss_inputs(case), W, BIAS, variant=case[5])
+
+
+def top2_gap_ok(ref, N):
+    """test_gpu_fuzz.py's criterion: eq. 7's max over the other speakers must not tie within what fp32 resolves."""
+    if N <= 2:
+        return True
+    Sm = W * np.asarray(ref["cos"], np.float64) + BIAS
+    Sm = Sm.reshape((-1,) + Sm.shape[-3:])
+    jj = np.arange(N)
+    Sm[:, jj, :, jj] = -np.inf
+    top2 = np.sort(Sm, axis=-1)[..., -2:]
+    return float((top2[..., 1] - top2[..., 0]).min()) >= 5e-6 * max(1.0, float(np.abs(top2[..., 1]).max()))
+
+
+def raw_inputs(case):
+    """Y [B][N M][D] with rows of very different norm (as test_loss_raw_is_normalize_unperm_then_loss), and a different
+    permutation per batch: src [B][N M] int32."""
+    B, N, M, D, _ = case
+    rng = np.random.default_rng(1000 * N + 100 * M + D + B)
+    Y = rng.standard_normal((B, N * M, D)) * (0.5 + 2.0 * rng.random((B, N * M, 1)))
+    src = np.stack([rng.permutation(N * M) for _ in range(B)]).astype(np.int32)
+    return np.ascontiguousarray(Y, dtype=np.float32), src
+
+
+def raw_reference(case, Y, src):
+    """fp64: normalise and gather, the closed form, dE back through (g - e (e . g)) / |y|, scatter."""
+    B, N, M, D, variant = case
+    y = Y.astype(np.float64)
+    norm = np.linalg.norm(y, axis=-1, keepdims=True)
+    e = y / norm
+    bi = np.arange(B)[:, None]
+    idx = src if src is not None else np.broadcast_to(np.arange(N * M), (B, N * M))
+    eg = e[bi, idx]                                             # row r of the block is Y[src[r]] / |Y[src[r]]|
+    ref = orc.closed_form(eg.reshape(B, N, M, D), W, BIAS, variant=variant, dtype=np.float64)
+    g = ref["dE"].reshape(B, N * M, D)
+    gy = (g - eg * (eg * g).sum(axis=-1, keepdims=True)) / norm[bi, idx]
+    dY = np.zeros_like(y)
+    dY[bi, idx] = gy
+    return dict(ref, dY=dY)

@@ -18,10 +18,10 @@ import torch
 
 import helpers_ref as hr
 from conftest import rel_fro
+from guarded import Buf, dev
 
 pytestmark = pytest.mark.gpu
 
-G = 64            # guard elements either side (keeps 16-byte alignment)
 ULP = 2.0 ** -24  # fp32 unit round-off
 
 
@@ -37,37 +37,6 @@ def GF():
 def lib(GF):
     from speaker_embedding_ge2e_loss_amd import _lib
     return _lib.load()
-
-
-def dev():
-    return torch.device("cuda:0")
-
-
-class Buf:
-    """n floats between two NaN guard bands.  Inputs carry data, outputs NaN poison."""
-
-    def __init__(self, shape, data=None, offset=0):
-        self.shape = tuple(int(s) for s in shape)
-        self.n = int(np.prod(self.shape))
-        self.lo = G + offset
-        self.buf = torch.full((self.n + 2 * G + offset,), float("nan"), device=dev(), dtype=torch.float32)
-        self.t = self.buf[self.lo:self.lo + self.n].view(self.shape)
-        if data is not None:
-            self.t.copy_(torch.as_tensor(np.ascontiguousarray(data, dtype=np.float32)).view(self.shape))
-
-    @property
-    def ptr(self):
-        return self.t.data_ptr()
-
-    def guards_intact(self):
-        return bool(torch.isnan(self.buf[:self.lo]).all()) and bool(torch.isnan(self.buf[self.lo + self.n:]).all())
-
-    def get(self, what, finite=True):
-        torch.cuda.synchronize()
-        assert self.guards_intact(), f"{what}: guard band overwritten"
-        if finite:
-            assert bool(torch.isfinite(self.t).all()), f"{what}: NaN poison (or inf) left in the output"
-        return self.t.cpu().numpy()
 
 
 def ok(code, what):
