@@ -2,7 +2,7 @@
 // implementation choice, workspace sizing, launches.  No allocation, no sync, no state.
 #include "../../include/ge2e_hip.h"
 
-#include <math.h>
+#include <cmath>
 #include <stdlib.h>
 
 #include "ge2e_common.hpp"
@@ -25,6 +25,29 @@ unsigned long long* g_prof = nullptr;  // diagnostic build only
 #endif
 
 bool shape_ok(int B, int N, int M, int D) { return B >= 1 && N >= 1 && M >= 2 && D >= 1; }
+
+bool variant_ok(int v) { return v == GE2E_VARIANT_SOFTMAX || v == GE2E_VARIANT_CONTRAST; }
+
+// The NULL rule of every loss entry point: inputs and the loss always, and whoever asks for dE takes dw and db with it.
+bool loss_ptrs_ok(const void* E, const void* w, const void* b, const void* loss, const void* dE, const void* dw,
+                  const void* db) {
+    return E && w && b && loss && (!dE || (dw && db));
+}
+
+template <class T>
+T log_eps_of(T eps) { return eps > T(0) ? std::log(eps) : T(-INFINITY); }   // std::log(float) is logf
+
+// The launch description of a loss entry point's argument list (P = Problem with T = float, ProblemF64 with T = double).
+// Everything else starts as zero: no cos_out, no grid cap, no test abort, not raw; ws and log_eps are the caller's.
+template <class P, class T>
+P make_problem(const T* E, int B, int N, int M, int D, const T* w, const T* b, T eps_cos, T eps, int variant, T* loss,
+               T* per_emb_loss, T* dE, T* dw, T* db) {
+    P p{};
+    p.E = E; p.w = w; p.b = b; p.loss = loss; p.per = per_emb_loss;
+    p.dE = dE; p.dw = dw; p.db = db;
+    p.B = B; p.N = N; p.M = M; p.D = D; p.variant = variant; p.eps_cos = eps_cos; p.eps = eps;
+    return p;
+}
 
 // AUTO at shapes both accept (measured at N=64, M=10, D=256, interleaved in one process, tools/compare_impls.py,
 // profiles/r02_team_vs_fused_split_by_B.txt): the eight-CU team kernel wins everywhere (28 us vs 117 us at B = 1,
@@ -79,7 +102,7 @@ size_t ws_bytes(int B, int N, int M, int D, int impl) {
 
 int run(Problem& p, int impl, void* workspace, size_t workspace_bytes, void* stream) {
     if (!shape_ok(p.B, p.N, p.M, p.D)) return GE2E_ERR_SHAPE;
-    if (p.variant != GE2E_VARIANT_SOFTMAX && p.variant != GE2E_VARIANT_CONTRAST) return GE2E_ERR_VARIANT;
+    if (!variant_ok(p.variant)) return GE2E_ERR_VARIANT;
     const int chosen = resolve(p.B, p.N, p.M, p.D, p.variant, impl);
     if (chosen < 0) return chosen;
     const size_t need = ws_bytes(p.B, p.N, p.M, p.D, chosen);
@@ -89,7 +112,7 @@ int run(Problem& p, int impl, void* workspace, size_t workspace_bytes, void* str
 #ifdef GE2E_PROFILE
     p.prof = g_prof;
 #endif
-    p.log_eps = p.eps > 0.f ? logf(p.eps) : -INFINITY;
+    p.log_eps = log_eps_of(p.eps);
     hipError_t err = hipSuccess;
     switch (chosen) {
         case GE2E_IMPL_GENERIC: err = launch_generic(p, (hipStream_t)stream); break;
@@ -148,12 +171,8 @@ int ge2e_loss_fwd_bwd(const float* E, int B, int N, int M, int D, const float* w
                       float eps_cos, float eps, int variant, int impl, float* loss,
                       float* per_emb_loss, float* dE, float* dw, float* db, void* workspace,
                       size_t workspace_bytes, void* stream) {
-    if (!E || !w || !b || !loss) return GE2E_ERR_NULL;
-    if (dE && (!dw || !db)) return GE2E_ERR_NULL;
-    Problem p{};
-    p.E = E; p.w = w; p.b = b; p.loss = loss; p.per = per_emb_loss;
-    p.dE = dE; p.dw = dw; p.db = db; p.cos_out = nullptr;
-    p.B = B; p.N = N; p.M = M; p.D = D; p.variant = variant; p.eps_cos = eps_cos; p.eps = eps;
+    if (!loss_ptrs_ok(E, w, b, loss, dE, dw, db)) return GE2E_ERR_NULL;
+    Problem p = make_problem<Problem>(E, B, N, M, D, w, b, eps_cos, eps, variant, loss, per_emb_loss, dE, dw, db);
     return run(p, impl, workspace, workspace_bytes, stream);
 }
 
@@ -167,17 +186,14 @@ size_t ge2e_workspace_bytes_f64(int B, int N, int M, int D, int variant) {
 int ge2e_loss_fwd_bwd_f64(const double* E, int B, int N, int M, int D, const double* w, const double* b, double eps_cos,
                           double eps, int variant, double* loss, double* per_emb_loss, double* dE, double* dw, double* db,
                           void* workspace, size_t workspace_bytes, void* stream) {
-    if (!E || !w || !b || !loss) return GE2E_ERR_NULL;
-    if (dE && (!dw || !db)) return GE2E_ERR_NULL;
+    if (!loss_ptrs_ok(E, w, b, loss, dE, dw, db)) return GE2E_ERR_NULL;
     if (!shape_ok(B, N, M, D)) return GE2E_ERR_SHAPE;
-    if (variant != GE2E_VARIANT_SOFTMAX && variant != GE2E_VARIANT_CONTRAST) return GE2E_ERR_VARIANT;
+    if (!variant_ok(variant)) return GE2E_ERR_VARIANT;
     if (!workspace || workspace_bytes < f64_workspace_bytes(B, N, M, D) || ((uintptr_t)workspace & 255)) return GE2E_ERR_WORKSPACE;
     if (((uintptr_t)E & 15) || ((uintptr_t)dE & 15)) return GE2E_ERR_ALIGN;
-    ProblemF64 p{};
-    p.E = E; p.w = w; p.b = b; p.loss = loss; p.per = per_emb_loss;
-    p.dE = dE; p.dw = dw; p.db = db; p.ws = (double*)workspace;
-    p.B = B; p.N = N; p.M = M; p.D = D; p.variant = variant; p.eps_cos = eps_cos; p.eps = eps;
-    p.log_eps = eps > 0.0 ? log(eps) : -INFINITY;
+    ProblemF64 p = make_problem<ProblemF64>(E, B, N, M, D, w, b, eps_cos, eps, variant, loss, per_emb_loss, dE, dw, db);
+    p.ws = (double*)workspace;
+    p.log_eps = log_eps_of(eps);
     return (int)launch_f64(p, (hipStream_t)stream);
 }
 
@@ -186,17 +202,13 @@ int ge2e_raw_supported(int N, int M, int D) { return (N >= 1 && M >= 2 && D >= 1
 int ge2e_loss_fwd_bwd_raw(const float* Y, const int* src, int B, int N, int M, int D, const float* w, const float* b,
                           float eps_cos, float eps, int variant, float* loss, float* per_emb_loss, float* dY, float* dw,
                           float* db, void* stream) {
-    if (!Y || !w || !b || !loss) return GE2E_ERR_NULL;
-    if (dY && (!dw || !db)) return GE2E_ERR_NULL;
+    if (!loss_ptrs_ok(Y, w, b, loss, dY, dw, db)) return GE2E_ERR_NULL;
     if (!shape_ok(B, N, M, D)) return GE2E_ERR_SHAPE;
-    if (variant != GE2E_VARIANT_SOFTMAX && variant != GE2E_VARIANT_CONTRAST) return GE2E_ERR_VARIANT;
+    if (!variant_ok(variant)) return GE2E_ERR_VARIANT;
     if (!wave_supports_raw(N, M, D)) return GE2E_ERR_IMPL;
     if (((uintptr_t)Y & 15) || ((uintptr_t)dY & 15)) return GE2E_ERR_ALIGN;
-    Problem p{};
-    p.E = Y; p.w = w; p.b = b; p.loss = loss; p.per = per_emb_loss;
-    p.dE = dY; p.dw = dw; p.db = db; p.cos_out = nullptr;
-    p.B = B; p.N = N; p.M = M; p.D = D; p.variant = variant; p.eps_cos = eps_cos; p.eps = eps;
-    p.log_eps = eps > 0.f ? logf(eps) : -INFINITY;
+    Problem p = make_problem<Problem>(Y, B, N, M, D, w, b, eps_cos, eps, variant, loss, per_emb_loss, dY, dw, db);
+    p.log_eps = log_eps_of(eps);
     p.raw = 1; p.src = src;
     return (int)launch_wave(p, (hipStream_t)stream);
 }
@@ -225,7 +237,7 @@ int ge2e_cos_sim(const float* E, int B, int N, int M, int D, float eps_cos, floa
     if (shape_ok(B, N, M, D) && cos_on_mfma(N, M, D) && workspace && workspace_bytes >= tiled_workspace_bytes(B, N, M, D) &&
         !((uintptr_t)workspace & 255) && !((uintptr_t)E & 15)) {
         p.ws = (float*)workspace;
-        p.log_eps = eps > 0.f ? logf(eps) : -INFINITY;
+        p.log_eps = log_eps_of(eps);
         return (int)launch_tiled_cos(p, (hipStream_t)stream);
     }
     return run(p, GE2E_IMPL_GENERIC, workspace, workspace_bytes, stream);
@@ -243,7 +255,7 @@ int ge2e_calc_loss(const float* sim, int B, int N, int M, float eps, int variant
                    float* per_emb_loss, void* stream) {
     if (!sim || !loss) return GE2E_ERR_NULL;
     if (B < 1 || N < 1 || M < 1) return GE2E_ERR_SHAPE;
-    if (variant != GE2E_VARIANT_SOFTMAX && variant != GE2E_VARIANT_CONTRAST) return GE2E_ERR_VARIANT;
+    if (!variant_ok(variant)) return GE2E_ERR_VARIANT;
     return (int)launch_calc_loss(sim, B, N, N, 0, M, eps, variant, loss, per_emb_loss, (hipStream_t)stream);
 }
 
@@ -282,7 +294,7 @@ int ge2e_calc_loss_bwd(const float* sim, int B, int N, int M, float eps, int var
                        const float* g_per, float* d_sim, void* stream) {
     if (!sim || !d_sim || (!g_loss && !g_per)) return GE2E_ERR_NULL;
     if (B < 1 || N < 1 || M < 1) return GE2E_ERR_SHAPE;
-    if (variant != GE2E_VARIANT_SOFTMAX && variant != GE2E_VARIANT_CONTRAST) return GE2E_ERR_VARIANT;
+    if (!variant_ok(variant)) return GE2E_ERR_VARIANT;
     return (int)launch_calc_loss_bwd(sim, B, N, N, 0, M, eps, variant, g_loss, g_per, d_sim, (hipStream_t)stream);
 }
 
@@ -311,14 +323,14 @@ int ge2e_calc_loss_rows(const float* sim, int B, int n, int N, int j0, int M, fl
                         float* per_emb_loss, void* stream) {
     if (!sim || !loss) return GE2E_ERR_NULL;
     if (!rows_ok(B, n, N, j0, M, 1)) return GE2E_ERR_SHAPE;
-    if (variant != GE2E_VARIANT_SOFTMAX && variant != GE2E_VARIANT_CONTRAST) return GE2E_ERR_VARIANT;
+    if (!variant_ok(variant)) return GE2E_ERR_VARIANT;
     return (int)launch_calc_loss(sim, B, n, N, j0, M, eps, variant, loss, per_emb_loss, (hipStream_t)stream);
 }
 int ge2e_calc_loss_rows_bwd(const float* sim, int B, int n, int N, int j0, int M, float eps, int variant, const float* g_loss,
                             const float* g_per, float* d_sim, void* stream) {
     if (!sim || !d_sim || (!g_loss && !g_per)) return GE2E_ERR_NULL;
     if (!rows_ok(B, n, N, j0, M, 1)) return GE2E_ERR_SHAPE;
-    if (variant != GE2E_VARIANT_SOFTMAX && variant != GE2E_VARIANT_CONTRAST) return GE2E_ERR_VARIANT;
+    if (!variant_ok(variant)) return GE2E_ERR_VARIANT;
     return (int)launch_calc_loss_bwd(sim, B, n, N, j0, M, eps, variant, g_loss, g_per, d_sim, (hipStream_t)stream);
 }
 
@@ -360,12 +372,8 @@ int ge2e_sample_batch(const void* store, int store_is_f64, const long long* spk_
 int ge2e_selftest_team_fallback(const float* E, int B, int N, int M, int D, const float* w, const float* b,
                                 float eps_cos, float eps, int variant, float* loss, float* per_emb_loss, float* dE,
                                 float* dw, float* db, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!E || !w || !b || !loss) return GE2E_ERR_NULL;
-    if (dE && (!dw || !db)) return GE2E_ERR_NULL;
-    Problem p{};
-    p.E = E; p.w = w; p.b = b; p.loss = loss; p.per = per_emb_loss;
-    p.dE = dE; p.dw = dw; p.db = db; p.cos_out = nullptr;
-    p.B = B; p.N = N; p.M = M; p.D = D; p.variant = variant; p.eps_cos = eps_cos; p.eps = eps;
+    if (!loss_ptrs_ok(E, w, b, loss, dE, dw, db)) return GE2E_ERR_NULL;
+    Problem p = make_problem<Problem>(E, B, N, M, D, w, b, eps_cos, eps, variant, loss, per_emb_loss, dE, dw, db);
     p.test_abort = 1;
     return run(p, GE2E_IMPL_TEAM, workspace, workspace_bytes, stream);
 }
@@ -374,12 +382,8 @@ int ge2e_selftest_team_fallback(const float* E, int B, int N, int M, int D, cons
 int ge2e_selftest_team_abort_midgrid(const float* E, int B, int N, int M, int D, const float* w, const float* b,
                                      float eps_cos, float eps, int variant, float* loss, float* per_emb_loss, float* dE,
                                      float* dw, float* db, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!E || !w || !b || !loss) return GE2E_ERR_NULL;
-    if (dE && (!dw || !db)) return GE2E_ERR_NULL;
-    Problem p{};
-    p.E = E; p.w = w; p.b = b; p.loss = loss; p.per = per_emb_loss;
-    p.dE = dE; p.dw = dw; p.db = db; p.cos_out = nullptr;
-    p.B = B; p.N = N; p.M = M; p.D = D; p.variant = variant; p.eps_cos = eps_cos; p.eps = eps;
+    if (!loss_ptrs_ok(E, w, b, loss, dE, dw, db)) return GE2E_ERR_NULL;
+    Problem p = make_problem<Problem>(E, B, N, M, D, w, b, eps_cos, eps, variant, loss, per_emb_loss, dE, dw, db);
     p.test_abort = 2;
     return run(p, GE2E_IMPL_TEAM, workspace, workspace_bytes, stream);
 }
@@ -389,13 +393,9 @@ int ge2e_selftest_team_abort_midgrid(const float* E, int B, int N, int M, int D,
 int ge2e_selftest_team_grid(const float* E, int B, int N, int M, int D, const float* w, const float* b, float eps_cos,
                             float eps, int variant, float* loss, float* per_emb_loss, float* dE, float* dw, float* db,
                             void* workspace, size_t workspace_bytes, void* stream, int max_workgroups) {
-    if (!E || !w || !b || !loss) return GE2E_ERR_NULL;
-    if (dE && (!dw || !db)) return GE2E_ERR_NULL;
+    if (!loss_ptrs_ok(E, w, b, loss, dE, dw, db)) return GE2E_ERR_NULL;
     if (max_workgroups < 64) return GE2E_ERR_SHAPE;
-    Problem p{};
-    p.E = E; p.w = w; p.b = b; p.loss = loss; p.per = per_emb_loss;
-    p.dE = dE; p.dw = dw; p.db = db; p.cos_out = nullptr;
-    p.B = B; p.N = N; p.M = M; p.D = D; p.variant = variant; p.eps_cos = eps_cos; p.eps = eps;
+    Problem p = make_problem<Problem>(E, B, N, M, D, w, b, eps_cos, eps, variant, loss, per_emb_loss, dE, dw, db);
     p.grid_cap = max_workgroups;
     return run(p, GE2E_IMPL_TEAM, workspace, workspace_bytes, stream);
 }

@@ -74,6 +74,14 @@ class _on_device:
         return False
 
 
+def _launch(name: str, dev: torch.device, *args) -> None:
+    """One call into libge2e_hip.so with `dev` current: guard, call, check.  The stream is one of `args`, named at the call
+    site (`_stream_ptr(t)` asks for t's own device, whichever is current)."""
+    with _on_device(dev):
+        code = getattr(_lib.load(), name)(*args)
+    _lib.check(code, name)
+
+
 # Per-(shape, device) workspace sizes and per-(device, stream) workspace tensors of the module path.  The size depends on
 # the device (its CU count), so the query runs with that device current.  A workspace is reused only by launches on the
 # SAME stream, which the stream itself serialises; callers that pass `workspace=` are unaffected.
@@ -85,6 +93,8 @@ class _on_device:
 #    creating streams does not keep a workspace (with a large launch's fall-back slices) per dead stream forever.  A
 #    dropped or outgrown workspace goes back to the caching allocator, which hands a block out again only in the order
 #    of the stream it was allocated on -- the launches still using it are ahead in that very stream.
+#  * The double-precision kernel has its own entries (key tag "f64"): its workspace has no control block, so it is never
+#    shared with the fp32 kernels' workspace, needs no initialisation launch, and no `workspace_override` stands in for it.
 _ws_bytes_cache: dict = {}
 _ws_cache: dict = {}
 _WS_CACHE_MAX = 8
@@ -112,19 +122,31 @@ class workspace_override:
         return False
 
 
-def _workspace_for(lib, dev: torch.device, stream: int, key: tuple) -> torch.Tensor:
+# Per dtype of the embeddings: the loss entry point, its workspace-size query, whether `impl` is an argument of both, the
+# tag of its workspace-cache keys, and whether its workspace starts with the team kernel's control block.
+_LOSS_ABI = {
+    torch.float32: ("ge2e_loss_fwd_bwd", "ge2e_workspace_bytes", True, (), True),
+    torch.float64: ("ge2e_loss_fwd_bwd_f64", "ge2e_workspace_bytes_f64", False, ("f64",), False),
+}
+
+
+def _workspace_for(lib, dev: torch.device, stream: int, dtype: torch.dtype, query: tuple, dev_idx: int) -> torch.Tensor:
+    """The cached workspace of (device, stream) for a launch whose size query takes `query` (shape, variant[, impl])."""
+    _, size_entry, _, tag, has_block = _LOSS_ABI[dtype]
+    key = query + tag + (dev_idx,)
     need = _ws_bytes_cache.get(key)
     if need is None:
-        need = _ws_bytes_cache[key] = int(lib.ge2e_workspace_bytes(*key[:6]))
-    for ws in _ws_override:
-        if ws.device == dev and ws.numel() >= need:
-            return ws
+        need = _ws_bytes_cache[key] = int(getattr(lib, size_entry)(*query))
+    if has_block:
+        for ws in _ws_override:
+            if ws.device == dev and ws.numel() >= need:
+                return ws
     if _capturing is not None and _capturing():
-        return alloc_workspace(need, dev)
-    k = (key[6], stream)
+        return alloc_workspace(need, dev, init=has_block)
+    k = (dev_idx, stream) + tag
     ws = _ws_cache.pop(k, None)                 # re-inserted below: dict order = recency
     if ws is None or ws.numel() < need:
-        ws = alloc_workspace(need, dev)
+        ws = alloc_workspace(need, dev, init=has_block)
         while len(_ws_cache) >= _WS_CACHE_MAX:
             _ws_cache.pop(next(iter(_ws_cache)))
     _ws_cache[k] = ws
@@ -141,15 +163,15 @@ def resolve_impl(B: int, N: int, M: int, D: int, variant: str = "softmax", impl:
     return _lib.IMPL_NAMES[code]
 
 
-def alloc_workspace(nbytes: int, device) -> torch.Tensor:
+def alloc_workspace(nbytes: int, device, init: bool = True) -> torch.Tensor:
     """A workspace tensor with the team kernel's control block written (ge2e_workspace_init: one small launch on the
     current stream, no sync), so that the first call on it already runs the team kernel.  The block is self-cleaning
-    afterwards; an uninitialised workspace would also be safe, its first call would merely take the fall-back."""
+    afterwards; an uninitialised workspace would also be safe, its first call would merely take the fall-back.
+    ``init=False``: the bare tensor, for the kernels whose workspace has no control block."""
     # torch's caching allocator returns >= 512-byte aligned blocks; the library wants 256
     ws = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
-    if ws.is_cuda:
-        with torch.cuda.device(ws.device):
-            _lib.check(_lib.load().ge2e_workspace_init(ws.data_ptr(), ws.numel(), _stream_ptr(ws)), "ge2e_workspace_init")
+    if init and ws.is_cuda:
+        _launch("ge2e_workspace_init", ws.device, ws.data_ptr(), ws.numel(), _stream_ptr(ws))
     return ws
 
 
@@ -195,131 +217,84 @@ def loss_fwd_bwd(embeddings: torch.Tensor, w: torch.Tensor, b: torch.Tensor, *,
     """
     lib = _lib.load()
     _require_cuda(embeddings, "embeddings")
-    if embeddings.dtype == torch.float64:
-        return _loss_fwd_bwd_f64(lib, embeddings, w, b, eps, eps_cos, variant, impl, need_grad, need_per, out, workspace)
-    e4, _ = _as_batched(embeddings)
-    B, N, M, D = e4.shape
-    dev = e4.device
-    _check_scalar_params(w, b, dev)
-    if out is None:
-        f32 = dict(dtype=torch.float32, device=dev)
-        sc = torch.empty(3 if need_grad else 1, B, **f32)  # loss | dw | db in one allocation
-        out = LossOutputs(
-            loss=sc[0],
-            per=torch.empty(B, N, M, **f32) if need_per else None,
-            dE=torch.empty(B, N, M, D, **f32) if need_grad else None,
-            dw=sc[1] if need_grad else None,
-            db=sc[2] if need_grad else None)
-    v, im = _lib.VARIANTS[variant], _lib.IMPLS[impl]
-    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-    with _on_device(dev) as guard:
-        stream = _stream_ptr(e4)
-        if workspace is None:
-            workspace = _workspace_for(lib, dev, stream, (B, N, M, D, v, im, guard.idx))
-        code = lib.ge2e_loss_fwd_bwd(
-            e4.data_ptr(), B, N, M, D, w.data_ptr(), b.data_ptr(), eps_cos, eps, v, im,
-            out.loss.data_ptr(), ptr(out.per), ptr(out.dE), ptr(out.dw), ptr(out.db),
-            workspace.data_ptr(), workspace.numel(), stream)
-    _lib.check(code, "ge2e_loss_fwd_bwd")
-    return out
-
-
-def _workspace_for_f64(lib, dev: torch.device, stream: int, shape: tuple, v: int, dev_idx: int) -> torch.Tensor:
-    """The double-precision kernel's workspace: its own entry of the per-(device, stream) cache (it has no control block,
-    so it is never shared with the fp32 kernels' workspace), from the allocator while the stream is being captured."""
-    key = shape + (v, "f64", dev_idx)
-    need = _ws_bytes_cache.get(key)
-    if need is None:
-        need = _ws_bytes_cache[key] = int(lib.ge2e_workspace_bytes_f64(*shape, v))
-    if _capturing is not None and _capturing():
-        return torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
-    k = (dev_idx, stream, "f64")
-    ws = _ws_cache.pop(k, None)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
-        while len(_ws_cache) >= _WS_CACHE_MAX:
-            _ws_cache.pop(next(iter(_ws_cache)))
-    _ws_cache[k] = ws
-    return ws
-
-
-def _loss_fwd_bwd_f64(lib, embeddings, w, b, eps, eps_cos, variant, impl, need_grad, need_per, out, workspace) -> LossOutputs:
-    if impl != "auto":
+    dtype = torch.float64 if embeddings.dtype == torch.float64 else torch.float32
+    entry, _, takes_impl, _, _ = _LOSS_ABI[dtype]
+    if not takes_impl and impl != "auto":
         raise ValueError(f'impl="{impl}" names a float32 kernel; float64 embeddings have one kernel (impl="auto")')
-    e4, _ = _as_batched(embeddings, torch.float64)
+    e4, _ = _as_batched(embeddings, dtype)
     B, N, M, D = e4.shape
     dev = e4.device
-    _check_scalar_params(w, b, dev, torch.float64)
-    if e4.data_ptr() % 16:         # a contiguous view at an odd storage offset
-        e4 = e4.clone()
-    if out is None:
-        f64 = dict(dtype=torch.float64, device=dev)
-        sc = torch.empty(3 if need_grad else 1, B, **f64)  # loss | dw | db in one allocation
-        out = LossOutputs(
-            loss=sc[0],
-            per=torch.empty(B, N, M, **f64) if need_per else None,
-            dE=torch.empty(B, N, M, D, **f64) if need_grad else None,
-            dw=sc[1] if need_grad else None,
-            db=sc[2] if need_grad else None)
-    else:
-        for name in ("loss", "per", "dE", "dw", "db"):
-            t = getattr(out, name)
+    _check_scalar_params(w, b, dev, dtype)
+    if dtype == torch.float64:     # (float32 leaves both checks to the library: GE2E_ERR_ALIGN)
+        if e4.data_ptr() % 16:     # a contiguous view at an odd storage offset
+            e4 = e4.clone()
+        for name, t in (vars(out).items() if out is not None else ()):
             if t is not None and (t.dtype != torch.float64 or not t.is_contiguous() or t.device != dev):
                 raise TypeError(f"out.{name} must be a contiguous float64 tensor on {dev}")
-    v = _lib.VARIANTS[variant]
+    if out is None:
+        out = _alloc_outputs(B, N, M, D, dtype, dev, need_grad, need_per)
+    query = (B, N, M, D, _lib.VARIANTS[variant]) + ((_lib.IMPLS[impl],) if takes_impl else ())
     ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    # (not through _launch: the guard has to span the stream read and the workspace lookup -- its size query and its
+    # control-block launch want `dev` current, its key wants the stream -- as well as the call)
     with _on_device(dev) as guard:
         stream = _stream_ptr(e4)
         if workspace is None:
-            workspace = _workspace_for_f64(lib, dev, stream, (B, N, M, D), v, guard.idx)
-        code = lib.ge2e_loss_fwd_bwd_f64(
-            e4.data_ptr(), B, N, M, D, w.data_ptr(), b.data_ptr(), eps_cos, eps, v,
+            workspace = _workspace_for(lib, dev, stream, dtype, query, guard.idx)
+        code = getattr(lib, entry)(
+            e4.data_ptr(), B, N, M, D, w.data_ptr(), b.data_ptr(), eps_cos, eps, *query[4:],
             out.loss.data_ptr(), ptr(out.per), ptr(out.dE), ptr(out.dw), ptr(out.db),
             workspace.data_ptr(), workspace.numel(), stream)
-    _lib.check(code, "ge2e_loss_fwd_bwd_f64")
+    _lib.check(code, entry)
     return out
+
+
+def _alloc_outputs(B: int, N: int, M: int, D: int, dtype: torch.dtype, dev: torch.device, need_grad: bool,
+                   need_per: bool) -> LossOutputs:
+    kw = dict(dtype=dtype, device=dev)
+    sc = torch.empty(3 if need_grad else 1, B, **kw)  # loss | dw | db in one allocation
+    return LossOutputs(
+        loss=sc[0],
+        per=torch.empty(B, N, M, **kw) if need_per else None,
+        dE=torch.empty(B, N, M, D, **kw) if need_grad else None,
+        dw=sc[1] if need_grad else None,
+        db=sc[2] if need_grad else None)
 
 
 # ---- the reference's static helpers (s3:33-38, 41-80, 95-112, 114-127), differentiable like the originals ----------
 # Forward AND backward run in libge2e_hip.so; the autograd.Functions below only carry tensors across the C ABI.
 
 def _cos_forward(e4: torch.Tensor, c3: Optional[torch.Tensor], eps: float, eps_cos: float) -> torch.Tensor:
-    lib = _lib.load()
     B, N, M, D = e4.shape
-    cos = torch.empty(B, N, M, N, dtype=torch.float32, device=e4.device)
-    with torch.cuda.device(e4.device):
-        if c3 is not None:
-            code = lib.ge2e_cos_sim_centroids(e4.data_ptr(), c3.data_ptr(), B, N, M, D, eps_cos, eps, cos.data_ptr(),
-                                              _stream_ptr(e4))
-            _lib.check(code, "ge2e_cos_sim_centroids")
-        else:
-            ws = alloc_workspace(lib.ge2e_cos_sim_workspace_bytes(B, N, M, D), e4.device)   # MFMA route where it exists
-            code = lib.ge2e_cos_sim(e4.data_ptr(), B, N, M, D, eps_cos, eps, cos.data_ptr(), ws.data_ptr(), ws.numel(),
-                                    _stream_ptr(e4))
-            _lib.check(code, "ge2e_cos_sim")
+    dev = e4.device
+    cos = torch.empty(B, N, M, N, dtype=torch.float32, device=dev)
+    if c3 is not None:
+        _launch("ge2e_cos_sim_centroids", dev, e4.data_ptr(), c3.data_ptr(), B, N, M, D, eps_cos, eps, cos.data_ptr(),
+                _stream_ptr(e4))
+    else:
+        with _on_device(dev):      # the size query too runs with the tensor's device current
+            ws = alloc_workspace(_lib.load().ge2e_cos_sim_workspace_bytes(B, N, M, D), dev)   # MFMA route where it exists
+        _launch("ge2e_cos_sim", dev, e4.data_ptr(), B, N, M, D, eps_cos, eps, cos.data_ptr(), ws.data_ptr(), ws.numel(),
+                _stream_ptr(e4))
     return cos
 
 
 class _CentroidsFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, e4):
-        lib = _lib.load()
         B, N, M, D = e4.shape
         cent = torch.empty(B, N, D, dtype=torch.float32, device=e4.device)
-        with torch.cuda.device(e4.device):
-            _lib.check(lib.ge2e_centroids(e4.data_ptr(), B, N, M, D, cent.data_ptr(), _stream_ptr(e4)), "ge2e_centroids")
+        _launch("ge2e_centroids", e4.device, e4.data_ptr(), B, N, M, D, cent.data_ptr(), _stream_ptr(e4))
         ctx.shape = (B, N, M, D)
         return cent
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
-        lib = _lib.load()
         B, N, M, D = ctx.shape
         g = g.contiguous().float()
         dE = torch.empty(B, N, M, D, dtype=torch.float32, device=g.device)
-        with torch.cuda.device(g.device):
-            _lib.check(lib.ge2e_centroids_bwd(g.data_ptr(), B, N, M, D, dE.data_ptr(), _stream_ptr(g)), "ge2e_centroids_bwd")
+        _launch("ge2e_centroids_bwd", g.device, g.data_ptr(), B, N, M, D, dE.data_ptr(), _stream_ptr(g))
         return dE
 
 
@@ -328,12 +303,9 @@ class _UttCentroidsFunction(torch.autograd.Function):
 
     @staticmethod
     def _run(x):
-        lib = _lib.load()
         B, N, M, D = x.shape
         out = torch.empty_like(x)
-        with torch.cuda.device(x.device):
-            _lib.check(lib.ge2e_utterance_centroids(x.data_ptr(), B, N, M, D, out.data_ptr(), _stream_ptr(x)),
-                       "ge2e_utterance_centroids")
+        _launch("ge2e_utterance_centroids", x.device, x.data_ptr(), B, N, M, D, out.data_ptr(), _stream_ptr(x))
         return out
 
     @staticmethod
@@ -366,25 +338,19 @@ class _CosSimFunction(torch.autograd.Function):
         dE = torch.empty_like(e4)
         dC = torch.empty_like(c3)
         ws = alloc_workspace(lib.ge2e_cos_sim_bwd_workspace_bytes(B, N, M, D), e4.device)
-        with torch.cuda.device(e4.device):
-            code = lib.ge2e_cos_sim_bwd(e4.data_ptr(), c3.data_ptr(), cos.data_ptr(), g.data_ptr(), B, N, M, D,
-                                        ctx.eps_cos, ctx.eps, dE.data_ptr(), dC.data_ptr(), ws.data_ptr(), ws.numel(),
-                                        _stream_ptr(e4))
-        _lib.check(code, "ge2e_cos_sim_bwd")
+        _launch("ge2e_cos_sim_bwd", e4.device, e4.data_ptr(), c3.data_ptr(), cos.data_ptr(), g.data_ptr(), B, N, M, D,
+                ctx.eps_cos, ctx.eps, dE.data_ptr(), dC.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr(e4))
         return dE, dC, None, None, None
 
 
 class _CalcLossFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, s4, eps, variant):
-        lib = _lib.load()
         B, N, M, _ = s4.shape
         loss = torch.empty(B, dtype=torch.float32, device=s4.device)
         per = torch.empty(B, N, M, dtype=torch.float32, device=s4.device)
-        with torch.cuda.device(s4.device):
-            code = lib.ge2e_calc_loss(s4.data_ptr(), B, N, M, eps, _lib.VARIANTS[variant], loss.data_ptr(), per.data_ptr(),
-                                      _stream_ptr(s4))
-        _lib.check(code, "ge2e_calc_loss")
+        _launch("ge2e_calc_loss", s4.device, s4.data_ptr(), B, N, M, eps, _lib.VARIANTS[variant], loss.data_ptr(),
+                per.data_ptr(), _stream_ptr(s4))
         ctx.save_for_backward(s4)
         ctx.eps, ctx.variant = eps, variant
         return loss, per
@@ -392,17 +358,14 @@ class _CalcLossFunction(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_loss, g_per):
-        lib = _lib.load()
         (s4,) = ctx.saved_tensors
         B, N, M, _ = s4.shape
         gl = g_loss.contiguous().float() if g_loss is not None else None
         gp = g_per.contiguous().float() if g_per is not None else None
         dS = torch.empty_like(s4)
-        with torch.cuda.device(s4.device):
-            code = lib.ge2e_calc_loss_bwd(s4.data_ptr(), B, N, M, ctx.eps, _lib.VARIANTS[ctx.variant],
-                                          gl.data_ptr() if gl is not None else None,
-                                          gp.data_ptr() if gp is not None else None, dS.data_ptr(), _stream_ptr(s4))
-        _lib.check(code, "ge2e_calc_loss_bwd")
+        _launch("ge2e_calc_loss_bwd", s4.device, s4.data_ptr(), B, N, M, ctx.eps, _lib.VARIANTS[ctx.variant],
+                gl.data_ptr() if gl is not None else None, gp.data_ptr() if gp is not None else None, dS.data_ptr(),
+                _stream_ptr(s4))
         return dS, None, None
 
 
@@ -433,14 +396,11 @@ class _CosSimRowsFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, e3, c2, j0, eps, eps_cos):
-        lib = _lib.load()
         n, M, D = e3.shape
         N = c2.shape[0]
         cos = torch.empty(n, M, N, dtype=torch.float32, device=e3.device)
-        with torch.cuda.device(e3.device):
-            code = lib.ge2e_cos_sim_rows(e3.data_ptr(), c2.data_ptr(), 1, n, N, j0, M, D, eps_cos, eps, cos.data_ptr(),
-                                         _stream_ptr(e3))
-        _lib.check(code, "ge2e_cos_sim_rows")
+        _launch("ge2e_cos_sim_rows", e3.device, e3.data_ptr(), c2.data_ptr(), 1, n, N, j0, M, D, eps_cos, eps,
+                cos.data_ptr(), _stream_ptr(e3))
         ctx.save_for_backward(e3, c2, cos)
         ctx.j0, ctx.eps, ctx.eps_cos = j0, eps, eps_cos
         return cos
@@ -454,26 +414,21 @@ class _CosSimRowsFunction(torch.autograd.Function):
         N = c2.shape[0]
         g = g.contiguous().float()
         dE, dC = torch.empty_like(e3), torch.empty_like(c2)
-        ws = torch.empty(max(int(lib.ge2e_cos_sim_rows_bwd_workspace_bytes(1, n, N, M, D)), 256), dtype=torch.uint8, device=e3.device)
-        with torch.cuda.device(e3.device):
-            code = lib.ge2e_cos_sim_rows_bwd(e3.data_ptr(), c2.data_ptr(), cos.data_ptr(), g.data_ptr(), 1, n, N, ctx.j0, M, D,
-                                             ctx.eps_cos, ctx.eps, dE.data_ptr(), dC.data_ptr(), ws.data_ptr(), ws.numel(),
-                                             _stream_ptr(e3))
-        _lib.check(code, "ge2e_cos_sim_rows_bwd")
+        ws = alloc_workspace(lib.ge2e_cos_sim_rows_bwd_workspace_bytes(1, n, N, M, D), e3.device, init=False)
+        _launch("ge2e_cos_sim_rows_bwd", e3.device, e3.data_ptr(), c2.data_ptr(), cos.data_ptr(), g.data_ptr(), 1, n, N,
+                ctx.j0, M, D, ctx.eps_cos, ctx.eps, dE.data_ptr(), dC.data_ptr(), ws.data_ptr(), ws.numel(),
+                _stream_ptr(e3))
         return dE, dC, None, None, None
 
 
 class _CalcLossRowsFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, s3, j0, eps, variant):
-        lib = _lib.load()
         n, M, N = s3.shape
         loss = torch.empty(1, dtype=torch.float32, device=s3.device)
         per = torch.empty(n, M, dtype=torch.float32, device=s3.device)
-        with torch.cuda.device(s3.device):
-            code = lib.ge2e_calc_loss_rows(s3.data_ptr(), 1, n, N, j0, M, eps, _lib.VARIANTS[variant], loss.data_ptr(),
-                                           per.data_ptr(), _stream_ptr(s3))
-        _lib.check(code, "ge2e_calc_loss_rows")
+        _launch("ge2e_calc_loss_rows", s3.device, s3.data_ptr(), 1, n, N, j0, M, eps, _lib.VARIANTS[variant],
+                loss.data_ptr(), per.data_ptr(), _stream_ptr(s3))
         ctx.save_for_backward(s3)
         ctx.j0, ctx.eps, ctx.variant = j0, eps, variant
         return loss[0], per
@@ -481,17 +436,14 @@ class _CalcLossRowsFunction(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_loss, g_per):
-        lib = _lib.load()
         (s3,) = ctx.saved_tensors
         n, M, N = s3.shape
         gl = g_loss.reshape(1).contiguous().float() if g_loss is not None else None
         gp = g_per.contiguous().float() if g_per is not None else None
         dS = torch.empty_like(s3)
-        with torch.cuda.device(s3.device):
-            code = lib.ge2e_calc_loss_rows_bwd(s3.data_ptr(), 1, n, N, ctx.j0, M, ctx.eps, _lib.VARIANTS[ctx.variant],
-                                               gl.data_ptr() if gl is not None else None,
-                                               gp.data_ptr() if gp is not None else None, dS.data_ptr(), _stream_ptr(s3))
-        _lib.check(code, "ge2e_calc_loss_rows_bwd")
+        _launch("ge2e_calc_loss_rows_bwd", s3.device, s3.data_ptr(), 1, n, N, ctx.j0, M, ctx.eps,
+                _lib.VARIANTS[ctx.variant], gl.data_ptr() if gl is not None else None,
+                gp.data_ptr() if gp is not None else None, dS.data_ptr(), _stream_ptr(s3))
         return dS, None, None, None
 
 
@@ -553,31 +505,24 @@ def calc_loss(sim_matrix: torch.Tensor, *, eps: float = SMALL_ERR, variant: str 
 class _NormalizeUnpermFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, y, src, unverified):
-        lib = _lib.load()
         rows, D = y.shape
         e = torch.zeros_like(y) if unverified else torch.empty_like(y)
         ctx.unverified = unverified
         rn = torch.empty(rows, dtype=torch.float32, device=y.device)
-        with torch.cuda.device(y.device):
-            code = lib.ge2e_normalize_unperm(y.data_ptr(), src.data_ptr() if src is not None else None, rows, D,
-                                             e.data_ptr(), rn.data_ptr(), _stream_ptr(y))
-        _lib.check(code, "ge2e_normalize_unperm")
+        _launch("ge2e_normalize_unperm", y.device, y.data_ptr(), src.data_ptr() if src is not None else None, rows, D,
+                e.data_ptr(), rn.data_ptr(), _stream_ptr(y))
         ctx.save_for_backward(e, rn, src)
         return e
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
-        lib = _lib.load()
         e, rn, src = ctx.saved_tensors
         g = g.contiguous().float()
         rows, D = e.shape
         dy = torch.zeros_like(e) if ctx.unverified else torch.empty_like(e)
-        with torch.cuda.device(e.device):
-            code = lib.ge2e_normalize_unperm_bwd(g.data_ptr(), e.data_ptr(), rn.data_ptr(),
-                                                 src.data_ptr() if src is not None else None, rows, D, dy.data_ptr(),
-                                                 _stream_ptr(e))
-        _lib.check(code, "ge2e_normalize_unperm_bwd")
+        _launch("ge2e_normalize_unperm_bwd", e.device, g.data_ptr(), e.data_ptr(), rn.data_ptr(),
+                src.data_ptr() if src is not None else None, rows, D, dy.data_ptr(), _stream_ptr(e))
         return dy, None, None
 
 
@@ -638,19 +583,14 @@ class _GE2ELossRawFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, y, src, w, b, N, M, eps, eps_cos, variant, unverified=False):
-        lib = _lib.load()
         rows, D = y.shape
-        dev = y.device
         need = any(ctx.needs_input_grad[i] for i in (0, 2, 3))
-        f32 = dict(dtype=torch.float32, device=dev)
-        sc = torch.empty(3, **f32)                                   # loss | dw | db
+        sc = torch.empty(3, dtype=torch.float32, device=y.device)    # loss | dw | db
         dY = (torch.zeros_like(y) if unverified else torch.empty_like(y)) if need else None
-        with _on_device(dev):
-            code = lib.ge2e_loss_fwd_bwd_raw(
+        _launch("ge2e_loss_fwd_bwd_raw", y.device,
                 y.data_ptr(), src.data_ptr() if src is not None else None, 1, N, M, D, w.data_ptr(), b.data_ptr(),
                 eps_cos, eps, _lib.VARIANTS[variant], sc.data_ptr(), None, dY.data_ptr() if need else None,
                 sc.data_ptr() + 4 if need else None, sc.data_ptr() + 8 if need else None, _stream_ptr(y))
-        _lib.check(code, "ge2e_loss_fwd_bwd_raw")
         ctx.w_shape, ctx.b_shape = w.shape, b.shape
         if need:
             ctx.save_for_backward(dY, sc)
@@ -660,21 +600,9 @@ class _GE2ELossRawFunction(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_out):
         dY, sc = ctx.saved_tensors
-        g = grad_out
-        if g.dtype != torch.float32 or not g.is_contiguous():
-            g = g.to(torch.float32).contiguous()
         rows, D = dY.shape
-        need_y, need_w, need_b = (ctx.needs_input_grad[i] for i in (0, 2, 3))
-        gY = torch.empty_like(dY) if need_y else None
-        gwb = torch.empty(2, dtype=torch.float32, device=dY.device) if (need_w or need_b) else None
-        with _on_device(dY.device):
-            code = _lib.load().ge2e_scale_grads(
-                dY.data_ptr(), sc.data_ptr() + 4, sc.data_ptr() + 8, g.data_ptr(), 1, 1, rows, 1, D,
-                gY.data_ptr() if need_y else None, gwb.data_ptr() if need_w else None,
-                gwb.data_ptr() + 4 if need_b else None, _stream_ptr(dY))
-        _lib.check(code, "ge2e_scale_grads")
-        gw = (gwb[0] if len(ctx.w_shape) == 0 else gwb[0].reshape(ctx.w_shape)) if need_w else None
-        gb = (gwb[1] if len(ctx.b_shape) == 0 else gwb[1].reshape(ctx.b_shape)) if need_b else None
+        gY, gw, gb = _scale_grads(dY, sc.data_ptr() + 4, sc.data_ptr() + 8, grad_out, 1, (1, rows, 1, D),
+                                  [ctx.needs_input_grad[i] for i in (0, 2, 3)], ctx.w_shape, ctx.b_shape)
         return gY, None, gw, gb, None, None, None, None, None, None
 
 
@@ -718,51 +646,57 @@ def eer_counts(sim_matrix: torch.Tensor, thresholds) -> torch.Tensor:
     B, N, M, _ = s.shape
     T = thr.numel()
     counts = torch.empty(B, T, 2, dtype=torch.int32, device=s.device)
-    lib = _lib.load()
-    with torch.cuda.device(s.device):
-        code = lib.ge2e_eer_counts(s.data_ptr(), B, N, M, thr.data_ptr(), T, counts.data_ptr(), _stream_ptr(s))
-    _lib.check(code, "ge2e_eer_counts")
+    _launch("ge2e_eer_counts", s.device, s.data_ptr(), B, N, M, thr.data_ptr(), T, counts.data_ptr(), _stream_ptr(s))
     return counts[0] if squeeze else counts
+
+
+def _scale_grads(dE, dw_ptr: int, db_ptr: int, g, g_count: int, dims: tuple, needs, w_shape, b_shape):
+    """The backward of every fp32 loss node, one launch: gE = g dE, gw = sum g dw, gb = sum g db (no host sync; out of place,
+    so a retained graph may run again).  ``dE`` and the device scalars at ``dw_ptr`` / ``db_ptr`` are what the forward
+    launch left; ``g`` is the incoming gradient, ``g_count`` (1 or B) values; ``dims`` = (B, N, M, D); ``needs`` says
+    which of (gE, gw, gb) to produce, the others are None.  gw / gb come back in the parameters' own shapes."""
+    if g.dtype != torch.float32 or not g.is_contiguous():
+        g = g.to(torch.float32).contiguous()
+    need_e, need_w, need_b = needs
+    gE = torch.empty_like(dE) if need_e else None
+    gwb = torch.empty(2, dtype=torch.float32, device=dE.device) if (need_w or need_b) else None
+    _launch("ge2e_scale_grads", dE.device, dE.data_ptr(), dw_ptr, db_ptr, g.data_ptr(), g_count, *dims,
+            gE.data_ptr() if need_e else None, gwb.data_ptr() if need_w else None,
+            gwb.data_ptr() + 4 if need_b else None, _stream_ptr(dE))
+    gw = (gwb[0] if len(w_shape) == 0 else gwb[0].reshape(w_shape)) if need_w else None
+    gb = (gwb[1] if len(b_shape) == 0 else gwb[1].reshape(b_shape)) if need_b else None
+    return gE, gw, gb
+
+
+def _loss_node_forward(ctx, embeddings, w, b, eps, eps_cos, variant, impl):
+    """forward of both loss nodes (the launch follows the embeddings' dtype): one fused kernel launch that also produces
+    dE, dw, db, kept for the backward."""
+    need = any(ctx.needs_input_grad[:3])
+    squeeze = embeddings.dim() == 3
+    # (no .detach(): inside Function.forward nothing is recorded, and only the data pointers cross the boundary)
+    o = loss_fwd_bwd(embeddings, w, b, eps=eps, eps_cos=eps_cos, variant=variant, impl=impl, need_grad=need)
+    ctx.squeeze = squeeze
+    ctx.w_shape, ctx.b_shape = w.shape, b.shape
+    if need:
+        ctx.save_for_backward(o.dE, o.dw, o.db)
+    return o.loss[0] if squeeze else o.loss
 
 
 class _GE2ELossFunction(torch.autograd.Function):
     """forward = one fused kernel launch that also produces dE, dw, db;
     backward only scales them by the incoming gradient (no host sync)."""
 
-    @staticmethod
-    def forward(ctx, embeddings, w, b, eps, eps_cos, variant, impl):
-        need = any(ctx.needs_input_grad[:3])
-        squeeze = embeddings.dim() == 3
-        # (no .detach(): inside Function.forward nothing is recorded, and only the data pointers cross the boundary)
-        o = loss_fwd_bwd(embeddings, w, b, eps=eps, eps_cos=eps_cos, variant=variant, impl=impl, need_grad=need)
-        ctx.squeeze = squeeze
-        ctx.w_shape, ctx.b_shape = w.shape, b.shape
-        if need:
-            ctx.save_for_backward(o.dE, o.dw, o.db)
-        return o.loss[0] if squeeze else o.loss
+    forward = staticmethod(_loss_node_forward)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_out):
         dE, dw, db = ctx.saved_tensors
-        g = grad_out                                             # 0-dim or (B,)
-        if g.dtype != torch.float32 or not g.is_contiguous():
-            g = g.to(torch.float32).contiguous()
-        B, N, M, D = dE.shape
-        need_e, need_w, need_b = ctx.needs_input_grad[:3]
-        # one launch: gE = g dE, gw = sum g dw, gb = sum g db (no host sync; out of place, so a retained graph may run again)
-        gE = torch.empty_like(dE) if need_e else None
-        gwb = torch.empty(2, dtype=torch.float32, device=dE.device) if (need_w or need_b) else None
-        with _on_device(dE.device):
-            code = _lib.load().ge2e_scale_grads(
-                dE.data_ptr(), dw.data_ptr(), db.data_ptr(), g.data_ptr(), g.numel(), B, N, M, D,
-                gE.data_ptr() if need_e else None, gwb.data_ptr() if need_w else None,
-                gwb.data_ptr() + 4 if need_b else None, _stream_ptr(dE))
-        _lib.check(code, "ge2e_scale_grads")
-        if need_e and ctx.squeeze:
+        # grad_out: 0-dim or (B,)
+        gE, gw, gb = _scale_grads(dE, dw.data_ptr(), db.data_ptr(), grad_out, grad_out.numel(), dE.shape,
+                                  ctx.needs_input_grad[:3], ctx.w_shape, ctx.b_shape)
+        if gE is not None and ctx.squeeze:
             gE = gE[0]
-        gw = (gwb[0] if len(ctx.w_shape) == 0 else gwb[0].reshape(ctx.w_shape)) if need_w else None
-        gb = (gwb[1] if len(ctx.b_shape) == 0 else gwb[1].reshape(ctx.b_shape)) if need_b else None
         return gE, gw, gb, None, None, None, None
 
 
@@ -770,16 +704,7 @@ class _GE2ELossF64Function(torch.autograd.Function):
     """The same node over ge2e_loss_fwd_bwd_f64: float64 embeddings, w, b in, float64 loss and gradients out.  The
     upstream gradient is applied in float64 (a handful of elementwise torch ops on the launch's own dE / dw / db)."""
 
-    @staticmethod
-    def forward(ctx, embeddings, w, b, eps, eps_cos, variant):
-        need = any(ctx.needs_input_grad[:3])
-        squeeze = embeddings.dim() == 3
-        o = loss_fwd_bwd(embeddings, w, b, eps=eps, eps_cos=eps_cos, variant=variant, need_grad=need)
-        ctx.squeeze = squeeze
-        ctx.w_shape, ctx.b_shape = w.shape, b.shape
-        if need:
-            ctx.save_for_backward(o.dE, o.dw, o.db)
-        return o.loss[0] if squeeze else o.loss
+    forward = staticmethod(_loss_node_forward)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
@@ -796,7 +721,7 @@ class _GE2ELossF64Function(torch.autograd.Function):
             gw = (dw * g).sum().reshape(ctx.w_shape)
         if need_b:
             gb = (db * g).sum().reshape(ctx.b_shape)
-        return gE, gw, gb, None, None, None
+        return gE, gw, gb, None, None, None, None
 
 
 # The autograd node in C++ (libge2e_torch.so,csrc_torch/ge2e_autograd.cpp: torch.ops.ge2e_amd.loss): the same two C-ABI
@@ -854,7 +779,7 @@ def ge2e_loss(embeddings: torch.Tensor, w: torch.Tensor, b: torch.Tensor, *, eps
     # (The static helpers -- cos_sim, calc_loss, centroids, ... -- compute in fp32 whatever they are given.)
     if in_dtype == torch.float64 and impl == "auto":
         return _GE2ELossF64Function.apply(embeddings, w.to(torch.float64), b.to(torch.float64), float(eps),
-                                          float(eps_cos), variant)
+                                          float(eps_cos), variant, impl)
     if in_dtype != torch.float32:
         embeddings = embeddings.float()
     op = None if _ws_override else _cpp_loss_op()         # (a caller-owned workspace -- a graph capture -- goes through Python)

@@ -34,6 +34,23 @@ def _check_replay(graph, outs, refs, what: str) -> None:
             raise RuntimeError(f"{what}: the captured graph does not reproduce the warm-up launch (nothing was captured?)")
 
 
+def _capture_launch(launch, outs, dev: torch.device, warmup: int, what: str) -> torch.cuda.CUDAGraph:
+    """One capture-safe ``launch()`` that writes the static tensors ``outs``, as a graph: torch's capture recipe (warm up on
+    a side stream, then capture on that stream), checked by a replay against the last warm-up launch."""
+    side = torch.cuda.Stream(device=dev)
+    side.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(side):
+        for _ in range(max(1, warmup)):
+            launch()
+        refs = [o.clone() for o in outs]
+    torch.cuda.current_stream(dev).wait_stream(side)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, stream=side):
+        launch()
+    _check_replay(graph, outs, refs, what)
+    return graph
+
+
 class GraphedLossStep:
     """``step = GraphedLossStep(loss_module, (N, M, D))``; then per training step::
 
@@ -98,17 +115,7 @@ class GraphedLossStep:
         def launch():
             GF.loss_fwd_bwd(e4, w, b, eps=eps, variant=m.variant, impl=m.impl, out=out, workspace=self.workspace)
 
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            for _ in range(max(1, warmup)):
-                launch()
-            ref = (out.loss.clone(), out.dE.clone())
-        torch.cuda.current_stream(dev).wait_stream(side)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph, stream=side):
-            launch()
-        _check_replay(self.graph, (out.loss, out.dE), ref, "GraphedLossStep(direct=True)")
+        self.graph = _capture_launch(launch, (out.loss, out.dE), dev, warmup, "GraphedLossStep(direct=True)")
         self.loss = out.loss[0]
         self.input_grad = out.dE[0]
         self.input.grad = self.input_grad
@@ -162,17 +169,7 @@ class StaticLossStep:
         def launch():
             GF.loss_fwd_bwd(self.e4, w, b, eps=eps, variant=m.variant, impl=m.impl, out=self.out, workspace=self.workspace)
 
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            for _ in range(max(1, warmup)):
-                launch()
-            ref = (self.sc.clone(), self.dE.clone())
-        torch.cuda.current_stream(dev).wait_stream(side)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph, stream=side):
-            launch()
-        _check_replay(self.graph, (self.sc, self.dE), ref, "GE2ELoss(graph=True)")
+        self.graph = _capture_launch(launch, (self.sc, self.dE), dev, warmup, "GE2ELoss(graph=True)")
 
     @staticmethod
     def key_of(m, shape):

@@ -54,23 +54,10 @@ class _GraphedLossFunction(torch.autograd.Function):
         if ctx.serial != step.serial:
             raise RuntimeError("GE2ELoss(graph=True): this loss belongs to an earlier forward; its static gradient buffers "
                                "have been overwritten by a later call (use graph=False to keep several losses alive)")
-        from . import _lib
-        g = grad_out
-        if g.dtype != torch.float32 or not g.is_contiguous():
-            g = g.to(torch.float32).contiguous()
         n, m, d = step.shape
-        need_e, need_w, need_b = ctx.needs_input_grad[:3]
-        gE = torch.empty_like(step.dE3) if need_e else None
-        gwb = torch.empty(2, dtype=torch.float32, device=g.device) if (need_w or need_b) else None
         o = step.out
-        with torch.cuda.device(g.device):
-            code = _lib.load().ge2e_scale_grads(
-                o.dE.data_ptr(), o.dw.data_ptr(), o.db.data_ptr(), g.data_ptr(), 1, 1, n, m, d,
-                gE.data_ptr() if need_e else None, gwb.data_ptr() if need_w else None,
-                gwb.data_ptr() + 4 if need_b else None, GF._stream_ptr(g))
-        _lib.check(code, "ge2e_scale_grads")
-        return (gE, gwb[0].reshape(step.dw0.shape) if need_w else None, gwb[1].reshape(step.db0.shape) if need_b else None,
-                None)
+        return GF._scale_grads(step.dE3, o.dw.data_ptr(), o.db.data_ptr(), grad_out, 1, (1, n, m, d),
+                               ctx.needs_input_grad[:3], step.dw0.shape, step.db0.shape) + (None,)
 
 
 def _has_hooks(t) -> bool:

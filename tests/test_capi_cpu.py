@@ -61,6 +61,56 @@ def test_argument_validation_returns_codes_without_gpu(lib):
     assert lib.ge2e_calc_loss(None, 1, 4, 5, 1e-6, 0, None, None, None) == -1
 
 
+# The order of the host checks is part of the ABI (callers tell a bad shape from a missing workspace by the code): for every
+# ADJACENT pair of checks of an entry point, one call that violates both must return the earlier one's code.  Pointers are
+# fake integers; every call fails a check, so nothing is launched.
+_LOSS_ARGS = ("E", "B", "N", "M", "D", "w", "b", "eps_cos", "eps", "variant", "loss", "per", "dE", "dw", "db")
+_ORDER_OK = dict(E=16, src=None, B=1, N=4, M=5, D=64, w=16, b=16, eps_cos=1e-8, eps=1e-6, variant=0, loss=16, per=None,
+                 dE=None, dw=None, db=None, ws=256, ws_bytes=1 << 40, stream=None, max_workgroups=64)
+_ORDER_ARGS = {
+    "ge2e_loss_fwd_bwd_f64": _LOSS_ARGS + ("ws", "ws_bytes", "stream"),
+    "ge2e_loss_fwd_bwd_raw": ("E", "src") + _LOSS_ARGS[1:] + ("stream",),
+    "ge2e_selftest_team_fallback": _LOSS_ARGS + ("ws", "ws_bytes", "stream"),
+    "ge2e_selftest_team_grid": _LOSS_ARGS + ("ws", "ws_bytes", "stream", "max_workgroups"),
+}
+_NULL, _SHAPE, _WORKSPACE, _VARIANT, _IMPL, _ALIGN = -1, -2, -3, -4, -5, -6
+_BAD = {_NULL: dict(E=None), _SHAPE: dict(M=1), _VARIANT: dict(variant=7), _WORKSPACE: dict(ws=None, ws_bytes=0),
+        _ALIGN: dict(E=24),
+        _IMPL: dict(N=64, M=10, D=512)}     # no one-wave raw shape (N = 64) and none of the team kernel (D > 256)
+_ORDERS = {
+    "ge2e_loss_fwd_bwd_f64": (_NULL, _SHAPE, _VARIANT, _WORKSPACE, _ALIGN),
+    "ge2e_loss_fwd_bwd_raw": (_NULL, _SHAPE, _VARIANT, _IMPL, _ALIGN),
+    "ge2e_selftest_team_fallback": (_NULL, _SHAPE, _VARIANT, _IMPL, _WORKSPACE, _ALIGN),
+    "ge2e_selftest_team_grid": (_NULL, _SHAPE, _VARIANT, _IMPL, _WORKSPACE, _ALIGN),
+}
+_ORDER_CASES = [(entry, dict(_BAD[first], **_BAD[second]), first)
+                for entry, order in _ORDERS.items() for first, second in zip(order, order[1:])]
+# ge2e_selftest_team_grid: its own SHAPE check (max_workgroups < 64) sits between NULL and the common sequence
+_ORDER_CASES += [("ge2e_selftest_team_grid", dict(E=None, max_workgroups=8), _NULL),
+                 ("ge2e_selftest_team_grid", dict(max_workgroups=8, variant=7), _SHAPE),
+                 ("ge2e_selftest_team_grid", dict(max_workgroups=8, ws=None, ws_bytes=0), _SHAPE)]
+# the second half of the NULL rule (dE without dw / db) is NULL too, ahead of everything else
+_ORDER_CASES += [(entry, dict(dE=32, M=1), _NULL) for entry in _ORDERS]
+
+
+@pytest.mark.parametrize("entry, violate, expect", _ORDER_CASES,
+                         ids=[f"{e[5:]}-{'+'.join(sorted(v))}" for e, v, _ in _ORDER_CASES])
+def test_checks_come_in_the_documented_order(lib, entry, violate, expect):
+    def call(**kw):
+        a = dict(_ORDER_OK, **kw)
+        return getattr(lib, entry)(*[a[k] for k in _ORDER_ARGS[entry]])
+
+    # each violation alone draws its own code (so the pair really violates two checks) ...
+    assert lib.ge2e_raw_supported(4, 5, 64) == 1 and lib.ge2e_raw_supported(64, 10, 512) == 0
+    assert lib.ge2e_resolve_impl(1, 4, 5, 64, 0, _lib.IMPLS["team"]) == _lib.IMPLS["team"]
+    assert lib.ge2e_resolve_impl(1, 64, 10, 512, 0, _lib.IMPLS["team"]) == _IMPL
+    for code, bad in _BAD.items():
+        if code in _ORDERS[entry] and all(violate.get(k, 0) == v for k, v in bad.items()):
+            assert call(**bad) == code, (entry, bad)
+    # ... and together the earlier check answers
+    assert call(**violate) == expect, (entry, violate)
+
+
 def test_workspace_and_impl_queries(lib):
     assert lib.ge2e_workspace_bytes(1, 4, 1, 8, 0, 0) == 0  # bad shape -> 0
     assert lib.ge2e_workspace_bytes(1, 64, 10, 256, 0, 1) > 64 * 256 * 4
