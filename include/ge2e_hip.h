@@ -120,6 +120,27 @@ int ge2e_loss_fwd_bwd_f64(const double* E, int B, int N, int M, int D,
                           void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * The RAGGED loss: every speaker has its own utterance count.  E [B][R][D] holds the rows of speaker j of batch bi
+ * contiguously at offsets[bi][j] .. offsets[bi][j+1]-1; offsets [B][N+1] is int32 ON THE DEVICE.  The B batches share N
+ * and R (a fixed row budget) and differ in their offsets.  Semantics: ge2e_loss_fwd_bwd's with M replaced by
+ * m_j = offsets[j+1] - offsets[j] wherever it appears (centroid = mean of the speaker's m_j rows, leave-one-out centroid
+ * = (sum_j - e_r) / (m_j - 1)); with all counts equal to M it is that loss.  per_row_loss [B][R] or NULL, dE [B][R][D] or
+ * NULL for forward only.  fp32, exact (contractions on v_mfma_f32_16x16x4_f32), any N >= 1, D >= 1, R >= 2 N, both
+ * variants; one kernel, no implementation choice; deterministic.  The workspace is this entry point's own
+ * (ge2e_workspace_bytes_ragged, 256-byte aligned, no control block, no initialisation).  Same error codes, checked on
+ * the host before anything is launched: GE2E_ERR_SHAPE for B, N, D < 1 or R < 2 N.
+ * THE CALLER GUARANTEES THE OFFSETS' CONTENTS -- offsets[0] = 0, offsets[N] = R, every step >= 2 -- which cannot be
+ * checked here without a synchronisation.  The kernel clamps every offset it reads into [0, R]: a table that breaks the
+ * contract yields wrong or non-finite numbers, never an access outside the buffers (a step of 1 divides by zero, like
+ * M = 1 in the reference).
+ */
+size_t ge2e_workspace_bytes_ragged(int B, int N, int R, int D, int variant);      /* 0 for a bad shape */
+int ge2e_loss_fwd_bwd_ragged(const float* E, const int* offsets, int B, int N, int R, int D,
+                             const float* w, const float* b, float eps_cos, float eps, int variant,
+                             float* loss, float* per_row_loss, float* dE, float* dw, float* db,
+                             void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * The same, fed with the encoder's RAW output (s2_model_GE2E_loss_speach_embed.py:34 +
  * s4_train_embed_model.py:186-192 folded into the loss kernel's load and store stages):
  *   Y   [B][N*M][D]  the encoder's projection BEFORE its L2-normalisation, rows in the encoder's own (permuted) order

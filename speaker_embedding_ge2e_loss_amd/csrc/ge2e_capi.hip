@@ -8,6 +8,7 @@
 #include "ge2e_common.hpp"
 #include "ge2e_generic.hpp"
 #include "ge2e_f64.hpp"
+#include "ge2e_ragged.hpp"
 #include "ge2e_helpers.hpp"
 #include "ge2e_fused.hpp"
 #include "ge2e_selftest.hpp"
@@ -26,6 +27,9 @@ unsigned long long* g_prof = nullptr;  // diagnostic build only
 
 bool shape_ok(int B, int N, int M, int D) { return B >= 1 && N >= 1 && M >= 2 && D >= 1; }
 
+// The ragged entry point's shape: R rows shared by N speakers of at least two rows each.
+bool ragged_shape_ok(int B, int N, int R, int D) { return B >= 1 && N >= 1 && D >= 1 && (long long)R >= 2LL * N; }
+
 bool variant_ok(int v) { return v == GE2E_VARIANT_SOFTMAX || v == GE2E_VARIANT_CONTRAST; }
 
 // The NULL rule of every loss entry point: inputs and the loss always, and whoever asks for dE takes dw and db with it.
@@ -37,15 +41,25 @@ bool loss_ptrs_ok(const void* E, const void* w, const void* b, const void* loss,
 template <class T>
 T log_eps_of(T eps) { return eps > T(0) ? std::log(eps) : T(-INFINITY); }   // std::log(float) is logf
 
-// The launch description of a loss entry point's argument list (P = Problem with T = float, ProblemF64 with T = double).
-// Everything else starts as zero: no cos_out, no grid cap, no test abort, not raw; ws and log_eps are the caller's.
+// The launch description of a loss entry point's argument list (P = Problem with T = float, ProblemF64 with T = double,
+// ProblemRagged with T = float), without its shape.  Everything else starts as zero: no cos_out, no grid cap, no test
+// abort, not raw; ws and log_eps are the caller's.
 template <class P, class T>
-P make_problem(const T* E, int B, int N, int M, int D, const T* w, const T* b, T eps_cos, T eps, int variant, T* loss,
-               T* per_emb_loss, T* dE, T* dw, T* db) {
+P make_problem_io(const T* E, const T* w, const T* b, T eps_cos, T eps, int variant, T* loss, T* per_emb_loss, T* dE, T* dw,
+                  T* db) {
     P p{};
     p.E = E; p.w = w; p.b = b; p.loss = loss; p.per = per_emb_loss;
     p.dE = dE; p.dw = dw; p.db = db;
-    p.B = B; p.N = N; p.M = M; p.D = D; p.variant = variant; p.eps_cos = eps_cos; p.eps = eps;
+    p.variant = variant; p.eps_cos = eps_cos; p.eps = eps;
+    return p;
+}
+
+// ... and with the dense (B, N, M, D) shape.
+template <class P, class T>
+P make_problem(const T* E, int B, int N, int M, int D, const T* w, const T* b, T eps_cos, T eps, int variant, T* loss,
+               T* per_emb_loss, T* dE, T* dw, T* db) {
+    P p = make_problem_io<P>(E, w, b, eps_cos, eps, variant, loss, per_emb_loss, dE, dw, db);
+    p.B = B; p.N = N; p.M = M; p.D = D;
     return p;
 }
 
@@ -195,6 +209,30 @@ int ge2e_loss_fwd_bwd_f64(const double* E, int B, int N, int M, int D, const dou
     p.ws = (double*)workspace;
     p.log_eps = log_eps_of(eps);
     return (int)launch_f64(p, (hipStream_t)stream);
+}
+
+// The ragged loss (every speaker its own utterance count): a kernel of its own (ge2e_ragged.hip) on a workspace of its own,
+// like the double-precision one.  Same checks, in the same order.  What the offsets HOLD is the caller's word: reading
+// them here would take a synchronisation; the kernel clamps them, so a broken table cannot reach outside the buffers.
+size_t ge2e_workspace_bytes_ragged(int B, int N, int R, int D, int variant) {
+    (void)variant;
+    return ragged_shape_ok(B, N, R, D) ? ragged_workspace_bytes(B, N, R, D) : 0;
+}
+
+int ge2e_loss_fwd_bwd_ragged(const float* E, const int* offsets, int B, int N, int R, int D, const float* w, const float* b,
+                             float eps_cos, float eps, int variant, float* loss, float* per_row_loss, float* dE, float* dw,
+                             float* db, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!offsets || !loss_ptrs_ok(E, w, b, loss, dE, dw, db)) return GE2E_ERR_NULL;
+    if (!ragged_shape_ok(B, N, R, D)) return GE2E_ERR_SHAPE;
+    if (!variant_ok(variant)) return GE2E_ERR_VARIANT;
+    if (!workspace || workspace_bytes < ragged_workspace_bytes(B, N, R, D) || ((uintptr_t)workspace & 255)) return GE2E_ERR_WORKSPACE;
+    if (((uintptr_t)E & 15) || ((uintptr_t)dE & 15)) return GE2E_ERR_ALIGN;
+    ProblemRagged p = make_problem_io<ProblemRagged>(E, w, b, eps_cos, eps, variant, loss, per_row_loss, dE, dw, db);
+    p.off = offsets;
+    p.B = B; p.N = N; p.R = R; p.D = D;
+    p.ws = (float*)workspace;
+    p.log_eps = log_eps_of(eps);
+    return (int)launch_ragged(p, (hipStream_t)stream);
 }
 
 int ge2e_raw_supported(int N, int M, int D) { return (N >= 1 && M >= 2 && D >= 1 && wave_supports_raw(N, M, D)) ? 1 : 0; }

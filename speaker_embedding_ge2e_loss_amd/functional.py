@@ -93,8 +93,9 @@ def _launch(name: str, dev: torch.device, *args) -> None:
 #    creating streams does not keep a workspace (with a large launch's fall-back slices) per dead stream forever.  A
 #    dropped or outgrown workspace goes back to the caching allocator, which hands a block out again only in the order
 #    of the stream it was allocated on -- the launches still using it are ahead in that very stream.
-#  * The double-precision kernel has its own entries (key tag "f64"): its workspace has no control block, so it is never
-#    shared with the fp32 kernels' workspace, needs no initialisation launch, and no `workspace_override` stands in for it.
+#  * The double-precision kernel and the ragged kernel have their own entries (key tags "f64", "ragged"): their
+#    workspaces have no control block, so they are never shared with the fp32 kernels' workspace, need no initialisation
+#    launch, and no `workspace_override` stands in for them.
 _ws_bytes_cache: dict = {}
 _ws_cache: dict = {}
 _WS_CACHE_MAX = 8
@@ -122,16 +123,19 @@ class workspace_override:
         return False
 
 
-# Per dtype of the embeddings: the loss entry point, its workspace-size query, whether `impl` is an argument of both, the
-# tag of its workspace-cache keys, and whether its workspace starts with the team kernel's control block.
+# Per dtype of the embeddings (and "ragged": fp32 rows with per-speaker counts): the loss entry point, its workspace-size
+# query, whether `impl` is an argument of both, the tag of its workspace-cache keys, and whether its workspace starts with
+# the team kernel's control block.
 _LOSS_ABI = {
     torch.float32: ("ge2e_loss_fwd_bwd", "ge2e_workspace_bytes", True, (), True),
     torch.float64: ("ge2e_loss_fwd_bwd_f64", "ge2e_workspace_bytes_f64", False, ("f64",), False),
+    "ragged": ("ge2e_loss_fwd_bwd_ragged", "ge2e_workspace_bytes_ragged", False, ("ragged",), False),
 }
 
 
-def _workspace_for(lib, dev: torch.device, stream: int, dtype: torch.dtype, query: tuple, dev_idx: int) -> torch.Tensor:
-    """The cached workspace of (device, stream) for a launch whose size query takes `query` (shape, variant[, impl])."""
+def _workspace_for(lib, dev: torch.device, stream: int, dtype, query: tuple, dev_idx: int) -> torch.Tensor:
+    """The cached workspace of (device, stream) for a launch whose size query takes `query` (shape, variant[, impl]);
+    `dtype` is the launch's key of _LOSS_ABI."""
     _, size_entry, _, tag, has_block = _LOSS_ABI[dtype]
     key = query + tag + (dev_idx,)
     need = _ws_bytes_cache.get(key)
@@ -259,6 +263,116 @@ def _alloc_outputs(B: int, N: int, M: int, D: int, dtype: torch.dtype, dev: torc
         dE=torch.empty(B, N, M, D, **kw) if need_grad else None,
         dw=sc[1] if need_grad else None,
         db=sc[2] if need_grad else None)
+
+
+# ---- the ragged loss: every speaker its own utterance count (ge2e_loss_fwd_bwd_ragged, csrc/ge2e_ragged.hip) ---------------
+
+def ragged_offsets(counts, rows: int) -> torch.Tensor:
+    """Utterance counts -> the row offsets ge2e_loss_fwd_bwd_ragged reads: a CPU int32 tensor (N+1,) for counts (N,), or
+    (B, N+1) for (B, N), with offsets[..., 0] = 0 and offsets[..., N] = rows.  ``counts`` is a sequence or an integer CPU
+    tensor.  Raises ValueError when a count is < 2 (a speaker with one utterance has no leave-one-out centroid: the
+    reference divides by M - 1 = 0, s3:110-111), when a row of counts does not sum to ``rows``, or when there is no
+    speaker.  Needs no GPU."""
+    c = counts if torch.is_tensor(counts) else torch.as_tensor(counts)
+    if c.dim() not in (1, 2) or c.shape[-1] < 1 or c.numel() < 1:
+        raise ValueError(f"counts must be (N,) or (B, N) with N >= 1, got shape {tuple(c.shape)}")
+    if c.is_cuda:
+        raise TypeError("counts must live on the host (a device tensor is taken as offsets, and only as torch.int32)")
+    if c.is_floating_point() or c.is_complex() or c.dtype == torch.bool:
+        raise TypeError(f"counts must be integers, got {c.dtype}")
+    c = c.to(torch.int64)
+    if bool((c < 2).any()):
+        raise ValueError("every speaker needs at least 2 utterances (the leave-one-out centroid divides by count - 1)")
+    if bool((c.sum(dim=-1) != int(rows)).any()):
+        raise ValueError(f"counts must sum to the number of rows ({int(rows)}), got {c.sum(dim=-1).tolist()}")
+    if int(rows) >= 2 ** 31:
+        raise ValueError("offsets are int32: fewer than 2^31 rows per batch")
+    off = torch.zeros(c.shape[:-1] + (c.shape[-1] + 1,), dtype=torch.int32)
+    off[..., 1:] = torch.cumsum(c, dim=-1)
+    return off
+
+
+# The last few offset tables uploaded from host counts, most recent last: a training loop that repeats its counts (or
+# cycles through a few bucketed layouts) pays the validation and the host-to-device copy once.
+_ragged_uploads: dict = {}
+_RAGGED_UPLOADS_MAX = 8
+
+
+def _ragged_offsets_on_device(spec, B: int, R: int, dev: torch.device) -> torch.Tensor:
+    """(B, N+1) int32 offsets on `dev` from what the caller gave: a torch.int32 DEVICE tensor is taken as offsets, as is
+    -- its contents cannot be validated without a host synchronisation, so they are the caller's word (like a tensor
+    `unperm` in normalize_unperm; the kernel clamps what it reads, a broken table gives wrong numbers and no wild
+    access).  Anything else is host counts: validated (ragged_offsets), uploaded, and remembered."""
+    if torch.is_tensor(spec) and spec.is_cuda:
+        if spec.dtype != torch.int32:
+            raise TypeError(f"device offsets must be torch.int32, got {spec.dtype} (host counts may be any integer type)")
+        if spec.device != dev:
+            raise RuntimeError(f"offsets are on {spec.device}, embeddings on {dev}: raw pointers cross the C ABI, all on one device")
+        if spec.dim() == 1:
+            spec = spec.unsqueeze(0).expand(B, -1)
+        if spec.dim() != 2 or spec.shape[0] != B or spec.shape[1] < 2:
+            raise ValueError(f"offsets must be (N+1,) or (B, N+1) with B = {B}, got {tuple(spec.shape)}")
+        return spec.contiguous()
+    off = ragged_offsets(spec, R)
+    if off.dim() == 1:
+        off = off.unsqueeze(0).expand(B, -1)
+    if off.shape[0] != B:
+        raise ValueError(f"counts are for {off.shape[0]} batches, embeddings hold {B}")
+    off = off.contiguous()
+    capturing = _capturing is not None and _capturing()
+    key = (off.numpy().tobytes(), B, str(dev))
+    hit = None if capturing else _ragged_uploads.pop(key, None)
+    if hit is None:
+        hit = off.to(dev)
+        if capturing:                   # (belongs to the capturing graph's pool: not for anybody else)
+            return hit
+        while len(_ragged_uploads) >= _RAGGED_UPLOADS_MAX:
+            _ragged_uploads.pop(next(iter(_ragged_uploads)))
+    _ragged_uploads[key] = hit
+    return hit
+
+
+def loss_fwd_bwd_ragged(embeddings: torch.Tensor, offsets_or_counts, w: torch.Tensor, b: torch.Tensor, *,
+                        eps: float = SMALL_ERR, eps_cos: float = EPS_COS, variant: str = "softmax",
+                        need_grad: bool = True, need_per: bool = False, out: Optional[LossOutputs] = None,
+                        workspace: Optional[torch.Tensor] = None) -> LossOutputs:
+    """One enqueue of ge2e_loss_fwd_bwd_ragged on the current stream.  No host sync (host counts: none after their first use).
+
+    ``embeddings`` (R, D) or (B, R, D) float32: the rows of speaker j contiguously, speaker after speaker.
+    ``offsets_or_counts``: host counts (N,) / (B, N) -- a sequence or an integer CPU tensor, validated -- or a torch.int32
+    DEVICE tensor of offsets (N+1,) / (B, N+1), taken as is and NOT verified.  Outputs as `loss_fwd_bwd` with (N, M)
+    flattened to R: loss (B,), per (B, R), dE (B, R, D), dw (B,), db (B,)."""
+    lib = _lib.load()
+    _require_cuda(embeddings, "embeddings")
+    if embeddings.dim() not in (2, 3):
+        raise ValueError(f"embeddings must be (R,D) or (B,R,D), got {tuple(embeddings.shape)}")
+    if not embeddings.is_contiguous():
+        raise RuntimeError("embeddings must be contiguous")
+    if embeddings.dtype != torch.float32:
+        raise TypeError(f"embeddings must be float32 at this boundary, got {embeddings.dtype}")
+    e3 = embeddings.unsqueeze(0) if embeddings.dim() == 2 else embeddings
+    B, R, D = e3.shape
+    dev = e3.device
+    _check_scalar_params(w, b, dev)
+    with _on_device(dev):
+        off = _ragged_offsets_on_device(offsets_or_counts, B, R, dev)
+    N = off.shape[1] - 1
+    if out is None:
+        o4 = _alloc_outputs(B, 1, R, D, torch.float32, dev, need_grad, need_per)
+        out = LossOutputs(loss=o4.loss, per=o4.per.view(B, R) if need_per else None,
+                          dE=o4.dE.view(B, R, D) if need_grad else None, dw=o4.dw, db=o4.db)
+    query = (B, N, R, D, _lib.VARIANTS[variant])
+    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    with _on_device(dev) as guard:
+        stream = _stream_ptr(e3)
+        if workspace is None:
+            workspace = _workspace_for(lib, dev, stream, "ragged", query, guard.idx)
+        code = lib.ge2e_loss_fwd_bwd_ragged(
+            e3.data_ptr(), off.data_ptr(), B, N, R, D, w.data_ptr(), b.data_ptr(), eps_cos, eps, query[4],
+            out.loss.data_ptr(), ptr(out.per), ptr(out.dE), ptr(out.dw), ptr(out.db),
+            workspace.data_ptr(), workspace.numel(), stream)
+    _lib.check(code, "ge2e_loss_fwd_bwd_ragged")
+    return out
 
 
 # ---- the reference's static helpers (s3:33-38, 41-80, 95-112, 114-127), differentiable like the originals ----------
@@ -724,6 +838,32 @@ class _GE2ELossF64Function(torch.autograd.Function):
         return gE, gw, gb, None, None, None, None
 
 
+class _GE2ELossRaggedFunction(torch.autograd.Function):
+    """The same node over ge2e_loss_fwd_bwd_ragged: embeddings (R,D) / (B,R,D) and device offsets in; the backward scales
+    the launch's own dE / dw / db by the incoming gradient with ge2e_scale_grads (a batch of R rows as N = 1, M = R)."""
+
+    @staticmethod
+    def forward(ctx, embeddings, off, w, b, eps, eps_cos, variant):
+        need = any(ctx.needs_input_grad[i] for i in (0, 2, 3))
+        o = loss_fwd_bwd_ragged(embeddings, off, w, b, eps=eps, eps_cos=eps_cos, variant=variant, need_grad=need)
+        ctx.squeeze = embeddings.dim() == 2
+        ctx.w_shape, ctx.b_shape = w.shape, b.shape
+        if need:
+            ctx.save_for_backward(o.dE, o.dw, o.db)
+        return o.loss[0] if ctx.squeeze else o.loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        dE, dw, db = ctx.saved_tensors
+        B, R, D = dE.shape
+        gE, gw, gb = _scale_grads(dE, dw.data_ptr(), db.data_ptr(), grad_out, grad_out.numel(), (B, 1, R, D),
+                                  [ctx.needs_input_grad[i] for i in (0, 2, 3)], ctx.w_shape, ctx.b_shape)
+        if gE is not None and ctx.squeeze:
+            gE = gE[0]
+        return gE, None, gw, gb, None, None, None
+
+
 # The autograd node in C++ (libge2e_torch.so,csrc_torch/ge2e_autograd.cpp: torch.ops.ge2e_amd.loss): the same two C-ABI
 # calls as _GE2ELossFunction without the Python dispatch around them -- the eager module step at B = 1 is host-bound.
 # Used when the library has been built (build.build() does); _GE2ELossFunction is the same node in Python.
@@ -787,4 +927,36 @@ def ge2e_loss(embeddings: torch.Tensor, w: torch.Tensor, b: torch.Tensor, *, eps
         loss = op(embeddings, w, b, float(eps), float(eps_cos), _lib.VARIANTS[variant], _lib.IMPLS[impl])
     else:
         loss = _GE2ELossFunction.apply(embeddings, w, b, float(eps), float(eps_cos), variant, impl)
+    return loss if in_dtype == torch.float32 else loss.to(in_dtype)
+
+
+def ge2e_loss_ragged(embeddings: torch.Tensor, counts, w: torch.Tensor, b: torch.Tensor, *, eps: float = SMALL_ERR,
+                     eps_cos: float = EPS_COS, variant: str = "softmax") -> torch.Tensor:
+    """Differentiable GE2E loss of speakers with DIFFERENT utterance counts: 0-dim for (R, D) input, (B,) for (B, R, D).
+
+    ``embeddings`` holds the rows of speaker 0, then speaker 1, ... (what concatenating each speaker's utterances
+    gives); ``counts`` says how many each has: (N,) for every batch alike or (B, N), a sequence or an integer CPU tensor,
+    every count >= 2, each row summing to R.  They are validated on the host and uploaded once (the last few tables are
+    kept, keyed by their contents).  A ``torch.int32`` DEVICE tensor is taken as the OFFSETS (N+1,) / (B, N+1) instead --
+    0, m_0, m_0 + m_1, ..., R -- as is and UNVERIFIED (checking would cost a synchronisation): the kernel clamps what it
+    reads, so a broken table gives wrong numbers, not a wild access.  With all counts equal to M this is
+    ``ge2e_loss(embeddings.view(N, M, D))``.  float16 / bfloat16 are computed in fp32 behind differentiable casts;
+    float64 is not implemented (there is no fp64 ragged kernel, and no silent fp32 arithmetic in its place)."""
+    _require_cuda(embeddings, "embeddings")
+    in_dtype = embeddings.dtype
+    if in_dtype == torch.float64:
+        raise NotImplementedError("ge2e_loss_ragged: float64 embeddings are not implemented (the ragged kernel is fp32 and "
+                                  "nothing casts float64 down silently); pass float32, or pad to equal counts for ge2e_loss")
+    if in_dtype != torch.float32:
+        embeddings = embeddings.float()
+    if embeddings.dim() not in (2, 3):
+        raise ValueError(f"embeddings must be (R,D) or (B,R,D), got {tuple(embeddings.shape)}")
+    if not embeddings.is_contiguous():
+        raise RuntimeError("embeddings must be contiguous")
+    if embeddings.data_ptr() % 16:     # a contiguous view at an odd storage offset
+        embeddings = embeddings.clone()
+    B, R = (1, embeddings.shape[0]) if embeddings.dim() == 2 else embeddings.shape[:2]
+    with _on_device(embeddings.device):
+        off = _ragged_offsets_on_device(counts, B, R, embeddings.device)
+    loss = _GE2ELossRaggedFunction.apply(embeddings, off, w, b, float(eps), float(eps_cos), variant)
     return loss if in_dtype == torch.float32 else loss.to(in_dtype)

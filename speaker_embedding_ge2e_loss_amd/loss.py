@@ -116,7 +116,7 @@ class GE2ELoss(nn.Module):
         self.w = nn.Parameter(torch.tensor(10.0).to(self.device), requires_grad=True)
         self.b = nn.Parameter(torch.tensor(-5.0).to(self.device), requires_grad=True)
 
-    def forward(self, embeddings):
+    def forward(self, embeddings, counts=None):
         """embeddings (N,M,D) [or (B,N,M,D)] on hp.general.device -> loss (s3:19-30).
 
         Like the reference, w is NOT clamped (s3:22 discards torch.clamp's result), the
@@ -124,7 +124,18 @@ class GE2ELoss(nn.Module):
         through both cosine norms.  Like the reference, the loss and the embeddings' gradient come back in the
         embeddings' dtype: float32 and float64 are computed natively (float64 with ``impl="auto"``; ``w.grad`` /
         ``b.grad`` stay fp32 like the parameters), float16 / bfloat16 are computed in fp32.
+
+        ``counts`` (not in the reference, which draws the same M utterances for every speaker): the RAGGED loss.
+        ``embeddings`` is then (R, D) [or (B, R, D)], the rows of speaker 0, speaker 1, ... one after the other, and
+        ``counts`` their utterance counts -- (N,) or (B, N) on the host, every count >= 2, summing to R -- or a
+        ``torch.int32`` device tensor of offsets, unverified (``functional.ge2e_loss_ragged``).  One kernel: ``impl`` must
+        be "auto"; float64 raises NotImplementedError.  With ``graph=True`` this route is eager too (nothing is captured).
         """
+        if counts is not None:
+            if self.impl != "auto":
+                raise ValueError(f'impl="{self.impl}" names a fixed-shape kernel; the ragged loss has one kernel (impl="auto")')
+            return GF.ge2e_loss_ragged(embeddings, counts, self.w, self.b, eps=self.hp.general.small_err,
+                                       variant=self.variant)
         if self.graph:
             loss = self._forward_graphed(embeddings)
             if loss is not None:
