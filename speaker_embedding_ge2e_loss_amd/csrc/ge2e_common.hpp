@@ -290,6 +290,31 @@ __device__ __forceinline__ void wave_argmax(float& v, int& i) {
         v = v0; i = i0;
     }
 }
+// the reductions above by the width W of the aligned lane group (result in all W lanes)
+template <int W>
+__device__ __forceinline__ float group_sum(float v) {
+    static_assert(W == 4 || W == 8 || W == 16 || W == 64, "quad, oct, row of 16 or the wave");
+    if constexpr (W == 4) return quad_sum(v);
+    else if constexpr (W == 8) return oct_sum(v);
+    else if constexpr (W == 16) return row16_sum(v);
+    else return wave_sum(v);
+}
+template <int W>
+__device__ __forceinline__ float group_max(float v) {
+    static_assert(W == 4 || W == 8 || W == 16 || W == 64, "quad, oct, row of 16 or the wave");
+    if constexpr (W == 4) return quad_max(v);
+    else if constexpr (W == 8) return oct_max(v);
+    else if constexpr (W == 16) return row16_max(v);
+    else return wave_max(v);
+}
+template <int W>
+__device__ __forceinline__ void group_argmax(float& v, int& i) {
+    static_assert(W == 4 || W == 8 || W == 16 || W == 64, "quad, oct, row of 16 or the wave");
+    if constexpr (W == 4) quad_argmax(v, i);
+    else if constexpr (W == 8) oct_argmax(v, i);
+    else if constexpr (W == 16) row16_argmax(v, i);
+    else wave_argmax(v, i);
+}
 
 // x / max(|x|, eps) bookkeeping shared by every kernel: from a squared norm give
 // the reciprocal of the clamped norm and kappa = clamped / true norm (0 for a zero

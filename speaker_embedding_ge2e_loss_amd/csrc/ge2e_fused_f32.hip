@@ -36,63 +36,21 @@
 // tile get an out-of-range offset, so they read 0 and their stores are dropped with no
 // predication branches (a predicated load makes hipcc branch and drain vmcnt around every element).
 #include "ge2e_common.hpp"
+#include "ge2e_dev.hpp"
 #include "ge2e_fused.hpp"
+#include "ge2e_row.hpp"
 
 namespace ge2e {
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int TR = 64;      // rows per tile
 constexpr int NC = 64;      // centroid slots
 constexpr int APITCH = 68;  // AT row pitch (floats): 16-B aligned rows, b128 reads conflict-free
 constexpr int MAX_SPT = 8;  // speakers per tile cap (KJ rows)
-constexpr unsigned OOB = 0x7FFFFF00u;  // lane offset that is out of range of every buffer here
 
 // RS / stashR columns
 constexpr int R_RNE = 0, R_C1 = 1, R_C3 = 3, R_C4 = 4, R_J = 5;
-
-__device__ __forceinline__ float dot4(const float4& a, const float4& b) {
-    return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w;
-}
-__device__ __forceinline__ float4 zero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
-__device__ __forceinline__ float4 scale4(const float4& a, float s) {
-    return make_float4(a.x * s, a.y * s, a.z * s, a.w * s);
-}
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ float4 bload4(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-    return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
-}
-__device__ __forceinline__ float bload1(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
-}
-template <int AUX = 0>  // cache-policy bits: 2 = nt (streaming)
-// NOTE the offset of a 16-byte store goes entirely into the VGPR (soffset = immediate 0).  With a
-// REGISTER soffset LLVM assumes the "VMEM store > 64 bit, then VALU write of its data VGPRs" hazard does
-// not exist and lets the very next instruction overwrite the store's data registers; on gfx950 with two
-// waves per SIMD that clobbered ~5 % of launches (4 rows x 64 columns at a time, always the younger
-// wave of a SIMD).  With an immediate soffset the hazard recognizer inserts the wait state itself.
-__device__ __forceinline__ void bstore4(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff, const float4& v) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, voff + soff, 0, AUX);
-}
-
-// unit_stats with the common case (norm above the cosine eps) on v_rsq_f32 + one Newton step
-// instead of sqrt and two IEEE divisions; the clamped case keeps the exact slow path.
-__device__ __forceinline__ void unit_stats_fast(float sq, float eps_cos, float& rn, float& kappa) {
-    if (sq > eps_cos * eps_cos && sq < 1e30f) {
-        float r = __builtin_amdgcn_rsqf(sq);
-        r = r * (1.5f - 0.5f * sq * r * r);
-        rn = r;
-        kappa = 1.0f;
-    } else {
-        unit_stats(sq, eps_cos, rn, kappa);
-    }
-}
 
 }  // namespace
 
@@ -360,9 +318,8 @@ __global__ __launch_bounds__(256, 1) void ge2e_fused_f32_kernel(Problem p, Fused
                 coef = quad_sum(coef);
                 ad = quad_sum(ad);                  // dL/dcos on the own-speaker column
                 const float rne1 = rv ? rne : 1.0f;
-                const float rho = rnu * inv_m1;
-                const float c2 = rho * (ad * rne1 + ad * ku * cosd * rnu * inv_m1);
-                const float fold = rv ? c2 * CST[(rv ? j : 0) * 4 + 2] / rne1 : 0.f;
+                const RowCoeffs rc = row_coeffs(ad, coef, rne1, ke, rnu, ku, cosd, inv_m1);
+                const float fold = rv ? rc.c2 * CST[(rv ? j : 0) * 4 + 2] / rne1 : 0.f;
                 const unsigned va = (unsigned)(((t * TR + rl) * NC + 16 * qk) * 4);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
@@ -379,12 +336,9 @@ __global__ __launch_bounds__(256, 1) void ge2e_fused_f32_kernel(Problem p, Fused
                     if (p.per) p.per[(size_t)bi * NM + r0 + rl] = per;
                 }
                 {
-                    const float c1 = (-ke * coef * rne1 - ad * rnu * inv_m1) - c2 / rne1;
-                    const float alpha = ad * rnu * (1.0f + ku * cosd * rho / rne1);
-                    const float beta = -ad * rnu * ku * cosd * rho;
                     const unsigned vr = (qk == 0) ? (unsigned)((t * TR + rl) * 32) : OOB;
-                    bstore4(rsW, vr, offR, make_float4(rne, c1, 0.f, alpha * inv_m1));
-                    bstore4(rsW, vr, offR + 16u, make_float4(beta * inv_m1, __int_as_float(j), 0.f, 0.f));
+                    bstore4(rsW, vr, offR, make_float4(rne, rc.c1, 0.f, rc.alpha * inv_m1));
+                    bstore4(rsW, vr, offR + 16u, make_float4(rc.beta * inv_m1, __int_as_float(j), 0.f, 0.f));
                 }
             }
             __syncthreads();

@@ -1,18 +1,17 @@
 // GE2E_IMPL_FUSED_SPLIT's per-workgroup body (one 512-thread workgroup per batch, three sweeps over E, split-fp16 MFMA) as a
 // device function: ge2e_fused_split.hip wraps it in a kernel of its own; the team kernels call it when a launch has to be
 // redone without teams (no team formed, a hand-off timed out, an untrusted control block) -- inside the SAME launch, where
-// rounds 2-4 queued a second, gated launch behind every team call.  Everything lives in namespace ge2e::fsplit (its helpers
-// have the names of the team kernels' own).
+// rounds 2-4 queued a second, gated launch behind every team call.  The tile constants live in namespace ge2e::fsplit: the
+// team kernels have their own NC and GP with other values.
 #pragma once
 #include "ge2e_common.hpp"
+#include "ge2e_dev.hpp"
 #include "ge2e_fused.hpp"
+#include "ge2e_row.hpp"
 #include "ge2e_split_gemm.hpp"
 
 namespace ge2e {
 namespace fsplit {
-
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int TR = 64;      // rows per tile
 constexpr int NC = 64;      // centroid slots
@@ -20,20 +19,7 @@ constexpr int APITCH = 68;  // S / staging row pitch (floats)
 constexpr int GP = 72;      // G image row pitch (halfs)
 constexpr int MAX_SPT = 6;  // speakers per tile cap (KJ rows; 8 would not fit the LDS budget)
 constexpr int NWAVE = 8;
-constexpr unsigned OOB = 0x7FFFFF00u;  // lane offset that is out of range of every buffer here
 
-// RS / stashR columns
-
-__device__ __forceinline__ float dot4(const float4& a, const float4& b) {
-    return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w;
-}
-__device__ __forceinline__ float4 zero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
-__device__ __forceinline__ float4 scale4(const float4& a, float s) {
-    return make_float4(a.x * s, a.y * s, a.z * s, a.w * s);
-}
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
-}
 // cache-policy bits of buffer instructions on gfx950: 1 = sc0, 2 = nt (streaming), 16 = sc1
 #ifndef GE2E_AUX_E1
 #define GE2E_AUX_E1 0   // sweep-1 read of E (first touch, re-read twice later)
@@ -44,43 +30,9 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, un
 #ifndef GE2E_AUX_DE
 #define GE2E_AUX_DE 2   // dE stores (never re-read here): nt keeps E resident for the re-reads, +4.5 % measured
 #endif
-template <int AUX = 0>
-__device__ __forceinline__ float4 bload4(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-    return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, AUX));
-}
-__device__ __forceinline__ float bload1(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
-}
-template <int AUX = 0>
-// NOTE the offset of a 16-byte store goes entirely into the VGPR (soffset = immediate 0).  With a
-// REGISTER soffset LLVM assumes the "VMEM store > 64 bit, then VALU write of its data VGPRs" hazard does
-// not exist and lets the very next instruction overwrite the store's data registers; on gfx950 with two
-// waves per SIMD that clobbered ~5 % of launches (4 rows x 64 columns at a time, always the younger
-// wave of a SIMD).  With an immediate soffset the hazard recognizer inserts the wait state itself.
-__device__ __forceinline__ void bstore4(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff, const float4& v) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, voff + soff, 0, AUX);
-}
-__device__ __forceinline__ void unit_stats_fast(float sq, float eps_cos, float& rn, float& kappa) {
-    if (sq > eps_cos * eps_cos && sq < 1e30f) {
-        float r = __builtin_amdgcn_rsqf(sq);
-        r = r * (1.5f - 0.5f * sq * r * r);
-        rn = r;
-        kappa = 1.0f;
-    } else {
-        unit_stats(sq, eps_cos, rn, kappa);
-    }
-}
-// write 4 scaled values as fp16 hi / lo at the same (row, col) of two images
-__device__ __forceinline__ void put_split4(_Float16* hi_img, _Float16* lo_img, int off, const float4& x) {
-    h4 hi, lo;
-    split4(x, hi, lo);
-    *reinterpret_cast<h4*>(hi_img + off) = hi;
-    *reinterpret_cast<h4*>(lo_img + off) = lo;
-}
 __device__ __forceinline__ float4 get_join4(const _Float16* hi_img, const _Float16* lo_img, int off) {
     return join4(*reinterpret_cast<const h4*>(hi_img + off), *reinterpret_cast<const h4*>(lo_img + off));
 }
-
 
 // One 512-thread workgroup works through the batches wg, wg + nwg, ... of the call; `smem_f` = fused_split_lds_bytes(D) of LDS,
 // workspace slice `wg` of p.ws.  Called by the kernel of its own (ge2e_fused_split.hip) and by the team kernels when a launch
@@ -355,8 +307,7 @@ __device__ __forceinline__ void body(const Problem& p, const FusedWs& wsl, float
                         g[i] = (i == jrel) ? -pos * (1.0f - pos) : ((8 * qk + i == besti) ? neg * (1.0f - neg) : 0.f);
                 }
                 float coef = 0.f, ad = 0.f;
-                const float rho_o = rnu * inv_m1;
-                const float own_o = rv ? rho_o * (rne1 + ku * cosd * rho_o) * cs.z / rne1 : 0.f;   // o / (dL/dS on the own column)
+                const float own_o = rv ? row_own_o(rne1, rnu, ku, cosd, inv_m1, cs.z) : 0.f;
 #pragma unroll
                 for (int i = 0; i < 8; ++i) {
                     if (!rv || 8 * qk + i >= N) g[i] = 0.f;
@@ -394,15 +345,10 @@ __device__ __forceinline__ void body(const Problem& p, const FusedWs& wsl, float
                 {
                     // dE_r = w gE rne + c1 e-hat + c2 s_j + KJ_j   (ge2e_fused_f32.hip header), stored for
                     // sweep 3 as the ready-made coefficients of acc, of the RAW row e and of c-hat_j images
-                    const float rho = rnu * inv_m1;
-                    const float c2 = rho * (ad * rne1 + ad * ku * cosd * rnu * inv_m1);
-                    const float c1 = (-ke * coef * rne1 - ad * rnu * inv_m1) - c2 / rne1;
-                    const float alpha = ad * rnu * (1.0f + ku * cosd * rho / rne1);
-                    const float beta = -ad * rnu * ku * cosd * rho;
-                    if (qk == 0)     // c4': the row's share of the c-hat_j coefficient of the speaker's KJ row
-                        RS[rl * 8 + 5] = rv ? inv_m1 * (beta * cs.z + cs.y * alpha * xo) : 0.f;
+                    const RowCoeffs rc = row_coeffs(ad, coef, rne1, ke, rnu, ku, cosd, inv_m1);
+                    if (qk == 0) RS[rl * 8 + 5] = rv ? row_c4_share(rc, inv_m1, cs.z, cs.y, xo) : 0.f;
                     const unsigned vr = (qk == 0) ? (unsigned)((t * TR + rl) * 16) : OOB;
-                    bstore4(rsW, vr, offR, make_float4(rne * (w * kSplitInv2), c1 * rne, 0.f, __int_as_float(j)));
+                    bstore4(rsW, vr, offR, make_float4(rne * (w * kSplitInv2), rc.c1 * rne, 0.f, __int_as_float(j)));
                 }
             }
             __syncthreads();

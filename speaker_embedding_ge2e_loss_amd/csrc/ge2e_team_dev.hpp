@@ -2,6 +2,7 @@
 // forward-only kernel): buffer-resource loads / stores, norm bookkeeping, the swizzled image layouts, MFMA wrappers.
 #pragma once
 #include "ge2e_common.hpp"
+#include "ge2e_dev.hpp"
 #include "ge2e_split_gemm.hpp"
 #include "ge2e_team.hpp"
 #include "ge2e_team_kernel.hpp"
@@ -11,7 +12,6 @@ namespace ge2e {
 
 namespace {
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int NC = 64;        // centroid slots: member m owns 8 m .. 8 m + 7
@@ -20,7 +20,6 @@ constexpr int XP = 68;        // X block pitch (floats)
 constexpr int STGPAD = 32;    // centroid stage: rows 16 banks apart -> the transposing reads of a 4 x 32 block never collide
 constexpr int RTMAX = 80;     // rows of a member's images
 constexpr int RBMAX = RTMAX / 16;
-constexpr unsigned OOB = 0x7FFFFF00u;
 constexpr int AUX_L2 = 16;    // sc1: served by L2, never by this CU's L1 (hand-off reads)
 constexpr int AUX_NT = 2;
 #ifndef GE2E_T2_DE_AUX
@@ -42,38 +41,9 @@ constexpr int AUX_NT = 2;
 #define GE2E_T2_E_AUX 2       // ... and of the E loads
 #endif
 
-__device__ __forceinline__ float dot4(const float4& a, const float4& b) {
-    return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w;
-}
-__device__ __forceinline__ float4 zero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
-__device__ __forceinline__ float4 scale4(const float4& a, float s) {
-    return make_float4(a.x * s, a.y * s, a.z * s, a.w * s);
-}
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
-}
-template <int AUX = 0>
-__device__ __forceinline__ float4 bload4(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-    return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, AUX));
-}
 template <int AUX = 0>
 __device__ __forceinline__ h8 bload_h8(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
     return __builtin_bit_cast(h8, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, AUX));
-}
-// whole offset in the VGPR, immediate soffset (ge2e_fused_split.hip: the register-soffset store hazard)
-template <int AUX = 0>
-__device__ __forceinline__ void bstore4(__amdgpu_buffer_rsrc_t r, unsigned voff, const float4& v) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, voff, 0, AUX);
-}
-__device__ __forceinline__ void unit_stats_fast(float sq, float eps_cos, float& rn, float& kappa) {
-    if (sq > eps_cos * eps_cos && sq < 1e30f) {
-        float r = __builtin_amdgcn_rsqf(sq);
-        r = r * (1.5f - 0.5f * sq * r * r);
-        rn = r;
-        kappa = 1.0f;
-    } else {
-        unit_stats(sq, eps_cos, rn, kappa);
-    }
 }
 // x / max(|x|, eps) bookkeeping without a branch: rn = 1 / max(|x|, eps), kappa = clamped / true norm (0 for a
 // zero vector), nc = max(|x|, eps).  v_rsq_f32 + one Newton step instead of sqrt and two IEEE divisions.
@@ -88,12 +58,6 @@ __device__ __forceinline__ void unit_stats_bf(float sq, float eps_cos, float eps
 __device__ __forceinline__ float rcp_nr(float x) {
     const float r = __builtin_amdgcn_rcpf(x);
     return r * (2.0f - x * r);
-}
-__device__ __forceinline__ void put_split4(_Float16* hi_img, _Float16* lo_img, int off, const float4& x) {
-    h4 hi, lo;
-    split4(x, hi, lo);
-    *reinterpret_cast<h4*>(hi_img + off) = hi;
-    *reinterpret_cast<h4*>(lo_img + off) = lo;
 }
 
 // Split-fp16 products on the MFMA builtins.  (An earlier version of this file issued them as inline asm with tied

@@ -25,6 +25,8 @@
 // Same algebra and same split arithmetic as ge2e_fused_split.hip.  Config 5 is bound by the contractions, config
 // 4 by the bytes the pipeline moves.
 #include "ge2e_common.hpp"
+#include "ge2e_dev.hpp"
+#include "ge2e_row.hpp"
 #include "ge2e_split_gemm.hpp"
 #include "ge2e_tiled.hpp"
 
@@ -33,23 +35,6 @@ namespace ge2e {
 namespace {
 
 constexpr int TP = 72;  // LDS tile pitch (halfs): 64 + 8
-
-__device__ __forceinline__ float dot4(const float4& a, const float4& b) {
-    return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w;
-}
-__device__ __forceinline__ float4 scale4(const float4& a, float s) {
-    return make_float4(a.x * s, a.y * s, a.z * s, a.w * s);
-}
-__device__ __forceinline__ void unit_stats_fast(float sq, float eps_cos, float& rn, float& kappa) {
-    if (sq > eps_cos * eps_cos && sq < 1e30f) {
-        float r = __builtin_amdgcn_rsqf(sq);
-        r = r * (1.5f - 0.5f * sq * r * r);
-        rn = r;
-        kappa = 1.0f;
-    } else {
-        unit_stats(sq, eps_cos, rn, kappa);
-    }
-}
 
 // 64 x 64 fp16 tile of a row-major global image (leading dimension ld halfs) -> LDS [64][TP];
 // rows >= rows_valid are zero.  256 threads, two 16-byte pieces each.
@@ -826,7 +811,7 @@ __global__ __launch_bounds__(C::NT, 2) void ge2e_tiled_sim(Problem p, TiledWs L)
 }
 
 // ---------------------------------------------------------------------------------------------
-// k_simrows (N <= 256, i.e. one 256-slot tile holds a row's whole similarity vector): k_sim and k_rows16 in ONE kernel --
+// k_simrows (N <= 256, i.e. one 256-slot tile holds a row's whole similarity vector): k_sim and k_rows<16> in ONE kernel --
 // the fp32 similarity block never goes to memory (2 x N M npad 4 bytes per batch less: 1.3 GB per launch at config 4,
 // where every kernel of this pipeline runs at the HBM rate) and one launch fewer.
 // The contraction is taken with the SLOTS as the A operand (C layout: register = slot, lane = row), so a row's 256
@@ -1045,20 +1030,16 @@ __global__ __launch_bounds__(C::NT, 2) void ge2e_tiled_simrows(Problem p, TiledW
             gsc = gn;
         }
         if (!rv[b2]) { ad0 = 0.f; gsc = 0.f; }
-        const float rho = rnu[b2] * inv_m1, t1 = ku[b2] * cosd[b2] * rho;
-        // the own-speaker column carries o = c2 |s_j| / (ra w)  (k_rows16 above)
-        og[b2] = rho * (rne[b2] + t1) * csz[b2] / rne[b2] * ad0 * kSplitScale;
+        // the own-speaker column carries o = c2 |s_j| / (ra w)  (k_rows below)
+        og[b2] = row_own_o(rne[b2], rnu[b2], ku[b2], cosd[b2], inv_m1, csz[b2]) * ad0 * kSplitScale;
         gs[b2] = gsc * kSplitScale;
         if (wa == 0 && h == 0 && rv[b2]) {
             const size_t gr = (size_t)bi * NM + rtile * C::TN + rloc;
             const float coef = w * coefsum, ad = w * ad0;
-            const float c2 = rho * (ad * rne[b2] + ad * ku[b2] * cosd[b2] * rnu[b2] * inv_m1);
-            const float c1 = (-ke[b2] * coef * rne[b2] - ad * rnu[b2] * inv_m1) - c2 / rne[b2];
-            const float alpha = ad * rnu[b2] * (1.0f + ku[b2] * cosd[b2] * rho / rne[b2]);
-            const float beta = -ad * rnu[b2] * ku[b2] * cosd[b2] * rho;
+            const RowCoeffs rc = row_coeffs(ad, coef, rne[b2], ke[b2], rnu[b2], ku[b2], cosd[b2], inv_m1);
             float* rs = p.ws + L.rs + gr * 8;
-            *reinterpret_cast<float4*>(rs) = make_float4(rne[b2] * (w * kSplitInv2), c1 * rne[b2], 0.f, 0.f);
-            *reinterpret_cast<float4*>(rs + 4) = make_float4(inv_m1 * (beta * csz[b2] + csy[b2] * alpha * xo[b2]), per,
+            *reinterpret_cast<float4*>(rs) = make_float4(rne[b2] * (w * kSplitInv2), rc.c1 * rne[b2], 0.f, 0.f);
+            *reinterpret_cast<float4*>(rs + 4) = make_float4(row_c4_share(rc, inv_m1, csz[b2], csy[b2], xo[b2]), per,
                                                               fmaf(eps, db_row, coefsum), db_row);
             if (p.per) p.per[gr] = per;
         }
@@ -1126,12 +1107,24 @@ __global__ __launch_bounds__(C::NT, 2) void ge2e_tiled_simrows(Problem p, TiledW
 }
 
 // ---------------------------------------------------------------------------------------------
-// k_rows: one wave per row; the row of X (<= 1024 centroids) lives in 16 registers per lane (4 x 4 consecutive slots).
+// k_rows: W lanes per row, 256 / W rows per workgroup; the row of X lives in 16 registers per lane: lane l of a row holds
+// the 4 consecutive centroid slots 4 W c + 4 l .. + 3 of up to four chunks c (16-byte reads of X and 8-byte writes of the
+// two G planes; 2-byte stores cost ~12x per byte).
+//   W = 64  one wave per row, up to 1024 centroids
+//   W = 16  N <= 256: four rows per wave (a wave per row is latency-bound: one short dependent chain per wave and 655 k
+//           waves per launch at cfg4)
+// Rows past the end: a whole wave of them leaves (W = 64); inside a wave dead rows recompute the last row and store nothing.
+template <int W>
 __global__ __launch_bounds__(256) void ge2e_tiled_rows(Problem p, TiledWs L) {
-    const int lane = threadIdx.x & 63;
-    const size_t gr = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);  // global row
+    const int l = threadIdx.x & (W - 1);
+    const size_t gr_ = (size_t)blockIdx.x * (256 / W) + threadIdx.x / W;  // global row
     const int N = p.N, M = p.M, NM = N * M, npad = L.npad;
-    if (gr >= (size_t)p.B * NM) return;
+    const size_t rows_total = (size_t)p.B * NM;
+    const bool live = gr_ < rows_total;
+    if constexpr (W == 64) {
+        if (!live) return;
+    }
+    const size_t gr = live ? gr_ : rows_total - 1;
     const int bi = (int)(gr / NM), r = (int)(gr - (size_t)bi * NM), j = r / M;
     const float w = p.w ? *p.w : p.w_imm, bias = p.b ? *p.b : p.b_imm;
     const float eps = p.eps, log_eps = p.log_eps;
@@ -1148,14 +1141,12 @@ __global__ __launch_bounds__(256) void ge2e_tiled_rows(Problem p, TiledWs L) {
     unit_stats_fast(uu, p.eps_cos, rnu, ku);
     const float cosd = eu * rne * rnu;
     const float sjj = w * (cosd + eps) + bias;
-    // lane l holds the 4 consecutive centroid slots 256 c + 4 l .. + 3 of up to four 256-slot chunks: 16-byte reads
-    // of X and 8-byte writes of the two G planes (2-byte stores cost ~12x per byte)
     float c0[4][4], g[4][4];
     float mx = -INFINITY, best = -INFINITY;
     int besti = 0x7fffffff;
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-        const int kb = 256 * c + 4 * lane;
+        const int kb = 4 * W * c + 4 * l;
         float4 xv = make_float4(0.f, 0.f, 0.f, 0.f);
         if (kb < npad) xv = *reinterpret_cast<const float4*>(X + kb);
         const float xe[4] = {xv.x, xv.y, xv.z, xv.w};
@@ -1172,26 +1163,26 @@ __global__ __launch_bounds__(256) void ge2e_tiled_rows(Problem p, TiledWs L) {
     }
     float per;
     if (p.variant == 0) {
-        mx = fmaxf(wave_max(mx), log_eps);
+        mx = fmaxf(group_max<W>(mx), log_eps);
         float zoff = 0.f;
 #pragma unroll
         for (int c = 0; c < 4; ++c)
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                const int k = 256 * c + 4 * lane + e;
+                const int k = 4 * W * c + 4 * l + e;
                 g[c][e] = (k < N) ? __expf(w * (c0[c][e] + eps) + bias - mx) : 0.f;
                 if (k != j) zoff += g[c][e];
             }
-        zoff = wave_sum(zoff) + __expf(log_eps - mx);
+        zoff = group_sum<W>(zoff) + __expf(log_eps - mx);
         const float z = zoff + __expf(sjj - mx);
         per = (mx - sjj) + __logf(z);
         const float rz = 1.0f / z;
 #pragma unroll
         for (int c = 0; c < 4; ++c)
 #pragma unroll
-            for (int e = 0; e < 4; ++e) g[c][e] = (256 * c + 4 * lane + e == j) ? -zoff * rz : g[c][e] * rz;
+            for (int e = 0; e < 4; ++e) g[c][e] = (4 * W * c + 4 * l + e == j) ? -zoff * rz : g[c][e] * rz;
     } else {
-        wave_argmax(best, besti);
+        group_argmax<W>(best, besti);
         const float pos = 1.0f / (1.0f + __expf(-sjj));
         const float neg = (N > 1) ? 1.0f / (1.0f + __expf(-best)) : 0.0f;
         per = 1.0f - pos + neg;
@@ -1199,18 +1190,17 @@ __global__ __launch_bounds__(256) void ge2e_tiled_rows(Problem p, TiledWs L) {
         for (int c = 0; c < 4; ++c)
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                const int k = 256 * c + 4 * lane + e;
+                const int k = 4 * W * c + 4 * l + e;
                 g[c][e] = (k == j) ? -pos * (1.0f - pos) : ((k == besti) ? neg * (1.0f - neg) : 0.f);
             }
     }
     float dwv = 0.f, dbv = 0.f, coef = 0.f, ad = 0.f;
-    const float rho_ = rnu * inv_m1, t1_ = ku * cosd * rho_;
-    const float own_o = rho_ * (rne + t1_) * cs.z / rne;     // o / (dL/dS on the own column)
+    const float own_o = row_own_o(rne, rnu, ku, cosd, inv_m1, cs.z);
     _Float16* GHh = reinterpret_cast<_Float16*>(p.ws + L.gh) + (size_t)bi * 2 * NM * npad + (size_t)r * npad;
     _Float16* GHl = GHh + (size_t)NM * npad;
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-        const int kb = 256 * c + 4 * lane;
+        const int kb = 4 * W * c + 4 * l;
         if (kb < npad) {
             float gv[4];
 #pragma unroll
@@ -1225,7 +1215,7 @@ __global__ __launch_bounds__(256) void ge2e_tiled_rows(Problem p, TiledWs L) {
                 // leave-one-out speaker row sum_i c3_i e-hat_i minus kap_j (sum_i c3_i xo_i) c-hat_j (ge2e_team.hip, S)
                 if (k == j) { ad = gv[e]; gv[e] = own_o * gv[e]; }
             }
-            if (p.dE) {      // (forward-only calls: nobody reads the dL/dS planes)
+            if (live && p.dE) {      // (forward-only calls: nobody reads the dL/dS planes)
                 h4 hi, lo;
                 split4(make_float4(gv[0] * kSplitScale, gv[1] * kSplitScale, gv[2] * kSplitScale, gv[3] * kSplitScale), hi, lo);
                 *reinterpret_cast<h4*>(GHh + kb) = hi;
@@ -1233,142 +1223,14 @@ __global__ __launch_bounds__(256) void ge2e_tiled_rows(Problem p, TiledWs L) {
             }
         }
     }
-    dwv = wave_sum(dwv); dbv = wave_sum(dbv);
-    coef = w * wave_sum(coef); ad = w * wave_sum(ad);
-    if (lane == 0) {
-        const float rho = rnu * inv_m1;
-        const float c2 = rho * (ad * rne + ad * ku * cosd * rnu * inv_m1);
-        const float c1 = (-ke * coef * rne - ad * rnu * inv_m1) - c2 / rne;
-        const float alpha = ad * rnu * (1.0f + ku * cosd * rho / rne);
-        const float beta = -ad * rnu * ku * cosd * rho;
+    dwv = group_sum<W>(dwv); dbv = group_sum<W>(dbv);
+    coef = w * group_sum<W>(coef); ad = w * group_sum<W>(ad);
+    if (l == 0 && live) {
+        const RowCoeffs rc = row_coeffs(ad, coef, rne, ke, rnu, ku, cosd, inv_m1);
         float* rs = p.ws + L.rs + gr * 8;
-        // ra, c1e; then the row's share of the c-hat_j coefficient of KJ_j: c4' = (beta |s_j| + kap_j alpha xo) / (M - 1)
-        *reinterpret_cast<float4*>(rs) = make_float4(rne * (w * kSplitInv2), c1 * rne, 0.f, 0.f);
-        *reinterpret_cast<float4*>(rs + 4) = make_float4(inv_m1 * (beta * cs.z + cs.y * alpha * xo), per, dwv, dbv);
-        if (p.per) p.per[gr] = per;
-    }
-}
-
-// k_rows for N <= 256: 16 lanes per row, 4 rows per wave (a wave per row is latency-bound: one short dependent chain
-// per wave and 655 k waves per launch at cfg4).  Lane l of a row holds the slots 64 c + 4 l .. + 3 of up to four chunks.
-__global__ __launch_bounds__(256) void ge2e_tiled_rows16(Problem p, TiledWs L) {
-    const int l16 = threadIdx.x & 15;
-    const size_t gr_ = (size_t)blockIdx.x * 16 + (threadIdx.x >> 4);  // global row
-    const int N = p.N, M = p.M, NM = N * M, npad = L.npad;
-    const size_t rows_total = (size_t)p.B * NM;
-    const bool live = gr_ < rows_total;
-    const size_t gr = live ? gr_ : rows_total - 1;      // dead rows recompute the last row and store nothing
-    const int bi = (int)(gr / NM), r = (int)(gr - (size_t)bi * NM), j = r / M;
-    const float w = p.w ? *p.w : p.w_imm, bias = p.b ? *p.b : p.b_imm;
-    const float eps = p.eps, log_eps = p.log_eps;
-    const float inv_m1 = 1.0f / (float)(M - 1);
-    const float* X = p.ws + L.x + ((size_t)bi * NM + r) * npad;
-    const float4 rst = *reinterpret_cast<const float4*>(p.ws + L.rst + gr * 4);      // rne ke ee
-    const float4 cs = *reinterpret_cast<const float4*>(p.ws + L.cst + ((size_t)bi * N + j) * 4);  // rn kap |s| |s|^2
-    const float rne = rst.x, ke = rst.y, ee = rst.z;
-    const float xo = X[j];
-    const float es = xo * cs.z / rne;
-    const float eu = (es - ee) * inv_m1;
-    const float uu = fmaxf((cs.w - 2.0f * es + ee) * (inv_m1 * inv_m1), 0.0f);
-    float rnu, ku;
-    unit_stats_fast(uu, p.eps_cos, rnu, ku);
-    const float cosd = eu * rne * rnu;
-    const float sjj = w * (cosd + eps) + bias;
-    float c0[4][4], g[4][4];
-    float mx = -INFINITY, best = -INFINITY;
-    int besti = 0x7fffffff;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        const int kb = 64 * c + 4 * l16;
-        float4 xv = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (kb < npad) xv = *reinterpret_cast<const float4*>(X + kb);
-        const float xe[4] = {xv.x, xv.y, xv.z, xv.w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int k = kb + e;
-            c0[c][e] = (k == j) ? cosd : xe[e];
-            if (k < N) {
-                const float sv = w * (c0[c][e] + eps) + bias;
-                mx = fmaxf(mx, sv);
-                if (k != j && sv > best) { best = sv; besti = k; }
-            }
-        }
-    }
-    float per;
-    if (p.variant == 0) {
-        mx = fmaxf(row16_max(mx), log_eps);
-        float zoff = 0.f;
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int k = 64 * c + 4 * l16 + e;
-                g[c][e] = (k < N) ? __expf(w * (c0[c][e] + eps) + bias - mx) : 0.f;
-                if (k != j) zoff += g[c][e];
-            }
-        zoff = row16_sum(zoff) + __expf(log_eps - mx);
-        const float z = zoff + __expf(sjj - mx);
-        per = (mx - sjj) + __logf(z);
-        const float rz = 1.0f / z;
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) g[c][e] = (64 * c + 4 * l16 + e == j) ? -zoff * rz : g[c][e] * rz;
-    } else {
-        row16_argmax(best, besti);
-        const float pos = 1.0f / (1.0f + __expf(-sjj));
-        const float neg = (N > 1) ? 1.0f / (1.0f + __expf(-best)) : 0.0f;
-        per = 1.0f - pos + neg;
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int k = 64 * c + 4 * l16 + e;
-                g[c][e] = (k == j) ? -pos * (1.0f - pos) : ((k == besti) ? neg * (1.0f - neg) : 0.f);
-            }
-    }
-    float dwv = 0.f, dbv = 0.f, coef = 0.f, ad = 0.f;
-    const float rho_ = rnu * inv_m1, t1_ = ku * cosd * rho_;
-    const float own_o = rho_ * (rne + t1_) * cs.z / rne;     // o / (dL/dS on the own column)
-    _Float16* GHh = reinterpret_cast<_Float16*>(p.ws + L.gh) + (size_t)bi * 2 * NM * npad + (size_t)r * npad;
-    _Float16* GHl = GHh + (size_t)NM * npad;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        const int kb = 64 * c + 4 * l16;
-        if (kb < npad) {
-            float gv[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int k = kb + e;
-                gv[e] = (k < N) ? g[c][e] : 0.f;
-                dwv += gv[e] * (c0[c][e] + eps);
-                dbv += gv[e];
-                coef += gv[e] * c0[c][e];
-                // the own-speaker column carries o = c2 |s_j| / (ra w): k_ge's contraction then adds the c2 s_j term of dE
-                // by itself, and what o adds to gC_j is, pushed through the centroid norm in k_spk, exactly the
-                // leave-one-out speaker row sum_i c3_i e-hat_i minus kap_j (sum_i c3_i xo_i) c-hat_j (ge2e_team.hip, S)
-                if (k == j) { ad = gv[e]; gv[e] = own_o * gv[e]; }
-            }
-            h4 hi, lo;
-            split4(make_float4(gv[0] * kSplitScale, gv[1] * kSplitScale, gv[2] * kSplitScale, gv[3] * kSplitScale), hi, lo);
-            if (live && p.dE) {      // (forward-only calls: nobody reads the dL/dS planes)
-                *reinterpret_cast<h4*>(GHh + kb) = hi;
-                *reinterpret_cast<h4*>(GHl + kb) = lo;
-            }
-        }
-    }
-    dwv = row16_sum(dwv); dbv = row16_sum(dbv);
-    coef = w * row16_sum(coef); ad = w * row16_sum(ad);
-    if (l16 == 0 && live) {
-        const float rho = rnu * inv_m1;
-        const float c2 = rho * (ad * rne + ad * ku * cosd * rnu * inv_m1);
-        const float c1 = (-ke * coef * rne - ad * rnu * inv_m1) - c2 / rne;
-        const float alpha = ad * rnu * (1.0f + ku * cosd * rho / rne);
-        const float beta = -ad * rnu * ku * cosd * rho;
-        float* rs = p.ws + L.rs + gr * 8;
-        // ra, c1e; then the row's share of the c-hat_j coefficient of KJ_j: c4' = (beta |s_j| + kap_j alpha xo) / (M - 1)
-        *reinterpret_cast<float4*>(rs) = make_float4(rne * (w * kSplitInv2), c1 * rne, 0.f, 0.f);
-        *reinterpret_cast<float4*>(rs + 4) = make_float4(inv_m1 * (beta * cs.z + cs.y * alpha * xo), per, dwv, dbv);
+        // ra, c1e; then the row's share c4' of the c-hat_j coefficient of KJ_j
+        *reinterpret_cast<float4*>(rs) = make_float4(rne * (w * kSplitInv2), rc.c1 * rne, 0.f, 0.f);
+        *reinterpret_cast<float4*>(rs + 4) = make_float4(row_c4_share(rc, inv_m1, cs.z, cs.y, xo), per, dwv, dbv);
         if (p.per) p.per[gr] = per;
     }
 }
@@ -1655,46 +1517,60 @@ TiledWs tiled_layout(int B, int N, int M, int D) {
 
 size_t tiled_workspace_bytes(int B, int N, int M, int D) { return tiled_layout(B, N, M, D).total * sizeof(float); }
 
+typedef GemmCfg<128, 128> C1;
+typedef GemmCfg<256, 256> C2;
+typedef GemmCfgDma C3;   // the same tile, operands by LDS-DMA: the contraction's K must be a multiple of 32
+
+// Allow the named kernels `bytes` of dynamic LDS.  Every launch, like the fused kernels: the attribute is per device and a
+// process may drive several.
+template <class... K>
+static hipError_t allow_lds(size_t bytes, K*... kernels) {
+    for (const void* fn : {reinterpret_cast<const void*>(kernels)...}) {
+        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+static unsigned tiles(int n, int t) { return (unsigned)((n + t - 1) / t); }
+// the DMA-fed contractions walk their tiles with one workgroup per CU (160 KB of LDS: one fits)
+static dim3 walk_grid(unsigned ntiles) {
+    int ncu = device_cu_count();
+    if (ncu < 8) ncu = 8;
+    ncu = ncu / 8 * 8;    // a workgroup's tiles b, b + grid, ... stay on one XCD when the grid is a multiple of 8
+    return dim3(ntiles < (unsigned)ncu ? ntiles : (unsigned)ncu);
+}
+// the 256 x 256 tile where both extents of a contraction's output reach it AND its grid still gives most of the CUs a
+// workgroup (a single batch of cfg5 has 160 big tiles), else 128 x 128
+constexpr unsigned kFill = 192;   // (measured: the long-K gC contraction gains from the big tile even at one workgroup per CU)
+
+// k_sim in the tile configuration its shape calls for
+static void launch_sim(const Problem& p, const TiledWs& L, hipStream_t stream) {
+    const int NM = p.N * p.M;
+    const bool big_sim = NM >= 256 && p.N >= 256 && (unsigned)p.B * tiles(NM, 256) * tiles(p.N, 256) >= kFill;
+    if (big_sim && p.D % 32 == 0)
+        hipLaunchKernelGGL(ge2e_tiled_sim<C3>, walk_grid((unsigned)p.B * tiles(NM, 256) * tiles(p.N, 256)), dim3(C2::NT), C2::LDS_BYTES, stream, p, L);
+    else if (big_sim)
+        hipLaunchKernelGGL(ge2e_tiled_sim<C2>, dim3((unsigned)p.B * tiles(NM, 256) * tiles(p.N, 256)), dim3(C2::NT), C2::LDS_BYTES, stream, p, L);
+    else
+        hipLaunchKernelGGL(ge2e_tiled_sim<C1>, dim3((unsigned)p.B * tiles(NM, 128) * tiles(p.N, 128)), dim3(C1::NT), C1::LDS_BYTES, stream, p, L);
+}
+
 hipError_t launch_tiled(const Problem& p, hipStream_t stream) {
     TiledWs L = tiled_layout(p.B, p.N, p.M, p.D);
     const int NM = p.N * p.M;
     const unsigned spk_blocks = (unsigned)((p.B * p.N + 3) / 4);
     const unsigned row_blocks = (unsigned)(((size_t)p.B * NM + 3) / 4);
-    typedef GemmCfg<128, 128> C1;
-    typedef GemmCfg<256, 256> C2;
-    typedef GemmCfgDma C3;   // the same tile, operands by LDS-DMA: the contraction's K must be a multiple of 32
-    {   // every launch, like the fused kernels: the attribute is per device and a process may drive several
-        const void* small[] = {reinterpret_cast<const void*>(ge2e_tiled_sim<C1>), reinterpret_cast<const void*>(ge2e_tiled_gc<C1>),
-                               reinterpret_cast<const void*>(ge2e_tiled_ge<C1>)};
-        const void* big[] = {reinterpret_cast<const void*>(ge2e_tiled_sim<C2>), reinterpret_cast<const void*>(ge2e_tiled_gc<C2>),
-                             reinterpret_cast<const void*>(ge2e_tiled_ge<C2>),
-                             reinterpret_cast<const void*>(ge2e_tiled_sim<C3>), reinterpret_cast<const void*>(ge2e_tiled_gc<C3>),
-                             reinterpret_cast<const void*>(ge2e_tiled_ge<C3>),
-                             reinterpret_cast<const void*>(ge2e_tiled_simrows<C3, false, false>), reinterpret_cast<const void*>(ge2e_tiled_simrows<C3, false, true>),
-                             reinterpret_cast<const void*>(ge2e_tiled_simrows<C3, true, false>), reinterpret_cast<const void*>(ge2e_tiled_simrows<C3, true, true>)};
-        for (const void* fn : small) {
-            const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)C1::LDS_BYTES);
-            if (e != hipSuccess) return e;
-        }
-        for (const void* fn : big) {
-            const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)C2::LDS_BYTES);
-            if (e != hipSuccess) return e;
-        }
-    }
-    auto tiles = [](int n, int t) { return (unsigned)((n + t - 1) / t); };
-    // the DMA-fed contractions walk their tiles with one workgroup per CU (160 KB of LDS: one fits)
-    int ncu = device_cu_count();
-    if (ncu < 8) ncu = 8;
-    ncu = ncu / 8 * 8;    // a workgroup's tiles b, b + grid, ... stay on one XCD when the grid is a multiple of 8
-    auto walk_grid = [&](unsigned ntiles) { return dim3(ntiles < (unsigned)ncu ? ntiles : (unsigned)ncu); };
-    // the 256 x 256 tile where both extents of the contraction's output reach it AND its grid still gives every CU
-    // most of the CUs a workgroup (a single batch of cfg5 has 160 big tiles), else 128 x 128
-    const unsigned fill = 192;   // (measured: the long-K gC contraction gains from the big tile even at one workgroup per CU)
-    const bool big_sim = NM >= 256 && p.N >= 256 && (unsigned)p.B * tiles(NM, 256) * tiles(p.N, 256) >= fill;
-    const bool big_gc = p.N >= 256 && p.D >= 256 && (unsigned)p.B * tiles(p.N, 256) * tiles(p.D, 256) >= fill;
-    const bool big_ge = NM >= 256 && p.D >= 256 && (unsigned)p.B * tiles(NM, 256) * tiles(p.D, 256) >= fill;
+    hipError_t e = allow_lds(C1::LDS_BYTES, ge2e_tiled_sim<C1>, ge2e_tiled_gc<C1>, ge2e_tiled_ge<C1>);
+    if (e != hipSuccess) return e;
+    e = allow_lds(C2::LDS_BYTES, ge2e_tiled_sim<C2>, ge2e_tiled_gc<C2>, ge2e_tiled_ge<C2>,
+                  ge2e_tiled_sim<C3>, ge2e_tiled_gc<C3>, ge2e_tiled_ge<C3>,
+                  ge2e_tiled_simrows<C3, false, false>, ge2e_tiled_simrows<C3, false, true>,
+                  ge2e_tiled_simrows<C3, true, false>, ge2e_tiled_simrows<C3, true, true>);
+    if (e != hipSuccess) return e;
+    const bool big_gc = p.N >= 256 && p.D >= 256 && (unsigned)p.B * tiles(p.N, 256) * tiles(p.D, 256) >= kFill;
+    const bool big_ge = NM >= 256 && p.D >= 256 && (unsigned)p.B * tiles(NM, 256) * tiles(p.D, 256) >= kFill;
     // one 256-slot tile holds a whole similarity row: similarity contraction + row pass in one kernel (config 4)
-    const bool fused_rows = L.npad <= 256 && p.N > 128 && NM >= 256 && p.D % 32 == 0 && (unsigned)p.B * tiles(NM, 256) >= fill;
+    const bool fused_rows = L.npad <= 256 && p.N > 128 && NM >= 256 && p.D % 32 == 0 && (unsigned)p.B * tiles(NM, 256) >= kFill;
     // k_gc has B ct dtiles tiles, each over ALL rows of its batch: at config 5 that is 192 workgroups for 256 CUs, one
     // round.  Cut the rows into S pieces when that fills the last round better (S = 4 there: three full rounds); the
     // partial sums go to the similarity block, dead once the row pass has run, and k_spk adds them in a fixed order.
@@ -1716,17 +1592,13 @@ hipError_t launch_tiled(const Problem& p, hipStream_t stream) {
             if (p.N == 256) hipLaunchKernelGGL((ge2e_tiled_simrows<C3, false, true>), g, dim3(C2::NT), C2::LDS_BYTES, stream, p, L);
             else hipLaunchKernelGGL((ge2e_tiled_simrows<C3, false, false>), g, dim3(C2::NT), C2::LDS_BYTES, stream, p, L);
         }
-    } else if (big_sim && p.D % 32 == 0)
-        hipLaunchKernelGGL(ge2e_tiled_sim<C3>, walk_grid((unsigned)p.B * tiles(NM, 256) * tiles(p.N, 256)), dim3(C2::NT), C2::LDS_BYTES, stream, p, L);
-    else if (big_sim)
-        hipLaunchKernelGGL(ge2e_tiled_sim<C2>, dim3((unsigned)p.B * tiles(NM, 256) * tiles(p.N, 256)), dim3(C2::NT), C2::LDS_BYTES, stream, p, L);
-    else
-        hipLaunchKernelGGL(ge2e_tiled_sim<C1>, dim3((unsigned)p.B * tiles(NM, 128) * tiles(p.N, 128)), dim3(C1::NT), C1::LDS_BYTES, stream, p, L);
+    } else
+        launch_sim(p, L, stream);
     if (fused_rows) {
     } else if (L.npad <= 256)
-        hipLaunchKernelGGL(ge2e_tiled_rows16, dim3((unsigned)(((size_t)p.B * NM + 15) / 16)), dim3(256), 0, stream, p, L);
+        hipLaunchKernelGGL(ge2e_tiled_rows<16>, dim3((unsigned)(((size_t)p.B * NM + 15) / 16)), dim3(256), 0, stream, p, L);
     else
-        hipLaunchKernelGGL(ge2e_tiled_rows, dim3(row_blocks), dim3(256), 0, stream, p, L);
+        hipLaunchKernelGGL(ge2e_tiled_rows<64>, dim3(row_blocks), dim3(256), 0, stream, p, L);
     if (p.dE) {
         if (big_gc && NM % 32 == 0)
             hipLaunchKernelGGL(ge2e_tiled_gc<C3>, walk_grid((unsigned)p.B * tiles(p.N, 256) * tiles(p.D, 256) * L.gc_split), dim3(C2::NT), C2::LDS_BYTES, stream, p, L);
@@ -1751,27 +1623,12 @@ hipError_t launch_tiled(const Problem& p, hipStream_t stream) {
 hipError_t launch_tiled_cos(const Problem& p, hipStream_t stream) {
     const TiledWs L = tiled_layout(p.B, p.N, p.M, p.D);
     const int NM = p.N * p.M;
-    typedef GemmCfg<128, 128> C1;
-    typedef GemmCfg<256, 256> C2;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(ge2e_tiled_sim<C1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)C1::LDS_BYTES);
+    hipError_t e = allow_lds(C1::LDS_BYTES, ge2e_tiled_sim<C1>);
     if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(ge2e_tiled_sim<C2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)C2::LDS_BYTES);
+    e = allow_lds(C2::LDS_BYTES, ge2e_tiled_sim<C2>, ge2e_tiled_sim<C3>);
     if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(ge2e_tiled_sim<GemmCfgDma>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)C2::LDS_BYTES);
-    if (e != hipSuccess) return e;
-    auto tiles = [](int n, int t) { return (unsigned)((n + t - 1) / t); };
-    const bool big_sim = NM >= 256 && p.N >= 256 && (unsigned)p.B * tiles(NM, 256) * tiles(p.N, 256) >= 192;
     launch_prep(p, L, stream);
-    if (big_sim && p.D % 32 == 0)
-    {   // (one workgroup per CU walks the tiles: see launch_tiled)
-        const int ncu = device_cu_count() < 8 ? 8 : device_cu_count();
-        const unsigned nt = (unsigned)p.B * tiles(NM, 256) * tiles(p.N, 256), cap = (unsigned)(ncu / 8 * 8);
-        hipLaunchKernelGGL(ge2e_tiled_sim<GemmCfgDma>, dim3(nt < cap ? nt : cap), dim3(C2::NT), C2::LDS_BYTES, stream, p, L);
-    }
-    else if (big_sim)
-        hipLaunchKernelGGL(ge2e_tiled_sim<C2>, dim3((unsigned)p.B * tiles(NM, 256) * tiles(p.N, 256)), dim3(C2::NT), C2::LDS_BYTES, stream, p, L);
-    else
-        hipLaunchKernelGGL(ge2e_tiled_sim<C1>, dim3((unsigned)p.B * tiles(NM, 128) * tiles(p.N, 128)), dim3(C1::NT), C1::LDS_BYTES, stream, p, L);
+    launch_sim(p, L, stream);
     hipLaunchKernelGGL(ge2e_tiled_cos, dim3((unsigned)(((size_t)p.B * NM + 3) / 4)), dim3(256), 0, stream, p, L);
     return hipGetLastError();
 }

@@ -433,11 +433,15 @@ def test_cos_sim_through_the_walked_dma_tiles(GF):
     assert np.abs(cos[B - 1].cpu().numpy() - orc.expand_form_cos_sim(t, orc.centroids(t)).numpy()).max() < 5e-6
 
 
-@pytest.mark.parametrize("shape", [(3, 256, 10, 256), (2, 200, 4, 64), (2, 129, 7, 128), (1, 256, 2, 64), (2, 255, 3, 192)])
+@pytest.mark.parametrize("shape", [(3, 256, 10, 256), (2, 200, 4, 64), (2, 129, 7, 128), (1, 256, 2, 64), (2, 255, 3, 192),
+                                   (96, 129, 2, 32), (96, 256, 2, 32)])
 @pytest.mark.parametrize("variant", ["softmax", "contrast"])
 def test_tiled_fused_similarity_and_row_pass(GF, shape, variant):
-    """129 <= N <= 256 (one 256-slot tile holds a similarity row): TILED runs the similarity contraction and the row pass
-    as ONE kernel (ge2e_tiled_simrows).  Uneven N (pad slots), row tiles that end inside a batch, both variants."""
+    """129 <= N <= 256 (one 256-slot tile holds a similarity row).  TILED runs the similarity contraction and the row pass
+    as ONE kernel (ge2e_tiled_simrows) once a launch has at least 192 row tiles of 256, B * ceil(N M / 256) >= 192: the two
+    B = 96 shapes (192 tiles each; N = 129: pad slots and a second row tile with 2 valid rows, N = 256: every slot of the
+    tile exists).  The five smaller launches (at most 30 tiles) take the separate similarity and row kernels over the same
+    range of N: uneven N, row tiles that end inside a batch.  Both variants."""
     B, N, M, D = shape
     E = orc.synth_embeddings(shape, "raw", seed=N + M)
     ref = orc.closed_form(E, 7.5, -2.0, variant=variant)
