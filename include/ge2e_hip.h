@@ -253,6 +253,24 @@ int ge2e_eer_counts(const float* sim, int B, int N, int M, const float* threshol
 int ge2e_sample_batch(const void* store, int store_is_f64, const long long* spk_offsets, const int* utter_idx,
                       const int* clip_start, int N, int M, int T, int L, int F, float* out, void* stream);
 
+/* ---- diagnostics (tests only): which kernels a call launches ---------------------------------------------------------
+ * Below ge2e_resolve_impl every launcher chooses again among kernels and template instantiations.  These queries print
+ * that choice -- made by the very functions the launchers switch on -- without a GPU and without launching anything:
+ * the names of the kernels the call would launch, in launch order, separated by commas, e.g.
+ *     tiled_prep<10,2>,tiled_sim<C3>,tiled_rows<64>,tiled_gc<C3>/4,tiled_spk,tiled_ge<C2>
+ * One name ("atom") per kernel instantiation; tiled_gc<C3> carries its row split (/1, /2, /4, /8) because the row
+ * pieces and the order of the final add differ per split.  Commas inside <> belong to a name.  Names are stable.
+ * snprintf-style: at most buf_bytes - 1 characters and a NUL are written to buf (host memory; NULL with buf_bytes = 0
+ * just measures), the full length is returned; < 0: the code the call itself would fail with for these arguments
+ * (GE2E_ERR_SHAPE, GE2E_ERR_VARIANT, GE2E_ERR_IMPL).  Grid sizes depend on the device and are no part of a plan.
+ *   ge2e_loss_plan     ge2e_loss_fwd_bwd(B, N, M, D, variant, impl) with dE != NULL (want_grad != 0) or dE == NULL;
+ *                      raw != 0: ge2e_loss_fwd_bwd_raw instead (impl is ignored)
+ *   ge2e_cos_sim_plan  ge2e_cos_sim on a workspace of ge2e_cos_sim_workspace_bytes (shapes off the matrix-core route: "generic")
+ *   ge2e_plan_atoms    every name the two queries above can print */
+int ge2e_loss_plan(int B, int N, int M, int D, int variant, int impl, int want_grad, int raw, char* buf, size_t buf_bytes);
+int ge2e_cos_sim_plan(int B, int N, int M, int D, char* buf, size_t buf_bytes);
+int ge2e_plan_atoms(char* buf, size_t buf_bytes);
+
 /* ---- diagnostics (tests only): device building blocks on caller data ------------------- */
 /* A,Bm [64][256], G [64][64] (|x| <= 1) -> X [64][64] = A.Bm^T, GE [64][256] = G.A,
  * GC [64][256] = G^T.Bm through the split-fp16 MFMA tile contractions. */

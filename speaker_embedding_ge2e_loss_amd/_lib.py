@@ -47,6 +47,9 @@ PROTOTYPES = {
     "ge2e_cos_sim_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "ge2e_cos_sim_centroids": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _fp, _fp]),
     "ge2e_calc_loss": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _fp, _fp, _fp]),
+    "ge2e_loss_plan": (C.c_int, [C.c_int] * 8 + [C.c_char_p, C.c_size_t]),
+    "ge2e_cos_sim_plan": (C.c_int, [C.c_int] * 4 + [C.c_char_p, C.c_size_t]),
+    "ge2e_plan_atoms": (C.c_int, [C.c_char_p, C.c_size_t]),
     "ge2e_selftest_split_gemm": (C.c_int, [_fp] * 7),
     "ge2e_selftest_wave_ops": (C.c_int, [_fp] * 3),
     "ge2e_selftest_rows16": (C.c_int, [_fp] * 6),
@@ -106,6 +109,47 @@ def load(path: str | None = None):
         raise GE2ELibraryError(f"ABI mismatch: library {lib.ge2e_abi_version()} != binding {ABI_VERSION}")
     _lib = lib
     return lib
+
+
+def split_plan(text: str) -> list[str]:
+    """The kernel names of a plan string: split at the commas outside <>."""
+    names, depth, cur = [], 0, ""
+    for ch in text:
+        depth += (ch == "<") - (ch == ">")
+        if ch == "," and depth == 0:
+            names.append(cur)
+            cur = ""
+        else:
+            cur += ch
+    return names + [cur] if cur else names
+
+
+def _plan(fn, *args) -> list[str]:
+    buf = C.create_string_buffer(4096)
+    n = fn(*args, buf, len(buf))
+    if n < 0:
+        raise ValueError(f"{fn.__name__}{args}: [{n}] {load().ge2e_strerror(n).decode()}")
+    if n >= len(buf):
+        buf = C.create_string_buffer(n + 1)
+        fn(*args, buf, len(buf))
+    return split_plan(buf.value.decode())
+
+
+def loss_plan(B: int, N: int, M: int, D: int, variant: str = "softmax", impl: str = "auto", want_grad: bool = True,
+              raw: bool = False) -> list[str]:
+    """Diagnostics: the kernels ge2e_loss_fwd_bwd (raw: ge2e_loss_fwd_bwd_raw) would launch, in order.  No GPU needed.
+    ValueError where the call itself would be refused."""
+    return _plan(load().ge2e_loss_plan, B, N, M, D, VARIANTS[variant], IMPLS[impl], int(want_grad), int(raw))
+
+
+def cos_sim_plan(B: int, N: int, M: int, D: int) -> list[str]:
+    """... ge2e_cos_sim on a workspace of ge2e_cos_sim_workspace_bytes would launch."""
+    return _plan(load().ge2e_cos_sim_plan, B, N, M, D)
+
+
+def plan_atoms() -> list[str]:
+    """Every kernel name the two queries can return."""
+    return _plan(load().ge2e_plan_atoms)
 
 
 def check(code: int, what: str):

@@ -16,6 +16,7 @@
 #include "ge2e_team_kernel.hpp"
 #include "ge2e_tail.hpp"
 #include "ge2e_wave.hpp"
+#include "ge2e_plan.hpp"
 
 using namespace ge2e;
 
@@ -235,6 +236,17 @@ int ge2e_loss_fwd_bwd_ragged(const float* E, const int* offsets, int B, int N, i
     return (int)launch_ragged(p, (hipStream_t)stream);
 }
 
+// ---- diagnostics: the launch plan of a call, from the launchers' own decision functions (ge2e_plan.hpp); no GPU needed ----
+int ge2e_loss_plan(int B, int N, int M, int D, int variant, int impl, int want_grad, int raw, char* buf, size_t buf_bytes) {
+    if (!shape_ok(B, N, M, D)) return GE2E_ERR_SHAPE;
+    if (!variant_ok(variant)) return GE2E_ERR_VARIANT;
+    if (raw) return wave_supports_raw(N, M, D) ? plan_string_loss(B, N, M, D, variant, GE2E_IMPL_WAVE, want_grad != 0, true, buf, buf_bytes) : GE2E_ERR_IMPL;
+    const int chosen = resolve(B, N, M, D, variant, impl);
+    return chosen < 0 ? chosen : plan_string_loss(B, N, M, D, variant, chosen, want_grad != 0, false, buf, buf_bytes);
+}
+
+int ge2e_plan_atoms(char* buf, size_t buf_bytes) { return plan_string_atoms(buf, buf_bytes); }
+
 int ge2e_raw_supported(int N, int M, int D) { return (N >= 1 && M >= 2 && D >= 1 && wave_supports_raw(N, M, D)) ? 1 : 0; }
 
 int ge2e_loss_fwd_bwd_raw(const float* Y, const int* src, int B, int N, int M, int D, const float* w, const float* b,
@@ -262,6 +274,11 @@ size_t ge2e_cos_sim_workspace_bytes(int B, int N, int M, int D) {
     const size_t g = ws_bytes(B, N, M, D, GE2E_IMPL_GENERIC);      // what run() asks for (the control block's room included)
     const size_t t = cos_on_mfma(N, M, D) ? tiled_workspace_bytes(B, N, M, D) : 0;
     return g > t ? g : t;
+}
+
+int ge2e_cos_sim_plan(int B, int N, int M, int D, char* buf, size_t buf_bytes) {
+    if (!shape_ok(B, N, M, D)) return GE2E_ERR_SHAPE;
+    return plan_string_cos(B, N, M, D, cos_on_mfma(N, M, D), buf, buf_bytes);
 }
 
 int ge2e_cos_sim(const float* E, int B, int N, int M, int D, float eps_cos, float eps, float* cos,

@@ -1,6 +1,7 @@
 // Workspace layout + launchers of the fused one-workgroup-per-batch kernels.
 #pragma once
 #include "ge2e_common.hpp"
+#include "ge2e_plan.hpp"
 
 namespace ge2e {
 

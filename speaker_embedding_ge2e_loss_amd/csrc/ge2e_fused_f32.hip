@@ -584,10 +584,12 @@ static hipError_t launch_nch(const Problem& p, const FusedWs& L, size_t lds, hip
     return hipGetLastError();
 }
 
+FusedPlan plan_fused_f32(int D) { return {D / 64 < 4 ? D / 64 : 4}; }
+
 hipError_t launch_fused_f32(const Problem& p, hipStream_t stream) {
     const size_t lds = fused_f32_lds_bytes(p.D);
     const FusedWs L = fused_f32_layout(p.N, p.M, p.D);
-    switch (p.D / 64) {
+    switch (plan_fused_f32(p.D).nch) {
         case 1: return launch_nch<1>(p, L, lds, stream);
         case 2: return launch_nch<2>(p, L, lds, stream);
         case 3: return launch_nch<3>(p, L, lds, stream);

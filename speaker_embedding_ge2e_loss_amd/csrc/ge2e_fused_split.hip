@@ -91,10 +91,12 @@ static hipError_t launch_nch(const Problem& p, const FusedWs& L, size_t lds, hip
     return hipGetLastError();
 }
 
+FusedPlan plan_fused_split(int D) { return {pad64(D) / 64 < 4 ? pad64(D) / 64 : 4}; }
+
 hipError_t launch_fused_split(const Problem& p, hipStream_t stream) {
     const size_t lds = fused_split_lds_bytes(p.D);
     const FusedWs L = fused_split_layout(p.N, p.M, p.D);
-    switch (pad64(p.D) / 64) {
+    switch (plan_fused_split(p.D).nch) {
         case 1: return launch_nch<1>(p, L, lds, stream);
         case 2: return launch_nch<2>(p, L, lds, stream);
         case 3: return launch_nch<3>(p, L, lds, stream);

@@ -34,6 +34,7 @@
 #include "ge2e_team_kernel.hpp"
 #include "ge2e_team_dev.hpp"
 #include "ge2e_fused.hpp"
+#include <algorithm>
 #include <atomic>
 
 namespace ge2e {
@@ -106,9 +107,7 @@ size_t team_workspace_bytes(int B, int N, int M, int D) {
 // ---------------------------------------------------------------------------------------------
 // D = 64 * NCH; MR >= M rows of a speaker are prefetched into registers; RBT > 0: the member's images have exactly
 // RBT 16-row blocks (compile-time trip counts for the metric shape), RBT == 0: L.rt / 16 at run time.
-// FWD: the forward-only instantiation of the metric shape (similarity + loss, dE == NULL known at compile time: no held /
-// fragment / partial-gradient registers, no gradient phases in the loop at all).
-template <int NCH, int MR, int RBT, bool CONTRAST, bool FWD = false>
+template <int NCH, int MR, int RBT, bool CONTRAST>
 __global__ __launch_bounds__(512, 2) void ge2e_team_kernel(Problem p, TeamKWs L, FusedWs F) {
     extern __shared__ __attribute__((aligned(16))) float smem_f[];
     constexpr int D = 64 * NCH;
@@ -193,7 +192,7 @@ __global__ __launch_bounds__(512, 2) void ge2e_team_kernel(Problem p, TeamKWs L,
     const float eps_cos2 = eps_cos * eps_cos;                                                  \
     const float fM = (float)mc_, inv_m = rcp_nr(fM), inv_m1 = rcp_nr((float)(mc_ - 1));       \
     (void)w; (void)bias; (void)eps_cos2; (void)fM; (void)inv_m; (void)inv_m1; (void)le_
-    const bool want_grad = !FWD && p.dE != nullptr;
+    const bool want_grad = p.dE != nullptr;
     const int tX = wid & 3, khX = wid >> 2;            // X: slot tile and K half of this wave
     constexpr float LOG2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
 
@@ -965,9 +964,9 @@ hipError_t launch_team_head_init(void* head, size_t bytes, bool raise_abort, hip
     return hipGetLastError();
 }
 
-template <int NCH, int MR, int RBT, bool CONTRAST, bool FWD = false>
+template <int NCH, int MR, int RBT, bool CONTRAST>
 static hipError_t launch_nch(Problem& p, TeamKWs& L, const FusedWs& F, hipStream_t stream) {
-    const void* fn = reinterpret_cast<const void*>(ge2e_team_kernel<NCH, MR, RBT, CONTRAST, FWD>);
+    const void* fn = reinterpret_cast<const void*>(ge2e_team_kernel<NCH, MR, RBT, CONTRAST>);
     static KernelLaunchState state;     // one per instantiation; per-device entries inside
     int nb = 0;
     hipError_t err = prepare_kernel(state, fn, 512, (unsigned)L.lds_bytes, &nb);
@@ -987,17 +986,26 @@ static hipError_t launch_nch(Problem& p, TeamKWs& L, const FusedWs& F, hipStream
     if (p.grid_cap > 0 && p.grid_cap < grid)      // diagnostics: fewer teams, more batches through each (whole XCD rounds)
         grid = p.grid_cap / (MAX_XCD * TEAM) * (MAX_XCD * TEAM) > 0 ? p.grid_cap / (MAX_XCD * TEAM) * (MAX_XCD * TEAM) : MAX_XCD * TEAM;
     if (nb < 1 || grid > nb * team_cu_count()) return hipErrorCooperativeLaunchTooLarge;
-    hipLaunchKernelGGL((ge2e_team_kernel<NCH, MR, RBT, CONTRAST, FWD>), dim3(grid), dim3(512), L.lds_bytes, stream, p, L, F);
+    hipLaunchKernelGGL((ge2e_team_kernel<NCH, MR, RBT, CONTRAST>), dim3(grid), dim3(512), L.lds_bytes, stream, p, L, F);
     return hipGetLastError();
 }
 template <int NCH, int MR>
-static hipError_t launch_variant(Problem& p, TeamKWs& L, const FusedWs& F, hipStream_t stream) {
-    if (NCH == 4 && MR == 10 && L.rt == 80 && p.M == 10 && p.N == 64 && p.D == 256) {   // the metric shape: compile-time N, M, D, trip counts
-        if (p.dE == nullptr)    // ... and its forward-only form (evaluation: s4:61-110, s5:42-44)
-            return p.variant == 1 ? launch_nch<4, 10, 5, true, true>(p, L, F, stream) : launch_nch<4, 10, 5, false, true>(p, L, F, stream);
-        return p.variant == 1 ? launch_nch<4, 10, 5, true>(p, L, F, stream) : launch_nch<4, 10, 5, false>(p, L, F, stream);
-    }
-    return p.variant == 1 ? launch_nch<NCH, MR, 0, true>(p, L, F, stream) : launch_nch<NCH, MR, 0, false>(p, L, F, stream);
+static hipError_t launch_variant(Problem& p, TeamKWs& L, const FusedWs& F, const TeamPlan& plan, hipStream_t stream) {
+    if (NCH == 4 && MR == 10 && plan.rbt == 5)      // the metric shape: compile-time N, M, D, trip counts
+        return plan.contrast ? launch_nch<4, 10, 5, true>(p, L, F, stream) : launch_nch<4, 10, 5, false>(p, L, F, stream);
+    return plan.contrast ? launch_nch<NCH, MR, 0, true>(p, L, F, stream) : launch_nch<NCH, MR, 0, false>(p, L, F, stream);
+}
+
+// The instantiation of a team call, training (ge2e_team_kernel) and forward-only (ge2e_team_fwd_kernel) alike:
+// NCH = ceil(D / 64) column chunks, MR = 10 or 16 row registers per speaker, and RBT = 5 compile-time row blocks at the
+// metric shape N = 64, M = 10, D = 256 (every member full: 8 speakers, 80 rows).
+TeamPlan plan_team(int N, int M, int D, int variant) {
+    TeamPlan t{};
+    t.nch = (D + 63) / 64 < 4 ? (D + 63) / 64 : 4;
+    t.mr = M <= 10 ? 10 : 16;
+    t.rbt = (team_layout(N, M, D).rt == 80 && M == 10 && N == 64 && D == 256) ? 5 : 0;
+    t.contrast = variant == 1;
+    return t;
 }
 
 hipError_t launch_team(const Problem& p_in, hipStream_t stream) {
@@ -1013,26 +1021,20 @@ hipError_t launch_team(const Problem& p_in, hipStream_t stream) {
     // the redo body's slices behind the teams' exchange areas; its LDS if that is larger than the team kernel's
     L.fb_off = align_up(L.head_bytes + (size_t)(team_grid(p.B) / TEAM) * team_exchange((p.D + 63) / 64 * 64).stride, 256);
     L.fb_wgs = team_fallback_grid(p.B);
-    if (fused_split_lds_bytes(p.D) > L.lds_bytes) L.lds_bytes = fused_split_lds_bytes(p.D);
-    hipError_t err;
-    if (p.dE == nullptr) {          // similarity + loss only: the pipelined forward kernel (ge2e_team_fwd.hip)
-        err = launch_team_fwd(p, L, F, stream);
-    } else if (p.M <= 10) {
-        switch ((p.D + 63) / 64) {
-            case 1: err = launch_variant<1, 10>(p, L, F, stream); break;
-            case 2: err = launch_variant<2, 10>(p, L, F, stream); break;
-            case 3: err = launch_variant<3, 10>(p, L, F, stream); break;
-            default: err = launch_variant<4, 10>(p, L, F, stream); break;
-        }
-    } else {
-        switch ((p.D + 63) / 64) {
-            case 1: err = launch_variant<1, 16>(p, L, F, stream); break;
-            case 2: err = launch_variant<2, 16>(p, L, F, stream); break;
-            case 3: err = launch_variant<3, 16>(p, L, F, stream); break;
-            default: err = launch_variant<4, 16>(p, L, F, stream); break;
-        }
+    L.lds_bytes = std::max(L.lds_bytes, fused_split_lds_bytes(p.D));
+    if (p.dE == nullptr)            // similarity + loss only: the pipelined forward kernel (ge2e_team_fwd.hip)
+        return launch_team_fwd(p, L, F, stream);
+    const TeamPlan plan = plan_team(p.N, p.M, p.D, p.variant);
+    switch (plan.mr * 10 + plan.nch) {
+        case 101: return launch_variant<1, 10>(p, L, F, plan, stream);
+        case 102: return launch_variant<2, 10>(p, L, F, plan, stream);
+        case 103: return launch_variant<3, 10>(p, L, F, plan, stream);
+        case 104: return launch_variant<4, 10>(p, L, F, plan, stream);
+        case 161: return launch_variant<1, 16>(p, L, F, plan, stream);
+        case 162: return launch_variant<2, 16>(p, L, F, plan, stream);
+        case 163: return launch_variant<3, 16>(p, L, F, plan, stream);
+        default: return launch_variant<4, 16>(p, L, F, plan, stream);
     }
-    return err;
 }
 
 }  // namespace ge2e

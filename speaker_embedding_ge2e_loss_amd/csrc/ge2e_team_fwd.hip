@@ -27,6 +27,8 @@
 //
 // LDS per member: e-hat hi / lo images 80 KB + X halves 43.5 KB + row scalars (double-buffered) 5 KB: one workgroup per CU.
 // Exchange per batch and team: 64 KB of centroid fragments (double-buffered by parity) + 128 bytes of scalars.
+#include <algorithm>
+
 #include "ge2e_common.hpp"
 #include "ge2e_split_gemm.hpp"
 #include "ge2e_team.hpp"
@@ -617,7 +619,7 @@ static hipError_t launch_fwd_nch(Problem& p, TeamKWs& L, const FusedWs& F, hipSt
     const void* fn = reinterpret_cast<const void*>(ge2e_team_fwd_kernel<NCH, MR, RBT, CONTRAST>);
     static KernelLaunchState state;
     unsigned lds = (unsigned)team_fwd_lds_bytes(L.rt, 64 * NCH);             // (NCH = ceil(D / 64): padded columns)
-    if (fused_split_lds_bytes(p.D) > lds) lds = (unsigned)fused_split_lds_bytes(p.D);   // ... or the redo body's
+    lds = std::max(lds, (unsigned)fused_split_lds_bytes(p.D));   // ... or the redo body's
     int nb = 0;
     hipError_t err = prepare_kernel(state, fn, 512, lds, &nb);
     if (err != hipSuccess) return err;
@@ -633,27 +635,24 @@ static hipError_t launch_fwd_nch(Problem& p, TeamKWs& L, const FusedWs& F, hipSt
     return hipGetLastError();
 }
 template <int NCH, int MR>
-static hipError_t launch_fwd_variant(Problem& p, TeamKWs& L, const FusedWs& F, hipStream_t stream) {
-    if (NCH == 4 && MR == 10 && L.rt == 80 && p.M == 10 && p.N == 64 && p.D == 256)     // the metric shape: compile-time N, M, D
-        return p.variant == 1 ? launch_fwd_nch<4, 10, 5, true>(p, L, F, stream) : launch_fwd_nch<4, 10, 5, false>(p, L, F, stream);
-    return p.variant == 1 ? launch_fwd_nch<NCH, MR, 0, true>(p, L, F, stream) : launch_fwd_nch<NCH, MR, 0, false>(p, L, F, stream);
+static hipError_t launch_fwd_variant(Problem& p, TeamKWs& L, const FusedWs& F, const TeamPlan& plan, hipStream_t stream) {
+    if (NCH == 4 && MR == 10 && plan.rbt == 5)      // the metric shape: compile-time N, M, D
+        return plan.contrast ? launch_fwd_nch<4, 10, 5, true>(p, L, F, stream) : launch_fwd_nch<4, 10, 5, false>(p, L, F, stream);
+    return plan.contrast ? launch_fwd_nch<NCH, MR, 0, true>(p, L, F, stream) : launch_fwd_nch<NCH, MR, 0, false>(p, L, F, stream);
 }
 
-// the team launch of a forward-only call (p.dE == NULL)
+// the team launch of a forward-only call (p.dE == NULL): the instantiation plan_team names, of this file's kernel
 hipError_t launch_team_fwd(Problem& p, TeamKWs& L, const FusedWs& F, hipStream_t stream) {
-    if (p.M <= 10) {
-        switch ((p.D + 63) / 64) {
-            case 1: return launch_fwd_variant<1, 10>(p, L, F, stream);
-            case 2: return launch_fwd_variant<2, 10>(p, L, F, stream);
-            case 3: return launch_fwd_variant<3, 10>(p, L, F, stream);
-            default: return launch_fwd_variant<4, 10>(p, L, F, stream);
-        }
-    }
-    switch ((p.D + 63) / 64) {
-        case 1: return launch_fwd_variant<1, 16>(p, L, F, stream);
-        case 2: return launch_fwd_variant<2, 16>(p, L, F, stream);
-        case 3: return launch_fwd_variant<3, 16>(p, L, F, stream);
-        default: return launch_fwd_variant<4, 16>(p, L, F, stream);
+    const TeamPlan plan = plan_team(p.N, p.M, p.D, p.variant);
+    switch (plan.mr * 10 + plan.nch) {
+        case 101: return launch_fwd_variant<1, 10>(p, L, F, plan, stream);
+        case 102: return launch_fwd_variant<2, 10>(p, L, F, plan, stream);
+        case 103: return launch_fwd_variant<3, 10>(p, L, F, plan, stream);
+        case 104: return launch_fwd_variant<4, 10>(p, L, F, plan, stream);
+        case 161: return launch_fwd_variant<1, 16>(p, L, F, plan, stream);
+        case 162: return launch_fwd_variant<2, 16>(p, L, F, plan, stream);
+        case 163: return launch_fwd_variant<3, 16>(p, L, F, plan, stream);
+        default: return launch_fwd_variant<4, 16>(p, L, F, plan, stream);
     }
 }
 

@@ -4,6 +4,7 @@
 #include "ge2e_common.hpp"
 #include "ge2e_team.hpp"   // formation + hand-off building blocks
 #include "ge2e_fused.hpp"  // FusedWs: the layout of the body that redoes a call without teams
+#include "ge2e_plan.hpp"
 
 namespace ge2e {
 

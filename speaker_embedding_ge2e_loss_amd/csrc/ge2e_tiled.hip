@@ -702,12 +702,20 @@ __global__ __launch_bounds__(256) void ge2e_tiled_prep(Problem p, TiledWs L) {
     }
 }
 // the instantiation for a shape: rows in registers when M <= 10 and D <= 768 (40 / 80 / 120 row registers per lane)
-static void launch_prep(const Problem& p, const TiledWs& L, hipStream_t stream) {
+static PrepPlan plan_prep(int M, int D) {
+    if (M <= 10 && D <= 256) return {10, 1};
+    if (M <= 10 && D <= 512) return {10, 2};
+    if (M <= 10 && D <= 768) return {10, 3};
+    return {0, 4};
+}
+static void launch_prep(const Problem& p, const TiledWs& L, const PrepPlan& plan, hipStream_t stream) {
     const dim3 grid((unsigned)((p.B * p.N + 3) / 4)), block(256);
-    if (p.M <= 10 && p.D <= 256) hipLaunchKernelGGL((ge2e_tiled_prep<10, 1>), grid, block, 0, stream, p, L);
-    else if (p.M <= 10 && p.D <= 512) hipLaunchKernelGGL((ge2e_tiled_prep<10, 2>), grid, block, 0, stream, p, L);
-    else if (p.M <= 10 && p.D <= 768) hipLaunchKernelGGL((ge2e_tiled_prep<10, 3>), grid, block, 0, stream, p, L);
-    else hipLaunchKernelGGL((ge2e_tiled_prep<0, 4>), grid, block, 0, stream, p, L);
+    switch (plan.np) {
+        case 1: hipLaunchKernelGGL((ge2e_tiled_prep<10, 1>), grid, block, 0, stream, p, L); break;
+        case 2: hipLaunchKernelGGL((ge2e_tiled_prep<10, 2>), grid, block, 0, stream, p, L); break;
+        case 3: hipLaunchKernelGGL((ge2e_tiled_prep<10, 3>), grid, block, 0, stream, p, L); break;
+        default: hipLaunchKernelGGL((ge2e_tiled_prep<0, 4>), grid, block, 0, stream, p, L); break;
+    }
 }
 
 // Workgroups go to the XCDs round-robin (workgroup b runs on XCD b % 8), each XCD with an L2 of its own.  Tiles are
@@ -1542,21 +1550,55 @@ static dim3 walk_grid(unsigned ntiles) {
 // the 256 x 256 tile where both extents of a contraction's output reach it AND its grid still gives most of the CUs a
 // workgroup (a single batch of cfg5 has 160 big tiles), else 128 x 128
 constexpr unsigned kFill = 192;   // (measured: the long-K gC contraction gains from the big tile even at one workgroup per CU)
+// ... fed by LDS-DMA where the contraction's K is a multiple of 32, from registers where not
+static int plan_tile(int B, int rows, int cols, int K) {
+    if (!(rows >= 256 && cols >= 256 && (unsigned)B * tiles(rows, 256) * tiles(cols, 256) >= kFill)) return kTileC1;
+    return K % 32 == 0 ? kTileC3 : kTileC2;
+}
 
-// k_sim in the tile configuration its shape calls for
-static void launch_sim(const Problem& p, const TiledWs& L, hipStream_t stream) {
+// ---- the decisions: every shape-dependent choice of launch_tiled / launch_tiled_cos, and nothing else ---------------------
+TiledCosPlan plan_tiled_cos(int B, int N, int M, int D) { return {plan_prep(M, D), plan_tile(B, N * M, N, D)}; }
+
+TiledPlan plan_tiled(int B, int N, int M, int D, int variant, bool want_grad) {
+    const int NM = N * M, npad = (N + 63) / 64 * 64;
+    TiledPlan t{};
+    t.prep = plan_prep(M, D);
+    // one 256-slot tile holds a whole similarity row: similarity contraction + row pass in one kernel (config 4)
+    t.simrows = npad <= 256 && N > 128 && NM >= 256 && D % 32 == 0 && (unsigned)B * tiles(NM, 256) >= kFill;
+    t.simrows_contrast = t.simrows && variant == 1;
+    t.simrows_full = t.simrows && N == 256;
+    t.sim = t.simrows ? kTileNone : plan_tile(B, NM, N, D);
+    t.rows = t.simrows ? 0 : npad <= 256 ? 16 : 64;
+    t.gc_split = 1;
+    t.reduce = !want_grad;      // forward only: nothing runs after k_rows that could carry the sums
+    if (!want_grad) return t;
+    t.gc = plan_tile(B, N, D, NM);
+    t.ge = plan_tile(B, NM, D, N);
+    // k_gc has B ct dtiles tiles, each over ALL rows of its batch: at config 5 that is 192 workgroups for 256 CUs, one
+    // round.  Cut the rows into S pieces when that fills the last round better (S = 4 there: three full rounds); the
+    // partial sums go to the similarity block, dead once the row pass has run, and k_spk adds them in a fixed order.
+    if (t.gc == kTileC3) {
+        const unsigned tiles_gc = (unsigned)B * tiles(N, 256) * tiles(D, 256);
+        auto fillq = [](unsigned wg) { return (double)wg / (double)((wg + 255) / 256 * 256); };
+        for (int sp : {2, 4, 8})
+            if (NM / 32 >= 8 * sp && (size_t)sp * N * D <= (size_t)NM * npad && fillq(tiles_gc * sp) > fillq(tiles_gc * t.gc_split) + 0.1) t.gc_split = sp;
+    }
+    return t;
+}
+
+// k_sim in the tile configuration its plan names
+static void launch_sim(const Problem& p, const TiledWs& L, int cfg, hipStream_t stream) {
     const int NM = p.N * p.M;
-    const bool big_sim = NM >= 256 && p.N >= 256 && (unsigned)p.B * tiles(NM, 256) * tiles(p.N, 256) >= kFill;
-    if (big_sim && p.D % 32 == 0)
-        hipLaunchKernelGGL(ge2e_tiled_sim<C3>, walk_grid((unsigned)p.B * tiles(NM, 256) * tiles(p.N, 256)), dim3(C2::NT), C2::LDS_BYTES, stream, p, L);
-    else if (big_sim)
-        hipLaunchKernelGGL(ge2e_tiled_sim<C2>, dim3((unsigned)p.B * tiles(NM, 256) * tiles(p.N, 256)), dim3(C2::NT), C2::LDS_BYTES, stream, p, L);
-    else
-        hipLaunchKernelGGL(ge2e_tiled_sim<C1>, dim3((unsigned)p.B * tiles(NM, 128) * tiles(p.N, 128)), dim3(C1::NT), C1::LDS_BYTES, stream, p, L);
+    switch (cfg) {
+        case kTileC3: hipLaunchKernelGGL(ge2e_tiled_sim<C3>, walk_grid((unsigned)p.B * tiles(NM, 256) * tiles(p.N, 256)), dim3(C2::NT), C2::LDS_BYTES, stream, p, L); break;
+        case kTileC2: hipLaunchKernelGGL(ge2e_tiled_sim<C2>, dim3((unsigned)p.B * tiles(NM, 256) * tiles(p.N, 256)), dim3(C2::NT), C2::LDS_BYTES, stream, p, L); break;
+        default: hipLaunchKernelGGL(ge2e_tiled_sim<C1>, dim3((unsigned)p.B * tiles(NM, 128) * tiles(p.N, 128)), dim3(C1::NT), C1::LDS_BYTES, stream, p, L); break;
+    }
 }
 
 hipError_t launch_tiled(const Problem& p, hipStream_t stream) {
     TiledWs L = tiled_layout(p.B, p.N, p.M, p.D);
+    const TiledPlan plan = plan_tiled(p.B, p.N, p.M, p.D, p.variant, p.dE != nullptr);
     const int NM = p.N * p.M;
     const unsigned spk_blocks = (unsigned)((p.B * p.N + 3) / 4);
     const unsigned row_blocks = (unsigned)(((size_t)p.B * NM + 3) / 4);
@@ -1567,54 +1609,38 @@ hipError_t launch_tiled(const Problem& p, hipStream_t stream) {
                   ge2e_tiled_simrows<C3, false, false>, ge2e_tiled_simrows<C3, false, true>,
                   ge2e_tiled_simrows<C3, true, false>, ge2e_tiled_simrows<C3, true, true>);
     if (e != hipSuccess) return e;
-    const bool big_gc = p.N >= 256 && p.D >= 256 && (unsigned)p.B * tiles(p.N, 256) * tiles(p.D, 256) >= kFill;
-    const bool big_ge = NM >= 256 && p.D >= 256 && (unsigned)p.B * tiles(NM, 256) * tiles(p.D, 256) >= kFill;
-    // one 256-slot tile holds a whole similarity row: similarity contraction + row pass in one kernel (config 4)
-    const bool fused_rows = L.npad <= 256 && p.N > 128 && NM >= 256 && p.D % 32 == 0 && (unsigned)p.B * tiles(NM, 256) >= kFill;
-    // k_gc has B ct dtiles tiles, each over ALL rows of its batch: at config 5 that is 192 workgroups for 256 CUs, one
-    // round.  Cut the rows into S pieces when that fills the last round better (S = 4 there: three full rounds); the
-    // partial sums go to the similarity block, dead once the row pass has run, and k_spk adds them in a fixed order.
-    if (big_gc && NM % 32 == 0) {
-        const unsigned tiles_gc = (unsigned)p.B * tiles(p.N, 256) * tiles(p.D, 256);
-        auto fillq = [](unsigned wg) { return (double)wg / (double)((wg + 255) / 256 * 256); };
-        int best = 1;
-        for (int sp : {2, 4, 8})
-            if (NM / 32 >= 8 * sp && (size_t)sp * p.N * p.D <= (size_t)NM * L.npad && fillq(tiles_gc * sp) > fillq(tiles_gc * best) + 0.1) best = sp;
-        L.gc_split = best;
-    }
-    launch_prep(p, L, stream);
-    if (fused_rows) {
+    L.gc_split = plan.gc_split;
+    launch_prep(p, L, plan.prep, stream);
+    if (plan.simrows) {
         const dim3 g((unsigned)p.B * tiles(NM, 256));
-        if (p.variant == 1) {
-            if (p.N == 256) hipLaunchKernelGGL((ge2e_tiled_simrows<C3, true, true>), g, dim3(C2::NT), C2::LDS_BYTES, stream, p, L);
+        if (plan.simrows_contrast) {
+            if (plan.simrows_full) hipLaunchKernelGGL((ge2e_tiled_simrows<C3, true, true>), g, dim3(C2::NT), C2::LDS_BYTES, stream, p, L);
             else hipLaunchKernelGGL((ge2e_tiled_simrows<C3, true, false>), g, dim3(C2::NT), C2::LDS_BYTES, stream, p, L);
         } else {
-            if (p.N == 256) hipLaunchKernelGGL((ge2e_tiled_simrows<C3, false, true>), g, dim3(C2::NT), C2::LDS_BYTES, stream, p, L);
+            if (plan.simrows_full) hipLaunchKernelGGL((ge2e_tiled_simrows<C3, false, true>), g, dim3(C2::NT), C2::LDS_BYTES, stream, p, L);
             else hipLaunchKernelGGL((ge2e_tiled_simrows<C3, false, false>), g, dim3(C2::NT), C2::LDS_BYTES, stream, p, L);
         }
     } else
-        launch_sim(p, L, stream);
-    if (fused_rows) {
-    } else if (L.npad <= 256)
-        hipLaunchKernelGGL(ge2e_tiled_rows<16>, dim3((unsigned)(((size_t)p.B * NM + 15) / 16)), dim3(256), 0, stream, p, L);
-    else
-        hipLaunchKernelGGL(ge2e_tiled_rows<64>, dim3(row_blocks), dim3(256), 0, stream, p, L);
-    if (p.dE) {
-        if (big_gc && NM % 32 == 0)
-            hipLaunchKernelGGL(ge2e_tiled_gc<C3>, walk_grid((unsigned)p.B * tiles(p.N, 256) * tiles(p.D, 256) * L.gc_split), dim3(C2::NT), C2::LDS_BYTES, stream, p, L);
-        else if (big_gc)
-            hipLaunchKernelGGL(ge2e_tiled_gc<C2>, dim3((unsigned)p.B * tiles(p.N, 256) * tiles(p.D, 256)), dim3(C2::NT), C2::LDS_BYTES, stream, p, L);
-        else
-            hipLaunchKernelGGL(ge2e_tiled_gc<C1>, dim3((unsigned)p.B * tiles(p.N, 128) * tiles(p.D, 128)), dim3(C1::NT), C1::LDS_BYTES, stream, p, L);
-        hipLaunchKernelGGL(ge2e_tiled_spk, dim3(spk_blocks), dim3(256), 0, stream, p, L);
-        if (big_ge && p.N % 32 == 0)
-            hipLaunchKernelGGL(ge2e_tiled_ge<C3>, walk_grid((unsigned)p.B * tiles(NM, 256) * tiles(p.D, 256)), dim3(C2::NT), C2::LDS_BYTES, stream, p, L);
-        else if (big_ge)
-            hipLaunchKernelGGL(ge2e_tiled_ge<C2>, dim3((unsigned)p.B * tiles(NM, 256) * tiles(p.D, 256)), dim3(C2::NT), C2::LDS_BYTES, stream, p, L);
-        else
-            hipLaunchKernelGGL(ge2e_tiled_ge<C1>, dim3((unsigned)p.B * tiles(NM, 128) * tiles(p.D, 128)), dim3(C1::NT), C1::LDS_BYTES, stream, p, L);
+        launch_sim(p, L, plan.sim, stream);
+    switch (plan.rows) {
+        case 16: hipLaunchKernelGGL(ge2e_tiled_rows<16>, dim3((unsigned)(((size_t)p.B * NM + 15) / 16)), dim3(256), 0, stream, p, L); break;
+        case 64: hipLaunchKernelGGL(ge2e_tiled_rows<64>, dim3(row_blocks), dim3(256), 0, stream, p, L); break;
+        default: break;     // the row pass ran inside simrows
     }
-    else   // forward only: nothing ran after k_rows that could carry the sums
+    switch (plan.gc) {
+        case kTileC3: hipLaunchKernelGGL(ge2e_tiled_gc<C3>, walk_grid((unsigned)p.B * tiles(p.N, 256) * tiles(p.D, 256) * L.gc_split), dim3(C2::NT), C2::LDS_BYTES, stream, p, L); break;
+        case kTileC2: hipLaunchKernelGGL(ge2e_tiled_gc<C2>, dim3((unsigned)p.B * tiles(p.N, 256) * tiles(p.D, 256)), dim3(C2::NT), C2::LDS_BYTES, stream, p, L); break;
+        case kTileC1: hipLaunchKernelGGL(ge2e_tiled_gc<C1>, dim3((unsigned)p.B * tiles(p.N, 128) * tiles(p.D, 128)), dim3(C1::NT), C1::LDS_BYTES, stream, p, L); break;
+        default: break;     // forward only
+    }
+    if (plan.gc != kTileNone) hipLaunchKernelGGL(ge2e_tiled_spk, dim3(spk_blocks), dim3(256), 0, stream, p, L);
+    switch (plan.ge) {
+        case kTileC3: hipLaunchKernelGGL(ge2e_tiled_ge<C3>, walk_grid((unsigned)p.B * tiles(NM, 256) * tiles(p.D, 256)), dim3(C2::NT), C2::LDS_BYTES, stream, p, L); break;
+        case kTileC2: hipLaunchKernelGGL(ge2e_tiled_ge<C2>, dim3((unsigned)p.B * tiles(NM, 256) * tiles(p.D, 256)), dim3(C2::NT), C2::LDS_BYTES, stream, p, L); break;
+        case kTileC1: hipLaunchKernelGGL(ge2e_tiled_ge<C1>, dim3((unsigned)p.B * tiles(NM, 128) * tiles(p.D, 128)), dim3(C1::NT), C1::LDS_BYTES, stream, p, L); break;
+        default: break;
+    }
+    if (plan.reduce)   // forward only: nothing ran after k_rows that could carry the sums
         hipLaunchKernelGGL(ge2e_tiled_reduce, dim3((unsigned)p.B), dim3(256), 0, stream, p, L);
     return hipGetLastError();
 }
@@ -1622,13 +1648,14 @@ hipError_t launch_tiled(const Problem& p, hipStream_t stream) {
 // Forward half only, for ge2e_cos_sim: preparation, similarity contraction on the matrix cores, cos output.
 hipError_t launch_tiled_cos(const Problem& p, hipStream_t stream) {
     const TiledWs L = tiled_layout(p.B, p.N, p.M, p.D);
+    const TiledCosPlan plan = plan_tiled_cos(p.B, p.N, p.M, p.D);
     const int NM = p.N * p.M;
     hipError_t e = allow_lds(C1::LDS_BYTES, ge2e_tiled_sim<C1>);
     if (e != hipSuccess) return e;
     e = allow_lds(C2::LDS_BYTES, ge2e_tiled_sim<C2>, ge2e_tiled_sim<C3>);
     if (e != hipSuccess) return e;
-    launch_prep(p, L, stream);
-    launch_sim(p, L, stream);
+    launch_prep(p, L, plan.prep, stream);
+    launch_sim(p, L, plan.sim, stream);
     hipLaunchKernelGGL(ge2e_tiled_cos, dim3((unsigned)(((size_t)p.B * NM + 3) / 4)), dim3(256), 0, stream, p, L);
     return hipGetLastError();
 }

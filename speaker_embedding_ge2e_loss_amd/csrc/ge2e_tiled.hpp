@@ -1,6 +1,7 @@
 // Workspace layout + launcher of GE2E_IMPL_TILED (see ge2e_tiled.hip).
 #pragma once
 #include "ge2e_common.hpp"
+#include "ge2e_plan.hpp"
 
 namespace ge2e {
 

@@ -337,12 +337,22 @@ hipError_t launch_mn(const Problem& p, hipStream_t stream) {
     return hipGetLastError();
 }
 template <int M, int NX, int NXL>
-hipError_t launch_m(const Problem& p, hipStream_t stream) {
-    if (p.raw) return p.N <= NX ? launch_mn<M, NX, true>(p, stream) : hipErrorInvalidValue;   // raw rows: the small shapes only
-    return p.N <= NX ? launch_mn<M, NX, false>(p, stream) : launch_mn<M, NXL, false>(p, stream);
+hipError_t launch_m(const Problem& p, const WavePlan& plan, hipStream_t stream) {
+    if (plan.raw) return launch_mn<M, NX, true>(p, stream);
+    return plan.nx == NX ? launch_mn<M, NX, false>(p, stream) : launch_mn<M, NXL, false>(p, stream);
 }
 
 }  // namespace
+
+// The instantiation of a call: the small one where the speakers fit it; raw rows: the small shapes only.
+WavePlan plan_wave(int N, int M, bool raw) {
+    for (const WaveShape& s : kShapes)
+        if (s.M == M) {
+            if (N <= s.NX) return {M, s.NX, raw};
+            return raw ? WavePlan{0, 0, raw} : WavePlan{M, s.NXL, false};
+        }
+    return {0, 0, raw};
+}
 
 bool wave_supports(int N, int M, int D) {
     if (D < 4 || D > 256 || (D & 3) || N < 1 || M < 2) return false;
@@ -363,15 +373,16 @@ bool wave_is_large(int N, int M) {
 }
 
 hipError_t launch_wave(const Problem& p, hipStream_t stream) {
-    switch (p.M) {
-        case 2: return launch_m<2, 6, 12>(p, stream);
-        case 3: return launch_m<3, 5, 10>(p, stream);
-        case 4: return launch_m<4, 4, 10>(p, stream);
-        case 5: return launch_m<5, 4, 8>(p, stream);
-        case 6: return launch_m<6, 3, 8>(p, stream);
-        case 8: return launch_m<8, 3, 8>(p, stream);
-        case 10: return launch_m<10, 2, 6>(p, stream);
-        case 16: return launch_m<16, 2, 3>(p, stream);
+    const WavePlan plan = plan_wave(p.N, p.M, p.raw != 0);
+    switch (plan.m) {
+        case 2: return launch_m<2, 6, 12>(p, plan, stream);
+        case 3: return launch_m<3, 5, 10>(p, plan, stream);
+        case 4: return launch_m<4, 4, 10>(p, plan, stream);
+        case 5: return launch_m<5, 4, 8>(p, plan, stream);
+        case 6: return launch_m<6, 3, 8>(p, plan, stream);
+        case 8: return launch_m<8, 3, 8>(p, plan, stream);
+        case 10: return launch_m<10, 2, 6>(p, plan, stream);
+        case 16: return launch_m<16, 2, 3>(p, plan, stream);
         default: return hipErrorInvalidValue;
     }
 }

@@ -1,6 +1,7 @@
 // Launcher of GE2E_IMPL_WAVE (ge2e_wave.hip): one wave per batch, registers only, no workspace.
 #pragma once
 #include "ge2e_common.hpp"
+#include "ge2e_plan.hpp"
 
 namespace ge2e {
 

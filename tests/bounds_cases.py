@@ -1,4 +1,5 @@
-"""Case tables of tests/test_gpu_bounds.py (a plain module: tests/test_bounds_cases.py checks it without a GPU).
+"""Case tables of tests/test_gpu_bounds.py and tests/test_gpu_plans.py (a plain module: tests/test_bounds_cases.py and
+tests/test_plan_cases.py check it without a GPU).
 
 Every shape sits on a padding edge of the kernel it names.  The edges are those the library reports (ge2e_resolve_impl,
 ge2e_raw_supported); test_bounds_cases.py scans those predicates and fails if a table misses one, so nothing here is
@@ -39,7 +40,7 @@ LOSS_CASES = [
     # ... and launches big enough for its 256-row tiles (>= 192 of them): similarity + row pass in one kernel (N = 256 has an
     # instantiation of its own), the 256 x 256 similarity and dE contractions fed by registers (D or N % 32 != 0) and by LDS-DMA.
     # Limits: the 256 x 256 centroid-gradient contraction (and its row split) needs >= 192 tiles with N, D >= 256, which does
-    # not fit in MAX_ELEMS, so it never runs here; of the large launches only the fused similarity + row pass runs as contrast
+    # not fit in MAX_ELEMS, so it never runs here (PLAN_CASES below has it); of the large launches only the fused similarity + row pass runs as contrast
     # (tens of thousands of contrast rows tie on most draws: SEEDS names draws that do not).
     ("tiled", 64, 130, 4, 32, S), ("tiled", 64, 256, 3, 32, S), ("tiled", 32, 257, 2, 8, S), ("tiled", 32, 257, 2, 32, S),
     ("tiled", 32, 130, 4, 264, S), ("tiled", 32, 128, 5, 264, S), ("tiled", 64, 130, 4, 32, C), ("tiled", 64, 256, 3, 32, C),
@@ -67,6 +68,99 @@ REQUIRED = {
     "tiled": {"N": {1, 15, 65, 130, 300}, "D": {8, 72, 200, 264, 776, 1024}, "B": {1, 3}},
     "wave": {"D": {4, 36, 252, 256}, "B": {1, 5, 2100}},
 }
+
+# What LOSS_CASES, RAW_CASES and COS_CASES leave out, one level below ge2e_resolve_impl: every launcher picks again among
+# kernels and template instantiations, and the library's plan queries (ge2e_loss_plan, ge2e_cos_sim_plan) name the pick.
+# Each entry is there for ONE kernel name ("atom") that no case of the three tables above launches -- test_plan_cases.py
+# holds the union over all four tables to ge2e_plan_atoms and fails naming the atom if an entry is taken out --, and
+# tests/test_gpu_plans.py runs it:  (atom, impl, B, N, M, D, variant, grad)   grad False: forward only (dE = NULL).
+#   team / team_fwd <NCH, MR, 0, variant>: NCH = ceil(D / 64), MR = 10 for M <= 10 else 16.  The tables above hold the D
+#     edges and the M edges one at a time; these are the cells of the product they miss, with uneven members (N % 8 != 0),
+#     D off the multiples of 64, one and several batches.  The variant is a template argument, so both run.
+#   fused_split<3>: 128 < D <= 192.
+#   tiled_gc<C2>, tiled_gc<C3>/S: the 256 x 256 centroid-gradient contraction needs N >= 256, D >= 256 and at least 192
+#     tiles, B ceil(N / 256) ceil(D / 256) >= 192: more than MAX_ELEMS, so tests/test_gpu_plans.py makes these inputs on
+#     the device.  Each shape is the one with the fewest elements at which the query names the atom (searched over N
+#     256..1024, M 2..6, D in 256, 264, 288, 512, 520, B <= 130): D = 264 has two d tiles, N > 256 two slot tiles, so 48
+#     batches fill 192 tiles.  gc<C2>: N M = 514 is no multiple of 32.  gc<C3>/1: 192 tiles fill three quarters of a round
+#     and so do 384; /2: 260 tiles are half of two rounds, 520 two thirds of three; /4 and /8 need 8 K-steps of 32 rows per
+#     piece, N M >= 1024 and 2048.  The query decides; PLAN_TILES keeps the counts.
+#     Softmax: the variant is a run-time argument of gc, ge, sim and rows, and tens of thousands of contrast rows tie.
+#   The DMA-fed kernels (C3) walk their tiles b, b + grid, ... with at most 256 workgroups: PLAN_TILES notes the tile count of
+#     every C3 kernel of a case, and for each of sim<C3>, gc<C3>, ge<C3> one case has more than 256 (gc<C2>'s case takes
+#     D = 288 instead of the smallest D = 264 for that: its similarity contraction then is sim<C3> with 288 tiles).
+PLAN_CASES = [
+    ("team<1,10,0,softmax>", "team", 3, 23, 7, 60, S, True), ("team_fwd<1,10,0,softmax>", "team", 3, 23, 7, 60, S, False),
+    ("team<1,10,0,contrast>", "team", 2, 40, 10, 64, C, True), ("team_fwd<1,10,0,contrast>", "team", 2, 40, 10, 64, C, False),
+    ("team<2,10,0,softmax>", "team", 3, 57, 5, 128, S, True), ("team_fwd<2,10,0,softmax>", "team", 3, 57, 5, 128, S, False),
+    ("team<3,10,0,softmax>", "team", 5, 33, 9, 132, S, True), ("team_fwd<3,10,0,softmax>", "team", 5, 33, 9, 132, S, False),
+    ("team<3,10,0,contrast>", "team", 2, 64, 10, 192, C, True), ("team_fwd<3,10,0,contrast>", "team", 2, 64, 10, 192, C, False),
+    ("team<1,16,0,contrast>", "team", 3, 17, 11, 36, C, True), ("team_fwd<1,16,0,contrast>", "team", 3, 17, 11, 36, C, False),
+    ("team<2,16,0,softmax>", "team", 2, 40, 16, 100, S, True), ("team_fwd<2,16,0,softmax>", "team", 2, 40, 16, 100, S, False),
+    ("team<2,16,0,contrast>", "team", 5, 9, 13, 128, C, True), ("team_fwd<2,16,0,contrast>", "team", 5, 9, 13, 128, C, False),
+    ("team<3,16,0,contrast>", "team", 3, 24, 12, 192, C, True), ("team_fwd<3,16,0,contrast>", "team", 3, 24, 12, 192, C, False),
+    ("team<4,16,0,softmax>", "team", 2, 33, 16, 200, S, True), ("team_fwd<4,16,0,softmax>", "team", 2, 33, 16, 200, S, False),
+    ("team<4,16,0,contrast>", "team", 3, 16, 11, 256, C, True), ("team_fwd<4,16,0,contrast>", "team", 3, 16, 11, 256, C, False),
+    ("fused_split<3>", "fused_split", 2, 20, 5, 132, S, True),
+    ("tiled_gc<C2>", "tiled", 48, 257, 2, 288, S, True), ("tiled_gc<C3>/1", "tiled", 48, 272, 2, 264, S, True),
+    ("tiled_gc<C3>/2", "tiled", 65, 272, 2, 264, S, True), ("tiled_gc<C3>/4", "tiled", 32, 528, 2, 264, S, True),
+    ("tiled_gc<C3>/8", "tiled", 25, 800, 3, 264, S, True),
+]
+
+
+def plan_id(c):
+    return "{}-{}".format(c[0], case_id(c[1:7]))
+
+
+def plan_is_small(c):
+    """Small enough for the fp64 closed form on the CPU and for the guarded C-ABI route of test_gpu_bounds.py."""
+    return c[2] * c[3] * c[4] * c[5] <= MAX_ELEMS
+
+
+def c3_tiles(c):
+    """Tiles of the 256 x 256 DMA-fed contractions of a tiled case, by kernel name (0: that kernel is not C3 here).  The
+    tile counts are launch_tiled's grid arithmetic; WHICH kernels are C3 is read off the plan, not recomputed."""
+    from speaker_embedding_ge2e_loss_amd import _lib
+    _, impl, B, N, M, D, variant, grad = c
+    t = lambda n: (n + 255) // 256  # noqa: E731
+    plan = _lib.loss_plan(B, N, M, D, variant, impl, grad)
+    split = next((int(a.split("/")[1]) for a in plan if a.startswith("tiled_gc<C3>")), 0)
+    return {"tiled_sim<C3>": B * t(N * M) * t(N) if "tiled_sim<C3>" in plan else 0,
+            "tiled_gc<C3>": B * t(N) * t(D) * split,
+            "tiled_ge<C3>": B * t(N * M) * t(D) if "tiled_ge<C3>" in plan else 0}
+
+
+# c3_tiles of the tiled PLAN_CASES as they stand (test_plan_cases.py keeps the note true): the walk runs more than one
+# round wherever a count passes 256
+PLAN_TILES = {
+    "tiled_gc<C2>": {"tiled_sim<C3>": 288, "tiled_gc<C3>": 0, "tiled_ge<C3>": 0},
+    "tiled_gc<C3>/1": {"tiled_sim<C3>": 0, "tiled_gc<C3>": 192, "tiled_ge<C3>": 0},
+    "tiled_gc<C3>/2": {"tiled_sim<C3>": 0, "tiled_gc<C3>": 520, "tiled_ge<C3>": 0},
+    "tiled_gc<C3>/4": {"tiled_sim<C3>": 0, "tiled_gc<C3>": 768, "tiled_ge<C3>": 0},
+    "tiled_gc<C3>/8": {"tiled_sim<C3>": 0, "tiled_gc<C3>": 1600, "tiled_ge<C3>": 500},
+}
+
+
+def table_plans(lib):
+    """{table: [(what, [atoms])]}: the plan of every call the GPU tests make from the four tables -- LOSS_CASES with and
+    without gradients (COMBOS has forward-only calls), RAW_CASES likewise, COS_CASES on the full workspace, PLAN_CASES."""
+    from speaker_embedding_ge2e_loss_amd import _lib
+    out = {"LOSS_CASES": [], "RAW_CASES": [], "COS_CASES": [], "PLAN_CASES": []}
+    for c in LOSS_CASES:
+        impl, B, N, M, D, variant = c
+        for grad in sorted({combo[2] for combo in COMBOS}):
+            out["LOSS_CASES"].append((f"{case_id(c)}/{'grad' if grad else 'fwd'}", _lib.loss_plan(B, N, M, D, variant, impl, grad)))
+    for c in RAW_CASES:
+        B, N, M, D, variant = resolve_raw(lib, c)
+        for grad in (True, False):
+            out["RAW_CASES"].append((f"raw {raw_id(c)}/{'grad' if grad else 'fwd'}", _lib.loss_plan(B, N, M, D, variant, want_grad=grad, raw=True)))
+    for c in COS_CASES:
+        out["COS_CASES"].append((f"cos {c}", _lib.cos_sim_plan(*c)))
+    for c in PLAN_CASES:
+        _, impl, B, N, M, D, variant, grad = c
+        out["PLAN_CASES"].append((plan_id(c), _lib.loss_plan(B, N, M, D, variant, impl, grad)))
+    return out
+
 
 # output combinations: (name, per, grads, misaligned)
 COMBOS = [("all", True, True, False), ("no_per", False, True, False), ("fwd_per", True, False, False),
