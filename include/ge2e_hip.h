@@ -141,6 +141,39 @@ int ge2e_loss_fwd_bwd_ragged(const float* E, const int* offsets, int B, int N, i
                              void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * The ragged loss FROM SPEAKER LABELS: the rows of E [B][R][D] come in any order and labels [B][R] (int32 ON THE DEVICE)
+ * names the speaker of each, 0 .. N-1.  ge2e_label_index builds, per batch and without leaving the device,
+ *   offsets [B][N+1]  offsets[j] = number of rows with a label < j          (offsets[0] = 0, offsets[N] = R)
+ *   order   [B][R]    order[p] = the original row that stands at sorted position p; STABLE: the rows of one speaker keep
+ *                     their original relative order, so order == numpy.argsort(labels, kind="stable")
+ * (one 256-thread workgroup per batch: histogram, scan, stable placement; exact and the same bits every launch, for any
+ * N >= 1 and R >= 1).  Its workspace, ge2e_label_index_workspace_bytes (256-byte aligned; 0 for few speakers, then it may
+ * be NULL), needs no initialisation.
+ * ge2e_loss_fwd_bwd_labeled computes ge2e_loss_fwd_bwd_ragged on the rows E[order[0]], E[order[1]], ... with those
+ * offsets, gathering as it loads -- nothing is materialised in sorted order -- and returns per_row_loss [B][R] and
+ * dE [B][R][D] in the CALLER'S row order (the same bits as the ragged entry on gathered rows, scattered back; with labels
+ * already sorted it is the ragged entry).  per_row_loss or dE may be NULL (dE = NULL: forward only, dw / db may then be
+ * NULL).  Two launches, the index kernel and the loss kernel; enqueue-only, deterministic, no allocation, no state.  Any
+ * N >= 1, D >= 1, R >= 2 N, both variants.  The workspace is this entry point's own (ge2e_workspace_bytes_labeled,
+ * 256-byte aligned, no control block, no initialisation): the ragged workspace, offsets and order of all B batches and
+ * the index kernel's counters.  Same error codes, checked on the host before anything is launched, in the ragged
+ * entry's order: GE2E_ERR_NULL, GE2E_ERR_SHAPE for B, N, D < 1 or R < 2 N, GE2E_ERR_VARIANT, GE2E_ERR_WORKSPACE,
+ * GE2E_ERR_ALIGN.
+ * THE CALLER GUARANTEES THE LABELS' CONTENTS -- every label in [0, N), every speaker at least 2 rows -- which cannot be
+ * checked here without a synchronisation.  Every label is clamped into [0, N-1] where it is read, so order is a
+ * permutation of 0..R-1 whatever the labels hold: labels that break the contract yield wrong or non-finite numbers, never
+ * an access outside the buffers (a speaker with 1 row divides by zero, like M = 1 in the reference).
+ */
+size_t ge2e_label_index_workspace_bytes(int B, int N, int R);                     /* may be 0 */
+int ge2e_label_index(const int* labels, int B, int N, int R, int* offsets, int* order,
+                     void* workspace, size_t workspace_bytes, void* stream);
+size_t ge2e_workspace_bytes_labeled(int B, int N, int R, int D, int variant);     /* 0 for a bad shape */
+int ge2e_loss_fwd_bwd_labeled(const float* E, const int* labels, int B, int N, int R, int D,
+                              const float* w, const float* b, float eps_cos, float eps, int variant,
+                              float* loss, float* per_row_loss, float* dE, float* dw, float* db,
+                              void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * The same, fed with the encoder's RAW output (s2_model_GE2E_loss_speach_embed.py:34 +
  * s4_train_embed_model.py:186-192 folded into the loss kernel's load and store stages):
  *   Y   [B][N*M][D]  the encoder's projection BEFORE its L2-normalisation, rows in the encoder's own (permuted) order

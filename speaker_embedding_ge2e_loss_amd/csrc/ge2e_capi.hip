@@ -9,6 +9,7 @@
 #include "ge2e_generic.hpp"
 #include "ge2e_f64.hpp"
 #include "ge2e_ragged.hpp"
+#include "ge2e_labels.hpp"
 #include "ge2e_helpers.hpp"
 #include "ge2e_fused.hpp"
 #include "ge2e_selftest.hpp"
@@ -230,6 +231,67 @@ int ge2e_loss_fwd_bwd_ragged(const float* E, const int* offsets, int B, int N, i
     if (((uintptr_t)E & 15) || ((uintptr_t)dE & 15)) return GE2E_ERR_ALIGN;
     ProblemRagged p = make_problem_io<ProblemRagged>(E, w, b, eps_cos, eps, variant, loss, per_row_loss, dE, dw, db);
     p.off = offsets;
+    p.B = B; p.N = N; p.R = R; p.D = D;
+    p.ws = (float*)workspace;
+    p.log_eps = log_eps_of(eps);
+    return (int)launch_ragged(p, (hipStream_t)stream);
+}
+
+// The ragged loss from one speaker label per row, rows in any order: the index kernel (ge2e_labels.hip) writes the offset
+// table and the row order into this entry's own workspace, the ragged kernel's gathering instantiation reads them.  Same
+// checks, in the same order.  What the labels HOLD is the caller's word: reading them here would take a synchronisation;
+// the index kernel clamps them, so the order is a permutation whatever they hold and nothing reaches outside the buffers.
+size_t ge2e_label_index_workspace_bytes(int B, int N, int R) {
+    return (B >= 1 && N >= 1 && R >= 1) ? label_index_workspace_bytes(B, N, R) : 0;
+}
+
+int ge2e_label_index(const int* labels, int B, int N, int R, int* offsets, int* order, void* workspace, size_t workspace_bytes,
+                     void* stream) {
+    if (!labels || !offsets || !order) return GE2E_ERR_NULL;
+    if (B < 1 || N < 1 || R < 1) return GE2E_ERR_SHAPE;
+    const size_t need = label_index_workspace_bytes(B, N, R);
+    if (need > 0 && (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 255))) return GE2E_ERR_WORKSPACE;
+    return (int)launch_label_index(labels, B, N, R, offsets, order, (int*)workspace, (hipStream_t)stream);
+}
+
+namespace {
+// ge2e_loss_fwd_bwd_labeled's workspace: the ragged kernel's slices, offsets [B][N+1], order [B][R], the index kernel's
+// counters; every part starts 256-byte aligned.
+struct LabeledLayout {
+    size_t off, order, index, total;   // bytes
+};
+LabeledLayout labeled_layout(int B, int N, int R, int D) {
+    LabeledLayout L;
+    L.off = ragged_workspace_bytes(B, N, R, D);
+    L.order = L.off + align_up((size_t)B * ((size_t)N + 1) * sizeof(int), 256);
+    L.index = L.order + align_up((size_t)B * R * sizeof(int), 256);
+    L.total = L.index + label_index_workspace_bytes(B, N, R);
+    return L;
+}
+}  // namespace
+
+size_t ge2e_workspace_bytes_labeled(int B, int N, int R, int D, int variant) {
+    (void)variant;
+    return ragged_shape_ok(B, N, R, D) ? labeled_layout(B, N, R, D).total : 0;
+}
+
+int ge2e_loss_fwd_bwd_labeled(const float* E, const int* labels, int B, int N, int R, int D, const float* w, const float* b,
+                              float eps_cos, float eps, int variant, float* loss, float* per_row_loss, float* dE, float* dw,
+                              float* db, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!labels || !loss_ptrs_ok(E, w, b, loss, dE, dw, db)) return GE2E_ERR_NULL;
+    if (!ragged_shape_ok(B, N, R, D)) return GE2E_ERR_SHAPE;
+    if (!variant_ok(variant)) return GE2E_ERR_VARIANT;
+    const LabeledLayout L = labeled_layout(B, N, R, D);
+    if (!workspace || workspace_bytes < L.total || ((uintptr_t)workspace & 255)) return GE2E_ERR_WORKSPACE;
+    if (((uintptr_t)E & 15) || ((uintptr_t)dE & 15)) return GE2E_ERR_ALIGN;
+    char* ws = (char*)workspace;
+    int* offsets = (int*)(ws + L.off);
+    int* order = (int*)(ws + L.order);
+    const hipError_t err = launch_label_index(labels, B, N, R, offsets, order, (int*)(ws + L.index), (hipStream_t)stream);
+    if (err != hipSuccess) return (int)err;
+    ProblemRagged p = make_problem_io<ProblemRagged>(E, w, b, eps_cos, eps, variant, loss, per_row_loss, dE, dw, db);
+    p.off = offsets;
+    p.order = order;
     p.B = B; p.N = N; p.R = R; p.D = D;
     p.ws = (float*)workspace;
     p.log_eps = log_eps_of(eps);

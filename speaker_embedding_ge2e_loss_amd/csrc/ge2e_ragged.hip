@@ -21,6 +21,10 @@
 // Every offset is clamped into [0, R] where it is read and spk[r] is in [0, N) whatever the offsets hold: offsets that
 // break the contract give wrong or non-finite numbers, never an access outside the buffers.
 // Deterministic: no atomics, every sum in a fixed order that does not depend on the batch's position in the launch.
+// ge2e_loss_fwd_bwd_labeled runs the kGather instantiation: the rows arrive in any order and order[r] (ge2e_labels.hip)
+// names the row of E that stands at sorted position r.  Every read of E, and the stores to dE and per, go through it; all
+// intermediates (spk, rowstat, A) stay in sorted order, so the arithmetic and its order are those of the plain form on
+// gathered rows.  A row still starts at a multiple of D floats: the 16-byte loads hold as before.
 #include "ge2e_ragged.hpp"
 
 #include <math.h>
@@ -54,6 +58,8 @@ __device__ __forceinline__ v4f load4(const float* row, int k, int len, bool row_
 }
 }  // namespace
 
+// kGather: row r of the sorted layout is row order[r] of E, dE and per (ge2e_loss_fwd_bwd_labeled); otherwise it is row r.
+template <bool kGather>
 __global__ __launch_bounds__(256) void ge2e_ragged_kernel(ProblemRagged p, size_t ws_stride) {
     const int lane = threadIdx.x & 63;
     const int wid = threadIdx.x >> 6;
@@ -82,6 +88,11 @@ __global__ __launch_bounds__(256) void ge2e_ragged_kernel(ProblemRagged p, size_
         const float* E = p.E + (size_t)bi * R * D;
         const int* offs = p.off + (size_t)bi * (N + 1);
         auto off_at = [&](int j) { return min(max(offs[j], 0), R); };   // j in [0, N]
+        [[maybe_unused]] const int* ord = kGather ? p.order + (size_t)bi * R : nullptr;
+        auto row = [&](int r) -> int {   // where sorted row r lives in E, dE and per
+            if constexpr (kGather) return ord[r];
+            else return r;
+        };
 
         // ---- phase 0: row -> speaker; speaker sums, counts and unit centroids ------------
         // the largest j in [0, N) with off[j] <= r: the speaker of row r under the contract, some speaker without it
@@ -99,7 +110,7 @@ __global__ __launch_bounds__(256) void ge2e_ragged_kernel(ProblemRagged p, size_
             float sq = 0.f;
             for (int d = lane; d < D; d += kWave) {
                 float s = 0.f;
-                for (int r = r0; r < r1; ++r) s += E[(size_t)r * D + d];
+                for (int r = r0; r < r1; ++r) s += E[(size_t)row(r) * D + d];
                 SS[(size_t)j * D + d] = s;
                 const float c = s / fm;
                 sq += c * c;
@@ -119,7 +130,7 @@ __global__ __launch_bounds__(256) void ge2e_ragged_kernel(ProblemRagged p, size_
         for (int r = wid; r < R; r += NW) {
             const int j = SPK[r];
             const float fm1 = CST[(size_t)j * 4 + CS_M1];
-            const float* er = E + (size_t)r * D;
+            const float* er = E + (size_t)row(r) * D;
             float ee = 0.f, uu = 0.f, eu = 0.f;
             for (int d = lane; d < D; d += kWave) {
                 const float e = er[d];
@@ -143,7 +154,7 @@ __global__ __launch_bounds__(256) void ge2e_ragged_kernel(ProblemRagged p, size_
             const int rt = t / KT, kt = t - rt * KT;
             const int ra = rt * 16 + l15, kb = kt * 16 + l15;
             const bool ra_ok = ra < R, kb_ok = kb < N;
-            const float* pa = E + (size_t)(ra_ok ? ra : 0) * D;
+            const float* pa = E + (size_t)(ra_ok ? row(ra) : 0) * D;
             const float* pb = CH + (size_t)(kb_ok ? kb : 0) * D;
             v4f acc = {0.f, 0.f, 0.f, 0.f};
             for (int d0 = 0; d0 < D; d0 += 16) {
@@ -219,7 +230,7 @@ __global__ __launch_bounds__(256) void ge2e_ragged_kernel(ProblemRagged p, size_
             ad = wave_sum(ad);
             loss_acc += per;
             if (lane == 0) {
-                if (p.per) p.per[(size_t)bi * R + r] = per;
+                if (p.per) p.per[(size_t)bi * R + row(r)] = per;
                 float* rs = RST + (size_t)r * 8;
                 rs[RS_AD] = ad; rs[RS_COEF] = coef;
             }
@@ -250,7 +261,7 @@ __global__ __launch_bounds__(256) void ge2e_ragged_kernel(ProblemRagged p, size_
                         const int r = r0 + 4 * q + s;
                         const bool r_ok = r < R;
                         const float a = (ka_ok && r_ok) ? A[(size_t)r * N + ka] * RST[(size_t)r * 8 + RS_RNE] : 0.f;
-                        const float b = (d_ok && r_ok) ? E[(size_t)r * D + dcol] : 0.f;
+                        const float b = (d_ok && r_ok) ? E[(size_t)row(r) * D + dcol] : 0.f;
                         acc = mfma_f32(a, b, acc);
                     }
                 }
@@ -275,7 +286,7 @@ __global__ __launch_bounds__(256) void ge2e_ragged_kernel(ProblemRagged p, size_
                     float dusum = 0.f;
                     for (int r = r0; r < r1; ++r) {
                         const float* rs = RST + (size_t)r * 8;
-                        const float e = E[(size_t)r * D + d];
+                        const float e = E[(size_t)row(r) * D + d];
                         const float eh = e * rs[RS_RNE];
                         const float uh = (s - e) / fm1 * rs[RS_RNU];
                         dusum += rs[RS_AD] * (eh - rs[RS_KU] * rs[RS_COSD] * uh) * rs[RS_RNU];
@@ -307,13 +318,14 @@ __global__ __launch_bounds__(256) void ge2e_ragged_kernel(ProblemRagged p, size_
                         const int j = SPK[r];
                         const float* rs = RST + (size_t)r * 8;
                         const float* cs = CST + (size_t)j * 4;
-                        const float e = E[(size_t)r * D + d];
+                        const size_t at = (size_t)row(r) * D + d;
+                        const float e = E[at];
                         const float s = SS[(size_t)j * D + d];
                         const float eh = e * rs[RS_RNE];
                         const float uh = (s - e) / cs[CS_M1] * rs[RS_RNU];
                         const float du = rs[RS_AD] * (eh - rs[RS_KU] * rs[RS_COSD] * uh) * rs[RS_RNU];
                         const float ge = acc[g] + rs[RS_AD] * uh;
-                        dE[(size_t)r * D + d] = (ge - rs[RS_KE] * rs[RS_COEF] * eh) * rs[RS_RNE] +
+                        dE[at] = (ge - rs[RS_KE] * rs[RS_COEF] * eh) * rs[RS_RNE] +
                                                 GC[(size_t)j * D + d] / cs[CS_M] + (DUS[(size_t)j * D + d] - du) / cs[CS_M1];
                     }
                 }
@@ -332,7 +344,8 @@ size_t ragged_workspace_bytes(int B, int N, int R, int D) {
 hipError_t launch_ragged(const ProblemRagged& p, hipStream_t stream) {
     const int grid = ragged_grid(p.B);
     const size_t stride = ragged_layout(p.N, p.R, p.D).total;
-    hipLaunchKernelGGL(ge2e_ragged_kernel, dim3(grid), dim3(256), 0, stream, p, stride);
+    if (p.order) hipLaunchKernelGGL(ge2e_ragged_kernel<true>, dim3(grid), dim3(256), 0, stream, p, stride);
+    else hipLaunchKernelGGL(ge2e_ragged_kernel<false>, dim3(grid), dim3(256), 0, stream, p, stride);
     return hipGetLastError();
 }
 

@@ -8,6 +8,7 @@ namespace ge2e {
 struct ProblemRagged {
     const float* E;    // [B][R][D]: the rows of speaker j of batch bi at off[bi][j] .. off[bi][j+1]-1
     const int* off;    // [B][N+1] on the device; the caller guarantees 0 = off[0] < ... < off[N] = R, steps >= 2
+    const int* order;  // [B][R] on the device or null: sorted row r is row order[r] of E, dE and per (a permutation per batch)
     const float* w;    // device scalar (s3:16)
     const float* b;    // device scalar (s3:17)
     float* loss;       // [B]

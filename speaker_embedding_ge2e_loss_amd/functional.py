@@ -93,8 +93,8 @@ def _launch(name: str, dev: torch.device, *args) -> None:
 #    creating streams does not keep a workspace (with a large launch's fall-back slices) per dead stream forever.  A
 #    dropped or outgrown workspace goes back to the caching allocator, which hands a block out again only in the order
 #    of the stream it was allocated on -- the launches still using it are ahead in that very stream.
-#  * The double-precision kernel and the ragged kernel have their own entries (key tags "f64", "ragged"): their
-#    workspaces have no control block, so they are never shared with the fp32 kernels' workspace, need no initialisation
+#  * The double-precision kernel, the ragged kernel and its labelled form have their own entries (key tags "f64",
+#    "ragged", "labeled"): their workspaces have no control block, so they are never shared with the fp32 kernels' workspace, need no initialisation
 #    launch, and no `workspace_override` stands in for them.
 _ws_bytes_cache: dict = {}
 _ws_cache: dict = {}
@@ -130,6 +130,7 @@ _LOSS_ABI = {
     torch.float32: ("ge2e_loss_fwd_bwd", "ge2e_workspace_bytes", True, (), True),
     torch.float64: ("ge2e_loss_fwd_bwd_f64", "ge2e_workspace_bytes_f64", False, ("f64",), False),
     "ragged": ("ge2e_loss_fwd_bwd_ragged", "ge2e_workspace_bytes_ragged", False, ("ragged",), False),
+    "labeled": ("ge2e_loss_fwd_bwd_labeled", "ge2e_workspace_bytes_labeled", False, ("labeled",), False),
 }
 
 
@@ -372,6 +373,159 @@ def loss_fwd_bwd_ragged(embeddings: torch.Tensor, offsets_or_counts, w: torch.Te
             out.loss.data_ptr(), ptr(out.per), ptr(out.dE), ptr(out.dw), ptr(out.db),
             workspace.data_ptr(), workspace.numel(), stream)
     _lib.check(code, "ge2e_loss_fwd_bwd_ragged")
+    return out
+
+
+# ---- the ragged loss from speaker labels: rows in any order (ge2e_loss_fwd_bwd_labeled, csrc/ge2e_labels.hip) ---------------
+
+def dense_labels(labels):
+    """Host speaker ids -> (dense ids, N): a CPU int32 tensor shaped like ``labels`` -- (R,) or (B, R) -- in which every
+    batch's ids are replaced by their rank among that batch's distinct ids (ascending: the smallest id becomes 0), and the
+    number of distinct speakers N.  ``labels`` is a sequence or an integer CPU tensor of ARBITRARY integers.  Raises
+    ValueError for a dtype that is not an integer, a speaker with fewer than 2 rows (it has no leave-one-out centroid;
+    the message names the id), and batches that do not all hold the same number of distinct speakers.  Needs no GPU."""
+    t = labels if torch.is_tensor(labels) else torch.as_tensor(labels)
+    if t.is_cuda:
+        raise TypeError("dense_labels takes host labels (device labels are taken as dense ids already)")
+    if t.is_floating_point() or t.is_complex() or t.dtype == torch.bool:
+        raise ValueError(f"labels must be integers, got {t.dtype}")
+    if t.dim() not in (1, 2) or t.shape[-1] < 1 or t.numel() < 1:
+        raise ValueError(f"labels must be (R,) or (B, R) with R >= 1, got shape {tuple(t.shape)}")
+    if t.shape[-1] >= 2 ** 31:
+        raise ValueError("row indices are int32: fewer than 2^31 rows per batch")
+    t = t.to(torch.int64)
+    out = torch.empty(t.shape, dtype=torch.int32)
+    n_all = None
+    for bi, (row, dst) in enumerate(zip(t.reshape(-1, t.shape[-1]), out.view(-1, t.shape[-1]))):
+        ids, inverse, counts = torch.unique(row, sorted=True, return_inverse=True, return_counts=True)
+        if bool((counts < 2).any()):
+            lone = int(ids[counts < 2][0])
+            raise ValueError(f"speaker {lone}" + (f" of batch {bi}" if t.dim() == 2 else "") + " has 1 row: every speaker "
+                             "needs at least 2 (the leave-one-out centroid divides by count - 1)")
+        if n_all is not None and len(ids) != n_all:
+            raise ValueError(f"every batch must hold the same number of distinct speakers: batch 0 has {n_all}, "
+                             f"batch {bi} has {len(ids)}")
+        n_all = len(ids)
+        dst.copy_(inverse)
+    return out, int(n_all)
+
+
+# The last few label tables uploaded from the host, most recent last, like _ragged_uploads: key -> (device ids, N).
+_label_uploads: dict = {}
+
+
+def _labels_on_device(labels, num_speakers, B: int, R: int, dev: torch.device):
+    """((B, R) int32 dense ids on `dev`, N) from what the caller gave.  A DEVICE tensor (torch.int32, or torch.int64 which
+    a torch op narrows -- no synchronisation) is taken as dense ids in [0, num_speakers), as is: its contents cannot be
+    validated without a host synchronisation, so they are the caller's word (the index kernel clamps what it reads: broken
+    labels give wrong numbers and no wild access), and ``num_speakers`` must be given.  Anything else is host labels of
+    arbitrary integer ids: validated and compacted (dense_labels), uploaded, and remembered."""
+    if torch.is_tensor(labels) and labels.device.type != "cpu":
+        if num_speakers is None:
+            raise ValueError("device labels need num_speakers: counting the distinct ids would take a host synchronisation")
+        if labels.dtype not in (torch.int32, torch.int64):
+            raise TypeError(f"device labels must be torch.int32 or torch.int64, got {labels.dtype}")
+        if labels.device != dev:
+            raise RuntimeError(f"labels are on {labels.device}, embeddings on {dev}: raw pointers cross the C ABI, all on one device")
+        N = int(num_speakers)
+        if labels.dim() == 1:
+            labels = labels.unsqueeze(0).expand(B, -1)
+        if labels.dim() != 2 or tuple(labels.shape) != (B, R):
+            raise ValueError(f"labels must be (R,) or (B, R) with B = {B}, R = {R}, got {tuple(labels.shape)}")
+        if N < 1 or R < 2 * N:
+            raise ValueError(f"{N} speakers need at least {2 * max(N, 1)} rows, got {R}")
+        return labels.to(torch.int32).contiguous(), N
+    raw = labels if torch.is_tensor(labels) else torch.as_tensor(labels)
+    if raw.dim() not in (1, 2) or raw.shape[-1] != R or (raw.dim() == 2 and raw.shape[0] != B):
+        raise ValueError(f"labels must be (R,) or (B, R) with B = {B}, R = {R}, got {tuple(raw.shape)}")
+    capturing = _capturing is not None and _capturing()
+    integral = not (raw.is_floating_point() or raw.is_complex() or raw.dtype == torch.bool)
+    key = (raw.to(torch.int64).contiguous().numpy().tobytes(), tuple(raw.shape), B, str(dev)) if integral else None
+    hit = None if capturing or key is None else _label_uploads.pop(key, None)
+    if hit is None:
+        ids, N = dense_labels(raw)
+        if ids.dim() == 1:
+            ids = ids.unsqueeze(0).expand(B, -1)
+        hit = (ids.contiguous().to(dev), N)
+        if capturing:                   # (belongs to the capturing graph's pool: not for anybody else)
+            return hit
+        while len(_label_uploads) >= _RAGGED_UPLOADS_MAX:
+            _label_uploads.pop(next(iter(_label_uploads)))
+    _label_uploads[key] = hit
+    if num_speakers is not None and int(num_speakers) != hit[1]:
+        raise ValueError(f"num_speakers = {int(num_speakers)}, the labels hold {hit[1]} distinct speakers")
+    return hit
+
+
+def label_index(labels: torch.Tensor, num_speakers: int):
+    """ge2e_label_index on the current stream, no host sync: DEVICE labels (R,) or (B, R), torch.int32 or torch.int64,
+    dense ids in [0, num_speakers) -> (offsets, order), torch.int32 on the device: offsets (N+1,) / (B, N+1) with
+    offsets[j] = number of rows with a label < j, and order (R,) / (B, R), the stable argsort of the labels.  Labels
+    outside [0, num_speakers) are clamped into it."""
+    _require_cuda(labels, "labels")
+    if labels.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"labels must be torch.int32 or torch.int64, got {labels.dtype}")
+    if labels.dim() not in (1, 2) or labels.numel() < 1:
+        raise ValueError(f"labels must be (R,) or (B, R) with R >= 1, got {tuple(labels.shape)}")
+    N = int(num_speakers)
+    if N < 1:
+        raise ValueError(f"num_speakers must be >= 1, got {N}")
+    lab = labels.to(torch.int32).contiguous()
+    squeeze = lab.dim() == 1
+    B, R = (1, lab.shape[0]) if squeeze else lab.shape
+    dev = lab.device
+    lib = _lib.load()
+    offsets = torch.empty(B, N + 1, dtype=torch.int32, device=dev)
+    order = torch.empty(B, R, dtype=torch.int32, device=dev)
+    with _on_device(dev):
+        need = int(lib.ge2e_label_index_workspace_bytes(B, N, R))
+        ws = alloc_workspace(need, dev, init=False) if need else None
+        code = lib.ge2e_label_index(lab.data_ptr(), B, N, R, offsets.data_ptr(), order.data_ptr(),
+                                    ws.data_ptr() if need else None, need, _stream_ptr(lab))
+    _lib.check(code, "ge2e_label_index")
+    return (offsets[0], order[0]) if squeeze else (offsets, order)
+
+
+def loss_fwd_bwd_labeled(embeddings: torch.Tensor, labels, w: torch.Tensor, b: torch.Tensor, *,
+                         num_speakers: Optional[int] = None, eps: float = SMALL_ERR, eps_cos: float = EPS_COS,
+                         variant: str = "softmax", need_grad: bool = True, need_per: bool = False,
+                         out: Optional[LossOutputs] = None, workspace: Optional[torch.Tensor] = None) -> LossOutputs:
+    """One enqueue of ge2e_loss_fwd_bwd_labeled on the current stream (two launches: the index kernel, the loss kernel).
+    No host sync (host labels: none after their first use).
+
+    ``embeddings`` (R, D) or (B, R, D) float32, rows in ANY order; ``labels`` (R,) / (B, R) names each row's speaker:
+    host labels -- a sequence or an integer CPU tensor of arbitrary ids, validated and compacted -- or a DEVICE tensor
+    (torch.int32 / torch.int64) of dense ids in [0, num_speakers), taken as is and NOT verified, with ``num_speakers``
+    given.  Outputs as `loss_fwd_bwd_ragged`, per (B, R) and dE (B, R, D) in the caller's row order."""
+    lib = _lib.load()
+    _require_cuda(embeddings, "embeddings")
+    if embeddings.dim() not in (2, 3):
+        raise ValueError(f"embeddings must be (R,D) or (B,R,D), got {tuple(embeddings.shape)}")
+    if not embeddings.is_contiguous():
+        raise RuntimeError("embeddings must be contiguous")
+    if embeddings.dtype != torch.float32:
+        raise TypeError(f"embeddings must be float32 at this boundary, got {embeddings.dtype}")
+    e3 = embeddings.unsqueeze(0) if embeddings.dim() == 2 else embeddings
+    B, R, D = e3.shape
+    dev = e3.device
+    _check_scalar_params(w, b, dev)
+    with _on_device(dev):
+        lab, N = _labels_on_device(labels, num_speakers, B, R, dev)
+    if out is None:
+        o4 = _alloc_outputs(B, 1, R, D, torch.float32, dev, need_grad, need_per)
+        out = LossOutputs(loss=o4.loss, per=o4.per.view(B, R) if need_per else None,
+                          dE=o4.dE.view(B, R, D) if need_grad else None, dw=o4.dw, db=o4.db)
+    query = (B, N, R, D, _lib.VARIANTS[variant])
+    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    with _on_device(dev) as guard:
+        stream = _stream_ptr(e3)
+        if workspace is None:
+            workspace = _workspace_for(lib, dev, stream, "labeled", query, guard.idx)
+        code = lib.ge2e_loss_fwd_bwd_labeled(
+            e3.data_ptr(), lab.data_ptr(), B, N, R, D, w.data_ptr(), b.data_ptr(), eps_cos, eps, query[4],
+            out.loss.data_ptr(), ptr(out.per), ptr(out.dE), ptr(out.dw), ptr(out.db),
+            workspace.data_ptr(), workspace.numel(), stream)
+    _lib.check(code, "ge2e_loss_fwd_bwd_labeled")
     return out
 
 
@@ -838,6 +992,18 @@ class _GE2ELossF64Function(torch.autograd.Function):
         return gE, gw, gb, None, None, None, None
 
 
+def _ragged_node_backward(ctx, grad_out):
+    """backward of the ragged nodes (inputs: embeddings, table, w, b, ...): the launch's own dE / dw / db scaled by the
+    incoming gradient with ge2e_scale_grads (a batch of R rows as N = 1, M = R)."""
+    dE, dw, db = ctx.saved_tensors
+    B, R, D = dE.shape
+    gE, gw, gb = _scale_grads(dE, dw.data_ptr(), db.data_ptr(), grad_out, grad_out.numel(), (B, 1, R, D),
+                              [ctx.needs_input_grad[i] for i in (0, 2, 3)], ctx.w_shape, ctx.b_shape)
+    if gE is not None and ctx.squeeze:
+        gE = gE[0]
+    return gE, gw, gb
+
+
 class _GE2ELossRaggedFunction(torch.autograd.Function):
     """The same node over ge2e_loss_fwd_bwd_ragged: embeddings (R,D) / (B,R,D) and device offsets in; the backward scales
     the launch's own dE / dw / db by the incoming gradient with ge2e_scale_grads (a batch of R rows as N = 1, M = R)."""
@@ -855,13 +1021,30 @@ class _GE2ELossRaggedFunction(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_out):
-        dE, dw, db = ctx.saved_tensors
-        B, R, D = dE.shape
-        gE, gw, gb = _scale_grads(dE, dw.data_ptr(), db.data_ptr(), grad_out, grad_out.numel(), (B, 1, R, D),
-                                  [ctx.needs_input_grad[i] for i in (0, 2, 3)], ctx.w_shape, ctx.b_shape)
-        if gE is not None and ctx.squeeze:
-            gE = gE[0]
+        gE, gw, gb = _ragged_node_backward(ctx, grad_out)
         return gE, None, gw, gb, None, None, None
+
+
+class _GE2ELossLabeledFunction(torch.autograd.Function):
+    """The ragged node over ge2e_loss_fwd_bwd_labeled: embeddings in any row order and device labels in; dE comes back in
+    the caller's row order, and the backward is the ragged node's."""
+
+    @staticmethod
+    def forward(ctx, embeddings, lab, w, b, eps, eps_cos, variant, num_speakers):
+        need = any(ctx.needs_input_grad[i] for i in (0, 2, 3))
+        o = loss_fwd_bwd_labeled(embeddings, lab, w, b, num_speakers=num_speakers, eps=eps, eps_cos=eps_cos,
+                                 variant=variant, need_grad=need)
+        ctx.squeeze = embeddings.dim() == 2
+        ctx.w_shape, ctx.b_shape = w.shape, b.shape
+        if need:
+            ctx.save_for_backward(o.dE, o.dw, o.db)
+        return o.loss[0] if ctx.squeeze else o.loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        gE, gw, gb = _ragged_node_backward(ctx, grad_out)
+        return gE, None, gw, gb, None, None, None, None
 
 
 # The autograd node in C++ (libge2e_torch.so,csrc_torch/ge2e_autograd.cpp: torch.ops.ge2e_amd.loss): the same two C-ABI
@@ -959,4 +1142,39 @@ def ge2e_loss_ragged(embeddings: torch.Tensor, counts, w: torch.Tensor, b: torch
     with _on_device(embeddings.device):
         off = _ragged_offsets_on_device(counts, B, R, embeddings.device)
     loss = _GE2ELossRaggedFunction.apply(embeddings, off, w, b, float(eps), float(eps_cos), variant)
+    return loss if in_dtype == torch.float32 else loss.to(in_dtype)
+
+
+def ge2e_loss_labeled(embeddings: torch.Tensor, labels, w: torch.Tensor, b: torch.Tensor, *,
+                      num_speakers: Optional[int] = None, eps: float = SMALL_ERR, eps_cos: float = EPS_COS,
+                      variant: str = "softmax") -> torch.Tensor:
+    """Differentiable GE2E loss of rows in ANY order with one speaker label each: 0-dim for (R, D) input, (B,) for
+    (B, R, D).  What `ge2e_loss_ragged` computes on the rows sorted by speaker (stable), with the embeddings' gradient in
+    the caller's row order; nothing is sorted or copied on the way: the index kernel orders the rows on the device and the
+    loss kernel gathers as it loads.
+
+    ``labels`` (R,) for every batch alike or (B, R).  On the HOST -- a sequence or an integer CPU tensor -- the ids are
+    arbitrary integers: every batch is compacted to dense ids by ascending id, validated (at least 2 rows per speaker, the
+    same number of speakers in every batch) and uploaded once (the last few tables are kept, keyed by their contents).
+    On the DEVICE -- torch.int32 or torch.int64 -- they are taken as dense ids in [0, num_speakers), as is and UNVERIFIED
+    (checking would cost a synchronisation), and ``num_speakers`` must be given: the kernel clamps what it reads, so broken
+    labels give wrong numbers, not a wild access.  float16 / bfloat16 are computed in fp32 behind differentiable casts;
+    float64 is not implemented (there is no fp64 ragged kernel, and no silent fp32 arithmetic in its place)."""
+    _require_cuda(embeddings, "embeddings")
+    in_dtype = embeddings.dtype
+    if in_dtype == torch.float64:
+        raise NotImplementedError("ge2e_loss_labeled: float64 embeddings are not implemented (the ragged kernel is fp32 and "
+                                  "nothing casts float64 down silently); pass float32, or group equal counts for ge2e_loss")
+    if in_dtype != torch.float32:
+        embeddings = embeddings.float()
+    if embeddings.dim() not in (2, 3):
+        raise ValueError(f"embeddings must be (R,D) or (B,R,D), got {tuple(embeddings.shape)}")
+    if not embeddings.is_contiguous():
+        raise RuntimeError("embeddings must be contiguous")
+    if embeddings.data_ptr() % 16:     # a contiguous view at an odd storage offset
+        embeddings = embeddings.clone()
+    B, R = (1, embeddings.shape[0]) if embeddings.dim() == 2 else embeddings.shape[:2]
+    with _on_device(embeddings.device):
+        lab, N = _labels_on_device(labels, num_speakers, B, R, embeddings.device)
+    loss = _GE2ELossLabeledFunction.apply(embeddings, lab, w, b, float(eps), float(eps_cos), variant, N)
     return loss if in_dtype == torch.float32 else loss.to(in_dtype)

@@ -116,7 +116,7 @@ class GE2ELoss(nn.Module):
         self.w = nn.Parameter(torch.tensor(10.0).to(self.device), requires_grad=True)
         self.b = nn.Parameter(torch.tensor(-5.0).to(self.device), requires_grad=True)
 
-    def forward(self, embeddings, counts=None):
+    def forward(self, embeddings, counts=None, labels=None, num_speakers=None):
         """embeddings (N,M,D) [or (B,N,M,D)] on hp.general.device -> loss (s3:19-30).
 
         Like the reference, w is NOT clamped (s3:22 discards torch.clamp's result), the
@@ -130,7 +130,20 @@ class GE2ELoss(nn.Module):
         ``counts`` their utterance counts -- (N,) or (B, N) on the host, every count >= 2, summing to R -- or a
         ``torch.int32`` device tensor of offsets, unverified (``functional.ge2e_loss_ragged``).  One kernel: ``impl`` must
         be "auto"; float64 raises NotImplementedError.  With ``graph=True`` this route is eager too (nothing is captured).
+
+        ``labels`` (instead of ``counts``): the same loss for rows in ANY order, one speaker label per row -- (R,) or
+        (B, R); arbitrary integer ids on the host (validated: at least 2 rows per speaker), or a ``torch.int32`` /
+        ``torch.int64`` device tensor of dense ids in [0, ``num_speakers``), unverified, with ``num_speakers`` given
+        (``functional.ge2e_loss_labeled``).  The gradient comes back in the caller's row order.  The same conditions:
+        ``impl`` "auto", no float64, eager with ``graph=True``.
         """
+        if labels is not None:
+            if counts is not None:
+                raise ValueError("pass counts (rows grouped by speaker) or labels (rows in any order), not both")
+            if self.impl != "auto":
+                raise ValueError(f'impl="{self.impl}" names a fixed-shape kernel; the ragged loss has one kernel (impl="auto")')
+            return GF.ge2e_loss_labeled(embeddings, labels, self.w, self.b, num_speakers=num_speakers,
+                                        eps=self.hp.general.small_err, variant=self.variant)
         if counts is not None:
             if self.impl != "auto":
                 raise ValueError(f'impl="{self.impl}" names a fixed-shape kernel; the ragged loss has one kernel (impl="auto")')
