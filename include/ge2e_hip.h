@@ -174,6 +174,46 @@ int ge2e_loss_fwd_bwd_labeled(const float* E, const int* labels, int B, int N, i
                               void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * The labelled loss WITH MASKING: the labels' contents need no guarantee any more.  labels [B][R] (int32 on the device)
+ * may hold anything and N is only an upper bound of the speaker ids (the data set's speaker count works).  Per batch,
+ * decided on the device without a synchronisation:
+ *   valid row       0 <= labels[r] < N (nothing is clamped); every other row is ignored -- e.g. padding labelled -1
+ *   active speaker  at least 2 valid rows carry its label; a speaker with 1 row (no leave-one-out centroid) or none is
+ *                   left out, rows and centroid alike
+ *   active row      valid, and its speaker is active; n_act / r_act count the active speakers / rows
+ * ge2e_label_index_masked writes (any N >= 1 and R >= 1, N may be far above R):
+ *   order    [B][R]    order[0 .. r_act) = the active rows sorted by (label, original index), then every other row in
+ *                      ascending original index: always a permutation of 0..R-1, and
+ *                      numpy.argsort(numpy.where(active_row, labels, N), kind="stable")
+ *   offsets  [B][N+1]  offsets[k] = number of active rows of the active speakers before the k-th one (ascending label),
+ *                      k <= n_act; offsets[k] = r_act for n_act < k <= N
+ *   speakers [B][N]    speakers[k] = the label of the k-th active speaker, k < n_act; -1 beyond
+ *   active   [B][2]    {n_act, r_act}
+ * with the same bits every launch and at every position of the stack.  Its workspace
+ * (ge2e_label_index_masked_workspace_bytes) follows ge2e_label_index's rule.
+ * ge2e_loss_fwd_bwd_labeled_masked computes ge2e_loss_fwd_bwd_ragged of the n_act active speakers on the rows
+ * E[order[0 .. r_act)] with offsets[0 .. n_act] -- the ragged entry's bits on that compacted batch; with every row
+ * active and n_act = N the bits of ge2e_loss_fwd_bwd_labeled -- and returns per_row_loss [B][R] and dE [B][R][D] in the
+ * CALLER'S row order, WRITTEN AS 0 FOR EVERY ROW THAT IS NOT ACTIVE.  Such rows of E are never read: they may hold NaN.
+ * A batch without active speakers has loss = dw = db = 0 and all of dE and per_row_loss 0.  active [B][2] receives
+ * {n_act, r_act} (NULL: not wanted); the other arguments are ge2e_loss_fwd_bwd_labeled's.  B, N, R, D >= 1 (R >= 2 N is
+ * NOT required: N is a bound), both variants.  The workspace is this entry point's own
+ * (ge2e_workspace_bytes_labeled_masked, 256-byte aligned, no control block, no initialisation, and the result does not
+ * depend on what it held): the ragged slices -- laid out for max(1, min(N, R / 2)) speakers, all that R rows can hold --
+ * offsets, order, speakers and active of all B batches, and the index kernel's counters.  Same error codes, checked on
+ * the host before anything is launched, in the labelled entry's order.  Two launches, enqueue-only, no allocation, no
+ * state: a fixed row budget R with padding rows makes a batch of varying size a static-shape call, fit for a HIP graph.
+ */
+size_t ge2e_label_index_masked_workspace_bytes(int B, int N, int R);              /* may be 0 */
+int ge2e_label_index_masked(const int* labels, int B, int N, int R, int* offsets, int* order, int* speakers, int* active,
+                            void* workspace, size_t workspace_bytes, void* stream);
+size_t ge2e_workspace_bytes_labeled_masked(int B, int N, int R, int D, int variant);   /* 0 for a bad shape */
+int ge2e_loss_fwd_bwd_labeled_masked(const float* E, const int* labels, int B, int N, int R, int D,
+                                     const float* w, const float* b, float eps_cos, float eps, int variant,
+                                     float* loss, float* per_row_loss, float* dE, float* dw, float* db, int* active,
+                                     void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * The same, fed with the encoder's RAW output (s2_model_GE2E_loss_speach_embed.py:34 +
  * s4_train_embed_model.py:186-192 folded into the loss kernel's load and store stages):
  *   Y   [B][N*M][D]  the encoder's projection BEFORE its L2-normalisation, rows in the encoder's own (permuted) order

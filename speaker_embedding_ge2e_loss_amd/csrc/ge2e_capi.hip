@@ -2,6 +2,7 @@
 // implementation choice, workspace sizing, launches.  No allocation, no sync, no state.
 #include "../../include/ge2e_hip.h"
 
+#include <algorithm>
 #include <cmath>
 #include <stdlib.h>
 
@@ -293,6 +294,79 @@ int ge2e_loss_fwd_bwd_labeled(const float* E, const int* labels, int B, int N, i
     p.off = offsets;
     p.order = order;
     p.B = B; p.N = N; p.R = R; p.D = D;
+    p.ws = (float*)workspace;
+    p.log_eps = log_eps_of(eps);
+    return (int)launch_ragged(p, (hipStream_t)stream);
+}
+
+// The labelled loss on labels of ANY content (include/ge2e_hip.h): the masked index kernel decides on the device which rows
+// and speakers count and leaves their numbers in `active`; the ragged kernel's masked instantiation takes its extents from
+// there.  N is a bound, so R >= 2 N is not asked for.
+size_t ge2e_label_index_masked_workspace_bytes(int B, int N, int R) {
+    return (B >= 1 && N >= 1 && R >= 1) ? label_index_masked_workspace_bytes(B, N, R) : 0;
+}
+
+int ge2e_label_index_masked(const int* labels, int B, int N, int R, int* offsets, int* order, int* speakers, int* active,
+                            void* workspace, size_t workspace_bytes, void* stream) {
+    if (!labels || !offsets || !order || !speakers || !active) return GE2E_ERR_NULL;
+    if (B < 1 || N < 1 || R < 1) return GE2E_ERR_SHAPE;
+    const size_t need = label_index_masked_workspace_bytes(B, N, R);
+    if (need > 0 && (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 255))) return GE2E_ERR_WORKSPACE;
+    return (int)launch_label_index_masked(labels, B, N, R, offsets, order, speakers, active, (int*)workspace,
+                                          (hipStream_t)stream);
+}
+
+namespace {
+bool masked_shape_ok(int B, int N, int R, int D) { return B >= 1 && N >= 1 && R >= 1 && D >= 1; }
+
+// R rows hold at most R / 2 speakers of two rows each: what the ragged kernel's slices are laid out for.
+int masked_speaker_capacity(int N, int R) { return std::max(1, std::min(N, R / 2)); }
+
+// ge2e_loss_fwd_bwd_labeled_masked's workspace: the ragged kernel's slices (for masked_speaker_capacity speakers), offsets
+// [B][N+1], order [B][R], speakers [B][N], active [B][2], the index kernel's counters; every part starts 256-byte aligned.
+struct MaskedLayout {
+    size_t off, order, speakers, active, index, total;   // bytes
+};
+MaskedLayout masked_layout(int B, int N, int R, int D) {
+    MaskedLayout L;
+    L.off = ragged_workspace_bytes(B, masked_speaker_capacity(N, R), R, D);
+    L.order = L.off + align_up((size_t)B * ((size_t)N + 1) * sizeof(int), 256);
+    L.speakers = L.order + align_up((size_t)B * R * sizeof(int), 256);
+    L.active = L.speakers + align_up((size_t)B * N * sizeof(int), 256);
+    L.index = L.active + align_up((size_t)B * 2 * sizeof(int), 256);
+    L.total = L.index + label_index_masked_workspace_bytes(B, N, R);
+    return L;
+}
+}  // namespace
+
+size_t ge2e_workspace_bytes_labeled_masked(int B, int N, int R, int D, int variant) {
+    (void)variant;
+    return masked_shape_ok(B, N, R, D) ? masked_layout(B, N, R, D).total : 0;
+}
+
+int ge2e_loss_fwd_bwd_labeled_masked(const float* E, const int* labels, int B, int N, int R, int D, const float* w,
+                                     const float* b, float eps_cos, float eps, int variant, float* loss, float* per_row_loss,
+                                     float* dE, float* dw, float* db, int* active, void* workspace, size_t workspace_bytes,
+                                     void* stream) {
+    if (!labels || !loss_ptrs_ok(E, w, b, loss, dE, dw, db)) return GE2E_ERR_NULL;
+    if (!masked_shape_ok(B, N, R, D)) return GE2E_ERR_SHAPE;
+    if (!variant_ok(variant)) return GE2E_ERR_VARIANT;
+    const MaskedLayout L = masked_layout(B, N, R, D);
+    if (!workspace || workspace_bytes < L.total || ((uintptr_t)workspace & 255)) return GE2E_ERR_WORKSPACE;
+    if (((uintptr_t)E & 15) || ((uintptr_t)dE & 15)) return GE2E_ERR_ALIGN;
+    char* ws = (char*)workspace;
+    int* offsets = (int*)(ws + L.off);
+    int* order = (int*)(ws + L.order);
+    if (!active) active = (int*)(ws + L.active);
+    const hipError_t err = launch_label_index_masked(labels, B, N, R, offsets, order, (int*)(ws + L.speakers), active,
+                                                     (int*)(ws + L.index), (hipStream_t)stream);
+    if (err != hipSuccess) return (int)err;
+    ProblemRagged p = make_problem_io<ProblemRagged>(E, w, b, eps_cos, eps, variant, loss, per_row_loss, dE, dw, db);
+    p.off = offsets;
+    p.order = order;
+    p.active = active;
+    p.B = B; p.N = N; p.R = R; p.D = D;
+    p.NA = masked_speaker_capacity(N, R);
     p.ws = (float*)workspace;
     p.log_eps = log_eps_of(eps);
     return (int)launch_ragged(p, (hipStream_t)stream);

@@ -98,6 +98,125 @@ __device__ __forceinline__ void index_batch(const int* lab, int N, int R, int* o
     }
 }
 
+// The MASKED form (ge2e_label_index_masked): the labels may hold anything.  A row is valid iff 0 <= label < N (nothing is
+// clamped), a speaker is active iff at least 2 valid rows carry its label, a row is active iff it is valid and its speaker
+// is active.  The same plan with two scans where the plain form has one:
+//   1  histogram of the VALID labels only
+//   2  per speaker the active flag (count >= 2); an exclusive scan of the flags gives the speaker's compact id k (the active
+//      speakers numbered by ascending label) and speakers[k]; an exclusive scan of the counts of the active speakers gives
+//      offsets[k] and the speaker's cursor.  The cursor of a speaker that is not active is -1, which is how step 3 tells.
+//      offsets[n_act .. N] = r_act, speakers[n_act .. N-1] = -1, active = {n_act, r_act}.
+//   3  the rows in row order as above; the key of an active row is its label, every other row has the key N, whose cursor is
+//      the tail cursor (one int of LDS, starting at r_act): the rows that do not count follow the active ones in ascending
+//      row index, so order is a permutation of 0..R-1 whatever the labels hold.
+// Whether a row is active is read from the cursors before any of the chunk moves (one barrier): cursors only grow from a
+// value >= 0, so the answer is the same for every chunk.
+// cnt: N counters (LDS or workspace); wtot: 2 kWaves ints of LDS; tail: one int of LDS.
+__device__ __forceinline__ void index_batch_masked(const int* lab, int N, int R, int* offs, int* ord, int* spkr, int* act,
+                                                   int* cnt, int* wtot, int* tail) {
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+
+    // ---- 1: histogram of the valid labels ----
+    for (int j = tid; j < N; j += kThreads) cnt[j] = 0;
+    __syncthreads();
+    for (long long r = tid; r < R; r += kThreads) {
+        const int l = lab[r];
+        if (l >= 0 && l < N) atomicAdd(&cnt[l], 1);
+    }
+    __syncthreads();
+
+    // ---- 2: active flags; scans of the flags and of the active counts ----
+    int ncarry = 0, rcarry = 0;
+    for (long long j0 = 0; j0 < N; j0 += kThreads) {
+        const long long j = j0 + tid;
+        const int c = j < N ? cnt[j] : 0;
+        const int f = c >= 2 ? 1 : 0, a = f ? c : 0;
+        const int incf = wave_inclusive_scan(f, lane), inca = wave_inclusive_scan(a, lane);
+        if (lane == kWave - 1) { wtot[wid] = incf; wtot[kWaves + wid] = inca; }
+        __syncthreads();
+        int beforef = 0, totalf = 0, beforea = 0, totala = 0;
+#pragma unroll
+        for (int i = 0; i < kWaves; ++i) {
+            const int tf = wtot[i], ta = wtot[kWaves + i];
+            if (i < wid) { beforef += tf; beforea += ta; }
+            totalf += tf; totala += ta;
+        }
+        if (j < N) {
+            if (f) {
+                const int k = ncarry + beforef + incf - f, o = rcarry + beforea + inca - a;
+                offs[k] = o; spkr[k] = (int)j; cnt[j] = o;
+            } else {
+                cnt[j] = -1;
+            }
+        }
+        ncarry += totalf; rcarry += totala;
+        __syncthreads();   // wtot is rewritten by the next round; the cursors are read by other threads below
+    }
+    for (long long k = (long long)ncarry + tid; k <= N; k += kThreads) offs[k] = rcarry;
+    for (long long k = (long long)ncarry + tid; k < N; k += kThreads) spkr[k] = -1;
+    if (tid == 0) { act[0] = ncarry; act[1] = rcarry; *tail = rcarry; }
+    __syncthreads();
+
+    // ---- 3: positions, chunk by chunk in row order; the rows that do not count go to the tail ----
+    for (long long r0 = 0; r0 < R; r0 += kThreads) {
+        const long long r = r0 + tid;
+        const bool valid = r < R;
+        int key = -1;
+        if (valid) {
+            const int l = lab[r];
+            key = (l >= 0 && l < N && cnt[l] >= 0) ? l : N;
+        }
+        __syncthreads();   // every key of the chunk is decided before a cursor moves
+        int rank = 0, group = 0, lead = lane;
+        bool todo = valid;
+        for (;;) {   // one round per distinct key of the wave; every lane of the wave takes every round
+            const unsigned long long open = __ballot(todo);
+            if (!open) break;
+            const int first = __ffsll((long long)open) - 1;
+            const bool same = todo && key == __shfl(key, first);
+            const unsigned long long g = __ballot(same);
+            if (same) {
+                rank = __popcll(g & ((1ull << lane) - 1ull));
+                group = __popcll(g);
+                lead = first;
+                todo = false;
+            }
+        }
+        for (int w = 0; w < kWaves; ++w) {
+            if (wid == w) {
+                int base = 0;
+                if (valid && rank == 0) {   // one lane per key: nobody else touches this cursor now
+                    int* cur = key < N ? &cnt[key] : tail;
+                    base = *cur;
+                    *cur = base + group;
+                }
+                base = __shfl(base, lead);
+                // (the clamp holds only for labels that change between the two reads: otherwise the positions are exact)
+                if (valid) ord[min(max(base + rank, 0), R - 1)] = (int)r;
+            }
+            __syncthreads();
+        }
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void ge2e_label_index_masked_kernel(const int* labels, int B, int N, int R,
+                                                                            int* offsets, int* order, int* speakers,
+                                                                            int* active, int* ws) {
+    __shared__ int lds_cnt[kLabelLdsSpeakers];
+    __shared__ int wtot[2 * kWaves];
+    __shared__ int tail;
+    for (int bi = blockIdx.x; bi < B; bi += gridDim.x) {
+        const int* lab = labels + (size_t)bi * R;
+        int* offs = offsets + (size_t)bi * ((size_t)N + 1);
+        int* ord = order + (size_t)bi * R;
+        int* spkr = speakers + (size_t)bi * N;
+        int* act = active + (size_t)bi * 2;
+        int* cnt = N <= kLabelLdsSpeakers ? lds_cnt : ws + (size_t)blockIdx.x * N;
+        index_batch_masked(lab, N, R, offs, ord, spkr, act, cnt, wtot, &tail);
+        // (index_batch_masked ends on a barrier: counters, wtot and tail are free for the next batch of this workgroup)
+    }
+}
+
 __global__ __launch_bounds__(kThreads) void ge2e_label_index_kernel(const int* labels, int B, int N, int R, int* offsets,
                                                                      int* order, int* ws) {
     __shared__ int lds_cnt[kLabelLdsSpeakers];
@@ -121,6 +240,15 @@ size_t label_index_workspace_bytes(int B, int N, int R) {
 hipError_t launch_label_index(const int* labels, int B, int N, int R, int* offsets, int* order, int* ws, hipStream_t stream) {
     hipLaunchKernelGGL(ge2e_label_index_kernel, dim3(ragged_grid(B)), dim3(kThreads), 0, stream, labels, B, N, R, offsets,
                        order, ws);
+    return hipGetLastError();
+}
+
+size_t label_index_masked_workspace_bytes(int B, int N, int R) { return label_index_workspace_bytes(B, N, R); }
+
+hipError_t launch_label_index_masked(const int* labels, int B, int N, int R, int* offsets, int* order, int* speakers,
+                                     int* active, int* ws, hipStream_t stream) {
+    hipLaunchKernelGGL(ge2e_label_index_masked_kernel, dim3(ragged_grid(B)), dim3(kThreads), 0, stream, labels, B, N, R,
+                       offsets, order, speakers, active, ws);
     return hipGetLastError();
 }
 

@@ -12,4 +12,10 @@ size_t label_index_workspace_bytes(int B, int N, int R);      // 0 while the cou
 // labels [B][R] -> offsets [B][N+1], order [B][R]; ws: label_index_workspace_bytes (unused, may be null, when that is 0)
 hipError_t launch_label_index(const int* labels, int B, int N, int R, int* offsets, int* order, int* ws, hipStream_t stream);
 
+// The masked form: labels of any content.  speakers [B][N], active [B][2] = {active speakers, active rows}; the same
+// workspace rule.
+size_t label_index_masked_workspace_bytes(int B, int N, int R);
+hipError_t launch_label_index_masked(const int* labels, int B, int N, int R, int* offsets, int* order, int* speakers,
+                                     int* active, int* ws, hipStream_t stream);
+
 }  // namespace ge2e

@@ -25,6 +25,14 @@
 // names the row of E that stands at sorted position r.  Every read of E, and the stores to dE and per, go through it; all
 // intermediates (spk, rowstat, A) stay in sorted order, so the arithmetic and its order are those of the plain form on
 // gathered rows.  A row still starts at a multiple of D floats: the 16-byte loads hold as before.
+// ge2e_loss_fwd_bwd_labeled_masked runs the kMasked instantiation, which gathers and takes the batch's EXTENTS from the
+// device: active[bi] = {n_act, r_act} (ge2e_label_index_masked) stand wherever N and R are loop bounds, tile counts or the
+// row length of A, so the arithmetic and its order are the plain form's on the n_act speakers and the r_act rows
+// order[0 .. r_act): the same bits.  p.N is only the stride of the offset table, p.R that of E, dE, per and order, and the
+// slice is laid out for p.NA speakers and p.R rows.  Every thread of the workgroup reads the same two words, so every
+// barrier stays uniform; both are clamped where they are read, to [0, NA] and [0, R]: whatever the memory holds, nothing
+// is accessed outside the buffers and no loop is unbounded.  The rows order[r_act .. R) of dE and per are written as 0
+// after the last phase; a batch without active speakers writes zeros and takes no phase.
 #include "ge2e_ragged.hpp"
 
 #include <math.h>
@@ -59,14 +67,17 @@ __device__ __forceinline__ v4f load4(const float* row, int k, int len, bool row_
 }  // namespace
 
 // kGather: row r of the sorted layout is row order[r] of E, dE and per (ge2e_loss_fwd_bwd_labeled); otherwise it is row r.
-template <bool kGather>
+// kMasked (with kGather): the batch's speaker and row counts are active[bi] (ge2e_loss_fwd_bwd_labeled_masked).
+template <bool kGather, bool kMasked>
 __global__ __launch_bounds__(256) void ge2e_ragged_kernel(ProblemRagged p, size_t ws_stride) {
+    static_assert(kGather || !kMasked, "the masked form gathers");
     const int lane = threadIdx.x & 63;
     const int wid = threadIdx.x >> 6;
     const int NW = blockDim.x >> 6;
     const int l15 = lane & 15, q = lane >> 4;
-    const int N = p.N, R = p.R, D = p.D;
-    const RaggedLayout L = ragged_layout(N, R, D);
+    const int D = p.D;
+    const int RC = p.R;   // rows per batch of E, dE, per and order
+    const RaggedLayout L = ragged_layout(kMasked ? p.NA : p.N, RC, D);
     float* ws = p.ws + (size_t)blockIdx.x * ws_stride;
     float* CH = ws + L.ch;
     float* SS = ws + L.ss;
@@ -81,18 +92,53 @@ __global__ __launch_bounds__(256) void ge2e_ragged_kernel(ProblemRagged p, size_
     const float w = *p.w, bias = *p.b;
     const float eps = p.eps, eps_cos = p.eps_cos, log_eps = p.log_eps;
     const bool contrast = p.variant == 1;
-    const bool vecD = (D & 3) == 0, vecN = (N & 3) == 0;
-    const int RT = (R + 15) >> 4, KT = (N + 15) >> 4, DT = (D + 15) >> 4;   // 16-wide tiles over rows, centroids, D
+    const bool vecD = (D & 3) == 0;
+    const int DT = (D + 15) >> 4;
 
     for (int bi = blockIdx.x; bi < p.B; bi += gridDim.x) {
-        const float* E = p.E + (size_t)bi * R * D;
-        const int* offs = p.off + (size_t)bi * (N + 1);
+        int N = p.N, R = RC;
+        if constexpr (kMasked) {   // the same two words for every thread of the workgroup
+            N = min(max(p.active[(size_t)bi * 2], 0), p.NA);
+            R = min(max(p.active[(size_t)bi * 2 + 1], 0), RC);
+        }
+        const bool vecN = (N & 3) == 0;
+        const int RT = (R + 15) >> 4, KT = (N + 15) >> 4;   // 16-wide tiles over rows, centroids (DT: over D)
+        const float* E = p.E + (size_t)bi * RC * D;
+        const int* offs = p.off + (size_t)bi * ((size_t)p.N + 1);
         auto off_at = [&](int j) { return min(max(offs[j], 0), R); };   // j in [0, N]
-        [[maybe_unused]] const int* ord = kGather ? p.order + (size_t)bi * R : nullptr;
+        [[maybe_unused]] const int* ord = kGather ? p.order + (size_t)bi * RC : nullptr;
         auto row = [&](int r) -> int {   // where sorted row r lives in E, dE and per
             if constexpr (kGather) return ord[r];
             else return r;
         };
+        // (kMasked) the rows that do not count: order[R .. RC) of dE and per are 0, one wave per row
+        [[maybe_unused]] auto zero_tail = [&]() {
+            for (int r = R + wid; r < RC; r += NW) {
+                const size_t at = (size_t)bi * RC + row(r);
+                if (p.per && lane == 0) p.per[at] = 0.f;
+                if (p.dE) {
+                    float* g = p.dE + at * D;
+                    if (vecD) {
+                        const v4f z = {0.f, 0.f, 0.f, 0.f};
+                        for (int d = 4 * lane; d < D; d += 4 * kWave) *reinterpret_cast<v4f*>(g + d) = z;
+                    } else {
+                        for (int d = lane; d < D; d += kWave) g[d] = 0.f;
+                    }
+                }
+            }
+        };
+        if constexpr (kMasked) {
+            if (N == 0) {   // no active speaker: zeros and no phase (uniform: every thread read the same N)
+                R = 0;      // every row of the batch is written
+                zero_tail();
+                if (threadIdx.x == 0) {
+                    p.loss[bi] = 0.f;
+                    if (p.dw) p.dw[bi] = 0.f;
+                    if (p.db) p.db[bi] = 0.f;
+                }
+                continue;
+            }
+        }
 
         // ---- phase 0: row -> speaker; speaker sums, counts and unit centroids ------------
         // the largest j in [0, N) with off[j] <= r: the speaker of row r under the contract, some speaker without it
@@ -230,7 +276,7 @@ __global__ __launch_bounds__(256) void ge2e_ragged_kernel(ProblemRagged p, size_
             ad = wave_sum(ad);
             loss_acc += per;
             if (lane == 0) {
-                if (p.per) p.per[(size_t)bi * R + row(r)] = per;
+                if (p.per) p.per[(size_t)bi * RC + row(r)] = per;
                 float* rs = RST + (size_t)r * 8;
                 rs[RS_AD] = ad; rs[RS_COEF] = coef;
             }
@@ -248,7 +294,7 @@ __global__ __launch_bounds__(256) void ge2e_ragged_kernel(ProblemRagged p, size_
         }
 
         if (p.dE) {
-            float* dE = p.dE + (size_t)bi * R * D;
+            float* dE = p.dE + (size_t)bi * RC * D;
             // ---- phase C1: dL/d c-hat = (A_off rne)^T . E on the matrix core, K = R ------
             for (int t = wid; t < KT * DT; t += NW) {
                 const int kt = t / DT, dt = t - kt * DT;
@@ -331,6 +377,7 @@ __global__ __launch_bounds__(256) void ge2e_ragged_kernel(ProblemRagged p, size_
                 }
             }
         }
+        if constexpr (kMasked) zero_tail();
         __syncthreads();  // workspace slice is reused by the next batch of this workgroup
     }
 }
@@ -343,9 +390,10 @@ size_t ragged_workspace_bytes(int B, int N, int R, int D) {
 
 hipError_t launch_ragged(const ProblemRagged& p, hipStream_t stream) {
     const int grid = ragged_grid(p.B);
-    const size_t stride = ragged_layout(p.N, p.R, p.D).total;
-    if (p.order) hipLaunchKernelGGL(ge2e_ragged_kernel<true>, dim3(grid), dim3(256), 0, stream, p, stride);
-    else hipLaunchKernelGGL(ge2e_ragged_kernel<false>, dim3(grid), dim3(256), 0, stream, p, stride);
+    const size_t stride = ragged_layout(p.active ? p.NA : p.N, p.R, p.D).total;
+    if (p.active) hipLaunchKernelGGL((ge2e_ragged_kernel<true, true>), dim3(grid), dim3(256), 0, stream, p, stride);
+    else if (p.order) hipLaunchKernelGGL((ge2e_ragged_kernel<true, false>), dim3(grid), dim3(256), 0, stream, p, stride);
+    else hipLaunchKernelGGL((ge2e_ragged_kernel<false, false>), dim3(grid), dim3(256), 0, stream, p, stride);
     return hipGetLastError();
 }
 

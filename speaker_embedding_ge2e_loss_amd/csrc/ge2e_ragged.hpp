@@ -9,6 +9,7 @@ struct ProblemRagged {
     const float* E;    // [B][R][D]: the rows of speaker j of batch bi at off[bi][j] .. off[bi][j+1]-1
     const int* off;    // [B][N+1] on the device; the caller guarantees 0 = off[0] < ... < off[N] = R, steps >= 2
     const int* order;  // [B][R] on the device or null: sorted row r is row order[r] of E, dE and per (a permutation per batch)
+    const int* active; // [B][2] on the device or null: {speakers, rows} that count in each batch (with order; see NA)
     const float* w;    // device scalar (s3:16)
     const float* b;    // device scalar (s3:17)
     float* loss;       // [B]
@@ -18,6 +19,7 @@ struct ProblemRagged {
     float* db;         // [B] or null
     float* ws;         // workspace
     int B, N, R, D;
+    int NA;            // with active: the speakers the workspace slices are laid out for; N is the offset table's stride
     int variant;
     float eps_cos;     // cosine_similarity eps (1e-8)
     float eps;         // hp.general.small_err (1e-6)

@@ -93,8 +93,8 @@ def _launch(name: str, dev: torch.device, *args) -> None:
 #    creating streams does not keep a workspace (with a large launch's fall-back slices) per dead stream forever.  A
 #    dropped or outgrown workspace goes back to the caching allocator, which hands a block out again only in the order
 #    of the stream it was allocated on -- the launches still using it are ahead in that very stream.
-#  * The double-precision kernel, the ragged kernel and its labelled form have their own entries (key tags "f64",
-#    "ragged", "labeled"): their workspaces have no control block, so they are never shared with the fp32 kernels' workspace, need no initialisation
+#  * The double-precision kernel, the ragged kernel and its labelled forms have their own entries (key tags "f64",
+#    "ragged", "labeled", "labeled_masked"): their workspaces have no control block, so they are never shared with the fp32 kernels' workspace, need no initialisation
 #    launch, and no `workspace_override` stands in for them.
 _ws_bytes_cache: dict = {}
 _ws_cache: dict = {}
@@ -131,6 +131,8 @@ _LOSS_ABI = {
     torch.float64: ("ge2e_loss_fwd_bwd_f64", "ge2e_workspace_bytes_f64", False, ("f64",), False),
     "ragged": ("ge2e_loss_fwd_bwd_ragged", "ge2e_workspace_bytes_ragged", False, ("ragged",), False),
     "labeled": ("ge2e_loss_fwd_bwd_labeled", "ge2e_workspace_bytes_labeled", False, ("labeled",), False),
+    "labeled_masked": ("ge2e_loss_fwd_bwd_labeled_masked", "ge2e_workspace_bytes_labeled_masked", False,
+                       ("labeled_masked",), False),
 }
 
 
@@ -205,6 +207,7 @@ class LossOutputs:
     dE: Optional[torch.Tensor]          # (B,N,M,D)
     dw: Optional[torch.Tensor]          # (B,)
     db: Optional[torch.Tensor]          # (B,)
+    active: Optional[torch.Tensor] = None   # (B,2) int32, loss_fwd_bwd_labeled(masked=True) only: active speakers, active rows
 
 
 def loss_fwd_bwd(embeddings: torch.Tensor, w: torch.Tensor, b: torch.Tensor, *,
@@ -378,12 +381,17 @@ def loss_fwd_bwd_ragged(embeddings: torch.Tensor, offsets_or_counts, w: torch.Te
 
 # ---- the ragged loss from speaker labels: rows in any order (ge2e_loss_fwd_bwd_labeled, csrc/ge2e_labels.hip) ---------------
 
-def dense_labels(labels):
+def dense_labels(labels, masked: bool = False):
     """Host speaker ids -> (dense ids, N): a CPU int32 tensor shaped like ``labels`` -- (R,) or (B, R) -- in which every
     batch's ids are replaced by their rank among that batch's distinct ids (ascending: the smallest id becomes 0), and the
     number of distinct speakers N.  ``labels`` is a sequence or an integer CPU tensor of ARBITRARY integers.  Raises
     ValueError for a dtype that is not an integer, a speaker with fewer than 2 rows (it has no leave-one-out centroid;
-    the message names the id), and batches that do not all hold the same number of distinct speakers.  Needs no GPU."""
+    the message names the id), and batches that do not all hold the same number of distinct speakers.  Needs no GPU.
+
+    ``masked=True``: ids for the masked loss, which takes the batch as it is.  Negative ids mark rows to ignore and become
+    -1; the non-negative ids of every batch are compacted by ascending id; N is the largest number of distinct non-negative
+    ids over the batches (at least 1).  A speaker with one row is no error (the kernel leaves it out) and the batches may
+    hold different numbers of speakers."""
     t = labels if torch.is_tensor(labels) else torch.as_tensor(labels)
     if t.is_cuda:
         raise TypeError("dense_labels takes host labels (device labels are taken as dense ids already)")
@@ -395,6 +403,15 @@ def dense_labels(labels):
         raise ValueError("row indices are int32: fewer than 2^31 rows per batch")
     t = t.to(torch.int64)
     out = torch.empty(t.shape, dtype=torch.int32)
+    if masked:
+        n_max = 1
+        for row, dst in zip(t.reshape(-1, t.shape[-1]), out.view(-1, t.shape[-1])):
+            keep = row >= 0
+            ids, inverse = torch.unique(row[keep], sorted=True, return_inverse=True)
+            dst.fill_(-1)
+            dst[keep] = inverse.to(torch.int32)
+            n_max = max(n_max, len(ids))
+        return out, int(n_max)
     n_all = None
     for bi, (row, dst) in enumerate(zip(t.reshape(-1, t.shape[-1]), out.view(-1, t.shape[-1]))):
         ids, inverse, counts = torch.unique(row, sorted=True, return_inverse=True, return_counts=True)
@@ -414,12 +431,16 @@ def dense_labels(labels):
 _label_uploads: dict = {}
 
 
-def _labels_on_device(labels, num_speakers, B: int, R: int, dev: torch.device):
+def _labels_on_device(labels, num_speakers, B: int, R: int, dev: torch.device, masked: bool = False):
     """((B, R) int32 dense ids on `dev`, N) from what the caller gave.  A DEVICE tensor (torch.int32, or torch.int64 which
     a torch op narrows -- no synchronisation) is taken as dense ids in [0, num_speakers), as is: its contents cannot be
     validated without a host synchronisation, so they are the caller's word (the index kernel clamps what it reads: broken
     labels give wrong numbers and no wild access), and ``num_speakers`` must be given.  Anything else is host labels of
-    arbitrary integer ids: validated and compacted (dense_labels), uploaded, and remembered."""
+    arbitrary integer ids: validated and compacted (dense_labels), uploaded, and remembered.
+    ``masked``: the labels of the masked loss.  Device labels may hold ANY values and ``num_speakers`` is a bound (rows
+    labelled outside [0, num_speakers) are ignored); torch.int64 is clamped into [-1, num_speakers] before it is narrowed,
+    so that 2**32 + 3 is ignored and not wrapped onto speaker 3.  Host labels go through dense_labels(masked=True), and a
+    ``num_speakers`` given with them is the bound to use, at least their distinct count."""
     if torch.is_tensor(labels) and labels.device.type != "cpu":
         if num_speakers is None:
             raise ValueError("device labels need num_speakers: counting the distinct ids would take a host synchronisation")
@@ -432,18 +453,26 @@ def _labels_on_device(labels, num_speakers, B: int, R: int, dev: torch.device):
             labels = labels.unsqueeze(0).expand(B, -1)
         if labels.dim() != 2 or tuple(labels.shape) != (B, R):
             raise ValueError(f"labels must be (R,) or (B, R) with B = {B}, R = {R}, got {tuple(labels.shape)}")
+        if masked:
+            if N < 1:
+                raise ValueError(f"num_speakers must be >= 1, got {N}")
+            if labels.dtype == torch.int64:
+                labels = labels.clamp(-1, N)
+            return labels.to(torch.int32).contiguous(), N
         if N < 1 or R < 2 * N:
             raise ValueError(f"{N} speakers need at least {2 * max(N, 1)} rows, got {R}")
         return labels.to(torch.int32).contiguous(), N
     raw = labels if torch.is_tensor(labels) else torch.as_tensor(labels)
     if raw.dim() not in (1, 2) or raw.shape[-1] != R or (raw.dim() == 2 and raw.shape[0] != B):
         raise ValueError(f"labels must be (R,) or (B, R) with B = {B}, R = {R}, got {tuple(raw.shape)}")
-    capturing = _capturing is not None and _capturing()
+    capturing = dev.type == "cuda" and _capturing is not None and _capturing()
     integral = not (raw.is_floating_point() or raw.is_complex() or raw.dtype == torch.bool)
     key = (raw.to(torch.int64).contiguous().numpy().tobytes(), tuple(raw.shape), B, str(dev)) if integral else None
+    if masked and key is not None:
+        key += ("masked",)
     hit = None if capturing or key is None else _label_uploads.pop(key, None)
     if hit is None:
-        ids, N = dense_labels(raw)
+        ids, N = dense_labels(raw, masked=True) if masked else dense_labels(raw)
         if ids.dim() == 1:
             ids = ids.unsqueeze(0).expand(B, -1)
         hit = (ids.contiguous().to(dev), N)
@@ -452,6 +481,10 @@ def _labels_on_device(labels, num_speakers, B: int, R: int, dev: torch.device):
         while len(_label_uploads) >= _RAGGED_UPLOADS_MAX:
             _label_uploads.pop(next(iter(_label_uploads)))
     _label_uploads[key] = hit
+    if masked:
+        if num_speakers is not None and int(num_speakers) < hit[1]:
+            raise ValueError(f"num_speakers = {int(num_speakers)} is a bound: the labels hold {hit[1]} distinct speakers")
+        return hit if num_speakers is None else (hit[0], int(num_speakers))
     if num_speakers is not None and int(num_speakers) != hit[1]:
         raise ValueError(f"num_speakers = {int(num_speakers)}, the labels hold {hit[1]} distinct speakers")
     return hit
@@ -486,17 +519,60 @@ def label_index(labels: torch.Tensor, num_speakers: int):
     return (offsets[0], order[0]) if squeeze else (offsets, order)
 
 
+def label_index_masked(labels: torch.Tensor, num_speakers: int):
+    """ge2e_label_index_masked on the current stream, no host sync: DEVICE labels (R,) or (B, R), torch.int32 or
+    torch.int64, of ANY content, and ``num_speakers`` = N as a bound -> (offsets, order, speakers, active), torch.int32 on
+    the device.  A row counts when 0 <= label < N and at least one more row carries its label.  order (R,) / (B, R): the
+    rows that count sorted by (label, index), then all the others by index; offsets (N+1,) / (B, N+1) over the speakers
+    that count, numbered by ascending label, and the number of rows that count from there on; speakers (N,) / (B, N): the
+    labels of those speakers, then -1; active (2,) / (B, 2): how many speakers and rows count."""
+    _require_cuda(labels, "labels")
+    if labels.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"labels must be torch.int32 or torch.int64, got {labels.dtype}")
+    if labels.dim() not in (1, 2) or labels.numel() < 1:
+        raise ValueError(f"labels must be (R,) or (B, R) with R >= 1, got {tuple(labels.shape)}")
+    N = int(num_speakers)
+    if N < 1:
+        raise ValueError(f"num_speakers must be >= 1, got {N}")
+    if labels.dtype == torch.int64:
+        labels = labels.clamp(-1, N)
+    lab = labels.to(torch.int32).contiguous()
+    squeeze = lab.dim() == 1
+    B, R = (1, lab.shape[0]) if squeeze else lab.shape
+    dev = lab.device
+    lib = _lib.load()
+    offsets = torch.empty(B, N + 1, dtype=torch.int32, device=dev)
+    order = torch.empty(B, R, dtype=torch.int32, device=dev)
+    speakers = torch.empty(B, N, dtype=torch.int32, device=dev)
+    active = torch.empty(B, 2, dtype=torch.int32, device=dev)
+    with _on_device(dev):
+        need = int(lib.ge2e_label_index_masked_workspace_bytes(B, N, R))
+        ws = alloc_workspace(need, dev, init=False) if need else None
+        code = lib.ge2e_label_index_masked(lab.data_ptr(), B, N, R, offsets.data_ptr(), order.data_ptr(),
+                                           speakers.data_ptr(), active.data_ptr(), ws.data_ptr() if need else None, need,
+                                           _stream_ptr(lab))
+    _lib.check(code, "ge2e_label_index_masked")
+    res = (offsets, order, speakers, active)
+    return tuple(t[0] for t in res) if squeeze else res
+
+
 def loss_fwd_bwd_labeled(embeddings: torch.Tensor, labels, w: torch.Tensor, b: torch.Tensor, *,
                          num_speakers: Optional[int] = None, eps: float = SMALL_ERR, eps_cos: float = EPS_COS,
                          variant: str = "softmax", need_grad: bool = True, need_per: bool = False,
-                         out: Optional[LossOutputs] = None, workspace: Optional[torch.Tensor] = None) -> LossOutputs:
+                         out: Optional[LossOutputs] = None, workspace: Optional[torch.Tensor] = None,
+                         masked: bool = False) -> LossOutputs:
     """One enqueue of ge2e_loss_fwd_bwd_labeled on the current stream (two launches: the index kernel, the loss kernel).
     No host sync (host labels: none after their first use).
 
     ``embeddings`` (R, D) or (B, R, D) float32, rows in ANY order; ``labels`` (R,) / (B, R) names each row's speaker:
     host labels -- a sequence or an integer CPU tensor of arbitrary ids, validated and compacted -- or a DEVICE tensor
     (torch.int32 / torch.int64) of dense ids in [0, num_speakers), taken as is and NOT verified, with ``num_speakers``
-    given.  Outputs as `loss_fwd_bwd_ragged`, per (B, R) and dE (B, R, D) in the caller's row order."""
+    given.  Outputs as `loss_fwd_bwd_ragged`, per (B, R) and dE (B, R, D) in the caller's row order.
+
+    ``masked=True``: ge2e_loss_fwd_bwd_labeled_masked, which takes the batch as it is.  ``num_speakers`` is a bound, rows
+    labelled outside [0, num_speakers) are ignored (host labels: negative ids), a speaker with fewer than 2 such rows is
+    left out, all decided on the device.  per and dE are 0 on the rows that do not count, and ``out.active`` (B, 2) int32
+    receives the numbers of speakers and rows that do (allocated here unless ``out`` is given, where it may be None)."""
     lib = _lib.load()
     _require_cuda(embeddings, "embeddings")
     if embeddings.dim() not in (2, 3):
@@ -510,22 +586,28 @@ def loss_fwd_bwd_labeled(embeddings: torch.Tensor, labels, w: torch.Tensor, b: t
     dev = e3.device
     _check_scalar_params(w, b, dev)
     with _on_device(dev):
-        lab, N = _labels_on_device(labels, num_speakers, B, R, dev)
+        lab, N = _labels_on_device(labels, num_speakers, B, R, dev, masked)
     if out is None:
         o4 = _alloc_outputs(B, 1, R, D, torch.float32, dev, need_grad, need_per)
         out = LossOutputs(loss=o4.loss, per=o4.per.view(B, R) if need_per else None,
-                          dE=o4.dE.view(B, R, D) if need_grad else None, dw=o4.dw, db=o4.db)
+                          dE=o4.dE.view(B, R, D) if need_grad else None, dw=o4.dw, db=o4.db,
+                          active=torch.empty(B, 2, dtype=torch.int32, device=dev) if masked else None)
     query = (B, N, R, D, _lib.VARIANTS[variant])
     ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    tag = "labeled_masked" if masked else "labeled"
+    entry = _LOSS_ABI[tag][0]
+    if masked and out.active is not None and (out.active.dtype != torch.int32 or not out.active.is_contiguous()
+                                              or out.active.device != dev or out.active.numel() != 2 * B):
+        raise TypeError(f"out.active must be a contiguous int32 tensor of shape ({B}, 2) on {dev}")
     with _on_device(dev) as guard:
         stream = _stream_ptr(e3)
         if workspace is None:
-            workspace = _workspace_for(lib, dev, stream, "labeled", query, guard.idx)
-        code = lib.ge2e_loss_fwd_bwd_labeled(
+            workspace = _workspace_for(lib, dev, stream, tag, query, guard.idx)
+        code = getattr(lib, entry)(
             e3.data_ptr(), lab.data_ptr(), B, N, R, D, w.data_ptr(), b.data_ptr(), eps_cos, eps, query[4],
             out.loss.data_ptr(), ptr(out.per), ptr(out.dE), ptr(out.dw), ptr(out.db),
-            workspace.data_ptr(), workspace.numel(), stream)
-    _lib.check(code, "ge2e_loss_fwd_bwd_labeled")
+            *((ptr(out.active),) if masked else ()), workspace.data_ptr(), workspace.numel(), stream)
+    _lib.check(code, entry)
     return out
 
 
@@ -1047,6 +1129,30 @@ class _GE2ELossLabeledFunction(torch.autograd.Function):
         return gE, None, gw, gb, None, None, None, None
 
 
+class _GE2ELossMaskedFunction(torch.autograd.Function):
+    """The ragged node over ge2e_loss_fwd_bwd_labeled_masked: labels of any content in; the loss and the launch's `active`
+    (int32, not differentiable) out.  dE is 0 on the rows that do not count, and the backward is the ragged node's."""
+
+    @staticmethod
+    def forward(ctx, embeddings, lab, w, b, eps, eps_cos, variant, num_speakers):
+        need = any(ctx.needs_input_grad[i] for i in (0, 2, 3))
+        o = loss_fwd_bwd_labeled(embeddings, lab, w, b, num_speakers=num_speakers, eps=eps, eps_cos=eps_cos,
+                                 variant=variant, need_grad=need, masked=True)
+        ctx.squeeze = embeddings.dim() == 2
+        ctx.w_shape, ctx.b_shape = w.shape, b.shape
+        if need:
+            ctx.save_for_backward(o.dE, o.dw, o.db)
+        active = o.active[0] if ctx.squeeze else o.active
+        ctx.mark_non_differentiable(active)
+        return (o.loss[0] if ctx.squeeze else o.loss), active
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out, _grad_active):
+        gE, gw, gb = _ragged_node_backward(ctx, grad_out)
+        return gE, None, gw, gb, None, None, None, None
+
+
 # The autograd node in C++ (libge2e_torch.so,csrc_torch/ge2e_autograd.cpp: torch.ops.ge2e_amd.loss): the same two C-ABI
 # calls as _GE2ELossFunction without the Python dispatch around them -- the eager module step at B = 1 is host-bound.
 # Used when the library has been built (build.build() does); _GE2ELossFunction is the same node in Python.
@@ -1147,7 +1253,7 @@ def ge2e_loss_ragged(embeddings: torch.Tensor, counts, w: torch.Tensor, b: torch
 
 def ge2e_loss_labeled(embeddings: torch.Tensor, labels, w: torch.Tensor, b: torch.Tensor, *,
                       num_speakers: Optional[int] = None, eps: float = SMALL_ERR, eps_cos: float = EPS_COS,
-                      variant: str = "softmax") -> torch.Tensor:
+                      variant: str = "softmax", masked: bool = False, return_active: bool = False):
     """Differentiable GE2E loss of rows in ANY order with one speaker label each: 0-dim for (R, D) input, (B,) for
     (B, R, D).  What `ge2e_loss_ragged` computes on the rows sorted by speaker (stable), with the embeddings' gradient in
     the caller's row order; nothing is sorted or copied on the way: the index kernel orders the rows on the device and the
@@ -1159,7 +1265,21 @@ def ge2e_loss_labeled(embeddings: torch.Tensor, labels, w: torch.Tensor, b: torc
     On the DEVICE -- torch.int32 or torch.int64 -- they are taken as dense ids in [0, num_speakers), as is and UNVERIFIED
     (checking would cost a synchronisation), and ``num_speakers`` must be given: the kernel clamps what it reads, so broken
     labels give wrong numbers, not a wild access.  float16 / bfloat16 are computed in fp32 behind differentiable casts;
-    float64 is not implemented (there is no fp64 ragged kernel, and no silent fp32 arithmetic in its place)."""
+    float64 is not implemented (there is no fp64 ragged kernel, and no silent fp32 arithmetic in its place).
+
+    ``masked=True`` takes the batch as it is (ge2e_loss_fwd_bwd_labeled_masked): ``num_speakers`` is an upper bound of the
+    ids (the data set's speaker count works; required for device labels), a row whose label is outside [0, num_speakers)
+    -- on the host: negative -- is ignored, and a speaker left with fewer than 2 rows is left out, rows and centroid
+    alike.  Device labels may hold any values; host labels may hold lone speakers and a different number of speakers per
+    batch.  Everything is decided on the device, without a synchronisation.  The rows that do not count are never read
+    and get a zero gradient; a batch in which nothing counts has loss 0.  ``return_active=True`` (with ``masked``) returns
+    ``(loss, active)``: active (2,) / (B, 2) int32 on the device, not differentiable, holds the numbers of speakers and
+    of rows that counted, so ``loss / active[..., 1].clamp(min=1)`` is the mean over those rows."""
+    if return_active and not masked:
+        raise ValueError("return_active needs masked=True: without masking every row counts")
+    if masked and embeddings.dtype == torch.float64:
+        raise NotImplementedError("ge2e_loss_labeled: float64 embeddings are not implemented (the ragged kernel is fp32 and "
+                                  "nothing casts float64 down silently); pass float32")
     _require_cuda(embeddings, "embeddings")
     in_dtype = embeddings.dtype
     if in_dtype == torch.float64:
@@ -1175,6 +1295,10 @@ def ge2e_loss_labeled(embeddings: torch.Tensor, labels, w: torch.Tensor, b: torc
         embeddings = embeddings.clone()
     B, R = (1, embeddings.shape[0]) if embeddings.dim() == 2 else embeddings.shape[:2]
     with _on_device(embeddings.device):
-        lab, N = _labels_on_device(labels, num_speakers, B, R, embeddings.device)
+        lab, N = _labels_on_device(labels, num_speakers, B, R, embeddings.device, masked)
+    if masked:
+        loss, active = _GE2ELossMaskedFunction.apply(embeddings, lab, w, b, float(eps), float(eps_cos), variant, N)
+        loss = loss if in_dtype == torch.float32 else loss.to(in_dtype)
+        return (loss, active) if return_active else loss
     loss = _GE2ELossLabeledFunction.apply(embeddings, lab, w, b, float(eps), float(eps_cos), variant, N)
     return loss if in_dtype == torch.float32 else loss.to(in_dtype)

@@ -116,7 +116,7 @@ class GE2ELoss(nn.Module):
         self.w = nn.Parameter(torch.tensor(10.0).to(self.device), requires_grad=True)
         self.b = nn.Parameter(torch.tensor(-5.0).to(self.device), requires_grad=True)
 
-    def forward(self, embeddings, counts=None, labels=None, num_speakers=None):
+    def forward(self, embeddings, counts=None, labels=None, num_speakers=None, masked=False, return_active=False):
         """embeddings (N,M,D) [or (B,N,M,D)] on hp.general.device -> loss (s3:19-30).
 
         Like the reference, w is NOT clamped (s3:22 discards torch.clamp's result), the
@@ -136,14 +136,23 @@ class GE2ELoss(nn.Module):
         ``torch.int64`` device tensor of dense ids in [0, ``num_speakers``), unverified, with ``num_speakers`` given
         (``functional.ge2e_loss_labeled``).  The gradient comes back in the caller's row order.  The same conditions:
         ``impl`` "auto", no float64, eager with ``graph=True``.
+
+        ``masked=True`` (with ``labels``): the batch as it is.  ``num_speakers`` is an upper bound of the ids, rows whose
+        label is outside [0, ``num_speakers``) -- on the host: negative, e.g. -1 on padding -- are ignored, a speaker left
+        with fewer than 2 rows is left out, device labels may hold anything; all decided on the device.
+        ``return_active=True`` returns ``(loss, active)``, active (2,) / (B, 2) int32 on the device: the numbers of
+        speakers and rows that counted (``functional.ge2e_loss_labeled``).
         """
+        if (masked or return_active) and labels is None:
+            raise ValueError("masked=True / return_active=True belong to labels=...: pass one speaker label per row")
         if labels is not None:
             if counts is not None:
                 raise ValueError("pass counts (rows grouped by speaker) or labels (rows in any order), not both")
             if self.impl != "auto":
                 raise ValueError(f'impl="{self.impl}" names a fixed-shape kernel; the ragged loss has one kernel (impl="auto")')
             return GF.ge2e_loss_labeled(embeddings, labels, self.w, self.b, num_speakers=num_speakers,
-                                        eps=self.hp.general.small_err, variant=self.variant)
+                                        eps=self.hp.general.small_err, variant=self.variant, masked=masked,
+                                        return_active=return_active)
         if counts is not None:
             if self.impl != "auto":
                 raise ValueError(f'impl="{self.impl}" names a fixed-shape kernel; the ragged loss has one kernel (impl="auto")')
