@@ -214,6 +214,49 @@ int ge2e_loss_fwd_bwd_labeled_masked(const float* E, const int* labels, int B, i
                                      void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * LABELLED EVALUATION: the cosines (and the EER counts) of the masked labelled loss, forward only, for rows in any order.
+ * Semantics per batch: ge2e_loss_fwd_bwd_labeled_masked's -- a row is valid iff 0 <= label < N, a speaker active iff at
+ * least 2 valid rows carry its label, a row active iff it is valid and its speaker is active; the active speakers get the
+ * compact ids 0 .. n_act-1 by ascending label (ge2e_label_index_masked's speakers / active).  For an active row r of
+ * compact speaker j and k < n_act:
+ *   cos[r][k] = cossim(e_r, c_k) + eps  (k != j),   cos[r][j] = cossim(e_r, (sum_j - e_r) / (m_j - 1)) + eps
+ * with c_k the mean of speaker k's active rows and F.cosine_similarity's eps_cos clamp.  Outputs, in the CALLER'S row order:
+ *   cos      [B][R][N]  column k = compact speaker k; WRITTEN AS 0 on every row that is not active and on every column
+ *                       k >= n_act: every element is written.  NULL: the matrix is never materialised (counts only)
+ *   col      [B][R]     the row's own column (its compact speaker id), -1 for a row that is not active; or NULL
+ *   speakers [B][N], active [B][2]   as ge2e_label_index_masked writes them; or NULL
+ *   counts   [B][T][2]  the calculate_ERR sweep (s5_eval_model.py:57-98 with w = 1, b = 0, s5:44) on cos itself, over the
+ *                       active rows and the columns < n_act:  [t][0] = #{(r,k), k != col[r] : cos[r][k] > thr[t]},
+ *                       [t][1] = #{r : cos[r][col[r]] > thr[t]}.  fp32 strict `>`, NaN accepts nothing; thresholds
+ *                       non-decreasing, T <= 4096, as for ge2e_eer_counts.  NULL (with thresholds NULL / T = 0): no counts
+ * At least one of cos and counts must be given.  Rows that are not active are never read: they may hold NaN.  n_act = 0:
+ * all of cos and counts 0.  Three launches (the index kernel, one wave per speaker for the centroids, one workgroup per
+ * 64 rows for the cosines: a single batch spreads over the chip), enqueue-only, no allocation, no state, static shapes:
+ * fit for a HIP graph.  The counts are accumulated with integer atomics only: the same bits every launch.  The
+ * workspace is this entry's own (ge2e_cos_sim_labeled_workspace_bytes, 256-byte aligned, per batch: centroids and sums for
+ * max(1, min(N, R / 2)) speakers, the index tables, the index kernel's counters; no control block, no initialisation, and
+ * the result does not depend on what it held).  Checked on the host before anything is launched, in this order:
+ * GE2E_ERR_NULL (E, labels, or both cos and counts NULL), GE2E_ERR_SHAPE (B, N, R, D < 1, T < 0, T > 4096, counts without
+ * thresholds or with T = 0), GE2E_ERR_WORKSPACE, GE2E_ERR_ALIGN (E not 16-byte aligned).
+ * ge2e_eer_counts_labeled: the same count on a CALLER-MADE sim [B][R][N] (e.g. w cos + b) with the col and active the
+ * first call returned; columns >= n_act and rows with col < 0 are never read.  Two launches (zeroing, counting).
+ */
+size_t ge2e_cos_sim_labeled_workspace_bytes(int B, int N, int R, int D);   /* 0 for a bad shape */
+int ge2e_cos_sim_labeled(const float* E, const int* labels, int B, int N, int R, int D,
+                         float eps_cos, float eps,
+                         const float* thresholds, int T,       /* NULL / 0: no counts */
+                         float* cos,      /* [B][R][N] or NULL */
+                         int* col,        /* [B][R]    or NULL */
+                         int* speakers,   /* [B][N]    or NULL */
+                         int* active,     /* [B][2]    or NULL */
+                         int* counts,     /* [B][T][2] or NULL */
+                         void* workspace, size_t workspace_bytes, void* stream);
+
+int ge2e_eer_counts_labeled(const float* sim, const int* col, const int* active,
+                            int B, int N, int R,
+                            const float* thresholds, int T, int* counts, void* stream);
+
+/*
  * The same, fed with the encoder's RAW output (s2_model_GE2E_loss_speach_embed.py:34 +
  * s4_train_embed_model.py:186-192 folded into the loss kernel's load and store stages):
  *   Y   [B][N*M][D]  the encoder's projection BEFORE its L2-normalisation, rows in the encoder's own (permuted) order

@@ -11,6 +11,7 @@
 #include "ge2e_f64.hpp"
 #include "ge2e_ragged.hpp"
 #include "ge2e_labels.hpp"
+#include "ge2e_labeled_eval.hpp"
 #include "ge2e_helpers.hpp"
 #include "ge2e_fused.hpp"
 #include "ge2e_selftest.hpp"
@@ -370,6 +371,49 @@ int ge2e_loss_fwd_bwd_labeled_masked(const float* E, const int* labels, int B, i
     p.ws = (float*)workspace;
     p.log_eps = log_eps_of(eps);
     return (int)launch_ragged(p, (hipStream_t)stream);
+}
+
+// The labelled EVALUATION calls (include/ge2e_hip.h, csrc/ge2e_labeled_eval.hip): the masked index kernel, unchanged, then
+// the centroid kernel and the row kernel, all on the stream.  Checks on the host in the labelled entry's order.
+size_t ge2e_cos_sim_labeled_workspace_bytes(int B, int N, int R, int D) {
+    return masked_shape_ok(B, N, R, D) ? labeled_eval_layout(B, N, R, D).total : 0;
+}
+
+int ge2e_cos_sim_labeled(const float* E, const int* labels, int B, int N, int R, int D, float eps_cos, float eps,
+                         const float* thresholds, int T, float* cos, int* col, int* speakers, int* active, int* counts,
+                         void* workspace, size_t workspace_bytes, void* stream) {
+    if (!E || !labels || (!cos && !counts)) return GE2E_ERR_NULL;
+    if (!masked_shape_ok(B, N, R, D) || T < 0 || T > 4096 || (counts && (!thresholds || T == 0))) return GE2E_ERR_SHAPE;
+    const LabeledEvalLayout L = labeled_eval_layout(B, N, R, D);
+    if (!workspace || workspace_bytes < L.total || ((uintptr_t)workspace & 255)) return GE2E_ERR_WORKSPACE;
+    if ((uintptr_t)E & 15) return GE2E_ERR_ALIGN;
+    char* ws = (char*)workspace;
+    if (!col) col = (int*)(ws + L.col);
+    if (!speakers) speakers = (int*)(ws + L.speakers);
+    if (!active) active = (int*)(ws + L.active);
+    ProblemLabeledEval p{};
+    p.E = E;
+    p.off = (int*)(ws + L.off);
+    p.order = (int*)(ws + L.order);
+    p.active = active;
+    p.thr = counts ? thresholds : nullptr;
+    p.cos = cos; p.col = col; p.counts = counts;
+    p.CH = (float*)(ws + L.ch); p.SS = (float*)(ws + L.ss); p.CST = (float*)(ws + L.cstat); p.spk = (int*)(ws + L.spk);
+    p.B = B; p.N = N; p.R = R; p.D = D;
+    p.NA = labeled_eval_capacity(N, R);
+    p.T = counts ? T : 0;
+    p.eps_cos = eps_cos; p.eps = eps;
+    const hipError_t err = launch_label_index_masked(labels, B, N, R, (int*)(ws + L.off), (int*)(ws + L.order), speakers,
+                                                     active, (int*)(ws + L.index), (hipStream_t)stream);
+    if (err != hipSuccess) return (int)err;
+    return (int)launch_labeled_eval(p, (hipStream_t)stream);
+}
+
+int ge2e_eer_counts_labeled(const float* sim, const int* col, const int* active, int B, int N, int R,
+                            const float* thresholds, int T, int* counts, void* stream) {
+    if (!sim || !col || !active || !thresholds || !counts) return GE2E_ERR_NULL;
+    if (B < 1 || N < 1 || R < 1 || T < 1 || T > 4096) return GE2E_ERR_SHAPE;
+    return (int)launch_eer_counts_labeled(sim, col, active, B, N, R, thresholds, T, counts, (hipStream_t)stream);
 }
 
 // ---- diagnostics: the launch plan of a call, from the launchers' own decision functions (ge2e_plan.hpp); no GPU needed ----

@@ -72,3 +72,48 @@ def calculate_ERR(model, hp, N: int = 4, M: int = 16, test_loader=None, verbose:
                 print("\nEER : %0.2f (thres:%0.2f, FAR:%0.2f, FRR:%0.2f)" % (r["EER"], r["thres"], r["FAR"], r["FRR"]))
             results.append(r)
     return results
+
+
+# ---- labelled evaluation: any utterance count per speaker, rows in any order (ge2e_cos_sim_labeled) ------------------------
+
+def eer_from_labeled_counts(counts, n_act: int, r_act: int, thresholds=THRESHOLDS):
+    """The sweep of `eer_from_counts` (s5:50-98) for a labelled batch of ``r_act`` counting rows over ``n_act`` counting
+    speakers, with the textbook rates: FAR = fa / (r_act (n_act - 1)) (0 when n_act < 2), FRR = (r_act - ta) / r_act (0
+    when r_act = 0).  The reference's own denominators (s5:81, 88) need an M -- one utterance count for every speaker --
+    that a ragged batch does not have, so only the normalised rates exist here; with equal counts this is
+    ``eer_from_counts(counts, N, M, normalized=True)``."""
+    n_act, r_act = int(n_act), int(r_act)
+    diff, EER, EER_thres, EER_FAR, EER_FRR = 1, 0, 0, 0, 0  # s5:50-54
+    for thres, (fa, ta) in zip(thresholds, counts):
+        fa, ta = int(fa), int(ta)
+        FAR = fa / (r_act * (n_act - 1)) if n_act >= 2 and r_act > 0 else 0
+        FRR = (r_act - ta) / r_act if r_act > 0 else 0
+        if diff > abs(FAR - FRR):             # s5:93-98
+            diff = abs(FAR - FRR)
+            EER = (FAR + FRR) / 2
+            EER_thres = thres
+            EER_FAR = FAR
+            EER_FRR = FRR
+    return {"EER": EER, "thres": EER_thres, "FAR": EER_FAR, "FRR": EER_FRR}
+
+
+def evaluate_labeled(model, loader, num_speakers=None, device="cuda:0", thresholds=THRESHOLDS, verbose: bool = True):
+    """`calculate_ERR` for a test set as it comes: ``loader`` yields (mel, speaker_ids) with ANY number of utterances per
+    speaker, in any order (negative ids: rows to ignore).  Per batch: the embeddings, ONE `cos_sim_labeled(...,
+    need_cos=False)` -- the similarity matrix is never materialised -- and one read-back of T * 2 + 2 integers; the dict of
+    `eer_from_labeled_counts` with ``n_act`` and ``r_act`` added.  ``num_speakers``: the bound for device ids (host ids are
+    compacted per batch)."""
+    results = []
+    T = len(thresholds)
+    with torch.no_grad():
+        for mel, speaker_ids in loader:
+            emb = model(mel.to(device)).contiguous().float()
+            out = GF.cos_sim_labeled(emb, speaker_ids, num_speakers=num_speakers, thresholds=thresholds, need_cos=False)
+            back = torch.cat([out.counts.reshape(-1), out.active.reshape(-1)]).cpu().numpy()   # the one read-back
+            n_act, r_act = int(back[2 * T]), int(back[2 * T + 1])
+            r = eer_from_labeled_counts(back[:2 * T].reshape(T, 2), n_act, r_act, thresholds)
+            r["n_act"], r["r_act"] = n_act, r_act
+            if verbose:
+                print("\nEER : %0.2f (thres:%0.2f, FAR:%0.2f, FRR:%0.2f)" % (r["EER"], r["thres"], r["FAR"], r["FRR"]))
+            results.append(r)
+    return results

@@ -94,7 +94,7 @@ def _launch(name: str, dev: torch.device, *args) -> None:
 #    dropped or outgrown workspace goes back to the caching allocator, which hands a block out again only in the order
 #    of the stream it was allocated on -- the launches still using it are ahead in that very stream.
 #  * The double-precision kernel, the ragged kernel and its labelled forms have their own entries (key tags "f64",
-#    "ragged", "labeled", "labeled_masked"): their workspaces have no control block, so they are never shared with the fp32 kernels' workspace, need no initialisation
+#    "ragged", "labeled", "labeled_masked", and "labeled_eval" of the labelled evaluation call): their workspaces have no control block, so they are never shared with the fp32 kernels' workspace, need no initialisation
 #    launch, and no `workspace_override` stands in for them.
 _ws_bytes_cache: dict = {}
 _ws_cache: dict = {}
@@ -133,6 +133,8 @@ _LOSS_ABI = {
     "labeled": ("ge2e_loss_fwd_bwd_labeled", "ge2e_workspace_bytes_labeled", False, ("labeled",), False),
     "labeled_masked": ("ge2e_loss_fwd_bwd_labeled_masked", "ge2e_workspace_bytes_labeled_masked", False,
                        ("labeled_masked",), False),
+    # (no loss: the labelled evaluation call, here for its workspace -- query (B, N, R, D))
+    "labeled_eval": ("ge2e_cos_sim_labeled", "ge2e_cos_sim_labeled_workspace_bytes", False, ("labeled_eval",), False),
 }
 
 
@@ -609,6 +611,110 @@ def loss_fwd_bwd_labeled(embeddings: torch.Tensor, labels, w: torch.Tensor, b: t
             *((ptr(out.active),) if masked else ()), workspace.data_ptr(), workspace.numel(), stream)
     _lib.check(code, entry)
     return out
+
+
+# ---- labelled evaluation: cosines and EER counts for rows in any order (ge2e_cos_sim_labeled, csrc/ge2e_labeled_eval.hip) ----
+
+@dataclass
+class LabeledCosOutputs:
+    cos: Optional[torch.Tensor]         # (B, R, N) float32: column k = compact speaker k; 0 on rows / columns that do not count
+    col: torch.Tensor                   # (B, R) int32: the row's own column, -1 for a row that does not count
+    speakers: torch.Tensor              # (B, N) int32: the label of compact speaker k, then -1
+    active: torch.Tensor                # (B, 2) int32: speakers and rows that count
+    counts: Optional[torch.Tensor]      # (B, T, 2) int32: [false accepts, own accepts] per threshold
+
+
+def _threshold_table(thresholds, dev: torch.device, device_ok: bool = False) -> torch.Tensor:
+    """`eer_counts`'s check: 1..4096 non-decreasing values, compared in fp32.  ``device_ok``: a float32 DEVICE tensor is
+    taken as it is -- reading it would take a host synchronisation, so its order is the caller's word (no upload: fit for
+    a graph capture)."""
+    if device_ok and torch.is_tensor(thresholds) and thresholds.device.type != "cpu":
+        if thresholds.dtype != torch.float32 or thresholds.device != dev or not 1 <= thresholds.numel() <= 4096:
+            raise TypeError(f"device thresholds must be 1..4096 torch.float32 values on {dev}")
+        return thresholds.reshape(-1).contiguous()
+    thr = torch.as_tensor(thresholds, dtype=torch.float64).to(torch.float32).reshape(-1)
+    if thr.numel() < 1 or thr.numel() > 4096 or bool((thr[1:] < thr[:-1]).any()):
+        raise ValueError("thresholds must be 1..4096 non-decreasing values")
+    return thr.to(dev)
+
+
+def cos_sim_labeled(embeddings: torch.Tensor, labels, *, num_speakers: Optional[int] = None, eps: float = SMALL_ERR,
+                    eps_cos: float = EPS_COS, thresholds=None, need_cos: bool = True,
+                    workspace: Optional[torch.Tensor] = None) -> LabeledCosOutputs:
+    """One enqueue of ge2e_cos_sim_labeled on the current stream (three launches: index, centroids, rows).  No host sync
+    (host labels: none after their first use).  FORWARD ONLY: no result requires grad and nothing is recorded for autograd
+    (differentiable labelled helpers do not exist; train through `ge2e_loss_labeled`).
+
+    ``embeddings`` (R, D) or (B, R, D) float32, rows in ANY order; ``labels`` as `loss_fwd_bwd_labeled(masked=True)` takes
+    them: host labels of arbitrary ids (negative: ignore the row), compacted, or a DEVICE tensor (torch.int32 /
+    torch.int64) taken as it is with ``num_speakers`` = N as a bound.  The masked loss's semantics: a row counts when
+    0 <= label < N and at least one more row carries its label.  Returns, for 2-D input without the batch dimension:
+    ``cos`` (R, N) -- column k is the k-th counting speaker by ascending label (``speakers[k]`` names it; with every speaker
+    counting a column is a label), the own column holds the leave-one-out cosine, + eps everywhere, 0 on every row and
+    column that does not count (None with ``need_cos=False``: the matrix is never materialised) -- ``col`` (R,),
+    ``speakers`` (N,), ``active`` (2,), and with ``thresholds`` (non-decreasing, at most 4096: a sequence, checked and
+    uploaded, or a float32 DEVICE tensor taken as it is) ``counts`` (T, 2): the calculate_ERR sweep on cos itself."""
+    lib = _lib.load()
+    _require_cuda(embeddings, "embeddings")
+    if embeddings.dim() not in (2, 3):
+        raise ValueError(f"embeddings must be (R,D) or (B,R,D), got {tuple(embeddings.shape)}")
+    if not embeddings.is_contiguous():
+        raise RuntimeError("embeddings must be contiguous")
+    if embeddings.dtype != torch.float32:
+        raise TypeError(f"embeddings must be float32 at this boundary, got {embeddings.dtype}")
+    if thresholds is None and not need_cos:
+        raise ValueError("nothing to compute: need_cos=False without thresholds")
+    squeeze = embeddings.dim() == 2
+    e3 = (embeddings.unsqueeze(0) if squeeze else embeddings).detach()
+    B, R, D = e3.shape
+    dev = e3.device
+    with _on_device(dev):
+        lab, N = _labels_on_device(labels, num_speakers, B, R, dev, True)
+        thr = _threshold_table(thresholds, dev, device_ok=True) if thresholds is not None else None
+    T = thr.numel() if thr is not None else 0
+    i32 = dict(dtype=torch.int32, device=dev)
+    out = LabeledCosOutputs(
+        cos=torch.empty(B, R, N, dtype=torch.float32, device=dev) if need_cos else None,
+        col=torch.empty(B, R, **i32), speakers=torch.empty(B, N, **i32), active=torch.empty(B, 2, **i32),
+        counts=torch.empty(B, T, 2, **i32) if T else None)
+    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    with _on_device(dev) as guard:
+        stream = _stream_ptr(e3)
+        if workspace is None:
+            workspace = _workspace_for(lib, dev, stream, "labeled_eval", (B, N, R, D), guard.idx)
+        code = lib.ge2e_cos_sim_labeled(e3.data_ptr(), lab.data_ptr(), B, N, R, D, eps_cos, eps, ptr(thr), T, ptr(out.cos),
+                                        out.col.data_ptr(), out.speakers.data_ptr(), out.active.data_ptr(), ptr(out.counts),
+                                        workspace.data_ptr(), workspace.numel(), stream)
+    _lib.check(code, "ge2e_cos_sim_labeled")
+    if squeeze:
+        out = LabeledCosOutputs(*(t[0] if t is not None else None
+                                  for t in (out.cos, out.col, out.speakers, out.active, out.counts)))
+    return out
+
+
+def eer_counts_labeled(sim: torch.Tensor, col: torch.Tensor, active: torch.Tensor, thresholds) -> torch.Tensor:
+    """ge2e_eer_counts_labeled: the calculate_ERR sweep on a caller-made ``sim`` (R, N) / (B, R, N) -- e.g. w * cos + b --
+    with the ``col`` and ``active`` `cos_sim_labeled` returned -> int32 (T, 2) / (B, T, 2).  Rows with col < 0 and columns
+    >= active[0] are never read.  ``thresholds``: `eer_counts`'s check (non-decreasing, else ValueError); a float32 DEVICE
+    tensor is taken as it is, as in `cos_sim_labeled`."""
+    _require_cuda(sim, "sim")
+    squeeze = sim.dim() == 2
+    s = sim.unsqueeze(0) if squeeze else sim
+    if s.dim() != 3:
+        raise ValueError(f"sim must be (R,N) or (B,R,N), got {tuple(sim.shape)}")
+    s = s.detach().contiguous().float()
+    B, R, N = s.shape
+    dev = s.device
+    for name, t, n in (("col", col, B * R), ("active", active, B * 2)):
+        _require_cuda(t, name)
+        if t.dtype != torch.int32 or t.numel() != n or t.device != dev:
+            raise TypeError(f"{name} must be a torch.int32 tensor of {n} elements on {dev}")
+    thr = _threshold_table(thresholds, dev, device_ok=True)
+    T = thr.numel()
+    counts = torch.empty(B, T, 2, dtype=torch.int32, device=dev)
+    _launch("ge2e_eer_counts_labeled", dev, s.data_ptr(), col.contiguous().data_ptr(), active.contiguous().data_ptr(), B, N,
+            R, thr.data_ptr(), T, counts.data_ptr(), _stream_ptr(s))
+    return counts[0] if squeeze else counts
 
 
 # ---- the reference's static helpers (s3:33-38, 41-80, 95-112, 114-127), differentiable like the originals ----------
