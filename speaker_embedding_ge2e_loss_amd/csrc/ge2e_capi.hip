@@ -2,7 +2,6 @@
 // implementation choice, workspace sizing, launches.  No allocation, no sync, no state.
 #include "../../include/ge2e_hip.h"
 
-#include <algorithm>
 #include <cmath>
 #include <stdlib.h>
 
@@ -34,12 +33,43 @@ bool shape_ok(int B, int N, int M, int D) { return B >= 1 && N >= 1 && M >= 2 &&
 // The ragged entry point's shape: R rows shared by N speakers of at least two rows each.
 bool ragged_shape_ok(int B, int N, int R, int D) { return B >= 1 && N >= 1 && D >= 1 && (long long)R >= 2LL * N; }
 
+// The masked entries' shape: N is a bound there, so R >= 2 N is not asked for.
+bool masked_shape_ok(int B, int N, int R, int D) { return B >= 1 && N >= 1 && R >= 1 && D >= 1; }
+
+// The index entry points' shape.
+bool index_shape_ok(int B, int N, int R) { return B >= 1 && N >= 1 && R >= 1; }
+
 bool variant_ok(int v) { return v == GE2E_VARIANT_SOFTMAX || v == GE2E_VARIANT_CONTRAST; }
 
 // The NULL rule of every loss entry point: inputs and the loss always, and whoever asks for dE takes dw and db with it.
 bool loss_ptrs_ok(const void* E, const void* w, const void* b, const void* loss, const void* dE, const void* dw,
                   const void* db) {
     return E && w && b && loss && (!dE || (dw && db));
+}
+
+// A caller's workspace: present, large enough, aligned (256 bytes; the cosine backward's asks for 16).
+bool workspace_ok(const void* workspace, size_t workspace_bytes, size_t need, uintptr_t align = 256) {
+    return workspace && workspace_bytes >= need && !((uintptr_t)workspace & (align - 1));
+}
+
+// The kernels move 16 bytes per lane to and from E / dE.  (A null pointer -- no dE -- is aligned.)
+bool aligned16(const void* p) { return !((uintptr_t)p & 15); }
+
+// The checks of every loss entry point behind its NULL rule, in the order that is part of the ABI: shape, variant,
+// [implementation], workspace, alignment of E and dE; GE2E_OK (0) when all hold.  `shape_good` is the entry's own shape
+// predicate.  `impl` and `need` run only once shape and variant hold, in this order: `impl` answers GE2E_OK or the code
+// of an implementation that cannot run the shape, `need` the workspace bytes of the call (0: it takes none, and the
+// workspace is not looked at).
+template <class Need, class Impl = int (*)()>
+int loss_checks(bool shape_good, int variant, Need need, const void* workspace, size_t workspace_bytes, const void* E,
+                const void* dE, Impl impl = [] { return GE2E_OK; }) {
+    if (!shape_good) return GE2E_ERR_SHAPE;
+    if (!variant_ok(variant)) return GE2E_ERR_VARIANT;
+    if (const int code = impl()) return code;
+    const size_t bytes = need();
+    if (bytes > 0 && !workspace_ok(workspace, workspace_bytes, bytes)) return GE2E_ERR_WORKSPACE;
+    if (!aligned16(E) || !aligned16(dE)) return GE2E_ERR_ALIGN;
+    return GE2E_OK;
 }
 
 template <class T>
@@ -65,6 +95,23 @@ P make_problem(const T* E, int B, int N, int M, int D, const T* w, const T* b, T
     P p = make_problem_io<P>(E, w, b, eps_cos, eps, variant, loss, per_emb_loss, dE, dw, db);
     p.B = B; p.N = N; p.M = M; p.D = D;
     return p;
+}
+
+// ... and with what the ragged kernel's three entry points add, on their checked workspace: they differ in `order` (null:
+// the rows lie speaker after speaker), `active` (null: every row and speaker counts) and NA (read with `active` only).
+ProblemRagged ragged_problem(ProblemRagged p, const int* off, const int* order, const int* active, int NA, int B, int N, int R,
+                             int D, void* workspace) {
+    p.off = off; p.order = order; p.active = active; p.NA = NA;
+    p.B = B; p.N = N; p.R = R; p.D = D;
+    p.ws = (float*)workspace;
+    p.log_eps = log_eps_of(p.eps);
+    return p;
+}
+
+// The labelled loss entries' workspace: the ragged kernel's slices -- with masking for speaker_capacity speakers, N being
+// a bound there -- then the index tables (ge2e_labels.hpp).
+IndexTables labeled_tables(int B, int N, int R, int D, bool masked) {
+    return index_tables(ragged_workspace_bytes(B, masked ? speaker_capacity(N, R) : N, R, D), B, N, R, masked);
 }
 
 // AUTO at shapes both accept (measured at N=64, M=10, D=256, interleaved in one process, tools/compare_impls.py,
@@ -119,13 +166,12 @@ size_t ws_bytes(int B, int N, int M, int D, int impl) {
 }
 
 int run(Problem& p, int impl, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!shape_ok(p.B, p.N, p.M, p.D)) return GE2E_ERR_SHAPE;
-    if (!variant_ok(p.variant)) return GE2E_ERR_VARIANT;
-    const int chosen = resolve(p.B, p.N, p.M, p.D, p.variant, impl);
-    if (chosen < 0) return chosen;
-    const size_t need = ws_bytes(p.B, p.N, p.M, p.D, chosen);
-    if (need > 0 && (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 255))) return GE2E_ERR_WORKSPACE;
-    if (((uintptr_t)p.E & 15) || ((uintptr_t)p.dE & 15)) return GE2E_ERR_ALIGN;
+    int chosen = 0;
+    size_t need = 0;
+    if (const int code = loss_checks(shape_ok(p.B, p.N, p.M, p.D), p.variant,
+                                     [&] { return need = ws_bytes(p.B, p.N, p.M, p.D, chosen); }, workspace, workspace_bytes, p.E, p.dE,
+                                     [&] { return (chosen = resolve(p.B, p.N, p.M, p.D, p.variant, impl)) < 0 ? chosen : GE2E_OK; }))
+        return code;
     p.ws = (float*)((char*)workspace + (need > 0 && chosen != GE2E_IMPL_TEAM ? team_head_bytes() : 0));
 #ifdef GE2E_PROFILE
     p.prof = g_prof;
@@ -205,10 +251,9 @@ int ge2e_loss_fwd_bwd_f64(const double* E, int B, int N, int M, int D, const dou
                           double eps, int variant, double* loss, double* per_emb_loss, double* dE, double* dw, double* db,
                           void* workspace, size_t workspace_bytes, void* stream) {
     if (!loss_ptrs_ok(E, w, b, loss, dE, dw, db)) return GE2E_ERR_NULL;
-    if (!shape_ok(B, N, M, D)) return GE2E_ERR_SHAPE;
-    if (!variant_ok(variant)) return GE2E_ERR_VARIANT;
-    if (!workspace || workspace_bytes < f64_workspace_bytes(B, N, M, D) || ((uintptr_t)workspace & 255)) return GE2E_ERR_WORKSPACE;
-    if (((uintptr_t)E & 15) || ((uintptr_t)dE & 15)) return GE2E_ERR_ALIGN;
+    if (const int code = loss_checks(shape_ok(B, N, M, D), variant, [&] { return f64_workspace_bytes(B, N, M, D); }, workspace,
+                                     workspace_bytes, E, dE))
+        return code;
     ProblemF64 p = make_problem<ProblemF64>(E, B, N, M, D, w, b, eps_cos, eps, variant, loss, per_emb_loss, dE, dw, db);
     p.ws = (double*)workspace;
     p.log_eps = log_eps_of(eps);
@@ -227,15 +272,11 @@ int ge2e_loss_fwd_bwd_ragged(const float* E, const int* offsets, int B, int N, i
                              float eps_cos, float eps, int variant, float* loss, float* per_row_loss, float* dE, float* dw,
                              float* db, void* workspace, size_t workspace_bytes, void* stream) {
     if (!offsets || !loss_ptrs_ok(E, w, b, loss, dE, dw, db)) return GE2E_ERR_NULL;
-    if (!ragged_shape_ok(B, N, R, D)) return GE2E_ERR_SHAPE;
-    if (!variant_ok(variant)) return GE2E_ERR_VARIANT;
-    if (!workspace || workspace_bytes < ragged_workspace_bytes(B, N, R, D) || ((uintptr_t)workspace & 255)) return GE2E_ERR_WORKSPACE;
-    if (((uintptr_t)E & 15) || ((uintptr_t)dE & 15)) return GE2E_ERR_ALIGN;
-    ProblemRagged p = make_problem_io<ProblemRagged>(E, w, b, eps_cos, eps, variant, loss, per_row_loss, dE, dw, db);
-    p.off = offsets;
-    p.B = B; p.N = N; p.R = R; p.D = D;
-    p.ws = (float*)workspace;
-    p.log_eps = log_eps_of(eps);
+    if (const int code = loss_checks(ragged_shape_ok(B, N, R, D), variant, [&] { return ragged_workspace_bytes(B, N, R, D); },
+                                     workspace, workspace_bytes, E, dE))
+        return code;
+    const ProblemRagged p = ragged_problem(make_problem_io<ProblemRagged>(E, w, b, eps_cos, eps, variant, loss, per_row_loss, dE, dw, db),
+                                           offsets, nullptr, nullptr, 0, B, N, R, D, workspace);
     return (int)launch_ragged(p, (hipStream_t)stream);
 }
 
@@ -243,106 +284,68 @@ int ge2e_loss_fwd_bwd_ragged(const float* E, const int* offsets, int B, int N, i
 // table and the row order into this entry's own workspace, the ragged kernel's gathering instantiation reads them.  Same
 // checks, in the same order.  What the labels HOLD is the caller's word: reading them here would take a synchronisation;
 // the index kernel clamps them, so the order is a permutation whatever they hold and nothing reaches outside the buffers.
+// The masked form (labels of ANY content, include/ge2e_hip.h) decides on the device which rows and speakers count and
+// leaves their numbers in `active`.
 size_t ge2e_label_index_workspace_bytes(int B, int N, int R) {
-    return (B >= 1 && N >= 1 && R >= 1) ? label_index_workspace_bytes(B, N, R) : 0;
+    return index_shape_ok(B, N, R) ? label_index_workspace_bytes(B, N, R) : 0;
 }
 
-int ge2e_label_index(const int* labels, int B, int N, int R, int* offsets, int* order, void* workspace, size_t workspace_bytes,
-                     void* stream) {
-    if (!labels || !offsets || !order) return GE2E_ERR_NULL;
-    if (B < 1 || N < 1 || R < 1) return GE2E_ERR_SHAPE;
-    const size_t need = label_index_workspace_bytes(B, N, R);
-    if (need > 0 && (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 255))) return GE2E_ERR_WORKSPACE;
-    return (int)launch_label_index(labels, B, N, R, offsets, order, (int*)workspace, (hipStream_t)stream);
+size_t ge2e_label_index_masked_workspace_bytes(int B, int N, int R) {
+    return index_shape_ok(B, N, R) ? label_index_masked_workspace_bytes(B, N, R) : 0;
 }
 
 namespace {
-// ge2e_loss_fwd_bwd_labeled's workspace: the ragged kernel's slices, offsets [B][N+1], order [B][R], the index kernel's
-// counters; every part starts 256-byte aligned.
-struct LabeledLayout {
-    size_t off, order, index, total;   // bytes
-};
-LabeledLayout labeled_layout(int B, int N, int R, int D) {
-    LabeledLayout L;
-    L.off = ragged_workspace_bytes(B, N, R, D);
-    L.order = L.off + align_up((size_t)B * ((size_t)N + 1) * sizeof(int), 256);
-    L.index = L.order + align_up((size_t)B * R * sizeof(int), 256);
-    L.total = L.index + label_index_workspace_bytes(B, N, R);
-    return L;
+// Both index entry points: `masked` adds speakers and active to the required pointers and picks the kernel.
+int label_index(bool masked, const int* labels, int B, int N, int R, int* offsets, int* order, int* speakers, int* active,
+                void* workspace, size_t workspace_bytes, void* stream) {
+    if (!labels || !offsets || !order || (masked && (!speakers || !active))) return GE2E_ERR_NULL;
+    if (!index_shape_ok(B, N, R)) return GE2E_ERR_SHAPE;
+    const size_t need = masked ? label_index_masked_workspace_bytes(B, N, R) : label_index_workspace_bytes(B, N, R);
+    if (need > 0 && !workspace_ok(workspace, workspace_bytes, need)) return GE2E_ERR_WORKSPACE;
+    if (masked) return (int)launch_label_index_masked(labels, B, N, R, offsets, order, speakers, active, (int*)workspace,
+                                                      (hipStream_t)stream);
+    return (int)launch_label_index(labels, B, N, R, offsets, order, (int*)workspace, (hipStream_t)stream);
 }
 }  // namespace
 
+int ge2e_label_index(const int* labels, int B, int N, int R, int* offsets, int* order, void* workspace, size_t workspace_bytes,
+                     void* stream) {
+    return label_index(false, labels, B, N, R, offsets, order, nullptr, nullptr, workspace, workspace_bytes, stream);
+}
+
+int ge2e_label_index_masked(const int* labels, int B, int N, int R, int* offsets, int* order, int* speakers, int* active,
+                            void* workspace, size_t workspace_bytes, void* stream) {
+    return label_index(true, labels, B, N, R, offsets, order, speakers, active, workspace, workspace_bytes, stream);
+}
+
 size_t ge2e_workspace_bytes_labeled(int B, int N, int R, int D, int variant) {
     (void)variant;
-    return ragged_shape_ok(B, N, R, D) ? labeled_layout(B, N, R, D).total : 0;
+    return ragged_shape_ok(B, N, R, D) ? labeled_tables(B, N, R, D, false).total : 0;
 }
 
 int ge2e_loss_fwd_bwd_labeled(const float* E, const int* labels, int B, int N, int R, int D, const float* w, const float* b,
                               float eps_cos, float eps, int variant, float* loss, float* per_row_loss, float* dE, float* dw,
                               float* db, void* workspace, size_t workspace_bytes, void* stream) {
     if (!labels || !loss_ptrs_ok(E, w, b, loss, dE, dw, db)) return GE2E_ERR_NULL;
-    if (!ragged_shape_ok(B, N, R, D)) return GE2E_ERR_SHAPE;
-    if (!variant_ok(variant)) return GE2E_ERR_VARIANT;
-    const LabeledLayout L = labeled_layout(B, N, R, D);
-    if (!workspace || workspace_bytes < L.total || ((uintptr_t)workspace & 255)) return GE2E_ERR_WORKSPACE;
-    if (((uintptr_t)E & 15) || ((uintptr_t)dE & 15)) return GE2E_ERR_ALIGN;
+    IndexTables L{};
+    if (const int code = loss_checks(ragged_shape_ok(B, N, R, D), variant, [&] { return (L = labeled_tables(B, N, R, D, false)).total; },
+                                     workspace, workspace_bytes, E, dE))
+        return code;
     char* ws = (char*)workspace;
     int* offsets = (int*)(ws + L.off);
     int* order = (int*)(ws + L.order);
     const hipError_t err = launch_label_index(labels, B, N, R, offsets, order, (int*)(ws + L.index), (hipStream_t)stream);
     if (err != hipSuccess) return (int)err;
-    ProblemRagged p = make_problem_io<ProblemRagged>(E, w, b, eps_cos, eps, variant, loss, per_row_loss, dE, dw, db);
-    p.off = offsets;
-    p.order = order;
-    p.B = B; p.N = N; p.R = R; p.D = D;
-    p.ws = (float*)workspace;
-    p.log_eps = log_eps_of(eps);
+    const ProblemRagged p = ragged_problem(make_problem_io<ProblemRagged>(E, w, b, eps_cos, eps, variant, loss, per_row_loss, dE, dw, db),
+                                           offsets, order, nullptr, 0, B, N, R, D, workspace);
     return (int)launch_ragged(p, (hipStream_t)stream);
 }
 
-// The labelled loss on labels of ANY content (include/ge2e_hip.h): the masked index kernel decides on the device which rows
-// and speakers count and leaves their numbers in `active`; the ragged kernel's masked instantiation takes its extents from
-// there.  N is a bound, so R >= 2 N is not asked for.
-size_t ge2e_label_index_masked_workspace_bytes(int B, int N, int R) {
-    return (B >= 1 && N >= 1 && R >= 1) ? label_index_masked_workspace_bytes(B, N, R) : 0;
-}
-
-int ge2e_label_index_masked(const int* labels, int B, int N, int R, int* offsets, int* order, int* speakers, int* active,
-                            void* workspace, size_t workspace_bytes, void* stream) {
-    if (!labels || !offsets || !order || !speakers || !active) return GE2E_ERR_NULL;
-    if (B < 1 || N < 1 || R < 1) return GE2E_ERR_SHAPE;
-    const size_t need = label_index_masked_workspace_bytes(B, N, R);
-    if (need > 0 && (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 255))) return GE2E_ERR_WORKSPACE;
-    return (int)launch_label_index_masked(labels, B, N, R, offsets, order, speakers, active, (int*)workspace,
-                                          (hipStream_t)stream);
-}
-
-namespace {
-bool masked_shape_ok(int B, int N, int R, int D) { return B >= 1 && N >= 1 && R >= 1 && D >= 1; }
-
-// R rows hold at most R / 2 speakers of two rows each: what the ragged kernel's slices are laid out for.
-int masked_speaker_capacity(int N, int R) { return std::max(1, std::min(N, R / 2)); }
-
-// ge2e_loss_fwd_bwd_labeled_masked's workspace: the ragged kernel's slices (for masked_speaker_capacity speakers), offsets
-// [B][N+1], order [B][R], speakers [B][N], active [B][2], the index kernel's counters; every part starts 256-byte aligned.
-struct MaskedLayout {
-    size_t off, order, speakers, active, index, total;   // bytes
-};
-MaskedLayout masked_layout(int B, int N, int R, int D) {
-    MaskedLayout L;
-    L.off = ragged_workspace_bytes(B, masked_speaker_capacity(N, R), R, D);
-    L.order = L.off + align_up((size_t)B * ((size_t)N + 1) * sizeof(int), 256);
-    L.speakers = L.order + align_up((size_t)B * R * sizeof(int), 256);
-    L.active = L.speakers + align_up((size_t)B * N * sizeof(int), 256);
-    L.index = L.active + align_up((size_t)B * 2 * sizeof(int), 256);
-    L.total = L.index + label_index_masked_workspace_bytes(B, N, R);
-    return L;
-}
-}  // namespace
-
+// The labelled loss on labels of ANY content (include/ge2e_hip.h): the masked index kernel's `active` gives the ragged
+// kernel's masked instantiation its extents.
 size_t ge2e_workspace_bytes_labeled_masked(int B, int N, int R, int D, int variant) {
     (void)variant;
-    return masked_shape_ok(B, N, R, D) ? masked_layout(B, N, R, D).total : 0;
+    return masked_shape_ok(B, N, R, D) ? labeled_tables(B, N, R, D, true).total : 0;
 }
 
 int ge2e_loss_fwd_bwd_labeled_masked(const float* E, const int* labels, int B, int N, int R, int D, const float* w,
@@ -350,11 +353,10 @@ int ge2e_loss_fwd_bwd_labeled_masked(const float* E, const int* labels, int B, i
                                      float* dE, float* dw, float* db, int* active, void* workspace, size_t workspace_bytes,
                                      void* stream) {
     if (!labels || !loss_ptrs_ok(E, w, b, loss, dE, dw, db)) return GE2E_ERR_NULL;
-    if (!masked_shape_ok(B, N, R, D)) return GE2E_ERR_SHAPE;
-    if (!variant_ok(variant)) return GE2E_ERR_VARIANT;
-    const MaskedLayout L = masked_layout(B, N, R, D);
-    if (!workspace || workspace_bytes < L.total || ((uintptr_t)workspace & 255)) return GE2E_ERR_WORKSPACE;
-    if (((uintptr_t)E & 15) || ((uintptr_t)dE & 15)) return GE2E_ERR_ALIGN;
+    IndexTables L{};
+    if (const int code = loss_checks(masked_shape_ok(B, N, R, D), variant, [&] { return (L = labeled_tables(B, N, R, D, true)).total; },
+                                     workspace, workspace_bytes, E, dE))
+        return code;
     char* ws = (char*)workspace;
     int* offsets = (int*)(ws + L.off);
     int* order = (int*)(ws + L.order);
@@ -362,21 +364,16 @@ int ge2e_loss_fwd_bwd_labeled_masked(const float* E, const int* labels, int B, i
     const hipError_t err = launch_label_index_masked(labels, B, N, R, offsets, order, (int*)(ws + L.speakers), active,
                                                      (int*)(ws + L.index), (hipStream_t)stream);
     if (err != hipSuccess) return (int)err;
-    ProblemRagged p = make_problem_io<ProblemRagged>(E, w, b, eps_cos, eps, variant, loss, per_row_loss, dE, dw, db);
-    p.off = offsets;
-    p.order = order;
-    p.active = active;
-    p.B = B; p.N = N; p.R = R; p.D = D;
-    p.NA = masked_speaker_capacity(N, R);
-    p.ws = (float*)workspace;
-    p.log_eps = log_eps_of(eps);
+    const ProblemRagged p = ragged_problem(make_problem_io<ProblemRagged>(E, w, b, eps_cos, eps, variant, loss, per_row_loss, dE, dw, db),
+                                           offsets, order, active, speaker_capacity(N, R), B, N, R, D, workspace);
     return (int)launch_ragged(p, (hipStream_t)stream);
 }
 
 // The labelled EVALUATION calls (include/ge2e_hip.h, csrc/ge2e_labeled_eval.hip): the masked index kernel, unchanged, then
-// the centroid kernel and the row kernel, all on the stream.  Checks on the host in the labelled entry's order.
+// the centroid kernel and the row kernel, all on the stream.  Checks on the host in the labelled entry's order (no loss:
+// no variant step, and no dE).
 size_t ge2e_cos_sim_labeled_workspace_bytes(int B, int N, int R, int D) {
-    return masked_shape_ok(B, N, R, D) ? labeled_eval_layout(B, N, R, D).total : 0;
+    return masked_shape_ok(B, N, R, D) ? labeled_eval_layout(B, N, R, D).t.total : 0;
 }
 
 int ge2e_cos_sim_labeled(const float* E, const int* labels, int B, int N, int R, int D, float eps_cos, float eps,
@@ -385,26 +382,26 @@ int ge2e_cos_sim_labeled(const float* E, const int* labels, int B, int N, int R,
     if (!E || !labels || (!cos && !counts)) return GE2E_ERR_NULL;
     if (!masked_shape_ok(B, N, R, D) || T < 0 || T > 4096 || (counts && (!thresholds || T == 0))) return GE2E_ERR_SHAPE;
     const LabeledEvalLayout L = labeled_eval_layout(B, N, R, D);
-    if (!workspace || workspace_bytes < L.total || ((uintptr_t)workspace & 255)) return GE2E_ERR_WORKSPACE;
-    if ((uintptr_t)E & 15) return GE2E_ERR_ALIGN;
+    if (!workspace_ok(workspace, workspace_bytes, L.t.total)) return GE2E_ERR_WORKSPACE;
+    if (!aligned16(E)) return GE2E_ERR_ALIGN;
     char* ws = (char*)workspace;
-    if (!col) col = (int*)(ws + L.col);
-    if (!speakers) speakers = (int*)(ws + L.speakers);
-    if (!active) active = (int*)(ws + L.active);
+    if (!col) col = (int*)(ws + L.t.extra);
+    if (!speakers) speakers = (int*)(ws + L.t.speakers);
+    if (!active) active = (int*)(ws + L.t.active);
     ProblemLabeledEval p{};
     p.E = E;
-    p.off = (int*)(ws + L.off);
-    p.order = (int*)(ws + L.order);
+    p.off = (int*)(ws + L.t.off);
+    p.order = (int*)(ws + L.t.order);
     p.active = active;
     p.thr = counts ? thresholds : nullptr;
     p.cos = cos; p.col = col; p.counts = counts;
     p.CH = (float*)(ws + L.ch); p.SS = (float*)(ws + L.ss); p.CST = (float*)(ws + L.cstat); p.spk = (int*)(ws + L.spk);
     p.B = B; p.N = N; p.R = R; p.D = D;
-    p.NA = labeled_eval_capacity(N, R);
+    p.NA = speaker_capacity(N, R);
     p.T = counts ? T : 0;
     p.eps_cos = eps_cos; p.eps = eps;
-    const hipError_t err = launch_label_index_masked(labels, B, N, R, (int*)(ws + L.off), (int*)(ws + L.order), speakers,
-                                                     active, (int*)(ws + L.index), (hipStream_t)stream);
+    const hipError_t err = launch_label_index_masked(labels, B, N, R, (int*)(ws + L.t.off), (int*)(ws + L.t.order), speakers,
+                                                     active, (int*)(ws + L.t.index), (hipStream_t)stream);
     if (err != hipSuccess) return (int)err;
     return (int)launch_labeled_eval(p, (hipStream_t)stream);
 }
@@ -433,10 +430,9 @@ int ge2e_loss_fwd_bwd_raw(const float* Y, const int* src, int B, int N, int M, i
                           float eps_cos, float eps, int variant, float* loss, float* per_emb_loss, float* dY, float* dw,
                           float* db, void* stream) {
     if (!loss_ptrs_ok(Y, w, b, loss, dY, dw, db)) return GE2E_ERR_NULL;
-    if (!shape_ok(B, N, M, D)) return GE2E_ERR_SHAPE;
-    if (!variant_ok(variant)) return GE2E_ERR_VARIANT;
-    if (!wave_supports_raw(N, M, D)) return GE2E_ERR_IMPL;
-    if (((uintptr_t)Y & 15) || ((uintptr_t)dY & 15)) return GE2E_ERR_ALIGN;
+    if (const int code = loss_checks(shape_ok(B, N, M, D), variant, [] { return (size_t)0; }, nullptr, 0, Y, dY,   // (no workspace)
+                                     [&] { return wave_supports_raw(N, M, D) ? GE2E_OK : GE2E_ERR_IMPL; }))
+        return code;
     Problem p = make_problem<Problem>(Y, B, N, M, D, w, b, eps_cos, eps, variant, loss, per_emb_loss, dY, dw, db);
     p.log_eps = log_eps_of(eps);
     p.raw = 1; p.src = src;
@@ -469,8 +465,8 @@ int ge2e_cos_sim(const float* E, int B, int N, int M, int D, float eps_cos, floa
     p.B = B; p.N = N; p.M = M; p.D = D; p.variant = GE2E_VARIANT_SOFTMAX; p.eps_cos = eps_cos; p.eps = eps;
     // (a caller that sized the workspace for the VALU kernel only -- ge2e_workspace_bytes(.., GE2E_IMPL_GENERIC), ABI 1's
     // rule -- gets the VALU kernel)
-    if (shape_ok(B, N, M, D) && cos_on_mfma(N, M, D) && workspace && workspace_bytes >= tiled_workspace_bytes(B, N, M, D) &&
-        !((uintptr_t)workspace & 255) && !((uintptr_t)E & 15)) {
+    if (shape_ok(B, N, M, D) && cos_on_mfma(N, M, D) && workspace_ok(workspace, workspace_bytes, tiled_workspace_bytes(B, N, M, D)) &&
+        aligned16(E)) {
         p.ws = (float*)workspace;
         p.log_eps = log_eps_of(eps);
         return (int)launch_tiled_cos(p, (hipStream_t)stream);
@@ -521,7 +517,7 @@ int ge2e_cos_sim_bwd(const float* E, const float* C, const float* cos, const flo
                      void* stream) {
     if (!E || !C || !cos || !g_cos || !dE || !dC) return GE2E_ERR_NULL;
     if (!shape_ok(B, N, M, D)) return GE2E_ERR_SHAPE;
-    if (!workspace || workspace_bytes < cos_bwd_workspace_bytes(B, N, N, M, D) || ((uintptr_t)workspace & 15)) return GE2E_ERR_WORKSPACE;
+    if (!workspace_ok(workspace, workspace_bytes, cos_bwd_workspace_bytes(B, N, N, M, D), 16)) return GE2E_ERR_WORKSPACE;
     return (int)launch_cos_bwd(E, C, cos, g_cos, B, N, N, 0, M, D, eps_cos, eps, dE, dC, (float*)workspace, (hipStream_t)stream);
 }
 
@@ -551,7 +547,7 @@ int ge2e_cos_sim_rows_bwd(const float* E, const float* C, const float* cos, cons
                           size_t workspace_bytes, void* stream) {
     if (!E || !C || !cos || !g_cos || !dE || !dC) return GE2E_ERR_NULL;
     if (!rows_ok(B, n, N, j0, M, D)) return GE2E_ERR_SHAPE;
-    if (!workspace || workspace_bytes < cos_bwd_workspace_bytes(B, n, N, M, D) || ((uintptr_t)workspace & 15)) return GE2E_ERR_WORKSPACE;
+    if (!workspace_ok(workspace, workspace_bytes, cos_bwd_workspace_bytes(B, n, N, M, D), 16)) return GE2E_ERR_WORKSPACE;
     return (int)launch_cos_bwd(E, C, cos, g_cos, B, n, N, j0, M, D, eps_cos, eps, dE, dC, (float*)workspace, (hipStream_t)stream);
 }
 int ge2e_calc_loss_rows(const float* sim, int B, int n, int N, int j0, int M, float eps, int variant, float* loss,
@@ -603,36 +599,43 @@ int ge2e_sample_batch(const void* store, int store_is_f64, const long long* spk_
                                     (hipStream_t)stream);
 }
 
-// GE2E_IMPL_TEAM with its abort word raised before the launch: no team forms, the launch redoes the call with one workgroup per batch.
+// The three launches of GE2E_IMPL_TEAM under test conditions: ge2e_loss_fwd_bwd's argument list, and the one field of the
+// problem that each of them sets.  `arg_ok`: the wrapper's own argument check, answered as a shape error behind the NULL rule.
+namespace {
+int selftest_team_run(int Problem::*field, int value, bool arg_ok, const float* E, int B, int N, int M, int D, const float* w,
+                      const float* b, float eps_cos, float eps, int variant, float* loss, float* per_emb_loss, float* dE,
+                      float* dw, float* db, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!loss_ptrs_ok(E, w, b, loss, dE, dw, db)) return GE2E_ERR_NULL;
+    if (!arg_ok) return GE2E_ERR_SHAPE;
+    Problem p = make_problem<Problem>(E, B, N, M, D, w, b, eps_cos, eps, variant, loss, per_emb_loss, dE, dw, db);
+    p.*field = value;
+    return run(p, GE2E_IMPL_TEAM, workspace, workspace_bytes, stream);
+}
+}  // namespace
+
+// The abort word raised before the launch: no team forms, the launch redoes the call with one workgroup per batch.
 int ge2e_selftest_team_fallback(const float* E, int B, int N, int M, int D, const float* w, const float* b,
                                 float eps_cos, float eps, int variant, float* loss, float* per_emb_loss, float* dE,
                                 float* dw, float* db, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!loss_ptrs_ok(E, w, b, loss, dE, dw, db)) return GE2E_ERR_NULL;
-    Problem p = make_problem<Problem>(E, B, N, M, D, w, b, eps_cos, eps, variant, loss, per_emb_loss, dE, dw, db);
-    p.test_abort = 1;
-    return run(p, GE2E_IMPL_TEAM, workspace, workspace_bytes, stream);
+    return selftest_team_run(&Problem::test_abort, 1, true, E, B, N, M, D, w, b, eps_cos, eps, variant, loss, per_emb_loss, dE,
+                             dw, db, workspace, workspace_bytes, stream);
 }
 
-// GE2E_IMPL_TEAM with the abort word raised by one workgroup in the middle of the grid's finish (some leave, some stay)
+// The abort word raised by one workgroup in the middle of the grid's finish (some leave, some stay)
 int ge2e_selftest_team_abort_midgrid(const float* E, int B, int N, int M, int D, const float* w, const float* b,
                                      float eps_cos, float eps, int variant, float* loss, float* per_emb_loss, float* dE,
                                      float* dw, float* db, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!loss_ptrs_ok(E, w, b, loss, dE, dw, db)) return GE2E_ERR_NULL;
-    Problem p = make_problem<Problem>(E, B, N, M, D, w, b, eps_cos, eps, variant, loss, per_emb_loss, dE, dw, db);
-    p.test_abort = 2;
-    return run(p, GE2E_IMPL_TEAM, workspace, workspace_bytes, stream);
+    return selftest_team_run(&Problem::test_abort, 2, true, E, B, N, M, D, w, b, eps_cos, eps, variant, loss, per_emb_loss, dE,
+                             dw, db, workspace, workspace_bytes, stream);
 }
 
-// GE2E_IMPL_TEAM on at most `max_workgroups` workgroups (a multiple of 64: eight per XCD form one team): many batches
-// through few teams, so that the hand-off counters of a team run far beyond what a full-size launch reaches.
+// At most `max_workgroups` workgroups (a multiple of 64: eight per XCD form one team): many batches through few teams, so
+// that the hand-off counters of a team run far beyond what a full-size launch reaches.
 int ge2e_selftest_team_grid(const float* E, int B, int N, int M, int D, const float* w, const float* b, float eps_cos,
                             float eps, int variant, float* loss, float* per_emb_loss, float* dE, float* dw, float* db,
                             void* workspace, size_t workspace_bytes, void* stream, int max_workgroups) {
-    if (!loss_ptrs_ok(E, w, b, loss, dE, dw, db)) return GE2E_ERR_NULL;
-    if (max_workgroups < 64) return GE2E_ERR_SHAPE;
-    Problem p = make_problem<Problem>(E, B, N, M, D, w, b, eps_cos, eps, variant, loss, per_emb_loss, dE, dw, db);
-    p.grid_cap = max_workgroups;
-    return run(p, GE2E_IMPL_TEAM, workspace, workspace_bytes, stream);
+    return selftest_team_run(&Problem::grid_cap, max_workgroups, max_workgroups >= 64, E, B, N, M, D, w, b, eps_cos, eps, variant,
+                             loss, per_emb_loss, dE, dw, db, workspace, workspace_bytes, stream);
 }
 
 int ge2e_selftest_split_gemm(const float* A, const float* Bm, const float* G, float* X, float* GE, float* GC,

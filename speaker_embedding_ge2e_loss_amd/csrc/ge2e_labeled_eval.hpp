@@ -27,27 +27,21 @@ struct ProblemLabeledEval {
     float eps_cos, eps;
 };
 
-// R rows hold at most R / 2 speakers of two rows each.
-inline int labeled_eval_capacity(int N, int R) { return N < R / 2 ? N : (R / 2 > 1 ? R / 2 : 1); }
-
-// ge2e_cos_sim_labeled's workspace, per BATCH (no per-workgroup slices): every part starts 256-byte aligned.
+// ge2e_cos_sim_labeled's workspace, per BATCH (no per-workgroup slices): the centroid planes for speaker_capacity(N, R)
+// speakers, spk, then the index tables (ge2e_labels.hpp) with col [B][R] as their extra part; every part starts 256-byte
+// aligned.
 struct LabeledEvalLayout {
-    size_t ch, ss, cstat, spk, off, order, speakers, active, col, index, total;   // bytes
+    size_t ch, ss, cstat, spk;   // bytes
+    IndexTables t;               // t.extra: col
 };
 inline LabeledEvalLayout labeled_eval_layout(int B, int N, int R, int D) {
     LabeledEvalLayout L;
-    const size_t NA = (size_t)labeled_eval_capacity(N, R), b = (size_t)B;
+    const size_t NA = (size_t)speaker_capacity(N, R), b = (size_t)B;
     L.ch = 0;
     L.ss = L.ch + align_up(b * NA * D * sizeof(float), 256);
     L.cstat = L.ss + align_up(b * NA * D * sizeof(float), 256);
     L.spk = L.cstat + align_up(b * NA * 4 * sizeof(float), 256);
-    L.off = L.spk + align_up(b * R * sizeof(int), 256);
-    L.order = L.off + align_up(b * ((size_t)N + 1) * sizeof(int), 256);
-    L.speakers = L.order + align_up(b * R * sizeof(int), 256);
-    L.active = L.speakers + align_up(b * N * sizeof(int), 256);
-    L.col = L.active + align_up(b * 2 * sizeof(int), 256);
-    L.index = L.col + align_up(b * R * sizeof(int), 256);
-    L.total = L.index + label_index_masked_workspace_bytes(B, N, R);
+    L.t = index_tables(L.spk + align_up(b * R * sizeof(int), 256), B, N, R, true, b * R * sizeof(int));
     return L;
 }
 

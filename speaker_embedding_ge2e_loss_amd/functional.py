@@ -6,8 +6,9 @@ there is no CPU fallback in the product.
 """
 from __future__ import annotations
 
+import functools
 from dataclasses import dataclass
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -38,6 +39,20 @@ def _as_batched(e: torch.Tensor, dtype: torch.dtype = torch.float32):
     if e.dtype != dtype:
         raise TypeError(f"embeddings must be {str(dtype)[6:]} at this boundary, got {e.dtype}")
     return (e.unsqueeze(0) if squeeze else e), squeeze
+
+
+def _as_rows(e: torch.Tensor):
+    """The embeddings of the row-list entry points: (R,D) -> view (1,R,D); (B,R,D) unchanged.  Returns the batched view,
+    whether the batch dimension was added, (B, R, D) and the device."""
+    if e.dim() not in (2, 3):
+        raise ValueError(f"embeddings must be (R,D) or (B,R,D), got {tuple(e.shape)}")
+    if not e.is_contiguous():
+        raise RuntimeError("embeddings must be contiguous")
+    if e.dtype != torch.float32:
+        raise TypeError(f"embeddings must be float32 at this boundary, got {e.dtype}")
+    squeeze = e.dim() == 2
+    e3 = e.unsqueeze(0) if squeeze else e
+    return e3, squeeze, e3.shape, e3.device
 
 
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
@@ -82,6 +97,28 @@ def _launch(name: str, dev: torch.device, *args) -> None:
     _lib.check(code, name)
 
 
+class _LRU(dict):
+    """A dict of at most ``cap`` entries whose order is recency: `recent` moves what it finds to the end, `put` drops from
+    the front.  (Whether to look at all -- not while a stream is being captured -- is each caller's own question.)"""
+
+    def __init__(self, cap: int):
+        super().__init__()
+        self.cap = cap
+
+    def recent(self, key):
+        hit = self.pop(key, None)
+        if hit is not None:
+            self[key] = hit
+        return hit
+
+    def put(self, key, value):
+        self.pop(key, None)
+        while len(self) >= self.cap:
+            self.pop(next(iter(self)))
+        self[key] = value
+        return value
+
+
 # Per-(shape, device) workspace sizes and per-(device, stream) workspace tensors of the module path.  The size depends on
 # the device (its CU count), so the query runs with that device current.  A workspace is reused only by launches on the
 # SAME stream, which the stream itself serialises; callers that pass `workspace=` are unaffected.
@@ -93,12 +130,12 @@ def _launch(name: str, dev: torch.device, *args) -> None:
 #    creating streams does not keep a workspace (with a large launch's fall-back slices) per dead stream forever.  A
 #    dropped or outgrown workspace goes back to the caching allocator, which hands a block out again only in the order
 #    of the stream it was allocated on -- the launches still using it are ahead in that very stream.
-#  * The double-precision kernel, the ragged kernel and its labelled forms have their own entries (key tags "f64",
-#    "ragged", "labeled", "labeled_masked", and "labeled_eval" of the labelled evaluation call): their workspaces have no control block, so they are never shared with the fp32 kernels' workspace, need no initialisation
-#    launch, and no `workspace_override` stands in for them.
-_ws_bytes_cache: dict = {}
-_ws_cache: dict = {}
+#  * The double-precision kernel, the ragged kernel, its labelled forms and the labelled evaluation call have their own
+#    entries (the key tags of _ENTRIES): their workspaces have no control block, so they are never shared with the fp32
+#    kernels' workspace, need no initialisation launch, and no `workspace_override` stands in for them.
 _WS_CACHE_MAX = 8
+_ws_bytes_cache: dict = {}
+_ws_cache = _LRU(_WS_CACHE_MAX)
 _capturing = getattr(torch.cuda, "is_current_stream_capturing", None)
 
 
@@ -123,43 +160,65 @@ class workspace_override:
         return False
 
 
-# Per dtype of the embeddings (and "ragged": fp32 rows with per-speaker counts): the loss entry point, its workspace-size
-# query, whether `impl` is an argument of both, the tag of its workspace-cache keys, and whether its workspace starts with
-# the team kernel's control block.
-_LOSS_ABI = {
-    torch.float32: ("ge2e_loss_fwd_bwd", "ge2e_workspace_bytes", True, (), True),
-    torch.float64: ("ge2e_loss_fwd_bwd_f64", "ge2e_workspace_bytes_f64", False, ("f64",), False),
-    "ragged": ("ge2e_loss_fwd_bwd_ragged", "ge2e_workspace_bytes_ragged", False, ("ragged",), False),
-    "labeled": ("ge2e_loss_fwd_bwd_labeled", "ge2e_workspace_bytes_labeled", False, ("labeled",), False),
-    "labeled_masked": ("ge2e_loss_fwd_bwd_labeled_masked", "ge2e_workspace_bytes_labeled_masked", False,
-                       ("labeled_masked",), False),
-    # (no loss: the labelled evaluation call, here for its workspace -- query (B, N, R, D))
-    "labeled_eval": ("ge2e_cos_sim_labeled", "ge2e_cos_sim_labeled_workspace_bytes", False, ("labeled_eval",), False),
+class _Entry(NamedTuple):
+    """An entry point that takes a cached workspace, and what the workspace cache has to know about it."""
+    entry: str                  # the call
+    size_query: str             # its workspace-size query: the dense shapes take (B, N, M, D, variant[, impl]), the
+    #                             row-list losses (B, N, R, D, variant), the evaluation call (B, N, R, D)
+    tag: tuple = ()             # what tells its workspace-cache keys from the dense fp32 loss's
+    dense_f32: bool = False     # the dense fp32 loss: `impl` is an argument of both, and the workspace starts with the
+    #                             team kernel's control block
+
+
+# The dense losses by the dtype of the embeddings, the row-list calls by name.
+_ENTRIES = {
+    torch.float32: _Entry("ge2e_loss_fwd_bwd", "ge2e_workspace_bytes", dense_f32=True),
+    torch.float64: _Entry("ge2e_loss_fwd_bwd_f64", "ge2e_workspace_bytes_f64", ("f64",)),
+    "ragged": _Entry("ge2e_loss_fwd_bwd_ragged", "ge2e_workspace_bytes_ragged", ("ragged",)),
+    "labeled": _Entry("ge2e_loss_fwd_bwd_labeled", "ge2e_workspace_bytes_labeled", ("labeled",)),
+    "labeled_masked": _Entry("ge2e_loss_fwd_bwd_labeled_masked", "ge2e_workspace_bytes_labeled_masked", ("labeled_masked",)),
+    "labeled_eval": _Entry("ge2e_cos_sim_labeled", "ge2e_cos_sim_labeled_workspace_bytes", ("labeled_eval",)),
 }
 
 
-def _workspace_for(lib, dev: torch.device, stream: int, dtype, query: tuple, dev_idx: int) -> torch.Tensor:
-    """The cached workspace of (device, stream) for a launch whose size query takes `query` (shape, variant[, impl]);
-    `dtype` is the launch's key of _LOSS_ABI."""
-    _, size_entry, _, tag, has_block = _LOSS_ABI[dtype]
-    key = query + tag + (dev_idx,)
+def _workspace_for(lib, dev: torch.device, stream: int, abi: _Entry, query: tuple, dev_idx: int) -> torch.Tensor:
+    """The cached workspace of (device, stream) for a call of `abi` whose size query takes `query`."""
+    key = query + abi.tag + (dev_idx,)
     need = _ws_bytes_cache.get(key)
     if need is None:
-        need = _ws_bytes_cache[key] = int(getattr(lib, size_entry)(*query))
-    if has_block:
+        need = _ws_bytes_cache[key] = int(getattr(lib, abi.size_query)(*query))
+    if abi.dense_f32:
         for ws in _ws_override:
             if ws.device == dev and ws.numel() >= need:
                 return ws
     if _capturing is not None and _capturing():
-        return alloc_workspace(need, dev, init=has_block)
-    k = (dev_idx, stream) + tag
-    ws = _ws_cache.pop(k, None)                 # re-inserted below: dict order = recency
+        return alloc_workspace(need, dev, init=abi.dense_f32)
+    k = (dev_idx, stream) + abi.tag
+    ws = _ws_cache.recent(k)
     if ws is None or ws.numel() < need:
-        ws = alloc_workspace(need, dev, init=has_block)
-        while len(_ws_cache) >= _WS_CACHE_MAX:
-            _ws_cache.pop(next(iter(_ws_cache)))
-    _ws_cache[k] = ws
+        ws = _ws_cache.put(k, alloc_workspace(need, dev, init=abi.dense_f32))
     return ws
+
+
+def _launch_rows(kind: str, e3: torch.Tensor, query: tuple, workspace: Optional[torch.Tensor], *args) -> None:
+    """One row-list call (`kind` of _ENTRIES) into libge2e_hip.so on the current stream of e3's device: guard, stream,
+    workspace -- the caller's, or the cached one for the size query's `query` -- call, check.  `args` is the entry's
+    argument list up to its trailing (workspace, workspace_bytes, stream)."""
+    lib = _lib.load()
+    abi = _ENTRIES[kind]
+    dev = e3.device
+    # (the guard spans the stream read and the workspace lookup -- its size query wants `dev` current, its key wants the
+    # stream -- as well as the call)
+    with _on_device(dev) as guard:
+        stream = _stream_ptr(e3)
+        if workspace is None:
+            workspace = _workspace_for(lib, dev, stream, abi, query, guard.idx)
+        code = getattr(lib, abi.entry)(*args, workspace.data_ptr(), workspace.numel(), stream)
+    _lib.check(code, abi.entry)
+
+
+def _ptr(t: Optional[torch.Tensor]):
+    return t.data_ptr() if t is not None else None
 
 
 def workspace_bytes(B: int, N: int, M: int, D: int, variant: str = "softmax", impl: str = "auto") -> int:
@@ -228,8 +287,8 @@ def loss_fwd_bwd(embeddings: torch.Tensor, w: torch.Tensor, b: torch.Tensor, *,
     lib = _lib.load()
     _require_cuda(embeddings, "embeddings")
     dtype = torch.float64 if embeddings.dtype == torch.float64 else torch.float32
-    entry, _, takes_impl, _, _ = _LOSS_ABI[dtype]
-    if not takes_impl and impl != "auto":
+    abi = _ENTRIES[dtype]
+    if not abi.dense_f32 and impl != "auto":
         raise ValueError(f'impl="{impl}" names a float32 kernel; float64 embeddings have one kernel (impl="auto")')
     e4, _ = _as_batched(embeddings, dtype)
     B, N, M, D = e4.shape
@@ -243,19 +302,19 @@ def loss_fwd_bwd(embeddings: torch.Tensor, w: torch.Tensor, b: torch.Tensor, *,
                 raise TypeError(f"out.{name} must be a contiguous float64 tensor on {dev}")
     if out is None:
         out = _alloc_outputs(B, N, M, D, dtype, dev, need_grad, need_per)
-    query = (B, N, M, D, _lib.VARIANTS[variant]) + ((_lib.IMPLS[impl],) if takes_impl else ())
-    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-    # (not through _launch: the guard has to span the stream read and the workspace lookup -- its size query and its
-    # control-block launch want `dev` current, its key wants the stream -- as well as the call)
+    query = (B, N, M, D, _lib.VARIANTS[variant]) + ((_lib.IMPLS[impl],) if abi.dense_f32 else ())
+    ptr = _ptr
+    # (the host-bound hot path: _launch_rows' body inline, without its call and its argument packing; the guard also spans
+    # the control-block launch of a new workspace)
     with _on_device(dev) as guard:
         stream = _stream_ptr(e4)
         if workspace is None:
-            workspace = _workspace_for(lib, dev, stream, dtype, query, guard.idx)
-        code = getattr(lib, entry)(
+            workspace = _workspace_for(lib, dev, stream, abi, query, guard.idx)
+        code = getattr(lib, abi.entry)(
             e4.data_ptr(), B, N, M, D, w.data_ptr(), b.data_ptr(), eps_cos, eps, *query[4:],
             out.loss.data_ptr(), ptr(out.per), ptr(out.dE), ptr(out.dw), ptr(out.db),
             workspace.data_ptr(), workspace.numel(), stream)
-    _lib.check(code, entry)
+    _lib.check(code, abi.entry)
     return out
 
 
@@ -269,6 +328,14 @@ def _alloc_outputs(B: int, N: int, M: int, D: int, dtype: torch.dtype, dev: torc
         dE=torch.empty(B, N, M, D, **kw) if need_grad else None,
         dw=sc[1] if need_grad else None,
         db=sc[2] if need_grad else None)
+
+
+def _alloc_row_outputs(B: int, R: int, D: int, dev: torch.device, need_grad: bool, need_per: bool,
+                       with_active: bool = False) -> LossOutputs:
+    """`_alloc_outputs` for a row-list loss: (N, M) flattened to R, float32, and the masked loss's `active`."""
+    o = _alloc_outputs(B, 1, R, D, torch.float32, dev, need_grad, need_per)
+    return LossOutputs(loss=o.loss, per=o.per.view(B, R) if need_per else None, dE=o.dE.view(B, R, D) if need_grad else None,
+                       dw=o.dw, db=o.db, active=torch.empty(B, 2, dtype=torch.int32, device=dev) if with_active else None)
 
 
 # ---- the ragged loss: every speaker its own utterance count (ge2e_loss_fwd_bwd_ragged, csrc/ge2e_ragged.hip) ---------------
@@ -300,8 +367,8 @@ def ragged_offsets(counts, rows: int) -> torch.Tensor:
 
 # The last few offset tables uploaded from host counts, most recent last: a training loop that repeats its counts (or
 # cycles through a few bucketed layouts) pays the validation and the host-to-device copy once.
-_ragged_uploads: dict = {}
 _RAGGED_UPLOADS_MAX = 8
+_ragged_uploads = _LRU(_RAGGED_UPLOADS_MAX)
 
 
 def _ragged_offsets_on_device(spec, B: int, R: int, dev: torch.device) -> torch.Tensor:
@@ -325,17 +392,11 @@ def _ragged_offsets_on_device(spec, B: int, R: int, dev: torch.device) -> torch.
     if off.shape[0] != B:
         raise ValueError(f"counts are for {off.shape[0]} batches, embeddings hold {B}")
     off = off.contiguous()
-    capturing = _capturing is not None and _capturing()
+    if _capturing is not None and _capturing():
+        return off.to(dev)              # (belongs to the capturing graph's pool: not for anybody else)
     key = (off.numpy().tobytes(), B, str(dev))
-    hit = None if capturing else _ragged_uploads.pop(key, None)
-    if hit is None:
-        hit = off.to(dev)
-        if capturing:                   # (belongs to the capturing graph's pool: not for anybody else)
-            return hit
-        while len(_ragged_uploads) >= _RAGGED_UPLOADS_MAX:
-            _ragged_uploads.pop(next(iter(_ragged_uploads)))
-    _ragged_uploads[key] = hit
-    return hit
+    hit = _ragged_uploads.recent(key)
+    return hit if hit is not None else _ragged_uploads.put(key, off.to(dev))
 
 
 def loss_fwd_bwd_ragged(embeddings: torch.Tensor, offsets_or_counts, w: torch.Tensor, b: torch.Tensor, *,
@@ -348,36 +409,18 @@ def loss_fwd_bwd_ragged(embeddings: torch.Tensor, offsets_or_counts, w: torch.Te
     ``offsets_or_counts``: host counts (N,) / (B, N) -- a sequence or an integer CPU tensor, validated -- or a torch.int32
     DEVICE tensor of offsets (N+1,) / (B, N+1), taken as is and NOT verified.  Outputs as `loss_fwd_bwd` with (N, M)
     flattened to R: loss (B,), per (B, R), dE (B, R, D), dw (B,), db (B,)."""
-    lib = _lib.load()
     _require_cuda(embeddings, "embeddings")
-    if embeddings.dim() not in (2, 3):
-        raise ValueError(f"embeddings must be (R,D) or (B,R,D), got {tuple(embeddings.shape)}")
-    if not embeddings.is_contiguous():
-        raise RuntimeError("embeddings must be contiguous")
-    if embeddings.dtype != torch.float32:
-        raise TypeError(f"embeddings must be float32 at this boundary, got {embeddings.dtype}")
-    e3 = embeddings.unsqueeze(0) if embeddings.dim() == 2 else embeddings
-    B, R, D = e3.shape
-    dev = e3.device
+    e3, _, (B, R, D), dev = _as_rows(embeddings)
     _check_scalar_params(w, b, dev)
     with _on_device(dev):
         off = _ragged_offsets_on_device(offsets_or_counts, B, R, dev)
     N = off.shape[1] - 1
     if out is None:
-        o4 = _alloc_outputs(B, 1, R, D, torch.float32, dev, need_grad, need_per)
-        out = LossOutputs(loss=o4.loss, per=o4.per.view(B, R) if need_per else None,
-                          dE=o4.dE.view(B, R, D) if need_grad else None, dw=o4.dw, db=o4.db)
+        out = _alloc_row_outputs(B, R, D, dev, need_grad, need_per)
     query = (B, N, R, D, _lib.VARIANTS[variant])
-    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-    with _on_device(dev) as guard:
-        stream = _stream_ptr(e3)
-        if workspace is None:
-            workspace = _workspace_for(lib, dev, stream, "ragged", query, guard.idx)
-        code = lib.ge2e_loss_fwd_bwd_ragged(
-            e3.data_ptr(), off.data_ptr(), B, N, R, D, w.data_ptr(), b.data_ptr(), eps_cos, eps, query[4],
-            out.loss.data_ptr(), ptr(out.per), ptr(out.dE), ptr(out.dw), ptr(out.db),
-            workspace.data_ptr(), workspace.numel(), stream)
-    _lib.check(code, "ge2e_loss_fwd_bwd_ragged")
+    _launch_rows("ragged", e3, query, workspace,
+                 e3.data_ptr(), off.data_ptr(), B, N, R, D, w.data_ptr(), b.data_ptr(), eps_cos, eps, query[4],
+                 out.loss.data_ptr(), _ptr(out.per), _ptr(out.dE), _ptr(out.dw), _ptr(out.db))
     return out
 
 
@@ -430,7 +473,21 @@ def dense_labels(labels, masked: bool = False):
 
 
 # The last few label tables uploaded from the host, most recent last, like _ragged_uploads: key -> (device ids, N).
-_label_uploads: dict = {}
+_label_uploads = _LRU(_RAGGED_UPLOADS_MAX)
+
+
+def _device_labels(labels: torch.Tensor, num_speakers, masked: bool, what: str = "device labels"):
+    """DEVICE labels as they cross the C ABI: (torch.int32 labels, N).  torch.int32 or torch.int64, which a torch op
+    narrows -- no synchronisation.  ``masked``: the labels may hold ANY values, so torch.int64 is clamped into
+    [-1, N] before it is narrowed: 2**32 + 3 is ignored and not wrapped onto speaker 3."""
+    if labels.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"{what} must be torch.int32 or torch.int64, got {labels.dtype}")
+    N = int(num_speakers)
+    if N < 1:
+        raise ValueError(f"num_speakers must be >= 1, got {N}")
+    if masked and labels.dtype == torch.int64:
+        labels = labels.clamp(-1, N)
+    return labels.to(torch.int32), N
 
 
 def _labels_on_device(labels, num_speakers, B: int, R: int, dev: torch.device, masked: bool = False):
@@ -446,43 +503,32 @@ def _labels_on_device(labels, num_speakers, B: int, R: int, dev: torch.device, m
     if torch.is_tensor(labels) and labels.device.type != "cpu":
         if num_speakers is None:
             raise ValueError("device labels need num_speakers: counting the distinct ids would take a host synchronisation")
-        if labels.dtype not in (torch.int32, torch.int64):
-            raise TypeError(f"device labels must be torch.int32 or torch.int64, got {labels.dtype}")
+        labels, N = _device_labels(labels, num_speakers, masked)
         if labels.device != dev:
             raise RuntimeError(f"labels are on {labels.device}, embeddings on {dev}: raw pointers cross the C ABI, all on one device")
-        N = int(num_speakers)
         if labels.dim() == 1:
             labels = labels.unsqueeze(0).expand(B, -1)
         if labels.dim() != 2 or tuple(labels.shape) != (B, R):
             raise ValueError(f"labels must be (R,) or (B, R) with B = {B}, R = {R}, got {tuple(labels.shape)}")
-        if masked:
-            if N < 1:
-                raise ValueError(f"num_speakers must be >= 1, got {N}")
-            if labels.dtype == torch.int64:
-                labels = labels.clamp(-1, N)
-            return labels.to(torch.int32).contiguous(), N
-        if N < 1 or R < 2 * N:
-            raise ValueError(f"{N} speakers need at least {2 * max(N, 1)} rows, got {R}")
-        return labels.to(torch.int32).contiguous(), N
+        if not masked and R < 2 * N:
+            raise ValueError(f"{N} speakers need at least {2 * N} rows, got {R}")
+        return labels.contiguous(), N
     raw = labels if torch.is_tensor(labels) else torch.as_tensor(labels)
     if raw.dim() not in (1, 2) or raw.shape[-1] != R or (raw.dim() == 2 and raw.shape[0] != B):
         raise ValueError(f"labels must be (R,) or (B, R) with B = {B}, R = {R}, got {tuple(raw.shape)}")
     capturing = dev.type == "cuda" and _capturing is not None and _capturing()
     integral = not (raw.is_floating_point() or raw.is_complex() or raw.dtype == torch.bool)
-    key = (raw.to(torch.int64).contiguous().numpy().tobytes(), tuple(raw.shape), B, str(dev)) if integral else None
-    if masked and key is not None:
-        key += ("masked",)
-    hit = None if capturing or key is None else _label_uploads.pop(key, None)
+    # (not integral: dense_labels below refuses them, nothing is kept)
+    key = (raw.to(torch.int64).contiguous().numpy().tobytes(), tuple(raw.shape), B, str(dev), masked) if integral else None
+    hit = None if capturing or key is None else _label_uploads.recent(key)
     if hit is None:
-        ids, N = dense_labels(raw, masked=True) if masked else dense_labels(raw)
+        ids, N = dense_labels(raw, masked=masked)
         if ids.dim() == 1:
             ids = ids.unsqueeze(0).expand(B, -1)
         hit = (ids.contiguous().to(dev), N)
         if capturing:                   # (belongs to the capturing graph's pool: not for anybody else)
             return hit
-        while len(_label_uploads) >= _RAGGED_UPLOADS_MAX:
-            _label_uploads.pop(next(iter(_label_uploads)))
-    _label_uploads[key] = hit
+        _label_uploads.put(key, hit)
     if masked:
         if num_speakers is not None and int(num_speakers) < hit[1]:
             raise ValueError(f"num_speakers = {int(num_speakers)} is a bound: the labels hold {hit[1]} distinct speakers")
@@ -492,33 +538,34 @@ def _labels_on_device(labels, num_speakers, B: int, R: int, dev: torch.device, m
     return hit
 
 
+def _label_index(labels: torch.Tensor, num_speakers: int, masked: bool):
+    """Both index calls: (offsets, order) and, ``masked``, (speakers, active) behind them, without the batch dimension for
+    1-D labels."""
+    _require_cuda(labels, "labels")
+    lab, N = _device_labels(labels, num_speakers, masked, what="labels")
+    if lab.dim() not in (1, 2) or lab.numel() < 1:
+        raise ValueError(f"labels must be (R,) or (B, R) with R >= 1, got {tuple(lab.shape)}")
+    lab = lab.contiguous()
+    squeeze = lab.dim() == 1
+    B, R = (1, lab.shape[0]) if squeeze else lab.shape
+    dev = lab.device
+    lib = _lib.load()
+    entry = "ge2e_label_index_masked" if masked else "ge2e_label_index"
+    res = [torch.empty(B, n, dtype=torch.int32, device=dev) for n in ((N + 1, R, N, 2) if masked else (N + 1, R))]
+    with _on_device(dev):
+        need = int(getattr(lib, entry + "_workspace_bytes")(B, N, R))
+        ws = alloc_workspace(need, dev, init=False) if need else None
+        code = getattr(lib, entry)(lab.data_ptr(), B, N, R, *(t.data_ptr() for t in res), _ptr(ws), need, _stream_ptr(lab))
+    _lib.check(code, entry)
+    return tuple(t[0] for t in res) if squeeze else tuple(res)
+
+
 def label_index(labels: torch.Tensor, num_speakers: int):
     """ge2e_label_index on the current stream, no host sync: DEVICE labels (R,) or (B, R), torch.int32 or torch.int64,
     dense ids in [0, num_speakers) -> (offsets, order), torch.int32 on the device: offsets (N+1,) / (B, N+1) with
     offsets[j] = number of rows with a label < j, and order (R,) / (B, R), the stable argsort of the labels.  Labels
     outside [0, num_speakers) are clamped into it."""
-    _require_cuda(labels, "labels")
-    if labels.dtype not in (torch.int32, torch.int64):
-        raise TypeError(f"labels must be torch.int32 or torch.int64, got {labels.dtype}")
-    if labels.dim() not in (1, 2) or labels.numel() < 1:
-        raise ValueError(f"labels must be (R,) or (B, R) with R >= 1, got {tuple(labels.shape)}")
-    N = int(num_speakers)
-    if N < 1:
-        raise ValueError(f"num_speakers must be >= 1, got {N}")
-    lab = labels.to(torch.int32).contiguous()
-    squeeze = lab.dim() == 1
-    B, R = (1, lab.shape[0]) if squeeze else lab.shape
-    dev = lab.device
-    lib = _lib.load()
-    offsets = torch.empty(B, N + 1, dtype=torch.int32, device=dev)
-    order = torch.empty(B, R, dtype=torch.int32, device=dev)
-    with _on_device(dev):
-        need = int(lib.ge2e_label_index_workspace_bytes(B, N, R))
-        ws = alloc_workspace(need, dev, init=False) if need else None
-        code = lib.ge2e_label_index(lab.data_ptr(), B, N, R, offsets.data_ptr(), order.data_ptr(),
-                                    ws.data_ptr() if need else None, need, _stream_ptr(lab))
-    _lib.check(code, "ge2e_label_index")
-    return (offsets[0], order[0]) if squeeze else (offsets, order)
+    return _label_index(labels, num_speakers, False)
 
 
 def label_index_masked(labels: torch.Tensor, num_speakers: int):
@@ -528,34 +575,7 @@ def label_index_masked(labels: torch.Tensor, num_speakers: int):
     rows that count sorted by (label, index), then all the others by index; offsets (N+1,) / (B, N+1) over the speakers
     that count, numbered by ascending label, and the number of rows that count from there on; speakers (N,) / (B, N): the
     labels of those speakers, then -1; active (2,) / (B, 2): how many speakers and rows count."""
-    _require_cuda(labels, "labels")
-    if labels.dtype not in (torch.int32, torch.int64):
-        raise TypeError(f"labels must be torch.int32 or torch.int64, got {labels.dtype}")
-    if labels.dim() not in (1, 2) or labels.numel() < 1:
-        raise ValueError(f"labels must be (R,) or (B, R) with R >= 1, got {tuple(labels.shape)}")
-    N = int(num_speakers)
-    if N < 1:
-        raise ValueError(f"num_speakers must be >= 1, got {N}")
-    if labels.dtype == torch.int64:
-        labels = labels.clamp(-1, N)
-    lab = labels.to(torch.int32).contiguous()
-    squeeze = lab.dim() == 1
-    B, R = (1, lab.shape[0]) if squeeze else lab.shape
-    dev = lab.device
-    lib = _lib.load()
-    offsets = torch.empty(B, N + 1, dtype=torch.int32, device=dev)
-    order = torch.empty(B, R, dtype=torch.int32, device=dev)
-    speakers = torch.empty(B, N, dtype=torch.int32, device=dev)
-    active = torch.empty(B, 2, dtype=torch.int32, device=dev)
-    with _on_device(dev):
-        need = int(lib.ge2e_label_index_masked_workspace_bytes(B, N, R))
-        ws = alloc_workspace(need, dev, init=False) if need else None
-        code = lib.ge2e_label_index_masked(lab.data_ptr(), B, N, R, offsets.data_ptr(), order.data_ptr(),
-                                           speakers.data_ptr(), active.data_ptr(), ws.data_ptr() if need else None, need,
-                                           _stream_ptr(lab))
-    _lib.check(code, "ge2e_label_index_masked")
-    res = (offsets, order, speakers, active)
-    return tuple(t[0] for t in res) if squeeze else res
+    return _label_index(labels, num_speakers, True)
 
 
 def loss_fwd_bwd_labeled(embeddings: torch.Tensor, labels, w: torch.Tensor, b: torch.Tensor, *,
@@ -575,41 +595,21 @@ def loss_fwd_bwd_labeled(embeddings: torch.Tensor, labels, w: torch.Tensor, b: t
     labelled outside [0, num_speakers) are ignored (host labels: negative ids), a speaker with fewer than 2 such rows is
     left out, all decided on the device.  per and dE are 0 on the rows that do not count, and ``out.active`` (B, 2) int32
     receives the numbers of speakers and rows that do (allocated here unless ``out`` is given, where it may be None)."""
-    lib = _lib.load()
     _require_cuda(embeddings, "embeddings")
-    if embeddings.dim() not in (2, 3):
-        raise ValueError(f"embeddings must be (R,D) or (B,R,D), got {tuple(embeddings.shape)}")
-    if not embeddings.is_contiguous():
-        raise RuntimeError("embeddings must be contiguous")
-    if embeddings.dtype != torch.float32:
-        raise TypeError(f"embeddings must be float32 at this boundary, got {embeddings.dtype}")
-    e3 = embeddings.unsqueeze(0) if embeddings.dim() == 2 else embeddings
-    B, R, D = e3.shape
-    dev = e3.device
+    e3, _, (B, R, D), dev = _as_rows(embeddings)
     _check_scalar_params(w, b, dev)
     with _on_device(dev):
         lab, N = _labels_on_device(labels, num_speakers, B, R, dev, masked)
     if out is None:
-        o4 = _alloc_outputs(B, 1, R, D, torch.float32, dev, need_grad, need_per)
-        out = LossOutputs(loss=o4.loss, per=o4.per.view(B, R) if need_per else None,
-                          dE=o4.dE.view(B, R, D) if need_grad else None, dw=o4.dw, db=o4.db,
-                          active=torch.empty(B, 2, dtype=torch.int32, device=dev) if masked else None)
+        out = _alloc_row_outputs(B, R, D, dev, need_grad, need_per, with_active=masked)
     query = (B, N, R, D, _lib.VARIANTS[variant])
-    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-    tag = "labeled_masked" if masked else "labeled"
-    entry = _LOSS_ABI[tag][0]
     if masked and out.active is not None and (out.active.dtype != torch.int32 or not out.active.is_contiguous()
                                               or out.active.device != dev or out.active.numel() != 2 * B):
         raise TypeError(f"out.active must be a contiguous int32 tensor of shape ({B}, 2) on {dev}")
-    with _on_device(dev) as guard:
-        stream = _stream_ptr(e3)
-        if workspace is None:
-            workspace = _workspace_for(lib, dev, stream, tag, query, guard.idx)
-        code = getattr(lib, entry)(
-            e3.data_ptr(), lab.data_ptr(), B, N, R, D, w.data_ptr(), b.data_ptr(), eps_cos, eps, query[4],
-            out.loss.data_ptr(), ptr(out.per), ptr(out.dE), ptr(out.dw), ptr(out.db),
-            *((ptr(out.active),) if masked else ()), workspace.data_ptr(), workspace.numel(), stream)
-    _lib.check(code, entry)
+    _launch_rows("labeled_masked" if masked else "labeled", e3, query, workspace,
+                 e3.data_ptr(), lab.data_ptr(), B, N, R, D, w.data_ptr(), b.data_ptr(), eps_cos, eps, query[4],
+                 out.loss.data_ptr(), _ptr(out.per), _ptr(out.dE), _ptr(out.dw), _ptr(out.db),
+                 *((_ptr(out.active),) if masked else ()))
     return out
 
 
@@ -654,20 +654,10 @@ def cos_sim_labeled(embeddings: torch.Tensor, labels, *, num_speakers: Optional[
     column that does not count (None with ``need_cos=False``: the matrix is never materialised) -- ``col`` (R,),
     ``speakers`` (N,), ``active`` (2,), and with ``thresholds`` (non-decreasing, at most 4096: a sequence, checked and
     uploaded, or a float32 DEVICE tensor taken as it is) ``counts`` (T, 2): the calculate_ERR sweep on cos itself."""
-    lib = _lib.load()
     _require_cuda(embeddings, "embeddings")
-    if embeddings.dim() not in (2, 3):
-        raise ValueError(f"embeddings must be (R,D) or (B,R,D), got {tuple(embeddings.shape)}")
-    if not embeddings.is_contiguous():
-        raise RuntimeError("embeddings must be contiguous")
-    if embeddings.dtype != torch.float32:
-        raise TypeError(f"embeddings must be float32 at this boundary, got {embeddings.dtype}")
+    e3, squeeze, (B, R, D), dev = _as_rows(embeddings.detach())
     if thresholds is None and not need_cos:
         raise ValueError("nothing to compute: need_cos=False without thresholds")
-    squeeze = embeddings.dim() == 2
-    e3 = (embeddings.unsqueeze(0) if squeeze else embeddings).detach()
-    B, R, D = e3.shape
-    dev = e3.device
     with _on_device(dev):
         lab, N = _labels_on_device(labels, num_speakers, B, R, dev, True)
         thr = _threshold_table(thresholds, dev, device_ok=True) if thresholds is not None else None
@@ -677,15 +667,9 @@ def cos_sim_labeled(embeddings: torch.Tensor, labels, *, num_speakers: Optional[
         cos=torch.empty(B, R, N, dtype=torch.float32, device=dev) if need_cos else None,
         col=torch.empty(B, R, **i32), speakers=torch.empty(B, N, **i32), active=torch.empty(B, 2, **i32),
         counts=torch.empty(B, T, 2, **i32) if T else None)
-    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-    with _on_device(dev) as guard:
-        stream = _stream_ptr(e3)
-        if workspace is None:
-            workspace = _workspace_for(lib, dev, stream, "labeled_eval", (B, N, R, D), guard.idx)
-        code = lib.ge2e_cos_sim_labeled(e3.data_ptr(), lab.data_ptr(), B, N, R, D, eps_cos, eps, ptr(thr), T, ptr(out.cos),
-                                        out.col.data_ptr(), out.speakers.data_ptr(), out.active.data_ptr(), ptr(out.counts),
-                                        workspace.data_ptr(), workspace.numel(), stream)
-    _lib.check(code, "ge2e_cos_sim_labeled")
+    _launch_rows("labeled_eval", e3, (B, N, R, D), workspace,
+                 e3.data_ptr(), lab.data_ptr(), B, N, R, D, eps_cos, eps, _ptr(thr), T, _ptr(out.cos), out.col.data_ptr(),
+                 out.speakers.data_ptr(), out.active.data_ptr(), _ptr(out.counts))
     if squeeze:
         out = LabeledCosOutputs(*(t[0] if t is not None else None
                                   for t in (out.cos, out.col, out.speakers, out.active, out.counts)))
@@ -1095,10 +1079,7 @@ def eer_counts(sim_matrix: torch.Tensor, thresholds) -> torch.Tensor:
     if s.dim() != 4 or s.shape[1] != s.shape[3]:
         raise ValueError(f"sim_matrix must be (N,M,N) or (B,N,M,N), got {tuple(sim_matrix.shape)}")
     s = s.contiguous().float()
-    thr = torch.as_tensor(thresholds, dtype=torch.float64).to(torch.float32).reshape(-1)
-    if thr.numel() < 1 or thr.numel() > 4096 or bool((thr[1:] < thr[:-1]).any()):
-        raise ValueError("thresholds must be 1..4096 non-decreasing values")
-    thr = thr.to(s.device)
+    thr = _threshold_table(thresholds, s.device, device_ok=False)
     B, N, M, _ = s.shape
     T = thr.numel()
     counts = torch.empty(B, T, 2, dtype=torch.int32, device=s.device)
@@ -1180,82 +1161,37 @@ class _GE2ELossF64Function(torch.autograd.Function):
         return gE, gw, gb, None, None, None, None
 
 
-def _ragged_node_backward(ctx, grad_out):
-    """backward of the ragged nodes (inputs: embeddings, table, w, b, ...): the launch's own dE / dw / db scaled by the
-    incoming gradient with ge2e_scale_grads (a batch of R rows as N = 1, M = R)."""
-    dE, dw, db = ctx.saved_tensors
-    B, R, D = dE.shape
-    gE, gw, gb = _scale_grads(dE, dw.data_ptr(), db.data_ptr(), grad_out, grad_out.numel(), (B, 1, R, D),
-                              [ctx.needs_input_grad[i] for i in (0, 2, 3)], ctx.w_shape, ctx.b_shape)
-    if gE is not None and ctx.squeeze:
-        gE = gE[0]
-    return gE, gw, gb
-
-
-class _GE2ELossRaggedFunction(torch.autograd.Function):
-    """The same node over ge2e_loss_fwd_bwd_ragged: embeddings (R,D) / (B,R,D) and device offsets in; the backward scales
-    the launch's own dE / dw / db by the incoming gradient with ge2e_scale_grads (a batch of R rows as N = 1, M = R)."""
+class _GE2ELossRowsFunction(torch.autograd.Function):
+    """The same node over the ragged kernel's three entry points: embeddings (R,D) / (B,R,D) and the device table of
+    ``launch`` in -- `loss_fwd_bwd_ragged` with offsets, or `loss_fwd_bwd_labeled` with labels and its ``num_speakers`` /
+    ``masked`` bound (functools.partial).  The masked launch's `active` (int32, not differentiable) comes out behind the
+    loss.  dE is in the caller's row order, 0 on the rows that do not count; the backward scales the launch's own dE / dw /
+    db by the incoming gradient with ge2e_scale_grads (a batch of R rows as N = 1, M = R)."""
 
     @staticmethod
-    def forward(ctx, embeddings, off, w, b, eps, eps_cos, variant):
+    def forward(ctx, embeddings, table, w, b, eps, eps_cos, variant, launch):
         need = any(ctx.needs_input_grad[i] for i in (0, 2, 3))
-        o = loss_fwd_bwd_ragged(embeddings, off, w, b, eps=eps, eps_cos=eps_cos, variant=variant, need_grad=need)
+        o = launch(embeddings, table, w, b, eps=eps, eps_cos=eps_cos, variant=variant, need_grad=need)
         ctx.squeeze = embeddings.dim() == 2
         ctx.w_shape, ctx.b_shape = w.shape, b.shape
         if need:
             ctx.save_for_backward(o.dE, o.dw, o.db)
-        return o.loss[0] if ctx.squeeze else o.loss
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_out):
-        gE, gw, gb = _ragged_node_backward(ctx, grad_out)
-        return gE, None, gw, gb, None, None, None
-
-
-class _GE2ELossLabeledFunction(torch.autograd.Function):
-    """The ragged node over ge2e_loss_fwd_bwd_labeled: embeddings in any row order and device labels in; dE comes back in
-    the caller's row order, and the backward is the ragged node's."""
-
-    @staticmethod
-    def forward(ctx, embeddings, lab, w, b, eps, eps_cos, variant, num_speakers):
-        need = any(ctx.needs_input_grad[i] for i in (0, 2, 3))
-        o = loss_fwd_bwd_labeled(embeddings, lab, w, b, num_speakers=num_speakers, eps=eps, eps_cos=eps_cos,
-                                 variant=variant, need_grad=need)
-        ctx.squeeze = embeddings.dim() == 2
-        ctx.w_shape, ctx.b_shape = w.shape, b.shape
-        if need:
-            ctx.save_for_backward(o.dE, o.dw, o.db)
-        return o.loss[0] if ctx.squeeze else o.loss
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_out):
-        gE, gw, gb = _ragged_node_backward(ctx, grad_out)
-        return gE, None, gw, gb, None, None, None, None
-
-
-class _GE2ELossMaskedFunction(torch.autograd.Function):
-    """The ragged node over ge2e_loss_fwd_bwd_labeled_masked: labels of any content in; the loss and the launch's `active`
-    (int32, not differentiable) out.  dE is 0 on the rows that do not count, and the backward is the ragged node's."""
-
-    @staticmethod
-    def forward(ctx, embeddings, lab, w, b, eps, eps_cos, variant, num_speakers):
-        need = any(ctx.needs_input_grad[i] for i in (0, 2, 3))
-        o = loss_fwd_bwd_labeled(embeddings, lab, w, b, num_speakers=num_speakers, eps=eps, eps_cos=eps_cos,
-                                 variant=variant, need_grad=need, masked=True)
-        ctx.squeeze = embeddings.dim() == 2
-        ctx.w_shape, ctx.b_shape = w.shape, b.shape
-        if need:
-            ctx.save_for_backward(o.dE, o.dw, o.db)
+        loss = o.loss[0] if ctx.squeeze else o.loss
+        if o.active is None:
+            return loss
         active = o.active[0] if ctx.squeeze else o.active
         ctx.mark_non_differentiable(active)
-        return (o.loss[0] if ctx.squeeze else o.loss), active
+        return loss, active
 
     @staticmethod
     @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_out, _grad_active):
-        gE, gw, gb = _ragged_node_backward(ctx, grad_out)
+    def backward(ctx, grad_out, *_grad_active):
+        dE, dw, db = ctx.saved_tensors
+        B, R, D = dE.shape
+        gE, gw, gb = _scale_grads(dE, dw.data_ptr(), db.data_ptr(), grad_out, grad_out.numel(), (B, 1, R, D),
+                                  [ctx.needs_input_grad[i] for i in (0, 2, 3)], ctx.w_shape, ctx.b_shape)
+        if gE is not None and ctx.squeeze:
+            gE = gE[0]
         return gE, None, gw, gb, None, None, None, None
 
 
@@ -1325,6 +1261,23 @@ def ge2e_loss(embeddings: torch.Tensor, w: torch.Tensor, b: torch.Tensor, *, eps
     return loss if in_dtype == torch.float32 else loss.to(in_dtype)
 
 
+def _rows_loss_input(embeddings: torch.Tensor, who: str, instead: str):
+    """What `ge2e_loss_ragged` and `ge2e_loss_labeled` do to their embeddings first: float64 is refused (``who`` and
+    ``instead`` word the message), float16 / bfloat16 are cast up (a differentiable torch op), a view at an odd storage
+    offset is copied.  Returns the fp32 embeddings, the caller's dtype, B and R."""
+    if embeddings.dtype == torch.float64:
+        raise NotImplementedError(f"{who}: float64 embeddings are not implemented (the ragged kernel is fp32 and nothing "
+                                  f"casts float64 down silently); pass float32, or {instead} for ge2e_loss")
+    _require_cuda(embeddings, "embeddings")
+    in_dtype = embeddings.dtype
+    if in_dtype != torch.float32:
+        embeddings = embeddings.float()
+    _, _, (B, R, _), _ = _as_rows(embeddings)
+    if embeddings.data_ptr() % 16:     # a contiguous view at an odd storage offset
+        embeddings = embeddings.clone()
+    return embeddings, in_dtype, B, R
+
+
 def ge2e_loss_ragged(embeddings: torch.Tensor, counts, w: torch.Tensor, b: torch.Tensor, *, eps: float = SMALL_ERR,
                      eps_cos: float = EPS_COS, variant: str = "softmax") -> torch.Tensor:
     """Differentiable GE2E loss of speakers with DIFFERENT utterance counts: 0-dim for (R, D) input, (B,) for (B, R, D).
@@ -1337,23 +1290,10 @@ def ge2e_loss_ragged(embeddings: torch.Tensor, counts, w: torch.Tensor, b: torch
     reads, so a broken table gives wrong numbers, not a wild access.  With all counts equal to M this is
     ``ge2e_loss(embeddings.view(N, M, D))``.  float16 / bfloat16 are computed in fp32 behind differentiable casts;
     float64 is not implemented (there is no fp64 ragged kernel, and no silent fp32 arithmetic in its place)."""
-    _require_cuda(embeddings, "embeddings")
-    in_dtype = embeddings.dtype
-    if in_dtype == torch.float64:
-        raise NotImplementedError("ge2e_loss_ragged: float64 embeddings are not implemented (the ragged kernel is fp32 and "
-                                  "nothing casts float64 down silently); pass float32, or pad to equal counts for ge2e_loss")
-    if in_dtype != torch.float32:
-        embeddings = embeddings.float()
-    if embeddings.dim() not in (2, 3):
-        raise ValueError(f"embeddings must be (R,D) or (B,R,D), got {tuple(embeddings.shape)}")
-    if not embeddings.is_contiguous():
-        raise RuntimeError("embeddings must be contiguous")
-    if embeddings.data_ptr() % 16:     # a contiguous view at an odd storage offset
-        embeddings = embeddings.clone()
-    B, R = (1, embeddings.shape[0]) if embeddings.dim() == 2 else embeddings.shape[:2]
+    embeddings, in_dtype, B, R = _rows_loss_input(embeddings, "ge2e_loss_ragged", "pad to equal counts")
     with _on_device(embeddings.device):
         off = _ragged_offsets_on_device(counts, B, R, embeddings.device)
-    loss = _GE2ELossRaggedFunction.apply(embeddings, off, w, b, float(eps), float(eps_cos), variant)
+    loss = _GE2ELossRowsFunction.apply(embeddings, off, w, b, float(eps), float(eps_cos), variant, loss_fwd_bwd_ragged)
     return loss if in_dtype == torch.float32 else loss.to(in_dtype)
 
 
@@ -1383,28 +1323,11 @@ def ge2e_loss_labeled(embeddings: torch.Tensor, labels, w: torch.Tensor, b: torc
     of rows that counted, so ``loss / active[..., 1].clamp(min=1)`` is the mean over those rows."""
     if return_active and not masked:
         raise ValueError("return_active needs masked=True: without masking every row counts")
-    if masked and embeddings.dtype == torch.float64:
-        raise NotImplementedError("ge2e_loss_labeled: float64 embeddings are not implemented (the ragged kernel is fp32 and "
-                                  "nothing casts float64 down silently); pass float32")
-    _require_cuda(embeddings, "embeddings")
-    in_dtype = embeddings.dtype
-    if in_dtype == torch.float64:
-        raise NotImplementedError("ge2e_loss_labeled: float64 embeddings are not implemented (the ragged kernel is fp32 and "
-                                  "nothing casts float64 down silently); pass float32, or group equal counts for ge2e_loss")
-    if in_dtype != torch.float32:
-        embeddings = embeddings.float()
-    if embeddings.dim() not in (2, 3):
-        raise ValueError(f"embeddings must be (R,D) or (B,R,D), got {tuple(embeddings.shape)}")
-    if not embeddings.is_contiguous():
-        raise RuntimeError("embeddings must be contiguous")
-    if embeddings.data_ptr() % 16:     # a contiguous view at an odd storage offset
-        embeddings = embeddings.clone()
-    B, R = (1, embeddings.shape[0]) if embeddings.dim() == 2 else embeddings.shape[:2]
+    embeddings, in_dtype, B, R = _rows_loss_input(embeddings, "ge2e_loss_labeled", "group equal counts")
     with _on_device(embeddings.device):
         lab, N = _labels_on_device(labels, num_speakers, B, R, embeddings.device, masked)
-    if masked:
-        loss, active = _GE2ELossMaskedFunction.apply(embeddings, lab, w, b, float(eps), float(eps_cos), variant, N)
-        loss = loss if in_dtype == torch.float32 else loss.to(in_dtype)
-        return (loss, active) if return_active else loss
-    loss = _GE2ELossLabeledFunction.apply(embeddings, lab, w, b, float(eps), float(eps_cos), variant, N)
-    return loss if in_dtype == torch.float32 else loss.to(in_dtype)
+    launch = functools.partial(loss_fwd_bwd_labeled, num_speakers=N, masked=masked)
+    res = _GE2ELossRowsFunction.apply(embeddings, lab, w, b, float(eps), float(eps_cos), variant, launch)
+    loss, active = res if masked else (res, None)
+    loss = loss if in_dtype == torch.float32 else loss.to(in_dtype)
+    return (loss, active) if return_active else loss

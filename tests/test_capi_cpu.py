@@ -66,12 +66,19 @@ def test_argument_validation_returns_codes_without_gpu(lib):
 # fake integers; every call fails a check, so nothing is launched.
 _LOSS_ARGS = ("E", "B", "N", "M", "D", "w", "b", "eps_cos", "eps", "variant", "loss", "per", "dE", "dw", "db")
 _ORDER_OK = dict(E=16, src=None, B=1, N=4, M=5, D=64, w=16, b=16, eps_cos=1e-8, eps=1e-6, variant=0, loss=16, per=None,
-                 dE=None, dw=None, db=None, ws=256, ws_bytes=1 << 40, stream=None, max_workgroups=64)
+                 dE=None, dw=None, db=None, ws=256, ws_bytes=1 << 40, stream=None, max_workgroups=64,
+                 table=16, R=20, active=None, thr=16, T=50, cos=16, col=None, speakers=None, counts=16)
+_ROW_ARGS = ("E", "table", "B", "N", "R", "D") + _LOSS_ARGS[5:]        # (B, R, D) rows plus a table: offsets or labels
 _ORDER_ARGS = {
     "ge2e_loss_fwd_bwd_f64": _LOSS_ARGS + ("ws", "ws_bytes", "stream"),
     "ge2e_loss_fwd_bwd_raw": ("E", "src") + _LOSS_ARGS[1:] + ("stream",),
     "ge2e_selftest_team_fallback": _LOSS_ARGS + ("ws", "ws_bytes", "stream"),
     "ge2e_selftest_team_grid": _LOSS_ARGS + ("ws", "ws_bytes", "stream", "max_workgroups"),
+    "ge2e_loss_fwd_bwd_ragged": _ROW_ARGS + ("ws", "ws_bytes", "stream"),
+    "ge2e_loss_fwd_bwd_labeled": _ROW_ARGS + ("ws", "ws_bytes", "stream"),
+    "ge2e_loss_fwd_bwd_labeled_masked": _ROW_ARGS + ("active", "ws", "ws_bytes", "stream"),
+    "ge2e_cos_sim_labeled": ("E", "table", "B", "N", "R", "D", "eps_cos", "eps", "thr", "T", "cos", "col", "speakers", "active",
+                             "counts", "ws", "ws_bytes", "stream"),
 }
 _NULL, _SHAPE, _WORKSPACE, _VARIANT, _IMPL, _ALIGN = -1, -2, -3, -4, -5, -6
 _BAD = {_NULL: dict(E=None), _SHAPE: dict(M=1), _VARIANT: dict(variant=7), _WORKSPACE: dict(ws=None, ws_bytes=0),
@@ -91,6 +98,23 @@ _ORDER_CASES += [("ge2e_selftest_team_grid", dict(E=None, max_workgroups=8), _NU
                  ("ge2e_selftest_team_grid", dict(max_workgroups=8, ws=None, ws_bytes=0), _SHAPE)]
 # the second half of the NULL rule (dE without dw / db) is NULL too, ahead of everything else
 _ORDER_CASES += [(entry, dict(dE=32, M=1), _NULL) for entry in _ORDERS]
+# The row-list entry points: the adjacent pairs of their common sequence are asserted next to each of them
+# (test_argument_validation_returns_codes_without_gpu of their own files); here is what those leave out.  Their shape
+# violation is a batch without rows.
+_ROW_BAD = {**_BAD, _SHAPE: dict(R=0)}
+_ROW_ORDERS = {
+    "ge2e_loss_fwd_bwd_ragged": (_NULL, _SHAPE, _VARIANT, _WORKSPACE, _ALIGN),
+    "ge2e_loss_fwd_bwd_labeled": (_NULL, _SHAPE, _VARIANT, _WORKSPACE, _ALIGN),
+    "ge2e_loss_fwd_bwd_labeled_masked": (_NULL, _SHAPE, _VARIANT, _WORKSPACE, _ALIGN),
+    "ge2e_cos_sim_labeled": (_NULL, _SHAPE, _WORKSPACE, _ALIGN),          # no loss: no variant step
+}
+# ... the second half of the NULL rule ahead of the shape,
+_ORDER_CASES += [(entry, dict(dE=32, R=0), _NULL) for entry in _ROW_ORDERS if entry != "ge2e_cos_sim_labeled"]
+# ... and of the evaluation call: its own half of the NULL rule (neither cos nor counts) ahead of a batch without rows, and
+# the threshold half of its shape rule (counts without thresholds, counts with T = 0) ahead of the workspace
+_ORDER_CASES += [("ge2e_cos_sim_labeled", dict(cos=None, counts=None, R=0), _NULL),
+                 ("ge2e_cos_sim_labeled", dict(thr=None, ws=None, ws_bytes=0), _SHAPE),
+                 ("ge2e_cos_sim_labeled", dict(T=0, ws=None, ws_bytes=0), _SHAPE)]
 
 
 @pytest.mark.parametrize("entry, violate, expect", _ORDER_CASES,
@@ -104,8 +128,9 @@ def test_checks_come_in_the_documented_order(lib, entry, violate, expect):
     assert lib.ge2e_raw_supported(4, 5, 64) == 1 and lib.ge2e_raw_supported(64, 10, 512) == 0
     assert lib.ge2e_resolve_impl(1, 4, 5, 64, 0, _lib.IMPLS["team"]) == _lib.IMPLS["team"]
     assert lib.ge2e_resolve_impl(1, 64, 10, 512, 0, _lib.IMPLS["team"]) == _IMPL
-    for code, bad in _BAD.items():
-        if code in _ORDERS[entry] and all(violate.get(k, 0) == v for k, v in bad.items()):
+    order, bads = (_ROW_ORDERS[entry], _ROW_BAD) if entry in _ROW_ORDERS else (_ORDERS[entry], _BAD)
+    for code, bad in bads.items():
+        if code in order and all(violate.get(k, 0) == v for k, v in bad.items()):
             assert call(**bad) == code, (entry, bad)
     # ... and together the earlier check answers
     assert call(**violate) == expect, (entry, violate)
