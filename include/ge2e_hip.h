@@ -214,6 +214,35 @@ int ge2e_loss_fwd_bwd_labeled_masked(const float* E, const int* labels, int B, i
                                      void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * The masked labelled loss on MANY WORKGROUPS PER BATCH: the wide route.  Arguments, semantics, error codes and the order
+ * of the host checks are ge2e_loss_fwd_bwd_labeled_masked's: a row is valid iff 0 <= label < N, a speaker active iff at
+ * least 2 valid rows carry its label, the loss is the ragged loss of the n_act active speakers on the r_act active rows,
+ * per_row_loss and dE come back in the caller's row order and are written as 0 on every row that does not count, such rows
+ * are never read, n_act = 0 gives zeros everywhere, dE = NULL is forward only; both variants, any B, N, R, D >= 1.
+ * What differs is the work decomposition: behind the index kernel come the centroids (one wave per speaker), the rows
+ * (one workgroup per 64 sorted rows), the final sums and, with dE, GC, the speakers and dE, each on many workgroups --
+ * 7 launches with a gradient, 4 without, one linear chain, enqueue-only, no allocation, no state, no synchronisation,
+ * grids sized from the shapes alone: fit for a HIP graph.  The low bits are therefore NOT the masked entry's; the result
+ * has the same bits on every launch, at every position of the stack and whatever the workspace held.
+ * Workspace (ge2e_workspace_bytes_labeled_wide; 256-byte aligned parts, no control block, no initialisation), with
+ * NA = max(1, min(N, R / 2)), NAp = NA rounded up to a multiple of 4, S = min(8, ceil(R / 128)) pieces of GC's K loop:
+ *   4 B (  4 NA D           CH, SS, GC, DUS
+ *        + S NA D           GC's pieces (S > 1 only)
+ *        + 4 NA             CST
+ *        + R NAp            A
+ *        + 8 R + R          row statistics, spk
+ *        + 4 ceil(R / 64) ) tile partials
+ *   + offsets, order, speakers, active of all B batches + the index kernel's counters, every part rounded up to 256 bytes.
+ * It GROWS WITH B -- 164 KB of A per batch at R = 640, N = 64: the route is meant for few, large batches.  The masked
+ * entry, one workgroup per batch, remains the choice when B fills the chip; nothing picks between the two.
+ */
+size_t ge2e_workspace_bytes_labeled_wide(int B, int N, int R, int D, int variant);   /* 0 for a bad shape */
+int ge2e_loss_fwd_bwd_labeled_wide(const float* E, const int* labels, int B, int N, int R, int D,
+                                   const float* w, const float* b, float eps_cos, float eps, int variant,
+                                   float* loss, float* per_row_loss, float* dE, float* dw, float* db, int* active,
+                                   void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * LABELLED EVALUATION: the cosines (and the EER counts) of the masked labelled loss, forward only, for rows in any order.
  * Semantics per batch: ge2e_loss_fwd_bwd_labeled_masked's -- a row is valid iff 0 <= label < N, a speaker active iff at
  * least 2 valid rows carry its label, a row active iff it is valid and its speaker is active; the active speakers get the

@@ -49,6 +49,9 @@ PROTOTYPES = {
     "ge2e_workspace_bytes_labeled_masked": (C.c_size_t, [C.c_int] * 5),
     "ge2e_loss_fwd_bwd_labeled_masked": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, C.c_float,
                                                    C.c_float, C.c_int, _fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_size_t, _fp]),
+    "ge2e_workspace_bytes_labeled_wide": (C.c_size_t, [C.c_int] * 5),
+    "ge2e_loss_fwd_bwd_labeled_wide": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, C.c_float,
+                                                 C.c_float, C.c_int, _fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_size_t, _fp]),
     "ge2e_cos_sim_labeled_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
     "ge2e_cos_sim_labeled": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _fp, C.c_int,
                                        _fp, _fp, _fp, _fp, _fp, _fp, C.c_size_t, _fp]),

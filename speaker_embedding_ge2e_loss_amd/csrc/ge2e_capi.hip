@@ -11,6 +11,7 @@
 #include "ge2e_ragged.hpp"
 #include "ge2e_labels.hpp"
 #include "ge2e_labeled_eval.hpp"
+#include "ge2e_labeled_wide.hpp"
 #include "ge2e_helpers.hpp"
 #include "ge2e_fused.hpp"
 #include "ge2e_selftest.hpp"
@@ -367,6 +368,40 @@ int ge2e_loss_fwd_bwd_labeled_masked(const float* E, const int* labels, int B, i
     const ProblemRagged p = ragged_problem(make_problem_io<ProblemRagged>(E, w, b, eps_cos, eps, variant, loss, per_row_loss, dE, dw, db),
                                            offsets, order, active, speaker_capacity(N, R), B, N, R, D, workspace);
     return (int)launch_ragged(p, (hipStream_t)stream);
+}
+
+// The masked labelled loss on many workgroups per batch (include/ge2e_hip.h, csrc/ge2e_labeled_wide.hip): the masked
+// entry's checks, the masked index kernel, then the chain of wide kernels on a workspace laid out per batch.
+size_t ge2e_workspace_bytes_labeled_wide(int B, int N, int R, int D, int variant) {
+    (void)variant;
+    return masked_shape_ok(B, N, R, D) ? labeled_wide_layout(B, N, R, D).t.total : 0;
+}
+
+int ge2e_loss_fwd_bwd_labeled_wide(const float* E, const int* labels, int B, int N, int R, int D, const float* w,
+                                   const float* b, float eps_cos, float eps, int variant, float* loss, float* per_row_loss,
+                                   float* dE, float* dw, float* db, int* active, void* workspace, size_t workspace_bytes,
+                                   void* stream) {
+    if (!labels || !loss_ptrs_ok(E, w, b, loss, dE, dw, db)) return GE2E_ERR_NULL;
+    LabeledWideLayout L{};
+    if (const int code = loss_checks(masked_shape_ok(B, N, R, D), variant, [&] { return (L = labeled_wide_layout(B, N, R, D)).t.total; },
+                                     workspace, workspace_bytes, E, dE))
+        return code;
+    char* ws = (char*)workspace;
+    int* offsets = (int*)(ws + L.t.off);
+    int* order = (int*)(ws + L.t.order);
+    if (!active) active = (int*)(ws + L.t.active);
+    const hipError_t err = launch_label_index_masked(labels, B, N, R, offsets, order, (int*)(ws + L.t.speakers), active,
+                                                     (int*)(ws + L.t.index), (hipStream_t)stream);
+    if (err != hipSuccess) return (int)err;
+    ProblemLabeledWide p = make_problem_io<ProblemLabeledWide>(E, w, b, eps_cos, eps, variant, loss, per_row_loss, dE, dw, db);
+    p.off = offsets; p.order = order; p.active = active;
+    p.CH = (float*)(ws + L.ch); p.SS = (float*)(ws + L.ss); p.GC = (float*)(ws + L.gc); p.DUS = (float*)(ws + L.dus);
+    p.GCP = (float*)(ws + L.gcp); p.CST = (float*)(ws + L.cstat); p.A = (float*)(ws + L.a);
+    p.RST = (float*)(ws + L.rowstat); p.spk = (int*)(ws + L.spk); p.PART = (float*)(ws + L.part);
+    p.B = B; p.N = N; p.R = R; p.D = D;
+    p.NA = speaker_capacity(N, R);
+    p.log_eps = log_eps_of(p.eps);
+    return (int)launch_labeled_wide(p, (hipStream_t)stream);
 }
 
 // The labelled EVALUATION calls (include/ge2e_hip.h, csrc/ge2e_labeled_eval.hip): the masked index kernel, unchanged, then

@@ -115,6 +115,10 @@ __device__ __forceinline__ void counting_end(const int* hist, int T, int* counts
 }
 
 // ---- kernel 1: centroids ---------------------------------------------------------------------------------------------
+// kLoss: the labelled loss's wide route (ge2e_labeled_wide.hip) runs the same kernel for its SS, CH and spk.  It keeps no
+// col and no counts, and its CST is the ragged kernel's {1 / |c|, kappa, m, m - 1}: kappa where the evaluation has a
+// spare word.  The sums and their order are the same in both forms.
+template <bool kLoss>
 __global__ __launch_bounds__(kThreads) void labeled_eval_centroids_kernel(ProblemLabeledEval p) {
     const int lane = threadIdx.x & 63;
     const int D = p.D, R = p.R, NA = p.NA;
@@ -122,7 +126,7 @@ __global__ __launch_bounds__(kThreads) void labeled_eval_centroids_kernel(Proble
     const long long total = (long long)p.B * NA, nwaves = (long long)gridDim.x * kWaves;
     for (long long w = (long long)blockIdx.x * kWaves + (threadIdx.x >> 6); w < total; w += nwaves) {
         const int bi = (int)(w / NA), k = (int)(w - (long long)bi * NA);
-        if (k == 0 && p.counts) {
+        if (!kLoss && k == 0 && p.counts) {
             int* c = p.counts + (size_t)bi * 2 * p.T;
             for (int t = lane; t < 2 * p.T; t += kWave) c[t] = 0;
         }
@@ -140,7 +144,7 @@ __global__ __launch_bounds__(kThreads) void labeled_eval_centroids_kernel(Proble
         for (int pp = r0 + lane; pp < r1; pp += kWave) {
             const int row = clampi(ord[pp], 0, R - 1);
             p.spk[(size_t)bi * R + pp] = k;
-            p.col[(size_t)bi * R + row] = k;
+            if constexpr (!kLoss) p.col[(size_t)bi * R + row] = k;
         }
         // the sums: a lane owns 4 (vecD) or 1 element of every stretch of 256 / 64; rows in ascending position
         float sq = 0.f;
@@ -192,7 +196,8 @@ __global__ __launch_bounds__(kThreads) void labeled_eval_centroids_kernel(Proble
         }
         if (lane == 0) {
             float* cs = p.CST + ((size_t)bi * NA + k) * 4;
-            cs[CS_RN] = rn; cs[CS_M] = fm; cs[CS_M1] = fm - 1.f; cs[3] = 0.f;
+            if constexpr (kLoss) { cs[0] = rn; cs[1] = kap; cs[2] = fm; cs[3] = fm - 1.f; }
+            else { cs[CS_RN] = rn; cs[CS_M] = fm; cs[CS_M1] = fm - 1.f; cs[3] = 0.f; }
         }
     }
 }
@@ -454,12 +459,17 @@ __global__ __launch_bounds__(kThreads) void eer_counts_labeled_kernel(const floa
 }
 }  // namespace
 
-hipError_t launch_labeled_eval(const ProblemLabeledEval& p, hipStream_t stream) {
+hipError_t launch_labeled_centroids(const ProblemLabeledEval& p, bool loss_stats, hipStream_t stream) {
     const long long waves = (long long)p.B * p.NA;
     const long long cblocks = (waves + kWaves - 1) / kWaves;
-    hipLaunchKernelGGL(labeled_eval_centroids_kernel, dim3((unsigned)std::min<long long>(cblocks, kMaxCentroidBlocks)),
-                       dim3(kThreads), 0, stream, p);
-    hipError_t err = hipGetLastError();
+    const dim3 grid((unsigned)std::min<long long>(cblocks, kMaxCentroidBlocks));
+    if (loss_stats) hipLaunchKernelGGL(labeled_eval_centroids_kernel<true>, grid, dim3(kThreads), 0, stream, p);
+    else hipLaunchKernelGGL(labeled_eval_centroids_kernel<false>, grid, dim3(kThreads), 0, stream, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_labeled_eval(const ProblemLabeledEval& p, hipStream_t stream) {
+    hipError_t err = launch_labeled_centroids(p, false, stream);
     if (err != hipSuccess) return err;
     const int tiles = (p.R + kTile - 1) / kTile;
     const long long items = (long long)p.B * tiles;

@@ -45,6 +45,10 @@ inline LabeledEvalLayout labeled_eval_layout(int B, int N, int R, int D) {
     return L;
 }
 
+// The centroid kernel alone: SS, CH, CST and spk of every active speaker (and col, for the evaluation).  `loss_stats`: the
+// labelled loss's wide route (ge2e_labeled_wide.hip), which reads E, off, order, active, B, N, R, D, NA, eps_cos and writes
+// CH, SS, spk and CST = {1 / |c|, kappa, m, m - 1}; col and counts are not touched.
+hipError_t launch_labeled_centroids(const ProblemLabeledEval& p, bool loss_stats, hipStream_t stream);
 // The two kernels of ge2e_cos_sim_labeled (centroids, rows), enqueued after the index kernel.
 hipError_t launch_labeled_eval(const ProblemLabeledEval& p, hipStream_t stream);
 // ge2e_eer_counts_labeled: a zeroing launch, then one workgroup per (batch, tile of 64 rows).

@@ -177,6 +177,7 @@ _ENTRIES = {
     "ragged": _Entry("ge2e_loss_fwd_bwd_ragged", "ge2e_workspace_bytes_ragged", ("ragged",)),
     "labeled": _Entry("ge2e_loss_fwd_bwd_labeled", "ge2e_workspace_bytes_labeled", ("labeled",)),
     "labeled_masked": _Entry("ge2e_loss_fwd_bwd_labeled_masked", "ge2e_workspace_bytes_labeled_masked", ("labeled_masked",)),
+    "labeled_wide": _Entry("ge2e_loss_fwd_bwd_labeled_wide", "ge2e_workspace_bytes_labeled_wide", ("labeled_wide",)),
     "labeled_eval": _Entry("ge2e_cos_sim_labeled", "ge2e_cos_sim_labeled_workspace_bytes", ("labeled_eval",)),
 }
 
@@ -578,11 +579,18 @@ def label_index_masked(labels: torch.Tensor, num_speakers: int):
     return _label_index(labels, num_speakers, True)
 
 
+def _masked_for(masked: Optional[bool], wide: bool) -> bool:
+    """``masked`` as the labelled calls use it: None is False, unless ``wide`` implies the masked semantics."""
+    if wide and masked is not None and not masked:
+        raise ValueError("wide=True implies the masked semantics (the wide route has no unmasked form): drop masked=False")
+    return bool(wide or masked)
+
+
 def loss_fwd_bwd_labeled(embeddings: torch.Tensor, labels, w: torch.Tensor, b: torch.Tensor, *,
                          num_speakers: Optional[int] = None, eps: float = SMALL_ERR, eps_cos: float = EPS_COS,
                          variant: str = "softmax", need_grad: bool = True, need_per: bool = False,
                          out: Optional[LossOutputs] = None, workspace: Optional[torch.Tensor] = None,
-                         masked: bool = False) -> LossOutputs:
+                         masked: Optional[bool] = None, wide: bool = False) -> LossOutputs:
     """One enqueue of ge2e_loss_fwd_bwd_labeled on the current stream (two launches: the index kernel, the loss kernel).
     No host sync (host labels: none after their first use).
 
@@ -594,7 +602,14 @@ def loss_fwd_bwd_labeled(embeddings: torch.Tensor, labels, w: torch.Tensor, b: t
     ``masked=True``: ge2e_loss_fwd_bwd_labeled_masked, which takes the batch as it is.  ``num_speakers`` is a bound, rows
     labelled outside [0, num_speakers) are ignored (host labels: negative ids), a speaker with fewer than 2 such rows is
     left out, all decided on the device.  per and dE are 0 on the rows that do not count, and ``out.active`` (B, 2) int32
-    receives the numbers of speakers and rows that do (allocated here unless ``out`` is given, where it may be None)."""
+    receives the numbers of speakers and rows that do (allocated here unless ``out`` is given, where it may be None).
+
+    ``wide=True``: ge2e_loss_fwd_bwd_labeled_wide, the masked loss (``masked`` is implied; ``masked=False`` beside it is a
+    ValueError) as a chain of many-workgroup kernels, seven launches with a gradient and four without: a single large
+    batch spreads over the chip where the masked entry keeps it on one workgroup.  The same outputs, held to the same
+    reference, with low bits of their own; its workspace grows with B (one (R, N) matrix per batch), so the masked entry
+    stays the choice for many small batches.  Nothing chooses between the two."""
+    masked = _masked_for(masked, wide)
     _require_cuda(embeddings, "embeddings")
     e3, _, (B, R, D), dev = _as_rows(embeddings)
     _check_scalar_params(w, b, dev)
@@ -606,7 +621,7 @@ def loss_fwd_bwd_labeled(embeddings: torch.Tensor, labels, w: torch.Tensor, b: t
     if masked and out.active is not None and (out.active.dtype != torch.int32 or not out.active.is_contiguous()
                                               or out.active.device != dev or out.active.numel() != 2 * B):
         raise TypeError(f"out.active must be a contiguous int32 tensor of shape ({B}, 2) on {dev}")
-    _launch_rows("labeled_masked" if masked else "labeled", e3, query, workspace,
+    _launch_rows("labeled_wide" if wide else "labeled_masked" if masked else "labeled", e3, query, workspace,
                  e3.data_ptr(), lab.data_ptr(), B, N, R, D, w.data_ptr(), b.data_ptr(), eps_cos, eps, query[4],
                  out.loss.data_ptr(), _ptr(out.per), _ptr(out.dE), _ptr(out.dw), _ptr(out.db),
                  *((_ptr(out.active),) if masked else ()))
@@ -1299,7 +1314,8 @@ def ge2e_loss_ragged(embeddings: torch.Tensor, counts, w: torch.Tensor, b: torch
 
 def ge2e_loss_labeled(embeddings: torch.Tensor, labels, w: torch.Tensor, b: torch.Tensor, *,
                       num_speakers: Optional[int] = None, eps: float = SMALL_ERR, eps_cos: float = EPS_COS,
-                      variant: str = "softmax", masked: bool = False, return_active: bool = False):
+                      variant: str = "softmax", masked: Optional[bool] = None, return_active: bool = False,
+                      wide: bool = False):
     """Differentiable GE2E loss of rows in ANY order with one speaker label each: 0-dim for (R, D) input, (B,) for
     (B, R, D).  What `ge2e_loss_ragged` computes on the rows sorted by speaker (stable), with the embeddings' gradient in
     the caller's row order; nothing is sorted or copied on the way: the index kernel orders the rows on the device and the
@@ -1320,13 +1336,17 @@ def ge2e_loss_labeled(embeddings: torch.Tensor, labels, w: torch.Tensor, b: torc
     batch.  Everything is decided on the device, without a synchronisation.  The rows that do not count are never read
     and get a zero gradient; a batch in which nothing counts has loss 0.  ``return_active=True`` (with ``masked``) returns
     ``(loss, active)``: active (2,) / (B, 2) int32 on the device, not differentiable, holds the numbers of speakers and
-    of rows that counted, so ``loss / active[..., 1].clamp(min=1)`` is the mean over those rows."""
+    of rows that counted, so ``loss / active[..., 1].clamp(min=1)`` is the mean over those rows.
+
+    ``wide=True`` computes the masked loss (``masked`` is implied) with ge2e_loss_fwd_bwd_labeled_wide, many workgroups per
+    batch: for few, large batches (`loss_fwd_bwd_labeled`)."""
+    masked = _masked_for(masked, wide)
     if return_active and not masked:
         raise ValueError("return_active needs masked=True: without masking every row counts")
     embeddings, in_dtype, B, R = _rows_loss_input(embeddings, "ge2e_loss_labeled", "group equal counts")
     with _on_device(embeddings.device):
         lab, N = _labels_on_device(labels, num_speakers, B, R, embeddings.device, masked)
-    launch = functools.partial(loss_fwd_bwd_labeled, num_speakers=N, masked=masked)
+    launch = functools.partial(loss_fwd_bwd_labeled, num_speakers=N, masked=masked, wide=wide)
     res = _GE2ELossRowsFunction.apply(embeddings, lab, w, b, float(eps), float(eps_cos), variant, launch)
     loss, active = res if masked else (res, None)
     loss = loss if in_dtype == torch.float32 else loss.to(in_dtype)

@@ -116,7 +116,8 @@ class GE2ELoss(nn.Module):
         self.w = nn.Parameter(torch.tensor(10.0).to(self.device), requires_grad=True)
         self.b = nn.Parameter(torch.tensor(-5.0).to(self.device), requires_grad=True)
 
-    def forward(self, embeddings, counts=None, labels=None, num_speakers=None, masked=False, return_active=False):
+    def forward(self, embeddings, counts=None, labels=None, num_speakers=None, masked=None, return_active=False,
+                wide=False):
         """embeddings (N,M,D) [or (B,N,M,D)] on hp.general.device -> loss (s3:19-30).
 
         Like the reference, w is NOT clamped (s3:22 discards torch.clamp's result), the
@@ -142,8 +143,11 @@ class GE2ELoss(nn.Module):
         with fewer than 2 rows is left out, device labels may hold anything; all decided on the device.
         ``return_active=True`` returns ``(loss, active)``, active (2,) / (B, 2) int32 on the device: the numbers of
         speakers and rows that counted (``functional.ge2e_loss_labeled``).
+
+        ``wide=True`` (with ``labels``): the masked loss -- ``masked`` is implied -- on many workgroups per batch, for few,
+        large batches (``functional.loss_fwd_bwd_labeled``).
         """
-        if (masked or return_active) and labels is None:
+        if (masked or return_active or wide) and labels is None:
             raise ValueError("masked=True / return_active=True belong to labels=...: pass one speaker label per row")
         if labels is not None:
             if counts is not None:
@@ -152,7 +156,7 @@ class GE2ELoss(nn.Module):
                 raise ValueError(f'impl="{self.impl}" names a fixed-shape kernel; the ragged loss has one kernel (impl="auto")')
             return GF.ge2e_loss_labeled(embeddings, labels, self.w, self.b, num_speakers=num_speakers,
                                         eps=self.hp.general.small_err, variant=self.variant, masked=masked,
-                                        return_active=return_active)
+                                        return_active=return_active, wide=wide)
         if counts is not None:
             if self.impl != "auto":
                 raise ValueError(f'impl="{self.impl}" names a fixed-shape kernel; the ragged loss has one kernel (impl="auto")')

@@ -1,0 +1,139 @@
+"""CPU: the host side of the labelled loss's wide route -- ge2e_loss_fwd_bwd_labeled_wide / ge2e_workspace_bytes_labeled_wide
+and the `wide=True` argument of the Python layer: declared, exported and bound, the ABI version unmoved, the masked entry's
+error codes in the masked entry's order (the argument table of test_masked_cpu.py, both entries called side by side), a
+workspace between the one plane it cannot do without and the sum of the planes the header lists, and the argument errors
+that are raised before any device is needed."""
+import ctypes
+import os
+import re
+
+import pytest
+import torch
+
+from speaker_embedding_ge2e_loss_amd import _lib, build
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SYMS = ("ge2e_workspace_bytes_labeled_wide", "ge2e_loss_fwd_bwd_labeled_wide")
+ERR_NULL, ERR_SHAPE, ERR_WORKSPACE, ERR_VARIANT, ERR_ALIGN = -1, -2, -3, -4, -6
+
+
+@pytest.fixture(scope="module")
+def lib():
+    build.build(verbose=False)
+    return _lib.load()
+
+
+def test_header_library_and_binding_have_the_two_symbols(lib):
+    text = open(os.path.join(ROOT, "include", "ge2e_hip.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    raw = ctypes.CDLL(build.LIB_PATH)
+    for s in SYMS:
+        assert re.search(r"\b%s\s*\(" % s, text), f"{s} not declared in include/ge2e_hip.h"
+        assert hasattr(raw, s), f"{s} not exported"
+        assert s in _lib.PROTOTYPES
+    assert lib.ge2e_abi_version() == 2 and "#define GE2E_ABI_VERSION 2" in text and _lib.ABI_VERSION == 2
+    # the masked entry's argument list, word for word
+    assert _lib.PROTOTYPES["ge2e_loss_fwd_bwd_labeled_wide"] == _lib.PROTOTYPES["ge2e_loss_fwd_bwd_labeled_masked"]
+    assert _lib.PROTOTYPES["ge2e_workspace_bytes_labeled_wide"] == (ctypes.c_size_t, [ctypes.c_int] * 5)
+    from speaker_embedding_ge2e_loss_amd import functional as GF
+    assert GF._ENTRIES["labeled_wide"].entry == SYMS[1] and GF._ENTRIES["labeled_wide"].size_query == SYMS[0]
+    assert GF._ENTRIES["labeled_wide"].tag != GF._ENTRIES["labeled_masked"].tag
+
+
+def test_argument_validation_returns_the_masked_entrys_codes(lib):
+    """The table of test_masked_cpu.test_argument_validation_returns_codes_without_gpu, on both entries."""
+    big = 1 << 40
+    ok = dict(E=16, labels=16, B=1, N=4, R=20, D=8, w=16, b=16, eps_cos=1e-8, eps=1e-6, variant=0, loss=16, per=None, dE=None,
+              dw=None, db=None, active=None, ws=256, ws_bytes=big, stream=None)
+    wide_need = lambda *s: lib.ge2e_workspace_bytes_labeled_wide(*s, 0)        # noqa: E731
+    masked_need = lambda *s: lib.ge2e_workspace_bytes_labeled_masked(*s, 0)    # noqa: E731
+    table = [
+        (dict(E=None), ERR_NULL), (dict(labels=None), ERR_NULL), (dict(loss=None), ERR_NULL), (dict(w=None), ERR_NULL),
+        (dict(b=None), ERR_NULL), (dict(dE=32), ERR_NULL), (dict(dE=32, dw=16), ERR_NULL), (dict(dE=32, db=16), ERR_NULL),
+        (dict(B=0), ERR_SHAPE), (dict(N=0), ERR_SHAPE), (dict(D=0), ERR_SHAPE), (dict(R=0), ERR_SHAPE), (dict(R=-3), ERR_SHAPE),
+        (dict(variant=7), ERR_VARIANT), (dict(variant=-1), ERR_VARIANT),
+        (lambda need: dict(ws_bytes=need(1, 4, 20, 8) - 1), ERR_WORKSPACE),          # short
+        (dict(ws=None, ws_bytes=0), ERR_WORKSPACE),                                  # missing
+        (dict(ws=264), ERR_WORKSPACE),                                               # not 256-byte aligned
+        (lambda need: dict(R=7, ws_bytes=need(1, 4, 7, 8) - 1), ERR_WORKSPACE),      # R < 2 N is a legal shape: N is a bound
+        (dict(R=1, N=50, ws=None), ERR_WORKSPACE), (dict(R=7, E=24), ERR_ALIGN), (dict(E=24), ERR_ALIGN),
+        (dict(dE=40, dw=16, db=16), ERR_ALIGN),
+        # the order of the checks: NULL, shape, variant, workspace, alignment
+        (dict(labels=None, R=0), ERR_NULL), (dict(R=0, variant=7), ERR_SHAPE), (dict(variant=7, ws=None), ERR_VARIANT),
+        (dict(ws=None, E=24), ERR_WORKSPACE),
+    ]
+    for kw, want in table:
+        codes = []
+        for f, need in ((lib.ge2e_loss_fwd_bwd_labeled_wide, wide_need), (lib.ge2e_loss_fwd_bwd_labeled_masked, masked_need)):
+            a = dict(ok, **(kw(need) if callable(kw) else kw))
+            codes.append(f(*[a[k] for k in ok]))
+        assert codes == [want, want], (kw, codes, want)
+
+
+def planes(B, N, R, D, split):
+    """Bytes of the planes include/ge2e_hip.h lists, with `split` planes for GC's pieces, and of the four index tables."""
+    NA = max(1, min(N, R // 2))
+    NAp = (NA + 3) // 4 * 4
+    own = 4 * NA * D + split * NA * D + 4 * NA + R * NAp + 8 * R + R + 4 * ((R + 63) // 64)
+    return 4 * B * own + 4 * B * (2 * N + R + 3)
+
+
+def test_workspace_bytes_labeled_wide(lib):
+    f = lib.ge2e_workspace_bytes_labeled_wide
+    for bad in ((0, 4, 20, 8), (1, 0, 20, 8), (1, 4, 20, 0), (1, 4, 0, 8), (-1, 4, 20, 8), (1, 4, -20, 8), (1, -4, 20, 8)):
+        assert f(*bad, 0) == 0, bad
+    for N, R in ((1251, 640), (1, 1), (64, 640), (12, 48), (4, 1), (7, 2100), (1100, 300), (1024, 16384), (9, 129)):
+        for D in (1, 37, 256):
+            prev = 0
+            for B in (1, 2, 3, 37, 600):
+                if B * R * N * D > 1 << 33:
+                    continue
+                NA = max(1, min(N, R // 2))
+                for variant in (0, 1):
+                    cur = f(B, N, R, D, variant)
+                    top = planes(B, N, R, D, 8) + lib.ge2e_label_index_masked_workspace_bytes(B, N, R) + 8192
+                    assert cur > 0 and cur % 256 == 0, (B, N, R, D, cur)
+                    assert 4 * B * R * NA <= cur <= top, (B, N, R, D, cur, top)
+                    assert cur == f(B, N, R, D, 0)
+                # monotone in B, and growing as soon as a batch's planes outgrow the alignment of the parts
+                assert cur >= prev and (cur > prev or B * R * NA * 4 < 256), (B, N, R, D, cur, prev)
+                prev = cur
+    # the pieces of GC are part of the size only where the rows are cut: R <= 128 has none
+    assert f(1, 12, 128, 16, 0) <= planes(1, 12, 128, 16, 0) + 8192
+    assert f(1, 12, 129, 16, 0) >= planes(1, 12, 129, 16, 2)
+    # the header's figure: 164 KB of A per batch at R = 640, N = 64
+    assert f(2, 64, 640, 256, 0) - f(1, 64, 640, 256, 0) >= 640 * 64 * 4 == 163840
+
+
+def test_python_argument_errors_before_any_device():
+    """As far as a machine without a GPU can say (a tensor on the `meta` device stands in for one that is not on the host)."""
+    from speaker_embedding_ge2e_loss_amd import GE2ELoss, HParams
+    from speaker_embedding_ge2e_loss_amd import functional as GF
+    lab = torch.zeros(8, dtype=torch.int32, device="meta")
+    e = torch.zeros(8, 4, device="meta")
+    mod = GE2ELoss(HParams("cpu"))
+    with pytest.raises(ValueError, match="masked=False"):
+        GF.ge2e_loss_labeled(e, lab, mod.w, mod.b, num_speakers=3, wide=True, masked=False)
+    with pytest.raises(ValueError, match="masked=False"):
+        GF.loss_fwd_bwd_labeled(e, lab, mod.w, mod.b, num_speakers=3, wide=True, masked=False)
+    with pytest.raises(ValueError, match="masked=False"):
+        mod(e, labels=lab, num_speakers=3, wide=True, masked=False)
+    # wide=True without labels: the error masked=True without labels gives
+    for kw in (dict(wide=True), dict(masked=True)):
+        with pytest.raises(ValueError, match="belong to labels") as info:
+            mod(e, **kw)
+        with pytest.raises(ValueError, match="belong to labels"):
+            mod(e, counts=[4, 4], **kw)
+    assert str(info.value) == "masked=True / return_active=True belong to labels=...: pass one speaker label per row"
+    # wide implies masked: return_active is allowed, float64 is refused as it is for masked=True
+    with pytest.raises(NotImplementedError, match="float64"):
+        GF.ge2e_loss_labeled(e.double(), lab, mod.w, mod.b, num_speakers=3, wide=True, return_active=True)
+    with pytest.raises(NotImplementedError, match="float64"):
+        mod(e.double(), labels=lab, num_speakers=3, wide=True, masked=True)
+    with pytest.raises(ValueError, match='impl="auto"'):
+        GE2ELoss(HParams("cpu"), impl="generic")(e, labels=lab, num_speakers=3, wide=True)
+    # the defaults are what they were: without wide, return_active still needs masked=True
+    with pytest.raises(ValueError, match="return_active"):
+        GF.ge2e_loss_labeled(e, lab, mod.w, mod.b, num_speakers=3, return_active=True)
+    assert GF._masked_for(None, False) is False and GF._masked_for(True, False) is True and GF._masked_for(False, False) is False
+    assert GF._masked_for(None, True) is True and GF._masked_for(True, True) is True
