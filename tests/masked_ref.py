@@ -13,6 +13,7 @@ One batch: labels (R,) of ANY integers and the bound N.
                     caller's rows and 0 on every other row; all zero when n_act = 0 (defined here, not by ragged_ref)
 """
 import numpy as np
+import torch
 
 import ragged_ref as rr
 
@@ -44,9 +45,10 @@ def index_ref_batched(labels, N):
     return {k: np.stack([r[k] for r in refs]) for k in ("offsets", "order", "speakers", "active")}
 
 
-def masked_loss(E, labels, N, w=10.0, b=-5.0, eps=rr.EPS, eps_cos=rr.EPS_COS, variant="softmax"):
+def masked_loss(E, labels, N, w=10.0, b=-5.0, eps=rr.EPS, eps_cos=rr.EPS_COS, variant="softmax", dtype=torch.float64):
     """numpy E (R, D), labels (R,), bound N -> dict of float64 numpy: loss (), per (R,), dE (R, D), dw (), db () in the caller's
-    row order, and the index reference under "index".  The rows that are not active are never looked at."""
+    row order, and the index reference under "index".  The rows that are not active are never looked at.  `dtype`: see
+    ragged_ref.ragged_loss."""
     E = np.asarray(E)
     idx = index_ref(labels, N)
     n_act, r_act = (int(v) for v in idx["active"])
@@ -56,7 +58,7 @@ def masked_loss(E, labels, N, w=10.0, b=-5.0, eps=rr.EPS, eps_cos=rr.EPS_COS, va
     if n_act == 0:
         return out
     rows = idx["order"][:r_act]
-    ref = rr.ragged_loss(E[rows], idx["counts"], w, b, eps=eps, eps_cos=eps_cos, variant=variant)
+    ref = rr.ragged_loss(E[rows], idx["counts"], w, b, eps=eps, eps_cos=eps_cos, variant=variant, dtype=dtype)
     out["loss"], out["dw"], out["db"] = ref["loss"], ref["dw"], ref["db"]
     out["per"][rows] = ref["per"]
     out["dE"][rows] = ref["dE"]

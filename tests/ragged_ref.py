@@ -20,14 +20,16 @@ import torch.nn.functional as F
 EPS, EPS_COS = 1e-6, 1e-8
 
 
-def ragged_loss(E, counts, w=10.0, b=-5.0, eps=EPS, eps_cos=EPS_COS, variant="softmax"):
-    """numpy E (R, D), counts (N,) -> dict of float64 numpy: loss (), per (R,), dE (R, D), dw (), db ()."""
+def ragged_loss(E, counts, w=10.0, b=-5.0, eps=EPS, eps_cos=EPS_COS, variant="softmax", dtype=torch.float64):
+    """numpy E (R, D), counts (N,) -> dict of float64 numpy: loss (), per (R,), dE (R, D), dw (), db ().
+    `dtype`: the type the formulas are evaluated in; float64 is the reference, float32 only a yardstick of what plain
+    fp32 arithmetic gives on an input (tests/test_gpu_rowlist_fuzz.py)."""
     counts = [int(c) for c in counts]
     n = len(counts)
-    e = torch.as_tensor(np.ascontiguousarray(E), dtype=torch.float64).clone().requires_grad_(True)
+    e = torch.as_tensor(np.ascontiguousarray(E), dtype=dtype).clone().requires_grad_(True)
     assert e.dim() == 2 and sum(counts) == e.shape[0] and min(counts) >= 2
-    wt = torch.tensor(float(w), dtype=torch.float64, requires_grad=True)
-    bt = torch.tensor(float(b), dtype=torch.float64, requires_grad=True)
+    wt = torch.tensor(float(w), dtype=dtype, requires_grad=True)
+    bt = torch.tensor(float(b), dtype=dtype, requires_grad=True)
     off = np.concatenate([[0], np.cumsum(counts)])
     rows = [e[off[j]:off[j + 1]] for j in range(n)]
     sums = [r.sum(dim=0) for r in rows]
@@ -55,8 +57,8 @@ def ragged_loss(E, counts, w=10.0, b=-5.0, eps=EPS, eps_cos=EPS_COS, variant="so
         raise ValueError(variant)
     loss = per.sum()
     loss.backward()
-    return {"loss": loss.detach().numpy().copy(), "per": per.detach().numpy().copy(), "dE": e.grad.numpy().copy(),
-            "dw": wt.grad.numpy().copy(), "db": bt.grad.numpy().copy()}
+    f64 = lambda t: t.detach().numpy().astype(np.float64)  # noqa: E731  (a copy)
+    return {"loss": f64(loss), "per": f64(per), "dE": f64(e.grad), "dw": f64(wt.grad), "db": f64(bt.grad)}
 
 
 def ragged_inputs(counts, D, seed):

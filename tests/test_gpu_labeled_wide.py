@@ -44,14 +44,14 @@ def GF(lib):
 
 
 # ---- the call ------------------------------------------------------------------------------------------------------------------
-def run(lib, E, labels, N, variant, want_grad=True, pattern=0xFF, want_per=True, want_active=True):
+def run(lib, E, labels, N, variant, want_grad=True, pattern=0xFF, want_per=True, want_active=True, w=W, b=BIAS):
     """One ge2e_loss_fwd_bwd_labeled_wide call on guarded buffers.  E (B, R, D) float32 (rows that do not count may hold
     NaN or Inf), labels (B, R) int32 -> numpy outputs, `active` among them."""
     E = np.ascontiguousarray(E, dtype=np.float32)
     labels = np.ascontiguousarray(labels, dtype=np.int32)
     B, R, D = E.shape
     what = f"wide B{B} N{N} R{R} D{D} {variant} {'fwd+bwd' if want_grad else 'fwd'} fill {pattern:#04x}"
-    e, lab, wb, bb = Buf(E.shape, E), IntBuf(labels.shape, labels), Buf((1,), [W]), Buf((1,), [BIAS])
+    e, lab, wb, bb = Buf(E.shape, E), IntBuf(labels.shape, labels), Buf((1,), [w]), Buf((1,), [b])
     outs = {"loss": Buf((B,))}
     if want_per:
         outs["per"] = Buf((B, R))

@@ -132,14 +132,14 @@ def run_index(lib, labels, N, pattern=0xFF):
     return res
 
 
-def run(lib, E, labels, N, variant, want_grad=True, pattern=0xFF, want_per=True, want_active=True):
+def run(lib, E, labels, N, variant, want_grad=True, pattern=0xFF, want_per=True, want_active=True, w=W, b=BIAS):
     """One ge2e_loss_fwd_bwd_labeled_masked call on guarded buffers.  E (B, R, D) float32 (rows that do not count may hold
     NaN), labels (B, R) int32 -> numpy outputs, `active` among them."""
     E = np.ascontiguousarray(E, dtype=np.float32)
     labels = np.ascontiguousarray(labels, dtype=np.int32)
     B, R, D = E.shape
     what = f"masked B{B} N{N} R{R} D{D} {variant} {'fwd+bwd' if want_grad else 'fwd'} fill {pattern:#04x}"
-    e, lab, wb, bb = Buf(E.shape, E), IntBuf(labels.shape, labels), Buf((1,), [W]), Buf((1,), [BIAS])
+    e, lab, wb, bb = Buf(E.shape, E), IntBuf(labels.shape, labels), Buf((1,), [w]), Buf((1,), [b])
     outs = {"loss": Buf((B,))}
     if want_per:
         outs["per"] = Buf((B, R))
@@ -189,13 +189,13 @@ def check_masked(o, ref, what, quiet=False, plus=True):
     check({k: o[k] for k in KEYS if k in o}, ref, what, quiet=quiet)
 
 
-def ragged_on_compacted(lib, E, ref, variant):
+def ragged_on_compacted(lib, E, ref, variant, w=W, b=BIAS):
     """ge2e_loss_fwd_bwd_ragged on the rows that count, per and dE scattered back (zeros elsewhere): what the masked call
     must return bit for bit."""
     idx = ref["index"]
     n_act, r_act = (int(v) for v in idx["active"])
     rows = idx["order"][:r_act]
-    want = run_ragged(lib, np.ascontiguousarray(E[rows])[None], idx["offsets"][:n_act + 1][None], variant, True, 0xFF)
+    want = run_ragged(lib, np.ascontiguousarray(E[rows])[None], idx["offsets"][:n_act + 1][None], variant, True, 0xFF, w=w, b=b)
     out = {k: want[k] for k in ("loss", "dw", "db")}
     for k in ("per", "dE"):
         back = np.zeros((1,) + E.shape[:1] + want[k].shape[2:], dtype=np.float32)
