@@ -316,6 +316,33 @@ __device__ __forceinline__ void group_argmax(float& v, int& i) {
     else wave_argmax(v, i);
 }
 
+// The fp64 forms (ge2e_f64.hip), over the wave only.  Butterfly reductions: every lane ends with the same bits (a + b and
+// b + a round alike); the order of the sum is part of the results.
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+__device__ __forceinline__ double wave_max(double v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v = fmax(v, __shfl_xor(v, o));
+    return v;
+}
+__device__ __forceinline__ void wave_argmax(double& v, int& i) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        const double ov = __shfl_xor(v, o);
+        const int oi = __shfl_xor(i, o);
+        if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
+    }
+}
+template <int W>
+__device__ __forceinline__ double group_sum(double v) { static_assert(W == 64, "fp64: the wave"); return wave_sum(v); }
+template <int W>
+__device__ __forceinline__ double group_max(double v) { static_assert(W == 64, "fp64: the wave"); return wave_max(v); }
+template <int W>
+__device__ __forceinline__ void group_argmax(double& v, int& i) { static_assert(W == 64, "fp64: the wave"); wave_argmax(v, i); }
+
 // x / max(|x|, eps) bookkeeping shared by every kernel: from a squared norm give
 // the reciprocal of the clamped norm and kappa = clamped / true norm (0 for a zero
 // vector).  ATen clamps the norm in place under no_grad, so the backward of

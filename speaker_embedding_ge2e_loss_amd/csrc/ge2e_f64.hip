@@ -15,35 +15,16 @@
 
 #include <math.h>
 
+#include "ge2e_rows_dev.hpp"
+
 namespace ge2e {
 
 namespace {
-constexpr int RS_RNE = 0, RS_KE = 1, RS_RNU = 2, RS_KU = 3, RS_COSD = 4, RS_AD = 5, RS_COEF = 6;
 constexpr int kMaxWaves = 16;
 constexpr int kF64MaxGrid = 512;   // two workgroups per CU of a whole MI355X; bounds the workspace (one slice each)
 
 typedef double v4d __attribute__((ext_vector_type(4)));
 
-// Butterfly reductions: every lane ends with the same bits (a + b and b + a round alike).
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ double wave_max_d(double v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-    return v;
-}
-// (value, index) arg-max; ties resolve to the lowest index (torch.max / numpy.argmax pick the first)
-__device__ __forceinline__ void wave_argmax_d(double& v, int& i) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        const double ov = __shfl_xor(v, o);
-        const int oi = __shfl_xor(i, o);
-        if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
-    }
-}
 __device__ __forceinline__ void unit_stats_d(double sq, double eps_cos, double& rn, double& kappa) {
     const double n = sqrt(sq);
     const double nc = fmax(n, eps_cos);
@@ -91,11 +72,11 @@ __global__ __launch_bounds__(256) void ge2e_f64_kernel(ProblemF64 p, size_t ws_s
                 const double c = s / fM;
                 sq += c * c;
             }
-            sq = wave_sum_d(sq);
+            sq = wave_sum(sq);
             double rn, kap;
             unit_stats_d(sq, eps_cos, rn, kap);
             for (int d = lane; d < D; d += kWave) CH[(size_t)j * D + d] = SS[(size_t)j * D + d] / fM * rn;
-            if (lane == 0) { CST[j * 2 + 0] = rn; CST[j * 2 + 1] = kap; }
+            if (lane == 0) { CST[j * 2 + CS_RN] = rn; CST[j * 2 + CS_KAP] = kap; }
         }
         __syncthreads();
 
@@ -109,7 +90,7 @@ __global__ __launch_bounds__(256) void ge2e_f64_kernel(ProblemF64 p, size_t ws_s
                 const double u = (SS[(size_t)j * D + d] - e) / fM1;
                 ee += e * e; uu += u * u; eu += e * u;
             }
-            ee = wave_sum_d(ee); uu = wave_sum_d(uu); eu = wave_sum_d(eu);
+            ee = wave_sum(ee); uu = wave_sum(uu); eu = wave_sum(eu);
             double rne, ke, rnu, ku;
             unit_stats_d(ee, eps_cos, rne, ke);
             unit_stats_d(uu, eps_cos, rnu, ku);
@@ -158,53 +139,12 @@ __global__ __launch_bounds__(256) void ge2e_f64_kernel(ProblemF64 p, size_t ws_s
             double* Arow = A + (size_t)r * N;
             const double cosd = RST[(size_t)r * 8 + RS_COSD];
             const double sjj = w * (cosd + eps) + bias;
-            double mx = -INFINITY, best = -INFINITY;
-            int besti = 0x7fffffff;
-            for (int k = lane; k < N; k += kWave) {
-                const double s = w * (Arow[k] + eps) + bias;
-                mx = fmax(mx, s);
-                if (k != j && s > best) { best = s; besti = k; }
-            }
-            double per, coef = 0.0, ad = 0.0;
-            if (!contrast) {
-                mx = fmax(wave_max_d(mx), log_eps);
-                // z_off = everything except the own-speaker term: 1 - p_jj = z_off / z has no cancellation when the
-                // softmax is peaked on the diagonal
-                double zoff = 0.0;
-                for (int k = lane; k < N; k += kWave)
-                    if (k != j) zoff += exp(w * (Arow[k] + eps) + bias - mx);
-                zoff = wave_sum_d(zoff) + exp(log_eps - mx);
-                const double z = zoff + exp(sjj - mx);
-                per = (mx - sjj) + log(z);
-                const double rz = 1.0 / z;
-                for (int k = lane; k < N; k += kWave) {
-                    const double c0 = Arow[k];
-                    const double g = (k == j) ? -zoff * rz : exp(w * (c0 + eps) + bias - mx) * rz;
-                    dw_acc += g * (c0 + eps);
-                    db_acc += g;
-                    const double a = w * g;
-                    coef += a * c0;
-                    if (k == j) { ad = a; Arow[k] = 0.0; } else { Arow[k] = a; }
-                }
-            } else {
-                wave_argmax_d(best, besti);
-                const double pos = 1.0 / (1.0 + exp(-sjj));
-                const double neg = (N > 1) ? 1.0 / (1.0 + exp(-best)) : 0.0;
-                per = 1.0 - pos + neg;
-                for (int k = lane; k < N; k += kWave) {
-                    const double c0 = Arow[k];
-                    double g = 0.0;
-                    if (k == j) g = -pos * (1.0 - pos);
-                    else if (k == besti) g = neg * (1.0 - neg);
-                    dw_acc += g * (c0 + eps);
-                    db_acc += g;
-                    const double a = w * g;
-                    coef += a * c0;
-                    if (k == j) { ad = a; Arow[k] = 0.0; } else { Arow[k] = a; }
-                }
-            }
-            coef = wave_sum_d(coef);
-            ad = wave_sum_d(ad);
+            double mx, best;
+            int besti;
+            row_scan<kWave>(Arow, lane, N, j, w, bias, eps, mx, best, besti);
+            const RowLoss<double> rl = row_loss<kWave>(Arow, lane, N, j, sjj, w, bias, eps, log_eps, contrast, mx, best, besti,
+                                                       true, dw_acc, db_acc);
+            const double per = rl.per, coef = rl.coef, ad = rl.ad;
             loss_acc += per;
             if (lane == 0) {
                 if (p.per) p.per[(size_t)bi * NM + r] = per;
@@ -212,8 +152,8 @@ __global__ __launch_bounds__(256) void ge2e_f64_kernel(ProblemF64 p, size_t ws_s
                 rs[RS_AD] = ad; rs[RS_COEF] = coef;
             }
         }
-        dw_acc = wave_sum_d(dw_acc);
-        db_acc = wave_sum_d(db_acc);
+        dw_acc = wave_sum(dw_acc);
+        db_acc = wave_sum(db_acc);
         if (lane == 0) { red[0][wid] = loss_acc; red[1][wid] = dw_acc; red[2][wid] = db_acc; }
         __syncthreads();
         if (threadIdx.x == 0) {
@@ -253,8 +193,8 @@ __global__ __launch_bounds__(256) void ge2e_f64_kernel(ProblemF64 p, size_t ws_s
             for (int j = wid; j < N; j += NW) {
                 double coef = 0.0;
                 for (int d = lane; d < D; d += kWave) coef += GC[(size_t)j * D + d] * CH[(size_t)j * D + d];
-                coef = wave_sum_d(coef);
-                const double rn = CST[j * 2 + 0], kap = CST[j * 2 + 1];
+                coef = wave_sum(coef);
+                const double rn = CST[j * 2 + CS_RN], kap = CST[j * 2 + CS_KAP];
                 for (int d = lane; d < D; d += kWave) {
                     GC[(size_t)j * D + d] = (GC[(size_t)j * D + d] - kap * coef * CH[(size_t)j * D + d]) * rn;
                     const double s = SS[(size_t)j * D + d];
@@ -262,10 +202,8 @@ __global__ __launch_bounds__(256) void ge2e_f64_kernel(ProblemF64 p, size_t ws_s
                     for (int i = 0; i < M; ++i) {
                         const int r = j * M + i;
                         const double* rs = RST + (size_t)r * 8;
-                        const double e = E[(size_t)r * D + d];
-                        const double eh = e * rs[RS_RNE];
-                        const double uh = (s - e) / fM1 * rs[RS_RNU];
-                        dusum += rs[RS_AD] * (eh - rs[RS_KU] * rs[RS_COSD] * uh) * rs[RS_RNU];
+                        dusum += loo_term(E[(size_t)r * D + d], s, fM1, rs[RS_RNE], rs[RS_RNU], rs[RS_KU], rs[RS_COSD],
+                                          rs[RS_AD]).du;
                     }
                     DUS[(size_t)j * D + d] = dusum;
                 }
@@ -294,14 +232,11 @@ __global__ __launch_bounds__(256) void ge2e_f64_kernel(ProblemF64 p, size_t ws_s
                     if (r < NM && d_ok) {
                         const int j = r / M;
                         const double* rs = RST + (size_t)r * 8;
-                        const double e = E[(size_t)r * D + d];
-                        const double s = SS[(size_t)j * D + d];
-                        const double eh = e * rs[RS_RNE];
-                        const double uh = (s - e) / fM1 * rs[RS_RNU];
-                        const double du = rs[RS_AD] * (eh - rs[RS_KU] * rs[RS_COSD] * uh) * rs[RS_RNU];
-                        const double ge = acc[g] + rs[RS_AD] * uh;
-                        dE[(size_t)r * D + d] = (ge - rs[RS_KE] * rs[RS_COEF] * eh) * rs[RS_RNE] + GC[(size_t)j * D + d] / fM +
-                                                (DUS[(size_t)j * D + d] - du) / fM1;
+                        const LooTerm<double> lo = loo_term(E[(size_t)r * D + d], SS[(size_t)j * D + d], fM1, rs[RS_RNE],
+                                                            rs[RS_RNU], rs[RS_KU], rs[RS_COSD], rs[RS_AD]);
+                        const double ge = acc[g] + rs[RS_AD] * lo.uh;
+                        dE[(size_t)r * D + d] = (ge - rs[RS_KE] * rs[RS_COEF] * lo.eh) * rs[RS_RNE] + GC[(size_t)j * D + d] / fM +
+                                                (DUS[(size_t)j * D + d] - lo.du) / fM1;
                     }
                 }
             }

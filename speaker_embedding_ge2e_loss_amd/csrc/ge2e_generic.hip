@@ -12,11 +12,11 @@
 //   phase C/D s4:200    the gradient autograd would produce (dE, dw, db)
 #include "ge2e_common.hpp"
 #include "ge2e_generic.hpp"
+#include "ge2e_rows_dev.hpp"
 
 namespace ge2e {
 
 namespace {
-constexpr int RS_RNE = 0, RS_KE = 1, RS_RNU = 2, RS_KU = 3, RS_COSD = 4, RS_AD = 5, RS_COEF = 6;
 constexpr int kMaxWaves = 16;
 }  // namespace
 
@@ -63,7 +63,7 @@ __global__ __launch_bounds__(256) void ge2e_generic_kernel(Problem p, size_t ws_
                 CH[j * D + d] = c;
                 CHT[(size_t)d * npad + j] = c;
             }
-            if (lane == 0) { CST[j * 4 + 0] = rn; CST[j * 4 + 1] = kap; }
+            if (lane == 0) { CST[j * 4 + CS_RN] = rn; CST[j * 4 + CS_KAP] = kap; }
         }
         __syncthreads();
 
@@ -104,46 +104,9 @@ __global__ __launch_bounds__(256) void ge2e_generic_kernel(Problem p, size_t ws_
                 }
             }
 
-            float per, coef = 0.f, ad = 0.f;
-            if (!contrast) {
-                mx = fmaxf(wave_max(mx), log_eps);
-                // z_off = everything except the own-speaker term: 1 - p_jj = z_off / z has no
-                // cancellation when the softmax is peaked on the diagonal (trained embeddings)
-                float zoff = 0.f;
-                for (int k = lane; k < N; k += kWave)
-                    if (k != j) zoff += expf(w * (Arow[k] + eps) + bias - mx);
-                zoff = wave_sum(zoff) + expf(log_eps - mx);
-                const float z = zoff + expf(sjj - mx);
-                per = (mx - sjj) + logf(z);
-                const float rz = 1.0f / z;
-                for (int k = lane; k < N; k += kWave) {
-                    const float c0 = Arow[k];
-                    const float g = (k == j) ? -zoff * rz : expf(w * (c0 + eps) + bias - mx) * rz;
-                    dw_acc += g * (c0 + eps);
-                    db_acc += g;
-                    const float a = w * g;
-                    coef += a * c0;
-                    if (k == j) { ad = a; Arow[k] = 0.f; } else { Arow[k] = a; }
-                }
-            } else {
-                wave_argmax(best, besti);
-                const float pos = 1.0f / (1.0f + expf(-sjj));
-                const float neg = (N > 1) ? 1.0f / (1.0f + expf(-best)) : 0.0f;
-                per = 1.0f - pos + neg;
-                for (int k = lane; k < N; k += kWave) {
-                    const float c0 = Arow[k];
-                    float g = 0.f;
-                    if (k == j) g = -pos * (1.0f - pos);
-                    else if (k == besti) g = neg * (1.0f - neg);
-                    dw_acc += g * (c0 + eps);
-                    db_acc += g;
-                    const float a = w * g;
-                    coef += a * c0;
-                    if (k == j) { ad = a; Arow[k] = 0.f; } else { Arow[k] = a; }
-                }
-            }
-            coef = wave_sum(coef);
-            ad = wave_sum(ad);
+            const RowLoss<float> rl = row_loss<kWave>(Arow, lane, N, j, sjj, w, bias, eps, log_eps, contrast, mx, best, besti,
+                                                      true, dw_acc, db_acc);
+            const float per = rl.per, coef = rl.coef, ad = rl.ad;
             loss_acc += per;
             if (lane == 0) {
                 if (p.per) p.per[(size_t)bi * NM + r] = per;
@@ -177,7 +140,7 @@ __global__ __launch_bounds__(256) void ge2e_generic_kernel(Problem p, size_t ws_
                     coef += acc * CH[k * D + d];
                 }
                 coef = wave_sum(coef);
-                const float rn = CST[k * 4 + 0], kap = CST[k * 4 + 1];
+                const float rn = CST[k * 4 + CS_RN], kap = CST[k * 4 + CS_KAP];
                 for (int d = lane; d < D; d += kWave)
                     GC[k * D + d] = (GC[k * D + d] - kap * coef * CH[k * D + d]) * rn;
             }
@@ -191,23 +154,19 @@ __global__ __launch_bounds__(256) void ge2e_generic_kernel(Problem p, size_t ws_
                     for (int i = 0; i < M; ++i) {
                         const int r = j * M + i;
                         const float* rs = RST + (size_t)r * 8;
-                        const float e = E[(size_t)r * D + d];
-                        const float eh = e * rs[RS_RNE];
-                        const float uh = (s - e) / fM1 * rs[RS_RNU];
-                        dusum += rs[RS_AD] * (eh - rs[RS_KU] * rs[RS_COSD] * uh) * rs[RS_RNU];
+                        dusum += loo_term(E[(size_t)r * D + d], s, fM1, rs[RS_RNE], rs[RS_RNU], rs[RS_KU], rs[RS_COSD],
+                                          rs[RS_AD]).du;
                     }
                     for (int i = 0; i < M; ++i) {
                         const int r = j * M + i;
                         const float* rs = RST + (size_t)r * 8;
-                        const float e = E[(size_t)r * D + d];
-                        const float eh = e * rs[RS_RNE];
-                        const float uh = (s - e) / fM1 * rs[RS_RNU];
-                        const float du = rs[RS_AD] * (eh - rs[RS_KU] * rs[RS_COSD] * uh) * rs[RS_RNU];
-                        float g = rs[RS_AD] * uh;
+                        const LooTerm<float> lo = loo_term(E[(size_t)r * D + d], s, fM1, rs[RS_RNE], rs[RS_RNU], rs[RS_KU],
+                                                           rs[RS_COSD], rs[RS_AD]);
+                        float g = rs[RS_AD] * lo.uh;
                         const float* Arow = A + (size_t)r * N;
                         for (int k = 0; k < N; ++k) g = fmaf(Arow[k], CH[k * D + d], g);
                         dE[(size_t)r * D + d] =
-                            (g - rs[RS_KE] * rs[RS_COEF] * eh) * rs[RS_RNE] + dcj + (dusum - du) / fM1;
+                            (g - rs[RS_KE] * rs[RS_COEF] * lo.eh) * rs[RS_RNE] + dcj + (dusum - lo.du) / fM1;
                     }
                 }
             }

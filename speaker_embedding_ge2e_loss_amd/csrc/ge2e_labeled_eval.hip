@@ -4,7 +4,7 @@
 // between workgroups, so a batch spreads over the chip here: two kernels, many workgroups per batch.
 //   centroids  one WAVE per (batch, compact speaker k): the speaker's rows E[order[p]], p = off[k] .. off[k+1]-1, summed in
 //              ascending p (the stable order: the sum's order is fixed).  SS[k] = the sum, CH[k] = the unit centroid,
-//              CST[k] = {1 / |c|, m, m - 1}, spk[p] = k, col[order[p]] = k.  The row indices of up to 64 positions come
+//              CST[k] = {1 / |c|, kappa, m, m - 1}, spk[p] = k, col[order[p]] = k.  The row indices of up to 64 positions come
 //              with ONE coalesced load and are handed out with v_readlane: no dependent order[p] -> row pair per row.
 //              The wave of speaker 0 zeroes the batch's counts.
 //   rows       one 256-thread workgroup per (batch, tile of 64 sorted positions), 16 positions per wave.  Per row the
@@ -33,6 +33,8 @@
 
 #include <algorithm>
 
+#include "ge2e_rows_dev.hpp"
+
 namespace ge2e {
 
 namespace {
@@ -40,29 +42,6 @@ constexpr int kThreads = 256, kWaves = kThreads / kWave;
 constexpr int kTile = 64, kWaveRows = kTile / kWaves;   // sorted positions per workgroup / per wave
 constexpr int kAcc = 4;                                 // column tiles (accumulators) in flight per wave
 constexpr int kMaxCentroidBlocks = 8192, kMaxRowBlocks = 1 << 20;
-constexpr int CS_RN = 0, CS_M = 1, CS_M1 = 2;
-
-typedef float v4f __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ v4f mfma_f32(float a, float b, v4f c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-
-// Elements k .. k+3 of a row of `len` floats (k a multiple of 4), zero where the row is absent or ends.  `vec`: the row
-// starts 16-byte aligned and len is a multiple of 4, so the four are there together or not at all.
-__device__ __forceinline__ v4f load4(const float* row, int k, int len, bool row_ok, bool vec) {
-    v4f v = {0.f, 0.f, 0.f, 0.f};
-    if (vec) {
-        if (row_ok && k < len) v = *reinterpret_cast<const v4f*>(row + k);
-    } else {
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-            if (row_ok && k + s < len) v[s] = row[k + s];
-    }
-    return v;
-}
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
 
 // ---- the counting epilogue, shared by the fused kernel and ge2e_eer_counts_labeled ---------------------------------
 // LDS: hist [2][T+1] (false accepts, own accepts), then the T thresholds.
@@ -115,9 +94,8 @@ __device__ __forceinline__ void counting_end(const int* hist, int T, int* counts
 }
 
 // ---- kernel 1: centroids ---------------------------------------------------------------------------------------------
-// kLoss: the labelled loss's wide route (ge2e_labeled_wide.hip) runs the same kernel for its SS, CH and spk.  It keeps no
-// col and no counts, and its CST is the ragged kernel's {1 / |c|, kappa, m, m - 1}: kappa where the evaluation has a
-// spare word.  The sums and their order are the same in both forms.
+// kLoss: the labelled loss's wide route (ge2e_labeled_wide.hip) runs the same kernel for its SS, CH, CST and spk.  It keeps
+// no col and no counts.  The sums and their order are the same in both forms.
 template <bool kLoss>
 __global__ __launch_bounds__(kThreads) void labeled_eval_centroids_kernel(ProblemLabeledEval p) {
     const int lane = threadIdx.x & 63;
@@ -196,49 +174,25 @@ __global__ __launch_bounds__(kThreads) void labeled_eval_centroids_kernel(Proble
         }
         if (lane == 0) {
             float* cs = p.CST + ((size_t)bi * NA + k) * 4;
-            if constexpr (kLoss) { cs[0] = rn; cs[1] = kap; cs[2] = fm; cs[3] = fm - 1.f; }
-            else { cs[CS_RN] = rn; cs[CS_M] = fm; cs[CS_M1] = fm - 1.f; cs[3] = 0.f; }
+            cs[CS_RN] = rn; cs[CS_KAP] = kap; cs[CS_M] = fm; cs[CS_M1] = fm - 1.f;
         }
     }
 }
 
 // ---- kernel 2: rows --------------------------------------------------------------------------------------------------
-// Elements k .. k+3 of a 16-byte aligned row whose length is a multiple of 4, WITHOUT a branch: the load always happens, at
-// element 0 where k is past the row, and the result is zeroed by a select.  `row` must be readable whatever `ok` says.
-__device__ __forceinline__ v4f load4_always(const float* row, int k, int len, bool ok) {
-    const bool in = k < len;
-    const v4f v = *reinterpret_cast<const v4f*>(row + (in ? k : 0));
-    const v4f z = {0.f, 0.f, 0.f, 0.f};
-    return (ok && in) ? v : z;
-}
-
-// The same without the select, for the centroid side of the contraction: past the row's end the E fragment is zero, so
-// whatever (finite) centroid element stands there adds nothing, and a centroid row that does not exist (its pointer is
-// row 0's) only feeds output columns that the epilogue drops.  No use of the value next to the load: it can stay in flight.
-__device__ __forceinline__ v4f load4_raw(const float* row, int k, int len) {
-    return *reinterpret_cast<const v4f*>(row + (k < len ? k : 0));
-}
-
-// kSteps > 0: D is a multiple of 4 and at most 16 kSteps.  The wave's E fragments stay in registers over all column tiles
-// and every loop over k is unrolled and free of branches, so the loads run ahead of the MFMAs that use them: the row
-// fragments all at once, the centroid fragments kAhead steps ahead in a ring of registers.  (With a branch per step the
-// kernel waited out one L2 round trip per 16 MFMAs; DESIGN.md 3.4e has the figures.)
-// kSteps == 0: any D; a plain loop over k that loads as it goes (L1 / L2), rows and centroids alike.
+// kSteps: the form of the cosine-tile stage (tile_rows and tile_cosines in ge2e_rows_dev.hpp have the reasons): > 0 with the
+// wave's E fragments in registers (D a multiple of 4 and at most 16 kSteps), 0 for any D.
 template <int kSteps>
 __global__ __launch_bounds__(kThreads) void labeled_eval_rows_kernel(ProblemLabeledEval p, int tiles) {
-    constexpr bool kHold = kSteps > 0;
-    constexpr int kAhead = kSteps < 4 ? (kSteps > 0 ? kSteps : 1) : 4;
     extern __shared__ int lds[];
     __shared__ int wtot[2][kWaves];
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const int l15 = lane & 15, q = lane >> 4;
+    const int q = lane >> 4;
     const int D = p.D, R = p.R, N = p.N, NA = p.NA;
     const int T = p.counts ? p.T : 0;
     int* hist = lds;
     float* thr_lds = reinterpret_cast<float*>(lds + 2 * (T + 1));
-    const bool vecD = (D & 3) == 0;
     const bool vecN = p.cos && (N & 3) == 0 && ((uintptr_t)p.cos & 15) == 0;
-    [[maybe_unused]] const int steps = (D + 15) >> 4;
     const float eps = p.eps, eps_cos = p.eps_cos;
     const v4f zero4 = {0.f, 0.f, 0.f, 0.f};
 
@@ -274,131 +228,32 @@ __global__ __launch_bounds__(kThreads) void labeled_eval_rows_kernel(ProblemLabe
 
         if (p0 < r_act) {   // uniform over the wave
             const int nrow = min(kWaveRows, r_act - p0);
-            // ---- row norms and the leave-one-out cosine from the explicit difference SS[j] - e_r, all 16 rows at once: the
-            // lane's row is position p0 + l15 (index, speaker and m - 1 come with one load each for the whole wave, no
-            // dependent chain per row), lane group q holds the elements d0 + 4 q .. + 3 of every step -- the MFMA's own
-            // fragments -- and the four groups' partial sums meet through two lane swaps, in a fixed order.  The lanes
-            // past the wave's last row point at its first one (an active row: readable) and zero what they load ----
-            const bool row_ok = l15 < nrow;
-            const int my_pp = p0 + (row_ok ? l15 : 0);
-            const int my_row = clampi(ord[my_pp], 0, R - 1);
-            const int sp = clampi(p.spk[(size_t)bi * R + my_pp], 0, n_act - 1);
-            const int my_j = row_ok ? sp : -1;
-            const float fm1 = CSTb[(size_t)sp * 4 + CS_M1];
-            const float* pe = E + (size_t)my_row * D;
-            const float* ps = SSb + (size_t)sp * D;
-            float* cr = cosb ? cosb + (size_t)my_row * N : nullptr;
-            [[maybe_unused]] v4f eh[kHold ? kSteps : 1];
-            float ee = 0.f, uu = 0.f, eu = 0.f;
-            auto row_step = [&](const v4f& sj, const v4f& e) {
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    const float u = (sj[t] - e[t]) / fm1;
-                    ee += e[t] * e[t]; uu += u * u; eu += e[t] * u;
-                }
-            };
-            if constexpr (kHold) {
-                v4f sh[kSteps];
-#pragma unroll
-                for (int s = 0; s < kSteps; ++s) eh[s] = load4_always(pe, 16 * s + 4 * q, D, row_ok);
-#pragma unroll
-                for (int s = 0; s < kSteps; ++s) sh[s] = load4_always(ps, 16 * s + 4 * q, D, row_ok);
-#pragma unroll
-                for (int s = 0; s < kSteps; ++s) row_step(sh[s], eh[s]);
-            } else {
-                for (int s = 0; s < steps; ++s)
-                    row_step(load4(ps, 16 * s + 4 * q, D, row_ok, vecD), load4(pe, 16 * s + 4 * q, D, row_ok, vecD));
-            }
-            float part[3] = {ee, uu, eu};
-#pragma unroll
-            for (int t = 0; t < 3; ++t) {   // lanes l15, l15 + 16, l15 + 32, l15 + 48: (q0 + q1) + (q2 + q3) in every lane
-                auto a = GE2E_SWAP16(__float_as_uint(part[t]));
-                const float h = __uint_as_float(a[0]) + __uint_as_float(a[1]);
-                auto b = GE2E_SWAP32(__float_as_uint(h));
-                part[t] = __uint_as_float(b[0]) + __uint_as_float(b[1]);
-            }
-            float my_rne, ke, rnu, ku;
-            unit_stats(part[0], eps_cos, my_rne, ke);
-            unit_stats(part[1], eps_cos, rnu, ku);
-            const float my_cosd = part[2] * my_rne * rnu;
+            // ---- row norms and the leave-one-out cosine of the wave's 16 positions (ge2e_rows_dev.hpp) ----
+            const TileRows<kSteps> t = tile_rows<kSteps>(E, SSb, CSTb, ord, p.spk + (size_t)bi * R, p0, nrow, n_act, R, D, eps_cos);
+            float* cr = cosb ? cosb + (size_t)t.row * N : nullptr;
             // ---- cos tiles on the matrix core: unit centroids x rows, K = D; kAcc column tiles at a time ----
             const int KT = (n_act + 15) >> 4;
-            for (int kt0 = 0; kt0 < KT; kt0 += kAcc) {
-                v4f acc[kAcc];
-                const float* pc[kAcc];
-                bool c_ok[kAcc];
-#pragma unroll
-                for (int a = 0; a < kAcc; ++a) {
-                    const int kb = (kt0 + a) * 16 + l15;
-                    acc[a] = zero4;
-                    c_ok[a] = kb < n_act;
-                    pc[a] = CHb + (size_t)(c_ok[a] ? kb : 0) * D;
-                }
-                if constexpr (kHold) {
-                    v4f ring[kAhead][kAcc];
-#pragma unroll
-                    for (int s = 0; s < kAhead; ++s)
-#pragma unroll
-                        for (int a = 0; a < kAcc; ++a) ring[s][a] = load4_raw(pc[a], 16 * s + 4 * q, D);
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int s = 0; s < kSteps; ++s) {
-                        v4f c[kAcc];
-#pragma unroll
-                        for (int a = 0; a < kAcc; ++a) c[a] = ring[s % kAhead][a];
-                        if (s + kAhead < kSteps) {   // (known at compile time: the loop is unrolled)
-#pragma unroll
-                            for (int a = 0; a < kAcc; ++a)
-                                ring[s % kAhead][a] = load4_raw(pc[a], 16 * (s + kAhead) + 4 * q, D);
-                        }
-                        // (left alone, the scheduler sinks every load to the step that uses it and the ring is gone)
-                        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                        for (int t = 0; t < 4; ++t)
-#pragma unroll
-                            for (int a = 0; a < kAcc; ++a) acc[a] = mfma_f32(c[a][t], eh[s][t], acc[a]);
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-                } else {
-                    for (int s = 0; s < steps; ++s) {
-                        const v4f e = load4(pe, 16 * s + 4 * q, D, row_ok, vecD);
-                        v4f c[kAcc];
-#pragma unroll
-                        for (int a = 0; a < kAcc; ++a) c[a] = load4(pc[a], 16 * s + 4 * q, D, c_ok[a], vecD);
-#pragma unroll
-                        for (int t = 0; t < 4; ++t)
-#pragma unroll
-                            for (int a = 0; a < kAcc; ++a) acc[a] = mfma_f32(c[a][t], e[t], acc[a]);
-                    }
-                }
+            tile_cosines<kSteps, kAcc>(t, CHb, n_act, D, [&](int kt0, const v4f (&acc)[kAcc]) {
                 // epilogue: the lane holds columns c0 .. c0+3 of row l15
 #pragma unroll
                 for (int a = 0; a < kAcc; ++a) {
                     const int c0 = (kt0 + a) * 16 + 4 * q;
-                    if (kt0 + a >= KT || !row_ok || c0 >= N) continue;
+                    if (kt0 + a >= KT || !t.row_ok || c0 >= N) continue;
                     v4f v;
 #pragma unroll
                     for (int g = 0; g < 4; ++g) {
                         const int c = c0 + g;
-                        const bool own = c == my_j;
-                        v[g] = c < n_act ? (own ? my_cosd : acc[a][g] * my_rne) + eps : 0.f;
+                        const bool own = c == t.j;
+                        v[g] = c < n_act ? (own ? t.cosd : acc[a][g] * t.rne) + eps : 0.f;
                         if (T && c < n_act) count_value(v[g], own, hist, thr_lds, T);
                     }
-                    if (cr) {
-                        if (vecN) {
-                            *reinterpret_cast<v4f*>(cr + c0) = v;
-                        } else {
-#pragma unroll
-                            for (int g = 0; g < 4; ++g)
-                                if (c0 + g < N) cr[c0 + g] = v[g];
-                        }
-                    }
+                    if (cr) store4(cr, c0, N, v, vecN);
                 }
-            }
+            });
             // the columns past the last tile of active speakers: 0
             if (cosb) {
                 for (int i = 0; i < nrow; ++i) {
-                    float* zr = cosb + (size_t)__builtin_amdgcn_readlane(my_row, i) * N;
+                    float* zr = cosb + (size_t)__builtin_amdgcn_readlane(t.row, i) * N;
                     for (int c = KT * 16 + lane; c < N; c += kWave) zr[c] = 0.f;
                 }
             }
@@ -476,13 +331,9 @@ hipError_t launch_labeled_eval(const ProblemLabeledEval& p, hipStream_t stream) 
     const unsigned grid = (unsigned)std::min<long long>(items, kMaxRowBlocks);
     const int T = p.counts ? p.T : 0;
     const size_t lds = (size_t)(3 * T + 2) * sizeof(int);
-    // the register-resident forms need 16-byte row loads; D <= 64, <= 128, <= 256 (steps of 16 that only hold zeros still
-    // run: at most half of them)
-    const int hold = (p.D & 3) ? 0 : p.D <= 64 ? 4 : p.D <= 128 ? 8 : p.D <= 256 ? 16 : 0;
-    if (hold == 4) hipLaunchKernelGGL((labeled_eval_rows_kernel<4>), dim3(grid), dim3(kThreads), lds, stream, p, tiles);
-    else if (hold == 8) hipLaunchKernelGGL((labeled_eval_rows_kernel<8>), dim3(grid), dim3(kThreads), lds, stream, p, tiles);
-    else if (hold == 16) hipLaunchKernelGGL((labeled_eval_rows_kernel<16>), dim3(grid), dim3(kThreads), lds, stream, p, tiles);
-    else hipLaunchKernelGGL((labeled_eval_rows_kernel<0>), dim3(grid), dim3(kThreads), lds, stream, p, tiles);
+    dispatch_tile_steps(p.D, [&](auto ks) {
+        hipLaunchKernelGGL((labeled_eval_rows_kernel<decltype(ks)::value>), dim3(grid), dim3(kThreads), lds, stream, p, tiles);
+    });
     return hipGetLastError();
 }
 

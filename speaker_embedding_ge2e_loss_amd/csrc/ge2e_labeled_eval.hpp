@@ -19,7 +19,7 @@ struct ProblemLabeledEval {
     int* counts;         // [B][T][2] or null
     float* CH;           // [B][NA][D] unit centroids
     float* SS;           // [B][NA][D] per-speaker sums
-    float* CST;          // [B][NA][4] 1 / |c|, m, m - 1, 0
+    float* CST;          // [B][NA][4] 1 / |c|, kappa, m, m - 1
     int* spk;            // [B][R]     sorted position -> compact speaker
     int B, N, R, D;
     int NA;              // speakers the centroid planes are laid out for: max(1, min(N, R / 2))
@@ -47,7 +47,7 @@ inline LabeledEvalLayout labeled_eval_layout(int B, int N, int R, int D) {
 
 // The centroid kernel alone: SS, CH, CST and spk of every active speaker (and col, for the evaluation).  `loss_stats`: the
 // labelled loss's wide route (ge2e_labeled_wide.hip), which reads E, off, order, active, B, N, R, D, NA, eps_cos and writes
-// CH, SS, spk and CST = {1 / |c|, kappa, m, m - 1}; col and counts are not touched.
+// CH, SS, spk and CST; col and counts are not touched.
 hipError_t launch_labeled_centroids(const ProblemLabeledEval& p, bool loss_stats, hipStream_t stream);
 // The two kernels of ge2e_cos_sim_labeled (centroids, rows), enqueued after the index kernel.
 hipError_t launch_labeled_eval(const ProblemLabeledEval& p, hipStream_t stream);

@@ -35,6 +35,7 @@
 #include <algorithm>
 
 #include "ge2e_labeled_eval.hpp"
+#include "ge2e_rows_dev.hpp"
 
 namespace ge2e {
 
@@ -47,53 +48,7 @@ constexpr int kGcTiles = 2;                                    // 16-speaker til
 constexpr int kGcAhead = 8;                                    // steps of gc whose loads are in flight together
 constexpr int kDeAhead = 2;                                    // steps of de whose loads are in flight together
 constexpr int kMaxBlocks = 1 << 20;
-constexpr int RS_RNE = 0, RS_KE = 1, RS_RNU = 2, RS_KU = 3, RS_COSD = 4, RS_AD = 5, RS_COEF = 6;
-constexpr int CS_RN = 0, CS_KAP = 1, CS_M = 2, CS_M1 = 3;
 static_assert(kWaveRows == 16, "a wave's rows are one MFMA tile");
-
-typedef float v4f __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ v4f mfma_f32(float a, float b, v4f c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
-
-// Elements k .. k+3 of a row of `len` floats (k a multiple of 4), zero where the row is absent or ends.  `vec`: the row
-// starts 16-byte aligned and len is a multiple of 4, so the four are there together or not at all.
-__device__ __forceinline__ v4f load4(const float* row, int k, int len, bool row_ok, bool vec) {
-    v4f v = {0.f, 0.f, 0.f, 0.f};
-    if (vec) {
-        if (row_ok && k < len) v = *reinterpret_cast<const v4f*>(row + k);
-    } else {
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-            if (row_ok && k + s < len) v[s] = row[k + s];
-    }
-    return v;
-}
-// The same without a branch, for a 16-byte aligned row whose length is a multiple of 4: the load always happens, at
-// element 0 where k is past the row, and a select zeroes it.  `row` must be readable whatever `ok` says.
-__device__ __forceinline__ v4f load4_always(const float* row, int k, int len, bool ok) {
-    const bool in = k < len;
-    const v4f v = *reinterpret_cast<const v4f*>(row + (in ? k : 0));
-    const v4f z = {0.f, 0.f, 0.f, 0.f};
-    return (ok && in) ? v : z;
-}
-// ... and without the select, for the centroid side of the cosines: past the row's end the E fragment is zero, and a
-// centroid row that does not exist (its pointer is row 0's) only feeds columns that the epilogue drops.
-__device__ __forceinline__ v4f load4_raw(const float* row, int k, int len) {
-    return *reinterpret_cast<const v4f*>(row + (k < len ? k : 0));
-}
-__device__ __forceinline__ void store4(float* row, int k, int len, const v4f& v, bool vec) {
-    if (vec) {
-        *reinterpret_cast<v4f*>(row + k) = v;
-    } else {
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-            if (k + s < len) row[k + s] = v[s];
-    }
-}
 
 // What a lane of the speakers kernel owns at column d: four elements where D % 4 == 0, one (then three zeros) otherwise.
 __device__ __forceinline__ v4f load_own(const float* row, int d, bool vec) {
@@ -118,23 +73,18 @@ __device__ __forceinline__ Extents extents(const ProblemLabeledWide& p, int bi) 
 
 // ---- rows: phases B0, B1, B2 ---------------------------------------------------------------------------------------------
 // kSteps > 0: D is a multiple of 4 and at most 16 kSteps; the wave's E fragments stay in registers over all column tiles
-// and every loop over k is unrolled and free of branches (labeled_eval_rows_kernel has the reasons).  kSteps == 0: any D, a
-// plain loop over k.
+// and every loop over k is unrolled and free of branches (tile_cosines has the reasons).  kSteps == 0: any D, a plain loop
+// over k.
 template <int kSteps>
 __global__ __launch_bounds__(kThreads) void wide_rows_kernel(ProblemLabeledWide p, int tiles) {
-    constexpr bool kHold = kSteps > 0;
-    constexpr int kAhead = kSteps < 4 ? (kSteps > 0 ? kSteps : 1) : 4;
     __shared__ float red[3][kWaves];
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const int l15 = lane & 15, q = lane >> 4;
     const int D = p.D, R = p.R, NA = p.NA;
     const int NAp = (NA + 3) & ~3;
-    const bool vecD = (D & 3) == 0;
-    [[maybe_unused]] const int steps = (D + 15) >> 4;
     const float eps = p.eps, eps_cos = p.eps_cos, log_eps = p.log_eps;
     const float w = *p.w, bias = *p.b;
     const bool contrast = p.variant == 1;
-    const v4f zero4 = {0.f, 0.f, 0.f, 0.f};
 
     const long long items = (long long)p.B * tiles;
     for (long long item = blockIdx.x; item < items; item += gridDim.x) {
@@ -161,122 +111,32 @@ __global__ __launch_bounds__(kThreads) void wide_rows_kernel(ProblemLabeledWide 
         const bool wave_active = p0 < r_act;   // uniform over the wave
         const int nrow = wave_active ? min(kWaveRows, r_act - p0) : 0;
         if (wave_active) {
-            // ---- B0: row norms and the leave-one-out cosine, all 16 rows at once on the MFMA's own row fragments: the lane's
-            // row is position p0 + l15, lane group q holds the elements d0 + 4 q .. + 3 of every step, and the four groups'
-            // partial sums meet through two lane swaps in a fixed order.  The lanes past the wave's last row point at its
-            // first one (an active row: readable) and zero what they load ----
-            const bool row_ok = l15 < nrow;
-            const int my_pp = p0 + (row_ok ? l15 : 0);
-            const int my_row = clampi(ord[my_pp], 0, R - 1);
-            const int sp = clampi(spk[my_pp], 0, n_act - 1);
-            const int my_j = row_ok ? sp : -1;
-            const float fm1 = CSTb[(size_t)sp * 4 + CS_M1];
-            const float* pe = E + (size_t)my_row * D;
-            const float* ps = SSb + (size_t)sp * D;
-            [[maybe_unused]] v4f eh[kHold ? kSteps : 1];
-            float ee = 0.f, uu = 0.f, eu = 0.f;
-            auto row_step = [&](const v4f& sj, const v4f& e) {
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    const float u = (sj[t] - e[t]) / fm1;
-                    ee += e[t] * e[t]; uu += u * u; eu += e[t] * u;
-                }
-            };
-            if constexpr (kHold) {
-                v4f sh[kSteps];
-#pragma unroll
-                for (int s = 0; s < kSteps; ++s) eh[s] = load4_always(pe, 16 * s + 4 * q, D, row_ok);
-#pragma unroll
-                for (int s = 0; s < kSteps; ++s) sh[s] = load4_always(ps, 16 * s + 4 * q, D, row_ok);
-#pragma unroll
-                for (int s = 0; s < kSteps; ++s) row_step(sh[s], eh[s]);
-            } else {
-                for (int s = 0; s < steps; ++s)
-                    row_step(load4(ps, 16 * s + 4 * q, D, row_ok, vecD), load4(pe, 16 * s + 4 * q, D, row_ok, vecD));
-            }
-            float part[3] = {ee, uu, eu};
-#pragma unroll
-            for (int t = 0; t < 3; ++t) {   // lanes l15, l15 + 16, l15 + 32, l15 + 48: (q0 + q1) + (q2 + q3) in every lane
-                auto a = GE2E_SWAP16(__float_as_uint(part[t]));
-                const float h = __uint_as_float(a[0]) + __uint_as_float(a[1]);
-                auto b = GE2E_SWAP32(__float_as_uint(h));
-                part[t] = __uint_as_float(b[0]) + __uint_as_float(b[1]);
-            }
-            float my_rne, ke, rnu, ku;
-            unit_stats(part[0], eps_cos, my_rne, ke);
-            unit_stats(part[1], eps_cos, rnu, ku);
-            const float my_cosd = part[2] * my_rne * rnu;
-            if (row_ok && q == 0) {
-                float* rs = RSTb + (size_t)my_pp * 8;
-                const v4f st = {my_rne, ke, rnu, ku};
+            // ---- B0: row norms and the leave-one-out cosine of the wave's 16 positions (ge2e_rows_dev.hpp) ----
+            const TileRows<kSteps> t = tile_rows<kSteps>(E, SSb, CSTb, ord, spk, p0, nrow, n_act, R, D, eps_cos);
+            if (t.row_ok && q == 0) {
+                float* rs = RSTb + (size_t)t.pp * 8;
+                const v4f st = {t.rne, t.ke, t.rnu, t.ku};
                 *reinterpret_cast<v4f*>(rs) = st;
-                rs[RS_COSD] = my_cosd;
+                rs[RS_COSD] = t.cosd;
             }
             // ---- B1: cos tiles on the matrix core: unit centroids x rows, K = D; kAcc column tiles at a time ----
-            float* ar = Ab + (size_t)my_pp * NAp;
+            float* ar = Ab + (size_t)t.pp * NAp;
             const int KT = (n_act + 15) >> 4;
-            for (int kt0 = 0; kt0 < KT; kt0 += kAcc) {
-                v4f acc[kAcc];
-                const float* pc[kAcc];
-                [[maybe_unused]] bool c_ok[kAcc];
-#pragma unroll
-                for (int a = 0; a < kAcc; ++a) {
-                    const int kb = (kt0 + a) * 16 + l15;
-                    acc[a] = zero4;
-                    c_ok[a] = kb < n_act;
-                    pc[a] = CHb + (size_t)(c_ok[a] ? kb : 0) * D;
-                }
-                if constexpr (kHold) {
-                    v4f ring[kAhead][kAcc];
-#pragma unroll
-                    for (int s = 0; s < kAhead; ++s)
-#pragma unroll
-                        for (int a = 0; a < kAcc; ++a) ring[s][a] = load4_raw(pc[a], 16 * s + 4 * q, D);
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int s = 0; s < kSteps; ++s) {
-                        v4f c[kAcc];
-#pragma unroll
-                        for (int a = 0; a < kAcc; ++a) c[a] = ring[s % kAhead][a];
-                        if (s + kAhead < kSteps) {   // (known at compile time: the loop is unrolled)
-#pragma unroll
-                            for (int a = 0; a < kAcc; ++a)
-                                ring[s % kAhead][a] = load4_raw(pc[a], 16 * (s + kAhead) + 4 * q, D);
-                        }
-                        // (left alone, the scheduler sinks every load to the step that uses it and the ring is gone)
-                        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                        for (int t = 0; t < 4; ++t)
-#pragma unroll
-                            for (int a = 0; a < kAcc; ++a) acc[a] = mfma_f32(c[a][t], eh[s][t], acc[a]);
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-                } else {
-                    for (int s = 0; s < steps; ++s) {
-                        const v4f e = load4(pe, 16 * s + 4 * q, D, row_ok, vecD);
-                        v4f c[kAcc];
-#pragma unroll
-                        for (int a = 0; a < kAcc; ++a) c[a] = load4(pc[a], 16 * s + 4 * q, D, c_ok[a], vecD);
-#pragma unroll
-                        for (int t = 0; t < 4; ++t)
-#pragma unroll
-                            for (int a = 0; a < kAcc; ++a) acc[a] = mfma_f32(c[a][t], e[t], acc[a]);
-                    }
-                }
+            tile_cosines<kSteps, kAcc>(t, CHb, n_act, D, [&](int kt0, const v4f (&acc)[kAcc]) {
                 // the lane holds columns c0 .. c0+3 of row l15: the cosine before eps, the own column replaced
 #pragma unroll
                 for (int a = 0; a < kAcc; ++a) {
                     const int c0 = (kt0 + a) * 16 + 4 * q;
-                    if (kt0 + a >= KT || !row_ok || c0 >= NAp) continue;
+                    if (kt0 + a >= KT || !t.row_ok || c0 >= NAp) continue;
                     v4f v;
 #pragma unroll
                     for (int g = 0; g < 4; ++g) {
                         const int c = c0 + g;
-                        v[g] = c < n_act ? (c == my_j ? my_cosd : acc[a][g] * my_rne) : 0.f;
+                        v[g] = c < n_act ? (c == t.j ? t.cosd : acc[a][g] * t.rne) : 0.f;
                     }
                     *reinterpret_cast<v4f*>(ar + c0) = v;
                 }
-            }
+            });
         }
         __syncthreads();   // A and the row statistics of the wave's rows, written lane by lane, are read row by row
 
@@ -292,62 +152,18 @@ __global__ __launch_bounds__(kThreads) void wide_rows_kernel(ProblemLabeledWide 
             float* rs = RSTb + (size_t)r * 8;
             const float cosd = rs[RS_COSD];
             const float sjj = w * (cosd + eps) + bias;
-            float mx = -INFINITY, best = -INFINITY;
-            int besti = 0x7fffffff;
-            for (int k = l15; k < n_act; k += 16) {
-                const float s = w * (Arow[k] + eps) + bias;
-                mx = fmaxf(mx, s);
-                if (k != j && s > best) { best = s; besti = k; }
-            }
-            float per, coef = 0.f, ad = 0.f, dwr = 0.f, dbr = 0.f;
-            if (!contrast) {
-                mx = fmaxf(row16_max(mx), log_eps);
-                // z_off = everything except the own-speaker term: 1 - p_jj = z_off / z has no cancellation when the
-                // softmax is peaked on the diagonal
-                float zoff = 0.f;
-                for (int k = l15; k < n_act; k += 16)
-                    if (k != j) zoff += expf(w * (Arow[k] + eps) + bias - mx);
-                zoff = row16_sum(zoff) + expf(log_eps - mx);
-                const float z = zoff + expf(sjj - mx);
-                per = (mx - sjj) + logf(z);
-                const float rz = 1.0f / z;
-                for (int k = l15; k < n_act; k += 16) {
-                    const float c0 = Arow[k];
-                    const float g = (k == j) ? -zoff * rz : expf(w * (c0 + eps) + bias - mx) * rz;
-                    dwr += g * (c0 + eps);
-                    dbr += g;
-                    const float a = w * g;
-                    coef += a * c0;
-                    if (k == j) ad = a;
-                    if (ok) Arow[k] = (k == j) ? 0.f : a;
-                }
-            } else {
-                row16_argmax(best, besti);
-                const float pos = 1.0f / (1.0f + expf(-sjj));
-                const float neg = (n_act > 1) ? 1.0f / (1.0f + expf(-best)) : 0.f;
-                per = 1.0f - pos + neg;
-                for (int k = l15; k < n_act; k += 16) {
-                    const float c0 = Arow[k];
-                    float g = 0.f;
-                    if (k == j) g = -pos * (1.0f - pos);
-                    else if (k == besti) g = neg * (1.0f - neg);
-                    dwr += g * (c0 + eps);
-                    dbr += g;
-                    const float a = w * g;
-                    coef += a * c0;
-                    if (k == j) ad = a;
-                    if (ok) Arow[k] = (k == j) ? 0.f : a;
-                }
-            }
-            coef = row16_sum(coef);
-            ad = row16_sum(ad);
+            float mx, best, dwr = 0.f, dbr = 0.f;
+            int besti;
+            row_scan<16>(Arow, l15, n_act, j, w, bias, eps, mx, best, besti);
+            const RowLoss<float> rl = row_loss<16>(Arow, l15, n_act, j, sjj, w, bias, eps, log_eps, contrast, mx, best, besti,
+                                                   ok, dwr, dbr);
             if (ok) {
                 dw_acc += dwr;
                 db_acc += dbr;
                 if (l15 == 0) {
-                    loss_acc += per;
-                    if (p.per) p.per[(size_t)bi * R + clampi(ord[r], 0, R - 1)] = per;
-                    rs[RS_AD] = ad; rs[RS_COEF] = coef;
+                    loss_acc += rl.per;
+                    if (p.per) p.per[(size_t)bi * R + clampi(ord[r], 0, R - 1)] = rl.per;
+                    rs[RS_AD] = rl.ad; rs[RS_COEF] = rl.coef;
                 }
             }
         }
@@ -561,11 +377,7 @@ __global__ __launch_bounds__(kThreads) void wide_speakers_kernel(ProblemLabeledW
                     if (ok) {
                         const v4f e = load_own(er, d, vecD);
 #pragma unroll
-                        for (int t = 0; t < 4; ++t) {
-                            const float eh = e[t] * rne;
-                            const float uh = (ss[t] - e[t]) / fm1 * rnu;
-                            dus[t] += ad * (eh - ku * cosd * uh) * rnu;
-                        }
+                        for (int t = 0; t < 4; ++t) dus[t] += loo_term(e[t], ss[t], fm1, rne, rnu, ku, cosd, ad).du;
                     }
                 }
             }
@@ -684,11 +496,9 @@ __global__ __launch_bounds__(kThreads) void wide_de_kernel(ProblemLabeledWide p,
             v4f o;
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                const float eh = e[g] * rne;
-                const float uh = (ss[g] - e[g]) / fm1 * rnu;
-                const float du = ad * (eh - ku * cosd * uh) * rnu;
-                const float ge = acc[t][g] + ad * uh;
-                o[g] = (ge - ke * coef * eh) * rne + gc[g] / fm + (dus[g] - du) / fm1;
+                const LooTerm<float> lo = loo_term(e[g], ss[g], fm1, rne, rnu, ku, cosd, ad);
+                const float ge = acc[t][g] + ad * lo.uh;
+                o[g] = (ge - ke * coef * lo.eh) * rne + gc[g] / fm + (dus[g] - lo.du) / fm1;
             }
             store4(out, d0, D, o, vecD);
         }
@@ -711,12 +521,9 @@ hipError_t launch_labeled_wide(const ProblemLabeledWide& p, hipStream_t stream) 
 
     const int tiles = wide_tiles(p.R);
     const unsigned rgrid = blocks_for((long long)p.B * tiles);
-    // the register-resident forms need 16-byte row loads; D <= 64, <= 128, <= 256
-    const int hold = (p.D & 3) ? 0 : p.D <= 64 ? 4 : p.D <= 128 ? 8 : p.D <= 256 ? 16 : 0;
-    if (hold == 4) hipLaunchKernelGGL((wide_rows_kernel<4>), dim3(rgrid), dim3(kThreads), 0, stream, p, tiles);
-    else if (hold == 8) hipLaunchKernelGGL((wide_rows_kernel<8>), dim3(rgrid), dim3(kThreads), 0, stream, p, tiles);
-    else if (hold == 16) hipLaunchKernelGGL((wide_rows_kernel<16>), dim3(rgrid), dim3(kThreads), 0, stream, p, tiles);
-    else hipLaunchKernelGGL((wide_rows_kernel<0>), dim3(rgrid), dim3(kThreads), 0, stream, p, tiles);
+    dispatch_tile_steps(p.D, [&](auto ks) {
+        hipLaunchKernelGGL((wide_rows_kernel<decltype(ks)::value>), dim3(rgrid), dim3(kThreads), 0, stream, p, tiles);
+    });
     if ((err = hipGetLastError()) != hipSuccess) return err;
 
     hipLaunchKernelGGL(wide_sums_kernel, dim3(blocks_for(p.B, kWaves)), dim3(kThreads), 0, stream, p, tiles);

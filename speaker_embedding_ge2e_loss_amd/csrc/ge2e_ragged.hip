@@ -37,33 +37,13 @@
 
 #include <math.h>
 
+#include "ge2e_rows_dev.hpp"
+
 namespace ge2e {
 
 namespace {
-constexpr int RS_RNE = 0, RS_KE = 1, RS_RNU = 2, RS_KU = 3, RS_COSD = 4, RS_AD = 5, RS_COEF = 6;
-constexpr int CS_RN = 0, CS_KAP = 1, CS_M = 2, CS_M1 = 3;
 constexpr int kMaxWaves = 16;
 constexpr int kRaggedMaxGrid = 512;   // two workgroups per CU of a whole MI355X; bounds the workspace (one slice each)
-
-typedef float v4f __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ v4f mfma_f32(float a, float b, v4f c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-
-// Elements k .. k+3 of a row of `len` floats (k a multiple of 4), zero where the row is absent or ends.  `vec`: the row
-// starts 16-byte aligned and len is a multiple of 4, so the four are there together or not at all.
-__device__ __forceinline__ v4f load4(const float* row, int k, int len, bool row_ok, bool vec) {
-    v4f v = {0.f, 0.f, 0.f, 0.f};
-    if (vec) {
-        if (row_ok && k < len) v = *reinterpret_cast<const v4f*>(row + k);
-    } else {
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-            if (row_ok && k + s < len) v[s] = row[k + s];
-    }
-    return v;
-}
 }  // namespace
 
 // kGather: row r of the sorted layout is row order[r] of E, dE and per (ge2e_loss_fwd_bwd_labeled); otherwise it is row r.
@@ -227,53 +207,12 @@ __global__ __launch_bounds__(256) void ge2e_ragged_kernel(ProblemRagged p, size_
             float* Arow = A + (size_t)r * N;
             const float cosd = RST[(size_t)r * 8 + RS_COSD];
             const float sjj = w * (cosd + eps) + bias;
-            float mx = -INFINITY, best = -INFINITY;
-            int besti = 0x7fffffff;
-            for (int k = lane; k < N; k += kWave) {
-                const float s = w * (Arow[k] + eps) + bias;
-                mx = fmaxf(mx, s);
-                if (k != j && s > best) { best = s; besti = k; }
-            }
-            float per, coef = 0.f, ad = 0.f;
-            if (!contrast) {
-                mx = fmaxf(wave_max(mx), log_eps);
-                // z_off = everything except the own-speaker term: 1 - p_jj = z_off / z has no cancellation when the
-                // softmax is peaked on the diagonal
-                float zoff = 0.f;
-                for (int k = lane; k < N; k += kWave)
-                    if (k != j) zoff += expf(w * (Arow[k] + eps) + bias - mx);
-                zoff = wave_sum(zoff) + expf(log_eps - mx);
-                const float z = zoff + expf(sjj - mx);
-                per = (mx - sjj) + logf(z);
-                const float rz = 1.0f / z;
-                for (int k = lane; k < N; k += kWave) {
-                    const float c0 = Arow[k];
-                    const float g = (k == j) ? -zoff * rz : expf(w * (c0 + eps) + bias - mx) * rz;
-                    dw_acc += g * (c0 + eps);
-                    db_acc += g;
-                    const float a = w * g;
-                    coef += a * c0;
-                    if (k == j) { ad = a; Arow[k] = 0.f; } else { Arow[k] = a; }
-                }
-            } else {
-                wave_argmax(best, besti);
-                const float pos = 1.0f / (1.0f + expf(-sjj));
-                const float neg = (N > 1) ? 1.0f / (1.0f + expf(-best)) : 0.f;
-                per = 1.0f - pos + neg;
-                for (int k = lane; k < N; k += kWave) {
-                    const float c0 = Arow[k];
-                    float g = 0.f;
-                    if (k == j) g = -pos * (1.0f - pos);
-                    else if (k == besti) g = neg * (1.0f - neg);
-                    dw_acc += g * (c0 + eps);
-                    db_acc += g;
-                    const float a = w * g;
-                    coef += a * c0;
-                    if (k == j) { ad = a; Arow[k] = 0.f; } else { Arow[k] = a; }
-                }
-            }
-            coef = wave_sum(coef);
-            ad = wave_sum(ad);
+            float mx, best;
+            int besti;
+            row_scan<kWave>(Arow, lane, N, j, w, bias, eps, mx, best, besti);
+            const RowLoss<float> rl = row_loss<kWave>(Arow, lane, N, j, sjj, w, bias, eps, log_eps, contrast, mx, best, besti,
+                                                      true, dw_acc, db_acc);
+            const float per = rl.per, coef = rl.coef, ad = rl.ad;
             loss_acc += per;
             if (lane == 0) {
                 if (p.per) p.per[(size_t)bi * RC + row(r)] = per;
@@ -332,10 +271,8 @@ __global__ __launch_bounds__(256) void ge2e_ragged_kernel(ProblemRagged p, size_
                     float dusum = 0.f;
                     for (int r = r0; r < r1; ++r) {
                         const float* rs = RST + (size_t)r * 8;
-                        const float e = E[(size_t)row(r) * D + d];
-                        const float eh = e * rs[RS_RNE];
-                        const float uh = (s - e) / fm1 * rs[RS_RNU];
-                        dusum += rs[RS_AD] * (eh - rs[RS_KU] * rs[RS_COSD] * uh) * rs[RS_RNU];
+                        dusum += loo_term(E[(size_t)row(r) * D + d], s, fm1, rs[RS_RNE], rs[RS_RNU], rs[RS_KU], rs[RS_COSD],
+                                          rs[RS_AD]).du;
                     }
                     DUS[(size_t)j * D + d] = dusum;
                 }
@@ -365,6 +302,9 @@ __global__ __launch_bounds__(256) void ge2e_ragged_kernel(ProblemRagged p, size_
                         const float* rs = RST + (size_t)r * 8;
                         const float* cs = CST + (size_t)j * 4;
                         const size_t at = (size_t)row(r) * D + d;
+                        // (loo_term's expressions, written out: through the helper the masked instantiation comes out with
+                        //  another register allocation and its forward call measured slower,
+                        //  profiles/exact_kernels_shared_steps.txt)
                         const float e = E[at];
                         const float s = SS[(size_t)j * D + d];
                         const float eh = e * rs[RS_RNE];
