@@ -286,6 +286,55 @@ int ge2e_eer_counts_labeled(const float* sim, const int* col, const int* active,
                             const float* thresholds, int T, int* counts, void* stream);
 
 /*
+ * DIFFERENTIABLE LABELLED HELPERS: the backward of ge2e_cos_sim_labeled's cosines, and the labelled counterpart of
+ * ge2e_calc_loss / ge2e_calc_loss_bwd, so that a caller can put a head of its own between the two (the reference's
+ * get_cos_sim / calc_loss recombined, for rows in any order).
+ *
+ * ge2e_cos_sim_labeled_bwd.  Semantics are ge2e_cos_sim_labeled's (valid row, active speaker, active row, compact columns
+ * by ascending label).  g_cos [B][R][N] is dL/dcos in the layout cos was returned in: the caller's row order, column k =
+ * compact speaker k.  dE [B][R][D] is dL/dE through all three paths of cos: the row's own normalisation; the other
+ * speakers' centroids, into every row of those speakers; the leave-one-out centroid on the own column, into the speaker's
+ * other rows.  The eps_cos clamps of F.cosine_similarity act as in the wide loss (the `+ eps` of cos is a constant and has
+ * no gradient).  dE comes back in the caller's row order, EVERY element is written, and it is 0 on every row that is not
+ * active.  Rows of E and g_cos that are not active and columns >= n_act of g_cos are never read: they may hold NaN.
+ * n_act = 0: dE all zero.  active [B][2] as ge2e_label_index_masked writes it, or NULL.
+ * The call is stateless: it runs the masked index kernel and the centroid kernel again from E and labels and recomputes
+ * the cosines it needs; it does not take the forward's cos.  Six launches, one linear chain -- index, centroids, the
+ * cos-grad rows kernel (one workgroup per 64 sorted rows: row statistics, the cosines on the matrix core, g_cos into the
+ * wide route's A / row statistics), then the wide loss's own GC, speakers and dE kernels -- enqueue-only, no allocation,
+ * no synchronisation, grids sized from the shapes alone: fit for a HIP graph.  No atomics; every sum has an order fixed
+ * by the shapes and the batch's labels: the same bits on every launch, at every position of the stack, whatever the
+ * workspace held.  Workspace (ge2e_cos_sim_labeled_bwd_workspace_bytes, 256-byte aligned, no initialisation): the wide
+ * entry's layout without the tile partials.  Checked on the host before anything is launched, in this order:
+ * GE2E_ERR_NULL (E, labels, g_cos or dE), GE2E_ERR_SHAPE (B, N, R, D < 1), GE2E_ERR_WORKSPACE, GE2E_ERR_ALIGN (E or dE not
+ * 16-byte aligned; g_cos needs float alignment only).
+ *
+ * ge2e_calc_loss_labeled / _bwd, on a CALLER-MADE sim [B][R][N] (e.g. w cos + b) with the col [B][R] and active [B][2] that
+ * ge2e_cos_sim_labeled returned.  A row counts iff 0 <= col[r] < n_act, n_act = clamp(active[0], 0, N); only the columns
+ * < n_act of a counting row are read.  With j = col[r]:
+ *   softmax   per_r = -sim[r][j] + log(sum_{k < n_act} exp sim[r][k] + eps)
+ *   contrast  per_r = 1 - sigmoid(sim[r][j]) + max_{k != j, k < n_act} sigmoid(sim[r][k])   (the max is 0 when n_act = 1;
+ *             ties go to the lowest index)
+ * in the stabilised arithmetic of the loss kernels.  per_row_loss [B][R] (required) is 0 on rows that do not count;
+ * loss [B] (or NULL) is the batch's sum of per_row_loss in a fixed order (a second small launch).
+ * d_sim[r][k] = (g_loss[b] + g_per[b][r]) d per_r / d sim[r][k], a NULL gradient counting as 0; EVERY element of d_sim is
+ * written: 0 on rows that do not count and on columns >= n_act.  No workspace.  Checks: GE2E_ERR_NULL (sim, col, active,
+ * per_row_loss / d_sim), GE2E_ERR_SHAPE (B, N, R < 1), GE2E_ERR_VARIANT.
+ */
+size_t ge2e_cos_sim_labeled_bwd_workspace_bytes(int B, int N, int R, int D);   /* 0 for a bad shape */
+int ge2e_cos_sim_labeled_bwd(const float* E, const int* labels, const float* g_cos,
+                             int B, int N, int R, int D, float eps_cos,
+                             float* dE, int* active /* [B][2] or NULL */,
+                             void* workspace, size_t workspace_bytes, void* stream);
+int ge2e_calc_loss_labeled(const float* sim, const int* col, const int* active, int B, int N, int R,
+                           float eps, int variant,
+                           float* loss /* [B] or NULL */, float* per_row_loss /* [B][R], required */, void* stream);
+int ge2e_calc_loss_labeled_bwd(const float* sim, const int* col, const int* active, int B, int N, int R,
+                               float eps, int variant,
+                               const float* g_loss /* [B] or NULL */, const float* g_per /* [B][R] or NULL */,
+                               float* d_sim /* [B][R][N] */, void* stream);
+
+/*
  * The same, fed with the encoder's RAW output (s2_model_GE2E_loss_speach_embed.py:34 +
  * s4_train_embed_model.py:186-192 folded into the loss kernel's load and store stages):
  *   Y   [B][N*M][D]  the encoder's projection BEFORE its L2-normalisation, rows in the encoder's own (permuted) order

@@ -12,6 +12,7 @@
 #include "ge2e_labels.hpp"
 #include "ge2e_labeled_eval.hpp"
 #include "ge2e_labeled_wide.hpp"
+#include "ge2e_labeled_helpers.hpp"
 #include "ge2e_helpers.hpp"
 #include "ge2e_fused.hpp"
 #include "ge2e_selftest.hpp"
@@ -446,6 +447,55 @@ int ge2e_eer_counts_labeled(const float* sim, const int* col, const int* active,
     if (!sim || !col || !active || !thresholds || !counts) return GE2E_ERR_NULL;
     if (B < 1 || N < 1 || R < 1 || T < 1 || T > 4096) return GE2E_ERR_SHAPE;
     return (int)launch_eer_counts_labeled(sim, col, active, B, N, R, thresholds, T, counts, (hipStream_t)stream);
+}
+
+// The DIFFERENTIABLE labelled helpers (include/ge2e_hip.h).  ge2e_cos_sim_labeled_bwd: stateless like every entry -- the
+// masked index kernel and the centroid kernel run again from E and labels, the cosines are recomputed -- then the cos-grad
+// rows kernel and the wide route's backward (csrc/ge2e_labeled_wide.hip), on the wide layout without its tile partials.
+size_t ge2e_cos_sim_labeled_bwd_workspace_bytes(int B, int N, int R, int D) {
+    return masked_shape_ok(B, N, R, D) ? labeled_wide_layout(B, N, R, D, false).t.total : 0;
+}
+
+int ge2e_cos_sim_labeled_bwd(const float* E, const int* labels, const float* g_cos, int B, int N, int R, int D, float eps_cos,
+                             float* dE, int* active, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!E || !labels || !g_cos || !dE) return GE2E_ERR_NULL;
+    if (!masked_shape_ok(B, N, R, D)) return GE2E_ERR_SHAPE;
+    const LabeledWideLayout L = labeled_wide_layout(B, N, R, D, false);
+    if (!workspace_ok(workspace, workspace_bytes, L.t.total)) return GE2E_ERR_WORKSPACE;
+    if (!aligned16(E) || !aligned16(dE)) return GE2E_ERR_ALIGN;
+    char* ws = (char*)workspace;
+    int* offsets = (int*)(ws + L.t.off);
+    int* order = (int*)(ws + L.t.order);
+    if (!active) active = (int*)(ws + L.t.active);
+    const hipError_t err = launch_label_index_masked(labels, B, N, R, offsets, order, (int*)(ws + L.t.speakers), active,
+                                                     (int*)(ws + L.t.index), (hipStream_t)stream);
+    if (err != hipSuccess) return (int)err;
+    ProblemLabeledWide p{};
+    p.E = E; p.dE = dE;
+    p.off = offsets; p.order = order; p.active = active;
+    p.CH = (float*)(ws + L.ch); p.SS = (float*)(ws + L.ss); p.GC = (float*)(ws + L.gc); p.DUS = (float*)(ws + L.dus);
+    p.GCP = (float*)(ws + L.gcp); p.CST = (float*)(ws + L.cstat); p.A = (float*)(ws + L.a);
+    p.RST = (float*)(ws + L.rowstat); p.spk = (int*)(ws + L.spk);
+    p.B = B; p.N = N; p.R = R; p.D = D;
+    p.NA = speaker_capacity(N, R);
+    p.eps_cos = eps_cos;
+    return (int)launch_labeled_cos_grad(p, g_cos, (hipStream_t)stream);
+}
+
+int ge2e_calc_loss_labeled(const float* sim, const int* col, const int* active, int B, int N, int R, float eps, int variant,
+                           float* loss, float* per_row_loss, void* stream) {
+    if (!sim || !col || !active || !per_row_loss) return GE2E_ERR_NULL;
+    if (B < 1 || N < 1 || R < 1) return GE2E_ERR_SHAPE;
+    if (!variant_ok(variant)) return GE2E_ERR_VARIANT;
+    return (int)launch_calc_loss_labeled(sim, col, active, B, N, R, eps, variant, loss, per_row_loss, (hipStream_t)stream);
+}
+
+int ge2e_calc_loss_labeled_bwd(const float* sim, const int* col, const int* active, int B, int N, int R, float eps, int variant,
+                               const float* g_loss, const float* g_per, float* d_sim, void* stream) {
+    if (!sim || !col || !active || !d_sim) return GE2E_ERR_NULL;
+    if (B < 1 || N < 1 || R < 1) return GE2E_ERR_SHAPE;
+    if (!variant_ok(variant)) return GE2E_ERR_VARIANT;
+    return (int)launch_calc_loss_labeled_bwd(sim, col, active, B, N, R, eps, variant, g_loss, g_per, d_sim, (hipStream_t)stream);
 }
 
 // ---- diagnostics: the launch plan of a call, from the launchers' own decision functions (ge2e_plan.hpp); no GPU needed ----

@@ -22,6 +22,9 @@
 //   de         one workgroup per (batch, tile of 64 positions, slab of 64 columns): CH^T . A^T over K = n_act, so that a
 //              lane ends with four consecutive columns of one row; D1's row epilogue; 16-byte stores through order where
 //              D % 4 == 0.  Positions r_act .. R-1 are written as 0.                                              phase D1
+// ge2e_cos_sim_labeled_bwd (launch_labeled_cos_grad) is the same chain with another rows kernel and without sums: centroids,
+// labeled_cos_grad_rows_kernel -- B0 and B1 as above, then the caller's dL/dcos where the loss's stood: A, RS_AD, RS_COEF --
+// and gc, speakers, de as they are (launch_labeled_wide_backward: one copy for both entries).
 // No floating-point atomics, no integer ones either; every sum has a fixed order that depends on the shapes and on the
 // batch's own labels only, never on the batch's place in the stack or on which workgroup took the work.  Grids are sized
 // from R and NA = speaker_capacity(N, R); n_act and r_act are read on the device and clamped to [0, NA] and [0, R] where
@@ -179,6 +182,100 @@ __global__ __launch_bounds__(kThreads) void wide_rows_kernel(ProblemLabeledWide 
             pt[0] = l; pt[1] = a; pt[2] = c;
         }
         __syncthreads();   // red is reused by the workgroup's next item
+    }
+}
+
+// ---- cos-grad rows: B0, B1 and, in place of B2, the caller's dL/dcos ---------------------------------------------------
+// ge2e_cos_sim_labeled_bwd's row kernel: wide_rows_kernel's decomposition, row statistics and cosine tiles; what it leaves
+// behind for gc, speakers and de is what row_loss leaves there, with a_k = g_cos[order[p]][k] for the softmax's gradient:
+// A[p][k] = a_k (own column j and the padding 0), RS_AD = a_j, RS_COEF = sum_{k != j} a_k cos_k + a_j cosd (cos before eps).
+// In tile_cosines' epilogue a lane holds four consecutive columns of one row: it takes the matching four words of g_cos --
+// one 16-byte load where N % 4 == 0, g_cos is 16-byte aligned (vecG) and all four count, element loads otherwise -- and
+// keeps a partial of coef over its columns in ascending order; the four lanes of a row join theirs as tile_rows does.  No
+// barrier, no second pass over A.  The loads of a group of kAcc tiles are issued behind the MFMAs of the group before it
+// (the first group's ahead of the stage) and stay in flight over the group's own MFMAs.  Every address is inside the
+// buffers and names an entry that counts (a column past n_act reads column 0, a lane past the wave's last row the wave's
+// first row, and a select drops the value): rows and columns of g_cos that do not count are never read.
+template <int kSteps>
+__global__ __launch_bounds__(kThreads) void labeled_cos_grad_rows_kernel(ProblemLabeledWide p, const float* g_cos, int tiles) {
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int q = lane >> 4;
+    const int D = p.D, R = p.R, N = p.N, NA = p.NA;
+    const int NAp = (NA + 3) & ~3;
+    const float eps_cos = p.eps_cos;
+    const bool vecG = (N & 3) == 0 && ((uintptr_t)g_cos & 15) == 0;
+
+    const long long items = (long long)p.B * tiles;
+    for (long long item = blockIdx.x; item < items; item += gridDim.x) {
+        const int bi = (int)(item / tiles), tile = (int)(item - (long long)bi * tiles);
+        const Extents x = extents(p, bi);
+        const int n_act = x.n_act, r_act = x.r_act;
+        const int p0 = tile * kTile + wid * kWaveRows;
+        if (p0 >= r_act) continue;   // uniform over the wave; no barrier in this kernel
+        const int* ord = p.order + (size_t)bi * R;
+        const int* spk = p.spk + (size_t)bi * R;
+        const float* E = p.E + (size_t)bi * R * D;
+        const float* CHb = p.CH + (size_t)bi * NA * D;
+        const float* SSb = p.SS + (size_t)bi * NA * D;
+        const float* CSTb = p.CST + (size_t)bi * NA * 4;
+        float* Ab = p.A + (size_t)bi * R * NAp;
+        float* RSTb = p.RST + (size_t)bi * R * 8;
+        const int nrow = min(kWaveRows, r_act - p0);
+
+        const TileRows<kSteps> t = tile_rows<kSteps>(E, SSb, CSTb, ord, spk, p0, nrow, n_act, R, D, eps_cos);
+        float* rs = RSTb + (size_t)t.pp * 8;
+        if (t.row_ok && q == 0) {
+            const v4f st = {t.rne, t.ke, t.rnu, t.ku};
+            *reinterpret_cast<v4f*>(rs) = st;
+            rs[RS_COSD] = t.cosd;
+        }
+        const float* gr = g_cos + ((size_t)bi * R + t.row) * N;   // (!row_ok: the wave's first row, an active one)
+        float* ar = Ab + (size_t)t.pp * NAp;
+        const int KT = (n_act + 15) >> 4;
+        // the lane's four words of g_cos in every tile of the group that starts at tile kt0
+        v4f gnext[kAcc];
+        auto load_g = [&](int kt0) {
+#pragma unroll
+            for (int a = 0; a < kAcc; ++a) {
+                const int c0 = (kt0 + a) * 16 + 4 * q;
+                if (vecG && c0 + 3 < n_act) {   // (the four count: only the lanes at the row's last columns go the other way)
+                    gnext[a] = *reinterpret_cast<const v4f*>(gr + c0);
+                } else {
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) gnext[a][g] = gr[c0 + g < n_act ? c0 + g : 0];
+                }
+            }
+        };
+        load_g(0);
+        float coef = 0.f;
+        tile_cosines<kSteps, kAcc>(t, CHb, n_act, D, [&](int kt0, const v4f (&acc)[kAcc]) {
+            v4f gc[kAcc];
+#pragma unroll
+            for (int a = 0; a < kAcc; ++a) gc[a] = gnext[a];
+            if (kt0 + kAcc < KT) load_g(kt0 + kAcc);   // uniform over the wave
+#pragma unroll
+            for (int a = 0; a < kAcc; ++a) {
+                const int c0 = (kt0 + a) * 16 + 4 * q;
+                if (kt0 + a >= KT || !t.row_ok || c0 >= NAp) continue;
+                v4f v;
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const int c = c0 + g;
+                    const bool in = c < n_act, own = c == t.j;
+                    const float ak = in ? gc[a][g] : 0.f;
+                    if (in) coef += ak * (own ? t.cosd : acc[a][g] * t.rne);
+                    if (own) rs[RS_AD] = ak;
+                    v[g] = own ? 0.f : ak;
+                }
+                *reinterpret_cast<v4f*>(ar + c0) = v;
+            }
+        });
+        // lanes l15, l15 + 16, l15 + 32, l15 + 48: (q0 + q1) + (q2 + q3) in every lane, as in tile_rows
+        auto s16 = GE2E_SWAP16(__float_as_uint(coef));
+        const float h = __uint_as_float(s16[0]) + __uint_as_float(s16[1]);
+        auto s32 = GE2E_SWAP32(__float_as_uint(h));
+        coef = __uint_as_float(s32[0]) + __uint_as_float(s32[1]);
+        if (t.row_ok && q == 0) rs[RS_COEF] = coef;
     }
 }
 
@@ -529,6 +626,12 @@ hipError_t launch_labeled_wide(const ProblemLabeledWide& p, hipStream_t stream) 
     hipLaunchKernelGGL(wide_sums_kernel, dim3(blocks_for(p.B, kWaves)), dim3(kThreads), 0, stream, p, tiles);
     if ((err = hipGetLastError()) != hipSuccess || !p.dE) return err;
 
+    return launch_labeled_wide_backward(p, stream);
+}
+
+hipError_t launch_labeled_wide_backward(const ProblemLabeledWide& p, hipStream_t stream) {
+    hipError_t err;
+    const int tiles = wide_tiles(p.R);
     const int S = wide_split(p.R), KTc = (p.NA + 16 * kGcTiles - 1) / (16 * kGcTiles), DB = (p.D + kSlab - 1) / kSlab;
     hipLaunchKernelGGL(wide_gc_kernel, dim3(blocks_for((long long)p.B * S * KTc * DB, kWaves)), dim3(kThreads), 0, stream, p,
                        S, KTc, DB);
@@ -537,6 +640,24 @@ hipError_t launch_labeled_wide(const ProblemLabeledWide& p, hipStream_t stream) 
     if ((err = hipGetLastError()) != hipSuccess) return err;
     hipLaunchKernelGGL(wide_de_kernel, dim3(blocks_for((long long)p.B * tiles * DB)), dim3(kThreads), 0, stream, p, tiles, DB);
     return hipGetLastError();
+}
+
+hipError_t launch_labeled_cos_grad(const ProblemLabeledWide& p, const float* g_cos, hipStream_t stream) {
+    ProblemLabeledEval c{};
+    c.E = p.E; c.off = p.off; c.order = p.order; c.active = p.active;
+    c.CH = p.CH; c.SS = p.SS; c.CST = p.CST; c.spk = p.spk;
+    c.B = p.B; c.N = p.N; c.R = p.R; c.D = p.D; c.NA = p.NA;
+    c.eps_cos = p.eps_cos; c.eps = p.eps;
+    hipError_t err = launch_labeled_centroids(c, true, stream);
+    if (err != hipSuccess) return err;
+    const int tiles = wide_tiles(p.R);
+    const unsigned rgrid = blocks_for((long long)p.B * tiles);
+    dispatch_tile_steps(p.D, [&](auto ks) {
+        hipLaunchKernelGGL((labeled_cos_grad_rows_kernel<decltype(ks)::value>), dim3(rgrid), dim3(kThreads), 0, stream, p,
+                           g_cos, tiles);
+    });
+    if ((err = hipGetLastError()) != hipSuccess) return err;
+    return launch_labeled_wide_backward(p, stream);
 }
 
 }  // namespace ge2e

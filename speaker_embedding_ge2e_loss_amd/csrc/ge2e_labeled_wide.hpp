@@ -50,12 +50,13 @@ struct ProblemLabeledWide {
 };
 
 // ge2e_loss_fwd_bwd_labeled_wide's workspace, per BATCH (no per-workgroup slices), byte offsets; every part starts
-// 256-byte aligned.  The index tables (ge2e_labels.hpp) come last.
+// 256-byte aligned.  The index tables (ge2e_labels.hpp) come last.  `partials` false: no tile partials (the cosine backward,
+// which has no loss to sum).
 struct LabeledWideLayout {
     size_t ch, ss, gc, dus, gcp, cstat, a, rowstat, spk, part;
     IndexTables t;
 };
-inline LabeledWideLayout labeled_wide_layout(int B, int N, int R, int D) {
+inline LabeledWideLayout labeled_wide_layout(int B, int N, int R, int D, bool partials = true) {
     LabeledWideLayout L;
     const size_t NA = (size_t)speaker_capacity(N, R), b = (size_t)B, f = sizeof(float);
     const size_t plane = align_up(b * NA * D * f, 256);
@@ -70,11 +71,18 @@ inline LabeledWideLayout labeled_wide_layout(int B, int N, int R, int D) {
     L.rowstat = L.a + align_up(b * R * (size_t)wide_nap((int)NA) * f, 256);
     L.spk = L.rowstat + align_up(b * R * 8 * f, 256);
     L.part = L.spk + align_up(b * R * sizeof(int), 256);
-    L.t = index_tables(L.part + align_up(b * wide_tiles(R) * 4 * f, 256), B, N, R, true);
+    L.t = index_tables(L.part + (partials ? align_up(b * wide_tiles(R) * 4 * f, 256) : 0), B, N, R, true);
     return L;
 }
 
-// The kernels behind the index kernel: centroids, rows, sums and, with p.dE, GC, speakers, dE.
+// The kernels behind the index kernel: centroids, rows, sums and, with p.dE, launch_labeled_wide_backward.
 hipError_t launch_labeled_wide(const ProblemLabeledWide& p, hipStream_t stream);
+// The backward behind a rows kernel: GC, speakers, dE (phases C1, C2, D1) from A, RST and the centroid planes.  One copy
+// for the wide loss and for ge2e_cos_sim_labeled_bwd.
+hipError_t launch_labeled_wide_backward(const ProblemLabeledWide& p, hipStream_t stream);
+// ge2e_cos_sim_labeled_bwd behind the index kernel: centroids, the cos-grad rows kernel (A, RS_AD and RS_COEF from the
+// caller's g_cos [B][R][N] instead of a loss), launch_labeled_wide_backward.  Its workspace is labeled_wide_layout's with
+// partials = false; w, b, loss, per, dw, db, PART, variant, eps and log_eps are not looked at.
+hipError_t launch_labeled_cos_grad(const ProblemLabeledWide& p, const float* g_cos, hipStream_t stream);
 
 }  // namespace ge2e

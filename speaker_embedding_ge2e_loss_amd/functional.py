@@ -130,8 +130,8 @@ class _LRU(dict):
 #    creating streams does not keep a workspace (with a large launch's fall-back slices) per dead stream forever.  A
 #    dropped or outgrown workspace goes back to the caching allocator, which hands a block out again only in the order
 #    of the stream it was allocated on -- the launches still using it are ahead in that very stream.
-#  * The double-precision kernel, the ragged kernel, its labelled forms and the labelled evaluation call have their own
-#    entries (the key tags of _ENTRIES): their workspaces have no control block, so they are never shared with the fp32
+#  * The double-precision kernel, the ragged kernel, its labelled forms, the labelled evaluation call and the backward of
+#    its cosines have their own entries (the key tags of _ENTRIES): their workspaces have no control block, so they are never shared with the fp32
 #    kernels' workspace, need no initialisation launch, and no `workspace_override` stands in for them.
 _WS_CACHE_MAX = 8
 _ws_bytes_cache: dict = {}
@@ -179,6 +179,7 @@ _ENTRIES = {
     "labeled_masked": _Entry("ge2e_loss_fwd_bwd_labeled_masked", "ge2e_workspace_bytes_labeled_masked", ("labeled_masked",)),
     "labeled_wide": _Entry("ge2e_loss_fwd_bwd_labeled_wide", "ge2e_workspace_bytes_labeled_wide", ("labeled_wide",)),
     "labeled_eval": _Entry("ge2e_cos_sim_labeled", "ge2e_cos_sim_labeled_workspace_bytes", ("labeled_eval",)),
+    "labeled_cos_bwd": _Entry("ge2e_cos_sim_labeled_bwd", "ge2e_cos_sim_labeled_bwd_workspace_bytes", ("labeled_cos_bwd",)),
 }
 
 
@@ -653,12 +654,61 @@ def _threshold_table(thresholds, dev: torch.device, device_ok: bool = False) -> 
     return thr.to(dev)
 
 
+def _cos_sim_labeled_run(e3: torch.Tensor, lab: torch.Tensor, N: int, thr: Optional[torch.Tensor], need_cos: bool,
+                         eps: float, eps_cos: float, workspace: Optional[torch.Tensor]) -> LabeledCosOutputs:
+    """The enqueue of ge2e_cos_sim_labeled on a batched e3 with labels that are on the device already."""
+    B, R, D = e3.shape
+    dev = e3.device
+    T = thr.numel() if thr is not None else 0
+    i32 = dict(dtype=torch.int32, device=dev)
+    out = LabeledCosOutputs(
+        cos=torch.empty(B, R, N, dtype=torch.float32, device=dev) if need_cos else None,
+        col=torch.empty(B, R, **i32), speakers=torch.empty(B, N, **i32), active=torch.empty(B, 2, **i32),
+        counts=torch.empty(B, T, 2, **i32) if T else None)
+    _launch_rows("labeled_eval", e3, (B, N, R, D), workspace,
+                 e3.data_ptr(), lab.data_ptr(), B, N, R, D, eps_cos, eps, _ptr(thr), T, _ptr(out.cos), out.col.data_ptr(),
+                 out.speakers.data_ptr(), out.active.data_ptr(), _ptr(out.counts))
+    return out
+
+
+class _CosSimLabeledFunction(torch.autograd.Function):
+    """The labelled cosines with a backward: ge2e_cos_sim_labeled, then ge2e_cos_sim_labeled_bwd on the saved embeddings
+    and device labels (the call is stateless: it builds its own index and centroids and recomputes the cosines)."""
+
+    @staticmethod
+    def forward(ctx, e3, lab, N, thr, eps, eps_cos, workspace):
+        out = _cos_sim_labeled_run(e3, lab, N, thr, True, eps, eps_cos, workspace)
+        ctx.save_for_backward(e3, lab)
+        ctx.N, ctx.eps_cos = N, eps_cos
+        ctx.set_materialize_grads(False)        # (no zero tensors made for the integer outputs, or for an unused cos)
+        plain = tuple(t for t in (out.col, out.speakers, out.active, out.counts) if t is not None)
+        ctx.mark_non_differentiable(*plain)
+        return out.cos, out.col, out.speakers, out.active, out.counts
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, *_):
+        if g is None:
+            return (None,) * 7
+        e3, lab = ctx.saved_tensors
+        B, R, D = e3.shape
+        g = g.contiguous().float()
+        dE = torch.empty_like(e3)
+        _launch_rows("labeled_cos_bwd", e3, (B, ctx.N, R, D), None,
+                     e3.data_ptr(), lab.data_ptr(), g.data_ptr(), B, ctx.N, R, D, ctx.eps_cos, dE.data_ptr(), None)
+        return dE, None, None, None, None, None, None
+
+
 def cos_sim_labeled(embeddings: torch.Tensor, labels, *, num_speakers: Optional[int] = None, eps: float = SMALL_ERR,
                     eps_cos: float = EPS_COS, thresholds=None, need_cos: bool = True,
-                    workspace: Optional[torch.Tensor] = None) -> LabeledCosOutputs:
+                    workspace: Optional[torch.Tensor] = None, differentiable: bool = False) -> LabeledCosOutputs:
     """One enqueue of ge2e_cos_sim_labeled on the current stream (three launches: index, centroids, rows).  No host sync
-    (host labels: none after their first use).  FORWARD ONLY: no result requires grad and nothing is recorded for autograd
-    (differentiable labelled helpers do not exist; train through `ge2e_loss_labeled`).
+    (host labels: none after their first use).  By default FORWARD ONLY: no result requires grad and nothing is recorded
+    for autograd.  ``differentiable=True`` records ``cos`` for autograd: its backward is ge2e_cos_sim_labeled_bwd (six
+    launches on the current stream, dL/dE through the row, the other speakers' centroids and the leave-one-out centroid),
+    so a head of the caller's own can stand between these cosines and `calc_loss_labeled`, or any other torch code;
+    ``col``, ``speakers``, ``active`` and ``counts`` stay plain tensors, and ``need_cos=False`` beside it is a ValueError.
+    `ge2e_loss_labeled` remains the one-call route to the reference's loss.
 
     ``embeddings`` (R, D) or (B, R, D) float32, rows in ANY order; ``labels`` as `loss_fwd_bwd_labeled(masked=True)` takes
     them: host labels of arbitrary ids (negative: ignore the row), compacted, or a DEVICE tensor (torch.int32 /
@@ -669,22 +719,19 @@ def cos_sim_labeled(embeddings: torch.Tensor, labels, *, num_speakers: Optional[
     column that does not count (None with ``need_cos=False``: the matrix is never materialised) -- ``col`` (R,),
     ``speakers`` (N,), ``active`` (2,), and with ``thresholds`` (non-decreasing, at most 4096: a sequence, checked and
     uploaded, or a float32 DEVICE tensor taken as it is) ``counts`` (T, 2): the calculate_ERR sweep on cos itself."""
+    if differentiable and not need_cos:
+        raise ValueError("differentiable=True is about cos: need_cos=False beside it leaves nothing to differentiate")
     _require_cuda(embeddings, "embeddings")
-    e3, squeeze, (B, R, D), dev = _as_rows(embeddings.detach())
+    e3, squeeze, (B, R, D), dev = _as_rows(embeddings if differentiable else embeddings.detach())
     if thresholds is None and not need_cos:
         raise ValueError("nothing to compute: need_cos=False without thresholds")
     with _on_device(dev):
         lab, N = _labels_on_device(labels, num_speakers, B, R, dev, True)
         thr = _threshold_table(thresholds, dev, device_ok=True) if thresholds is not None else None
-    T = thr.numel() if thr is not None else 0
-    i32 = dict(dtype=torch.int32, device=dev)
-    out = LabeledCosOutputs(
-        cos=torch.empty(B, R, N, dtype=torch.float32, device=dev) if need_cos else None,
-        col=torch.empty(B, R, **i32), speakers=torch.empty(B, N, **i32), active=torch.empty(B, 2, **i32),
-        counts=torch.empty(B, T, 2, **i32) if T else None)
-    _launch_rows("labeled_eval", e3, (B, N, R, D), workspace,
-                 e3.data_ptr(), lab.data_ptr(), B, N, R, D, eps_cos, eps, _ptr(thr), T, _ptr(out.cos), out.col.data_ptr(),
-                 out.speakers.data_ptr(), out.active.data_ptr(), _ptr(out.counts))
+    if differentiable:
+        out = LabeledCosOutputs(*_CosSimLabeledFunction.apply(e3, lab, N, thr, float(eps), float(eps_cos), workspace))
+    else:
+        out = _cos_sim_labeled_run(e3, lab, N, thr, need_cos, eps, eps_cos, workspace)
     if squeeze:
         out = LabeledCosOutputs(*(t[0] if t is not None else None
                                   for t in (out.cos, out.col, out.speakers, out.active, out.counts)))
@@ -714,6 +761,65 @@ def eer_counts_labeled(sim: torch.Tensor, col: torch.Tensor, active: torch.Tenso
     _launch("ge2e_eer_counts_labeled", dev, s.data_ptr(), col.contiguous().data_ptr(), active.contiguous().data_ptr(), B, N,
             R, thr.data_ptr(), T, counts.data_ptr(), _stream_ptr(s))
     return counts[0] if squeeze else counts
+
+
+def _check_col_active(sim: torch.Tensor, col: torch.Tensor, active: torch.Tensor, B: int, R: int) -> None:
+    """``col`` and ``active`` as `cos_sim_labeled` returned them: torch.int32 of B R and 2 B elements (asked first: no
+    device is needed to say so), then everything on sim's ROCm device."""
+    for name, t, n in (("col", col, B * R), ("active", active, B * 2)):
+        if not torch.is_tensor(t) or t.dtype != torch.int32 or t.numel() != n:
+            raise TypeError(f"{name} must be a torch.int32 tensor of {n} elements, as cos_sim_labeled returned it")
+    for name, t in (("sim", sim), ("col", col), ("active", active)):
+        _require_cuda(t, name)
+        if t.device != sim.device:
+            raise TypeError(f"{name} is on {t.device}, sim on {sim.device}")
+
+
+class _CalcLossLabeledFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, s3, col, active, eps, variant):
+        B, R, N = s3.shape
+        loss = torch.empty(B, dtype=torch.float32, device=s3.device)
+        per = torch.empty(B, R, dtype=torch.float32, device=s3.device)
+        _launch("ge2e_calc_loss_labeled", s3.device, s3.data_ptr(), col.data_ptr(), active.data_ptr(), B, N, R, eps,
+                _lib.VARIANTS[variant], loss.data_ptr(), per.data_ptr(), _stream_ptr(s3))
+        ctx.save_for_backward(s3, col, active)
+        ctx.eps, ctx.variant = eps, variant
+        ctx.set_materialize_grads(False)        # (an output nobody used arrives as None and crosses the ABI as NULL)
+        return loss, per
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_loss, g_per):
+        if g_loss is None and g_per is None:
+            return (None,) * 5
+        s3, col, active = ctx.saved_tensors
+        B, R, N = s3.shape
+        gl = g_loss.contiguous().float() if g_loss is not None else None
+        gp = g_per.contiguous().float() if g_per is not None else None
+        dS = torch.empty_like(s3)
+        _launch("ge2e_calc_loss_labeled_bwd", s3.device, s3.data_ptr(), col.data_ptr(), active.data_ptr(), B, N, R, ctx.eps,
+                _lib.VARIANTS[ctx.variant], _ptr(gl), _ptr(gp), dS.data_ptr(), _stream_ptr(s3))
+        return dS, None, None, None, None
+
+
+def calc_loss_labeled(sim: torch.Tensor, col: torch.Tensor, active: torch.Tensor, *, eps: float = SMALL_ERR,
+                      variant: str = "softmax"):
+    """ge2e_calc_loss_labeled: calc_loss on a caller-made ``sim`` (R, N) / (B, R, N) -- e.g. w * cos + b -- with the ``col``
+    and ``active`` `cos_sim_labeled` returned -> (loss () / (B,), per_row_loss (R,) / (B, R)), differentiable in ``sim``
+    (ge2e_calc_loss_labeled_bwd).  A row counts when 0 <= col < active[0]; per_row_loss and the gradient are 0 on the other
+    rows and on the columns >= active[0], none of which is read.  loss is the batch's sum of per_row_loss."""
+    if variant not in _lib.VARIANTS:
+        raise ValueError(f"variant must be one of {sorted(_lib.VARIANTS)}, got {variant!r}")
+    if not torch.is_tensor(sim) or sim.dim() not in (2, 3):
+        raise ValueError(f"sim must be a tensor (R,N) or (B,R,N), got {tuple(sim.shape) if torch.is_tensor(sim) else type(sim).__name__}")
+    squeeze = sim.dim() == 2
+    s = sim.unsqueeze(0) if squeeze else sim
+    B, R, N = s.shape
+    _check_col_active(s, col, active, B, R)
+    loss, per = _CalcLossLabeledFunction.apply(s.contiguous().float(), col.contiguous(), active.contiguous(), float(eps),
+                                               variant)
+    return (loss[0], per[0]) if squeeze else (loss, per)
 
 
 # ---- the reference's static helpers (s3:33-38, 41-80, 95-112, 114-127), differentiable like the originals ----------
