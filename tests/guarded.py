@@ -22,6 +22,11 @@ def dev():
     return torch.device("cuda:0")
 
 
+def same_bits(a, b):
+    """Two float32 arrays a caller fetched: the same shape and the same bits (NaN payloads and the sign of zero included)."""
+    return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
+
+
 class _Guarded:
     """n elements between two guard bands of `FILL`; inputs carry data, outputs `FILL` as poison.  `offset` shifts the inner
     region by that many elements (offset = 1: one element past a 16-byte boundary).  Subclasses say what a guard is."""

@@ -9,16 +9,11 @@ import numpy as np
 import pytest
 
 import bounds_cases as bc
-from speaker_embedding_ge2e_loss_amd import _lib, build
+from capi import built_lib as lib  # noqa: F401
+from speaker_embedding_ge2e_loss_amd import _lib
 
 VAR = _lib.VARIANTS
 IMPL = _lib.IMPLS
-
-
-@pytest.fixture(scope="module")
-def lib():
-    build.build(verbose=False)
-    return _lib.load()
 
 
 def accepts(lib, impl, N, M, D, B=1):

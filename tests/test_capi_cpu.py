@@ -2,25 +2,13 @@
 rejects bad arguments before touching the GPU.  No compute is launched here."""
 import ctypes
 import os
-import re
 
 import pytest
 
+from capi import built_lib as lib  # noqa: F401
+from capi import header_symbols
 from speaker_embedding_ge2e_loss_amd import _lib, build
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def lib():
-    build.build(verbose=False)
-    return _lib.load()
-
-
-def header_symbols():
-    text = open(os.path.join(ROOT, "include", "ge2e_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(ge2e_[a-z_0-9]+)\s*\(", text)))
 
 
 def test_library_exports_every_declared_symbol(lib):

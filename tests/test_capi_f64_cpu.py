@@ -1,27 +1,19 @@
 """CPU: the double-precision entry point of the C ABI (ge2e_loss_fwd_bwd_f64 / ge2e_workspace_bytes_f64) is declared,
 exported and bound, sizes its workspace sanely and rejects bad arguments on the host, before anything is launched."""
 import ctypes
-import os
 import re
 
-import pytest
 
+from capi import built_lib as lib  # noqa: F401
+from capi import header_text
 from speaker_embedding_ge2e_loss_amd import _lib, build
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMS = ("ge2e_workspace_bytes_f64", "ge2e_loss_fwd_bwd_f64")
 ERR_NULL, ERR_SHAPE, ERR_WORKSPACE, ERR_VARIANT, ERR_ALIGN = -1, -2, -3, -4, -6
 
 
-@pytest.fixture(scope="module")
-def lib():
-    build.build(verbose=False)
-    return _lib.load()
-
-
 def test_header_library_and_binding_have_both_symbols(lib):
-    text = open(os.path.join(ROOT, "include", "ge2e_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text = header_text()
     raw = ctypes.CDLL(build.LIB_PATH)
     for s in SYMS:
         assert re.search(r"\b%s\s*\(" % s, text), f"{s} not declared in include/ge2e_hip.h"

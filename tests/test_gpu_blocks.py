@@ -4,15 +4,9 @@ import numpy as np
 import pytest
 import torch
 
+from capi import lib  # noqa: F401
+
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def lib():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from speaker_embedding_ge2e_loss_amd import _lib
-    return _lib.load()
 
 
 def test_wave_ops(lib):

@@ -7,7 +7,7 @@ sizes the kernels see are exactly the ones include/ge2e_hip.h documents -- not w
   - inputs sit between NaN (int32: sentinel) guards, outputs are NaN-poisoned between guards, the workspace is exactly
     ge2e_workspace_bytes long (that same number is passed as workspace_bytes), 256-byte aligned, between 256-byte guards;
   - every guard must come back bit for bit, no requested output may keep poison, E must be unchanged;
-  - results pass the existing gate (check / TOL of test_gpu_parity.py, non-strict, against the fp64 closed form);
+  - results pass the existing gate (check_dense / TOL of tests/dense_harness.py, non-strict, against the fp64 closed form);
   - every case runs on a workspace filled with 0xFF bytes (NaN as fp32 and as fp16 halves) and on one filled with 0x00,
     ge2e_workspace_init after each fill: the two runs must agree bit for bit on every output (test_gpu_determinism.py
     holds the kernels to bitwise repeatability, so a difference means workspace contents leak into a result).
@@ -26,89 +26,13 @@ import pytest
 import torch
 
 import bounds_cases as bc
+from capi import lib, ok  # noqa: F401
 from conftest import rel_fro
-from guarded import SENTINEL, Buf, IntBuf, Workspace
+from dense_harness import EPS, EPS_COS, FILLS, TOL, call_loss, check_dense, check_forward, ids, note
+from guarded import SENTINEL, Buf, IntBuf, Workspace, same_bits
 from oracle import ge2e_oracle as orc
-from test_gpu_parity import TOL, check
 
 pytestmark = pytest.mark.gpu
-
-EPS_COS, EPS = orc.EPS_COS, orc.SMALL_ERR
-FILLS = (0xFF, 0x00)
-WORST = {}
-
-
-@pytest.fixture(scope="module")
-def lib():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from speaker_embedding_ge2e_loss_amd import _lib
-    return _lib.load()
-
-
-def ids():
-    from speaker_embedding_ge2e_loss_amd import _lib
-    return _lib.VARIANTS, _lib.IMPLS, _lib.IMPL_NAMES
-
-
-def ok(code, what):
-    assert code == 0, f"{what} returned {code}"
-
-
-def note(impl, **errs):
-    """Keep and print the worst figure of every kind seen for `impl` so far."""
-    w = WORST.setdefault(impl, {})
-    for k, v in errs.items():
-        w[k] = max(w.get(k, 0.0), float(v))
-    print(f"[bounds worst] {impl:>12s} " + "  ".join(f"{k} {v:.3e}" for k, v in sorted(w.items())))
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
-
-
-def check_forward(o, ref, impl, what):
-    """The loss and per lines of test_gpu_parity.check, with the same numbers (forward-only calls have nothing else)."""
-    lt = TOL[impl][0]
-    loss_ref = np.asarray(ref["loss"], np.float64)
-    floor = 3e-7 * np.abs(np.asarray(ref["per"], np.float64)).sum(axis=(-1, -2))
-    nm = int(np.prod(np.asarray(ref["per"]).shape[-2:]))
-    assert np.all(np.abs(o["loss"] - loss_ref) <= lt * np.abs(loss_ref) + floor + 1e-6 + 2e-7 * nm), \
-        f"{what} loss {o['loss']} vs {loss_ref}"
-    if "per" in o:
-        assert np.allclose(o["per"], ref["per"], rtol=20 * lt, atol=2e-5), f"{what} per"
-
-
-def call_loss(lib, case, E, combo, pattern):
-    """One ge2e_loss_fwd_bwd call on guarded buffers; returns the outputs that were asked for (numpy)."""
-    VAR, IMPL, _ = ids()
-    impl, B, N, M, D, variant = case
-    name, want_per, want_grad, misaligned = combo
-    what = f"{bc.case_id(case)}/{name}/fill {pattern:#04x}"
-    off = 1 if misaligned else 0          # the header promises 16-byte alignment for E and dE only
-    e, w, b = Buf(E.shape, E), Buf((1,), [bc.W]), Buf((1,), [bc.BIAS])
-    outs = {"loss": Buf((B,), offset=off)}
-    if want_per:
-        outs["per"] = Buf((B, N, M), offset=off)
-    if want_grad:
-        outs.update(dE=Buf(E.shape), dw=Buf((B,), offset=off), db=Buf((B,), offset=off))
-    if misaligned:
-        assert all(outs[k].ptr % 16 == 4 for k in ("loss", "per", "dw", "db")) and outs["dE"].ptr % 16 == 0
-    nbytes = int(lib.ge2e_workspace_bytes(B, N, M, D, VAR[variant], IMPL[impl]))     # for the REQUESTED impl, as a caller would
-    ws = Workspace(nbytes, pattern)
-    ok(lib.ge2e_workspace_init(ws.ptr, nbytes, None), what + " ge2e_workspace_init")
-    ptr = lambda k: outs[k].ptr if k in outs else None  # noqa: E731
-    code = lib.ge2e_loss_fwd_bwd(e.ptr, B, N, M, D, w.ptr, b.ptr, EPS_COS, EPS, VAR[variant], IMPL[impl], ptr("loss"),
-                                 ptr("per"), ptr("dE"), ptr("dw"), ptr("db"), ws.ptr, nbytes, None)
-    torch.cuda.synchronize()
-    ok(code, what + " ge2e_loss_fwd_bwd")
-    ws.check(what)
-    res = {k: v.get(f"{what} {k}") for k, v in outs.items()}        # guards intact, no NaN / inf left
-    for k, v in (("E", e), ("w", w), ("b", b)):
-        assert v.guards_intact(), f"{what}: guard of {k} overwritten"
-    assert same_bits(e.get(what + " E"), E), f"{what}: E was modified"
-    return res
-
 
 @pytest.mark.parametrize("case", bc.LOSS_CASES, ids=bc.case_id)
 def test_loss_between_guards_on_an_exact_workspace(lib, case):
@@ -125,7 +49,7 @@ def test_loss_between_guards_on_an_exact_workspace(lib, case):
         for k in o:
             assert same_bits(o[k], o0[k]), f"{what}: {k} depends on what the workspace held before the call"
         if "dE" in o:                      # per = NULL: its line of the gate has nothing to look at
-            check(o if "per" in o else dict(o, per=ref["per"]), ref, ran, what)
+            check_dense(o if "per" in o else dict(o, per=ref["per"]), ref, ran, what)
         else:
             check_forward(o, ref, ran, what)
         errs = {"loss": np.max(np.abs(o["loss"] - ref["loss"]) / np.maximum(np.abs(ref["loss"]), 1e-30))}

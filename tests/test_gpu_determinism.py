@@ -4,20 +4,12 @@ Guards against intra-kernel races / register hazards (one was found in the 8-wav
 ge2e_fused_split.hip).  Small N makes a single tile with many pad rows, the shape that exposed it."""
 import numpy as np
 import pytest
-import torch
 
+from capi import functional as GF  # noqa: F401
+from dense_harness import impls_for, run_hip
 from oracle import ge2e_oracle as orc
-from test_gpu_parity import run_hip, impls_for
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def GF():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from speaker_embedding_ge2e_loss_amd import functional
-    return functional
 
 
 @pytest.mark.parametrize("shape", [(1, 6, 10, 256), (3, 64, 10, 256), (2, 16, 8, 128), (1, 4, 16, 64),

@@ -20,6 +20,7 @@ import numpy as np
 import pytest
 import torch
 
+from capi import functional as GF  # noqa: F401
 from oracle import ge2e_oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -30,14 +31,6 @@ KINDS = ("unit", "raw", "clustered")
 WS = (10.0, -3.0, 200.0)
 VARIANTS = ("softmax", "contrast")
 GRID = 512          # the kernel's largest grid: more batches than this and the stride loop runs
-
-
-@pytest.fixture(scope="module")
-def GF():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from speaker_embedding_ge2e_loss_amd import functional
-    return functional
 
 
 def inputs64(shape, kind, seed):

@@ -4,20 +4,12 @@ import os
 
 import numpy as np
 import pytest
-import torch
 
+from capi import functional as GF  # noqa: F401
+from dense_harness import check_dense, impls_for, run_hip
 from oracle import ge2e_oracle as orc
-from test_gpu_parity import check, impls_for, run_hip
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def GF():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from speaker_embedding_ge2e_loss_amd import functional
-    return functional
 
 
 def cases(n, seed):
@@ -62,4 +54,4 @@ def test_random_shapes(GF, case):
         if resolved in seen and impl == "auto":
             continue
         seen.add(resolved)
-        check(run_hip(GF, E, w, b, variant, impl), ref, impl, f"{case}/{impl}->{resolved}")
+        check_dense(run_hip(GF, E, w, b, variant, impl), ref, impl, f"{case}/{impl}->{resolved}")

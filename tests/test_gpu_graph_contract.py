@@ -1,7 +1,7 @@
 """GE2ELoss(hp, graph=True) -- loss.py's _forward_graphed over graphed.StaticLossStep, the route the README recommends for a
 training step -- where its correctness depends on state kept across calls: the team kernel's control block under graph
 replay, the device the capture runs on, the autograd contract of the ``loss.backward()`` shortcut, and the default random
-generator.  Every number is held to the fp64 closed form (test_gpu_parity.check, strict); where bits are the claim, to the
+generator.  Every number is held to the fp64 closed form (dense_harness.check_dense, strict); where bits are the claim, to the
 eager module or an eager launch too -- never to the graph route alone."""
 import os
 import socket
@@ -10,30 +10,23 @@ import numpy as np
 import pytest
 import torch
 
+from capi import functional as GF  # noqa: F401
+from dense_harness import check_dense
 from oracle import ge2e_oracle as orc
-from test_gpu_parity import check
 
 pytestmark = pytest.mark.gpu
 
 CTL_BYTES = 2048        # sizeof(TeamCtl), csrc/ge2e_team.hpp: the control block at the head of a team workspace
 
 
-@pytest.fixture(scope="module")
-def GF():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from speaker_embedding_ge2e_loss_amd import functional
-    return functional
-
-
 def _fp64(E, w, b, impl, what, loss, dE=None, dw=None, db=None, per=None):
-    """check() against closed_form(E, w, b) in fp64, strict.  A route that does not produce a quantity (the graph route has no
+    """check_dense() against closed_form(E, w, b) in fp64, strict.  A route that does not produce a quantity (the graph route has no
     per-row losses; a forward-only launch no gradients; DDP keeps dE inside the encoder's backward) passes the oracle's own
     value for it, so that only what the route produced is under test."""
     ref = orc.closed_form(np.asarray(E, np.float64), float(w), float(b))
     cpu = lambda t, k: ref[k] if t is None else t.detach().double().cpu().numpy()  # noqa: E731
-    check({"loss": cpu(loss, "loss"), "per": cpu(per, "per"), "dE": cpu(dE, "dE"), "dw": cpu(dw, "dw"), "db": cpu(db, "db")},
-          ref, impl, what, strict=True)
+    check_dense({"loss": cpu(loss, "loss"), "per": cpu(per, "per"), "dE": cpu(dE, "dE"), "dw": cpu(dw, "dw"), "db": cpu(db, "db")},
+                ref, impl, what, strict=True)
 
 
 def _inputs(shape, seed, k):

@@ -17,6 +17,8 @@ import pytest
 import torch
 
 import helpers_ref as hr
+from capi import functional as GF  # noqa: F401
+from capi import ok
 from conftest import rel_fro
 from guarded import Buf, dev
 
@@ -26,21 +28,9 @@ ULP = 2.0 ** -24  # fp32 unit round-off
 
 
 @pytest.fixture(scope="module")
-def GF():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from speaker_embedding_ge2e_loss_amd import functional
-    return functional
-
-
-@pytest.fixture(scope="module")
 def lib(GF):
     from speaker_embedding_ge2e_loss_amd import _lib
     return _lib.load()
-
-
-def ok(code, what):
-    assert code == 0, f"{what} returned {code}"
 
 
 def grad_close(got, ref, what, floor=0.0, tol=1e-5):

@@ -8,11 +8,11 @@ of tests/guarded.py: inputs between NaN / sentinel guards, outputs poisoned, the
 ge2e_workspace_bytes_labeled (ge2e_label_index_workspace_bytes) bytes between guard bands, filled with 0xFF bytes in one run
 and 0x00 in another (the two must agree bit for bit), every guard intact afterwards.
 
-Gate: test_gpu_ragged.check, unchanged (the exact-fp32 row of test_gpu_parity.TOL through the formulas of that module's
+Gate: rowlist_harness.check_rows, unchanged (the exact-fp32 row of dense_harness.TOL through the formulas of that module's
 docstring): the arithmetic is the same kernel's.  Inputs: ragged_ref.ragged_inputs, seeded; w = 10, b = -5.
 
 How the shuffled cases are made: the LABELS of the sorted layout are permuted (seeded) and the rows are placed so that the
-stable sort of those labels brings back the sorted batch of test_gpu_ragged.case -- any interleaving of the speakers, one fp64
+stable sort of those labels brings back the sorted batch of rowlist_cases.case -- any interleaving of the speakers, one fp64
 reference per batch shared with tests/test_gpu_ragged.py.  (That the order IS the stable one is the index tests' business,
 where it is held to numpy exactly; the golden test shuffles rows with a plain permutation.)  `-s` prints every figure
 before it is asserted.
@@ -21,26 +21,13 @@ import numpy as np
 import pytest
 import torch
 
+from capi import GF, lib  # noqa: F401
 from conftest import golden_names, load_golden
-from guarded import Buf, IntBuf, Workspace
-from test_gpu_ragged import BIAS, DEV, EDGE, EPS, EPS_COS, VAR, VARIANTS, W, batch_of, case, check, offsets_of, same_bits
-from test_gpu_ragged import run as run_ragged
+from rowlist_cases import EDGE, case
+from rowlist_harness import BIAS, DEV, VARIANTS, W, batch_of, check_rows, offsets_of, run_index, run_ragged, same_bits
+from rowlist_harness import run_labeled as run
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def lib():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from speaker_embedding_ge2e_loss_amd import _lib
-    return _lib.load()
-
-
-@pytest.fixture(scope="module")
-def GF(lib):
-    from speaker_embedding_ge2e_loss_amd import functional
-    return functional
 
 
 # ---- references ----------------------------------------------------------------------------------------------------------------
@@ -54,7 +41,7 @@ def index_ref(labels, N):
 
 def shuffled(counts, D, seed, variant, sort=False):
     """One batch in shuffled row order: (E (R, D), labels (R,), order (R,), sorted E, its fp64 reference).  E[order] is the
-    sorted batch of test_gpu_ragged.case(counts, D, seed, variant) bit for bit.  `sort`: the labels stay sorted."""
+    sorted batch of rowlist_cases.case(counts, D, seed, variant) bit for bit.  `sort`: the labels stay sorted."""
     Es, ref = case(counts, D, seed, variant)
     lab = np.repeat(np.arange(len(counts)), counts).astype(np.int32)
     if not sort:
@@ -73,52 +60,6 @@ def scattered(ref, order):
         v[order] = ref[k]
         out[k] = v
     return out
-
-
-# ---- the calls -------------------------------------------------------------------------------------------------------------------
-def run_index(lib, labels, N, pattern=0xFF):
-    """One ge2e_label_index call on guarded buffers: labels (B, R) int32 -> (offsets (B, N+1), order (B, R))."""
-    labels = np.ascontiguousarray(labels, dtype=np.int32)
-    B, R = labels.shape
-    what = f"label_index B{B} N{N} R{R} fill {pattern:#04x}"
-    lab, off, order = IntBuf(labels.shape, labels), IntBuf((B, N + 1)), IntBuf((B, R))
-    nbytes = int(lib.ge2e_label_index_workspace_bytes(B, N, R))
-    assert nbytes % 256 == 0
-    ws = Workspace(nbytes, pattern)
-    code = lib.ge2e_label_index(lab.ptr, B, N, R, off.ptr, order.ptr, ws.ptr if nbytes else None, nbytes, None)
-    torch.cuda.synchronize()
-    assert code == 0, f"{what} returned {code}"
-    ws.check(what)
-    res = off.get(what + " offsets"), order.get(what + " order")
-    assert lab.guards_intact() and np.array_equal(lab.get(what + " labels", written=False), labels), f"{what}: labels modified"
-    return res
-
-
-def run(lib, E, labels, N, variant, want_grad=True, pattern=0xFF, w=W, b=BIAS, finite=True):
-    """One ge2e_loss_fwd_bwd_labeled call on guarded buffers.  E (B, R, D) float32, labels (B, R) int32 -> numpy outputs."""
-    E = np.ascontiguousarray(E, dtype=np.float32)
-    labels = np.ascontiguousarray(labels, dtype=np.int32)
-    B, R, D = E.shape
-    what = f"labeled B{B} N{N} R{R} D{D} {variant} {'fwd+bwd' if want_grad else 'fwd'} fill {pattern:#04x}"
-    e, lab, wb, bb = Buf(E.shape, E), IntBuf(labels.shape, labels), Buf((1,), [w]), Buf((1,), [b])
-    outs = {"loss": Buf((B,)), "per": Buf((B, R))}
-    if want_grad:
-        outs.update(dE=Buf(E.shape), dw=Buf((B,)), db=Buf((B,)))
-    nbytes = int(lib.ge2e_workspace_bytes_labeled(B, N, R, D, VAR[variant]))
-    assert nbytes > 0 and nbytes % 256 == 0
-    ws = Workspace(nbytes, pattern)
-    ptr = lambda k: outs[k].ptr if k in outs else None  # noqa: E731
-    code = lib.ge2e_loss_fwd_bwd_labeled(e.ptr, lab.ptr, B, N, R, D, wb.ptr, bb.ptr, EPS_COS, EPS, VAR[variant], ptr("loss"),
-                                         ptr("per"), ptr("dE"), ptr("dw"), ptr("db"), ws.ptr, nbytes, None)
-    torch.cuda.synchronize()
-    assert code == 0, f"{what} returned {code}"
-    ws.check(what)
-    res = {k: v.get(f"{what} {k}", finite=finite) for k, v in outs.items()}       # guards intact, no NaN poison left
-    for k, v in (("E", e), ("labels", lab), ("w", wb), ("b", bb)):
-        assert v.guards_intact(), f"{what}: guard of {k} overwritten"
-    assert same_bits(e.get(what + " E"), E), f"{what}: E was modified"
-    assert np.array_equal(lab.get(what + " labels", written=False), labels), f"{what}: the labels were modified"
-    return res
 
 
 # ---- 1. the index kernel: exact integer equality with numpy ----------------------------------------------------------------------
@@ -180,8 +121,8 @@ def test_edge_shapes_shuffled(lib, name, variant):
     for k in full:
         assert same_bits(full[k], zero[k]), f"{name}/{variant}: {k} depends on what the workspace held before the call"
     assert same_bits(fwd["loss"], full["loss"]) and same_bits(fwd["per"], full["per"]), f"{name}/{variant}: forward-only differs"
-    check(batch_of(full, 0), ref, f"{name}/{variant}")
-    check(batch_of(fwd, 0), ref, f"{name}/{variant}/fwd")
+    check_rows(batch_of(full, 0), ref, f"{name}/{variant}")
+    check_rows(batch_of(fwd, 0), ref, f"{name}/{variant}/fwd")
 
 
 # ---- 3. the same bits as the ragged entry on gathered rows ---------------------------------------------------------------------------
@@ -216,7 +157,7 @@ def test_batches_with_their_own_shuffles(lib, variant):
     again = run(lib, E, lab, 4, variant, True, 0x00)
     flipped = run(lib, E[::-1], lab[::-1], 4, variant, True, 0xFF)
     for i in range(3):
-        check(batch_of(a, i), scattered(cases[i][4], cases[i][2]), f"B3 batch {i} {counts[i]} {variant}")
+        check_rows(batch_of(a, i), scattered(cases[i][4], cases[i][2]), f"B3 batch {i} {counts[i]} {variant}")
     for k in a:
         assert same_bits(a[k], again[k]), f"{variant} {k}: two launches differ"
         for i in range(3):   # the batch at index 0 sits at index 2 of the flipped stack, and the other way round
@@ -231,7 +172,7 @@ def test_past_the_grid(lib, variant):
     E, lab = np.stack([c[0] for c in cases]), np.stack([c[1] for c in cases])
     o = run(lib, E, lab, 2, variant, True, 0xFF)
     for i in range(B):
-        check(batch_of(o, i), scattered(cases[i][4], cases[i][2]), f"B515 batch {i} {variant}", quiet=i % 103 != 0)
+        check_rows(batch_of(o, i), scattered(cases[i][4], cases[i][2]), f"B515 batch {i} {variant}", quiet=i % 103 != 0)
     fwd = run(lib, E, lab, 2, variant, False, 0x00)
     assert same_bits(fwd["loss"], o["loss"]) and same_bits(fwd["per"], o["per"])
 
@@ -254,7 +195,7 @@ def test_golden_vectors_shuffled(lib, name):
         assert np.abs(o["dE"] - ref["dE"]).max() <= 1e-5 * np.abs(ref["dE"]).max()
         assert np.allclose(o["loss"], ref["loss"], rtol=1e-5)
         return
-    check(o, ref, name, strict=True)
+    check_rows(o, ref, name, strict=True)
 
 
 # ---- 6. the clamp: labels that break the contract stay inside the buffers --------------------------------------------------------------
@@ -314,8 +255,8 @@ def test_python_surface(GF):
     assert raw.per.shape == (1, R) and raw.dE.shape == (1, R, D) and torch.equal(raw.loss[0], loss.detach())
     # (3 * loss).backward() against 3 x the fp64 reference; e.grad in the caller's row order
     three = {k: 3 * ref[k] for k in ("loss", "per", "dE", "dw", "db")}
-    check({"loss": 3 * loss.item(), "per": 3 * raw.per[0].cpu().numpy(), "dE": e.grad.cpu().numpy(), "dw": w.grad.item(),
-           "db": b.grad.item()}, three, "3 * ge2e_loss_labeled")
+    check_rows({"loss": 3 * loss.item(), "per": 3 * raw.per[0].cpu().numpy(), "dE": e.grad.cpu().numpy(), "dw": w.grad.item(),
+                "db": b.grad.item()}, three, "3 * ge2e_loss_labeled")
     # ... and it is the ragged function on the rows the caller sorts, with the gradient scattered back
     es = torch.as_tensor(E[order], device=dev).requires_grad_(True)
     ls = GF.ge2e_loss_ragged(es, counts, w.detach(), b.detach())
@@ -357,8 +298,8 @@ def test_python_surface(GF):
     (losses * torch.tensor(g, device=dev)).sum().backward()
     for i in range(3):
         r = scattered(cases[i][4], cases[i][2])
-        check({"loss": g[i] * losses[i].item(), "per": g[i] * r["per"], "dE": es.grad[i].cpu().numpy(), "dw": g[i] * r["dw"],
-               "db": g[i] * r["db"]}, {k: g[i] * r[k] for k in ("loss", "per", "dE", "dw", "db")}, f"stack batch {i}")
+        check_rows({"loss": g[i] * losses[i].item(), "per": g[i] * r["per"], "dE": es.grad[i].cpu().numpy(), "dw": g[i] * r["dw"],
+                    "db": g[i] * r["db"]}, {k: g[i] * r[k] for k in ("loss", "per", "dE", "dw", "db")}, f"stack batch {i}")
 
     # dtypes: bf16 in, bf16 out (computed in fp32 behind differentiable casts); fp64 is not silently cast down
     eb = torch.as_tensor(E, device=dev).bfloat16().requires_grad_(True)

@@ -12,7 +12,6 @@ Gates: max|cos - ref| <= 3e-6 on the entries that count -- the project's bound f
 with the float64 reference only for inputs whose reference cosines keep at least 1.2e-5 (four times the gate) from every
 threshold; each such test asserts that margin before anything is launched.  `-s` prints every figure before it is asserted.
 """
-import functools
 import os
 
 import numpy as np
@@ -20,10 +19,12 @@ import pytest
 import torch
 
 import labeled_eval_ref as ler
+from capi import GF, lib  # noqa: F401
 from conftest import golden_names, load_golden
-from guarded import Buf, IntBuf, Workspace
-from test_gpu_masked import INDEX_CASES, LOSS_CASES, draw, inputs
-from test_gpu_ragged import DEV, EPS, EPS_COS, same_bits
+from rowlist_cases import EDGE_CASES, INDEX_CASES, draw, edge_case, host_ids, inputs
+from rowlist_cases import cos_reference as reference
+from rowlist_harness import DEV, batch_of, run_counts, same_bits
+from rowlist_harness import run_cos as run
 
 pytestmark = pytest.mark.gpu
 
@@ -31,20 +32,6 @@ GATE = 3e-6
 MARGIN = 4 * GATE
 Z = np.load(os.path.join(os.path.dirname(__file__), "golden", "callers", "eer.npz"))
 EER_CASES = sorted({k.split(".")[0] for k in Z.files})
-
-
-@pytest.fixture(scope="module")
-def lib():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from speaker_embedding_ge2e_loss_amd import _lib
-    return _lib.load()
-
-
-@pytest.fixture(scope="module")
-def GF(lib):
-    from speaker_embedding_ge2e_loss_amd import functional
-    return functional
 
 
 def thresholds_of(kind):
@@ -55,66 +42,6 @@ def thresholds_of(kind):
     # its cosines stay 3.8e-5 and 4.0e-5 away from every entry (test_fused_counts asserts >= 1.2e-5 before it launches)
     t = np.sort(np.random.default_rng(30).uniform(-0.2, 1.0, 32))
     return np.sort(np.concatenate([t, t[11:12]]))
-
-
-# ---- the calls ---------------------------------------------------------------------------------------------------------------
-def run(lib, E, labels, N, thr=None, want_cos=True, pattern=0xFF, want_index=True):
-    """One ge2e_cos_sim_labeled call on guarded buffers.  E (B, R, D) float32 (rows that do not count may hold NaN), labels
-    (B, R) int32 -> dict of numpy outputs."""
-    E = np.ascontiguousarray(E, dtype=np.float32)
-    labels = np.ascontiguousarray(labels, dtype=np.int32)
-    B, R, D = E.shape
-    T = 0 if thr is None else len(thr)
-    what = f"cos_sim_labeled B{B} N{N} R{R} D{D} T{T} {'cos' if want_cos else 'no cos'} fill {pattern:#04x}"
-    e, lab = Buf(E.shape, E), IntBuf(labels.shape, labels)
-    th = Buf((T,), np.asarray(thr, dtype=np.float64).astype(np.float32)) if T else None
-    fouts, iouts = {}, {}
-    if want_cos:
-        fouts["cos"] = Buf((B, R, N))
-    if want_index:
-        iouts.update(col=IntBuf((B, R)), speakers=IntBuf((B, N)), active=IntBuf((B, 2)))
-    if T:
-        iouts["counts"] = IntBuf((B, T, 2))
-    nbytes = int(lib.ge2e_cos_sim_labeled_workspace_bytes(B, N, R, D))
-    assert nbytes > 0 and nbytes % 256 == 0
-    ws = Workspace(nbytes, pattern)
-    ptr = lambda d, k: d[k].ptr if k in d else None  # noqa: E731
-    code = lib.ge2e_cos_sim_labeled(e.ptr, lab.ptr, B, N, R, D, EPS_COS, EPS, th.ptr if T else None, T, ptr(fouts, "cos"),
-                                    ptr(iouts, "col"), ptr(iouts, "speakers"), ptr(iouts, "active"), ptr(iouts, "counts"),
-                                    ws.ptr, nbytes, None)
-    torch.cuda.synchronize()
-    assert code == 0, f"{what} returned {code}"
-    ws.check(what)
-    res = {k: v.get(f"{what} {k}") for k, v in fouts.items()}       # guards intact, every element written and finite
-    res.update({k: v.get(f"{what} {k}") for k, v in iouts.items()})  # ... no sentinel poison left
-    assert e.guards_intact() and lab.guards_intact() and (th is None or th.guards_intact()), f"{what}: an input's guard"
-    assert same_bits(e.get(what + " E", finite=False), E), f"{what}: E was modified"
-    assert np.array_equal(lab.get(what + " labels", written=False), labels), f"{what}: the labels were modified"
-    return res
-
-
-def run_counts(lib, sim, col, active, thr):
-    """One ge2e_eer_counts_labeled call on guarded buffers: sim (B, R, N) float32 of any content -> counts (B, T, 2)."""
-    sim = np.ascontiguousarray(sim, dtype=np.float32)
-    B, R, N = sim.shape
-    T = len(thr)
-    what = f"eer_counts_labeled B{B} N{N} R{R} T{T}"
-    s, c, a = Buf(sim.shape, sim), IntBuf((B, R), col), IntBuf((B, 2), active)
-    th = Buf((T,), np.asarray(thr, dtype=np.float64).astype(np.float32))
-    out = IntBuf((B, T, 2))
-    code = lib.ge2e_eer_counts_labeled(s.ptr, c.ptr, a.ptr, B, N, R, th.ptr, T, out.ptr, None)
-    torch.cuda.synchronize()
-    assert code == 0, f"{what} returned {code}"
-    got = out.get(what + " counts")
-    assert s.guards_intact() and c.guards_intact() and a.guards_intact() and th.guards_intact(), f"{what}: an input's guard"
-    assert same_bits(s.get(what + " sim", finite=False), sim), f"{what}: sim was modified"
-    return got
-
-
-def reference(E, labels, N):
-    """The float64 reference of one batch as a dict."""
-    cos, col, speakers, active = ler.cos_ref(E, labels, N)
-    return {"cos": cos, "col": col, "speakers": speakers, "active": active}
 
 
 def check(o, ref, what):
@@ -133,40 +60,12 @@ def check(o, ref, what):
         assert not rest.any() and not np.signbit(rest).any(), f"{what}: cos is not +0 where nothing counts"
 
 
-def batch_of(o, i):
-    return {k: v[i] for k, v in o.items()}
-
-
 def counts_of(cos, col, active, thr):
     """numpy's `>` on a call's own fp32 cos, per batch."""
     return np.stack([ler.counts_ref(cos[i], col[i], active[i][0], thr) for i in range(len(cos))])
 
 
 # ---- 1. edge shapes, with the rows that do not count (3.) and the fused counts on the call's own cos ----------------------------
-def _edge_cases():
-    rng = np.random.default_rng(67)
-    cases = {name: (labels, N, D) for name, (labels, N, D, _) in LOSS_CASES.items()}
-    cases["nact67_of_2_rows_D36"] = (np.repeat(np.arange(67), 2)[rng.permutation(134)].astype(np.int32), 67, 36)   # five column tiles
-    cases["D1"] = (draw(6, 20, 3, 1, 2, 61), 6, 1)
-    cases["D37_scalar_loads"] = (draw(10, 40, 4, 2, 3, 62), 10, 37)
-    cases["D260_past_the_held_rows"] = (draw(10, 40, 4, 2, 3, 63), 10, 260)     # vector loads, a partial 17th K step
-    return cases
-
-
-EDGE_CASES = _edge_cases()
-
-
-@functools.lru_cache(maxsize=None)
-def edge_case(name):
-    """(E, labels, N, float64 reference) of one batch: computed once, shared, read-only."""
-    labels, N, D = EDGE_CASES[name]
-    E = inputs(labels, N, D, 4000 + len(labels) + D)
-    ref = reference(E, labels, N)
-    for v in [E] + list(ref.values()):
-        v.setflags(write=False)
-    return E, labels, N, ref
-
-
 @pytest.mark.parametrize("name", list(EDGE_CASES))
 def test_edge_shapes(lib, name):
     E, labels, N, ref = edge_case(name)
@@ -346,12 +245,6 @@ def test_golden_fixtures(lib, name):
 
 
 # ---- 8. the Python surface -------------------------------------------------------------------------------------------------------
-def host_ids(labels, N, seed):
-    """Arbitrary host ids for dense labels: the valid ones keep their order, every other row a negative id of its own."""
-    ids = np.sort(np.random.default_rng(seed).choice(10 ** 6, size=N, replace=False))
-    return np.where((labels >= 0) & (labels < N), ids[np.clip(labels, 0, N - 1)], -1 - np.arange(len(labels)))
-
-
 def test_python_surface(GF):
     dev = torch.device(DEV)
     E, labels, N, ref = edge_case("nact17_of_N40_D36")

@@ -9,7 +9,7 @@ another (the two must agree bit for bit), guards intact and inputs unmodified af
 with NaN on every entry that must not be read (rows that are not active, columns >= n_act); E holds NaN on the rows that do
 not count.
 
-Gates are the project's own.  dE against fp64: test_gpu_ragged's gradient gate -- relative Frobenius norm <= GT = 1e-5 or
+Gates are the project's own.  dE against fp64: rowlist_harness.check_rows' gradient gate -- relative Frobenius norm <= GT = 1e-5 or
 max-abs <= 1e-8, and max-abs <= 4 GT max(1, max|ref|) -- and the same at factor 2 between two fp32 results.  per / loss /
 d_sim of calc_loss_labeled: the gates tests/test_gpu_helpers.py holds ge2e_calc_loss / _bwd to (per rtol 2e-4 atol 2e-5, loss
 rtol 2e-5 + 3e-7 sum|per| + 2e-7 rows, d_sim rel-Frobenius < 1e-5, and for one speaker with eps > 0, where d_sim vanishes by
@@ -24,89 +24,18 @@ import torch
 import labeled_grad_ref as lgr
 import masked_ref as mr
 import rowlist_cases as rc
+from capi import GF, lib  # noqa: F401
 from conftest import rel_fro
-from guarded import Buf, IntBuf, Workspace
-from test_gpu_labeled_eval import EDGE_CASES, host_ids
-from test_gpu_labeled_wide import run as run_wide
-from test_gpu_masked import LOSS_CASES, draw, inputs
-from test_gpu_ragged import BIAS, DEV, EPS, EPS_COS, GT, VAR, VARIANTS, W, check, same_bits
-from test_gpu_rowlist_inputs import two_part
+from rowlist_cases import EDGE_CASES, LOSS_CASES, draw, host_ids, inputs
+from rowlist_harness import (BIAS, DEV, EPS, EPS_COS, GT, VAR, VARIANTS, W, check_rows, run_bwd, run_calc, run_wide, same_bits,
+                             two_part)
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope="module")
-def lib():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from speaker_embedding_ge2e_loss_amd import _lib
-    return _lib.load()
-
-
-@pytest.fixture(scope="module")
-def GF(lib):
-    from speaker_embedding_ge2e_loss_amd import functional
-    return functional
-
-
-# ---- the calls ---------------------------------------------------------------------------------------------------------------
-def run_bwd(lib, E, labels, N, g_cos, pattern=0xFF, want_active=True, g_offset=0):
-    """One ge2e_cos_sim_labeled_bwd call on guarded buffers.  E (B, R, D) and g_cos (B, R, N) float32 (NaN where they must not be
-    read), labels (B, R) int32 -> {"dE", "active"}.  `g_offset`: g_cos starts that many floats past a 16-byte boundary."""
-    E = np.ascontiguousarray(E, dtype=np.float32)
-    g_cos = np.ascontiguousarray(g_cos, dtype=np.float32)
-    labels = np.ascontiguousarray(labels, dtype=np.int32)
-    B, R, D = E.shape
-    what = f"cos_sim_labeled_bwd B{B} N{N} R{R} D{D} fill {pattern:#04x} g_cos+{g_offset}"
-    e, lab, g = Buf(E.shape, E), IntBuf(labels.shape, labels), Buf(g_cos.shape, g_cos, offset=g_offset)
-    dE = Buf(E.shape)
-    act = IntBuf((B, 2)) if want_active else None
-    nbytes = int(lib.ge2e_cos_sim_labeled_bwd_workspace_bytes(B, N, R, D))
-    assert nbytes > 0 and nbytes % 256 == 0
-    ws = Workspace(nbytes, pattern)
-    code = lib.ge2e_cos_sim_labeled_bwd(e.ptr, lab.ptr, g.ptr, B, N, R, D, EPS_COS, dE.ptr, act.ptr if act else None, ws.ptr,
-                                        nbytes, None)
-    torch.cuda.synchronize()
-    assert code == 0, f"{what} returned {code}"
-    ws.check(what)
-    res = {"dE": dE.get(what + " dE")}                      # guards intact, every element written and finite
-    if act:
-        res["active"] = act.get(what + " active")
-    assert e.guards_intact() and lab.guards_intact() and g.guards_intact(), f"{what}: an input's guard"
-    assert same_bits(e.get(what + " E", finite=False), E), f"{what}: E was modified"
-    assert same_bits(g.get(what + " g_cos", finite=False), g_cos), f"{what}: g_cos was modified"
-    assert np.array_equal(lab.get(what + " labels", written=False), labels), f"{what}: the labels were modified"
-    return res
-
-
-def run_calc(lib, sim, col, active, eps, variant, gl=None, gp=None, want_loss=True):
-    """ge2e_calc_loss_labeled and ge2e_calc_loss_labeled_bwd on guarded buffers: sim (B, R, N) -> loss (B,), per (B, R), dS."""
-    sim = np.ascontiguousarray(sim, dtype=np.float32)
-    B, R, N = sim.shape
-    what = f"calc_loss_labeled B{B} N{N} R{R} {variant} eps {eps}"
-    s, c, a = Buf(sim.shape, sim), IntBuf((B, R), col), IntBuf((B, 2), active)
-    loss, per, dS = Buf((B,)), Buf((B, R)), Buf(sim.shape)
-    bl = Buf((B,), gl) if gl is not None else None
-    bp = Buf((B, R), gp) if gp is not None else None
-    code = lib.ge2e_calc_loss_labeled(s.ptr, c.ptr, a.ptr, B, N, R, eps, VAR[variant], loss.ptr if want_loss else None,
-                                      per.ptr, None)
-    assert code == 0, f"{what} returned {code}"
-    code = lib.ge2e_calc_loss_labeled_bwd(s.ptr, c.ptr, a.ptr, B, N, R, eps, VAR[variant], bl.ptr if bl else None,
-                                          bp.ptr if bp else None, dS.ptr, None)
-    torch.cuda.synchronize()
-    assert code == 0, f"{what} (backward) returned {code}"
-    out = {"per": per.get(what + " per"), "dS": dS.get(what + " d_sim")}        # every element written and finite
-    if want_loss:
-        out["loss"] = loss.get(what + " loss")
-    for v in (s, c, a, bl, bp):
-        assert v is None or v.guards_intact(), f"{what}: an input's guard"
-    assert same_bits(s.get(what + " sim", finite=False), sim), f"{what}: sim was modified"
-    return out
-
-
 # ---- gates -------------------------------------------------------------------------------------------------------------------
 def grad_gate(got, ref, what, factor=1.0):
-    """test_gpu_ragged.check's gate on dE."""
+    """rowlist_harness.check_rows' gate on dE."""
     ref = np.asarray(ref, np.float64)
     scale = max(1.0, float(np.abs(ref).max()))
     fro, mabs = rel_fro(got, ref), float(np.abs(got - ref).max())
@@ -400,8 +329,8 @@ def test_python_surface(GF, lib):
         for what, got in routes.items():
             assert got["active"].tolist() == idx["active"].tolist(), what
             assert got["loss"].shape == () and got["per"].shape == (R,) and got["dE"].shape == (R, D)
-            check(got, ref, f"[chain {variant}] {what} against masked_ref")
-            check(got, as_ref(wide), f"[chain {variant}] {what} against ge2e_loss_labeled(wide=True)", factor=2.0)
+            check_rows(got, ref, f"[chain {variant}] {what} against masked_ref")
+            check_rows(got, as_ref(wide), f"[chain {variant}] {what} against ge2e_loss_labeled(wide=True)", factor=2.0)
             assert plus_zero(got["dE"][~idx["active_row"]]) and plus_zero(got["per"][~idx["active_row"]])
 
 
@@ -442,8 +371,8 @@ def test_graph_capture_of_forward_and_backward(GF):
             assert torch.equal(got, want), f"replay differs from the eager calls: {k}"
         ref = mr.masked_loss(e.detach().cpu().numpy()[0], labels, N, W, BIAS)
         assert out[2][0].tolist() == ref["index"]["active"].tolist()
-        check({"loss": out[0][0].item(), "per": out[1][0].detach().cpu().numpy(), "dE": out[3][0].cpu().numpy(), "dw": out[4].item(),
-               "db": out[5].item()}, ref, f"replay with active {ref['index']['active'].tolist()}")
+        check_rows({"loss": out[0][0].item(), "per": out[1][0].detach().cpu().numpy(), "dE": out[3][0].cpu().numpy(), "dw": out[4].item(),
+                    "db": out[5].item()}, ref, f"replay with active {ref['index']['active'].tolist()}")
 
 
 # ---- 8. degenerate inputs ---------------------------------------------------------------------------------------------------------------
@@ -451,7 +380,7 @@ def test_graph_capture_of_forward_and_backward(GF):
 @pytest.mark.parametrize("kind", ["identical_rows", "zero_row"])
 def test_degenerate_rows_through_the_chain(GF, kind, variant):
     """Held as tests/test_gpu_rowlist_inputs.py holds these kinds: the clamped speaker's rows relative to the largest entry,
-    every other row at the ordinary bound (its `two_part`)."""
+    every other row at the ordinary bound (rowlist_harness.two_part)."""
     E, labels, N, ref, deg = rc.degenerate_case(kind, variant)
     idx = ref["index"]
     got = chain(GF, E, torch.as_tensor(labels, device=DEV), variant, num_speakers=N)

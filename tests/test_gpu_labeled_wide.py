@@ -8,9 +8,9 @@ tests/guarded.py: inputs between NaN / sentinel guards, outputs poisoned, the wo
 ge2e_workspace_bytes_labeled_wide bytes between guard bands, filled with 0xFF bytes in one run and 0x00 in another (the two
 must agree bit for bit), every guard intact afterwards, inputs unmodified.
 
-Gate: test_gpu_ragged.check, unchanged.  The agreement with ge2e_loss_fwd_bwd_labeled_masked on the same inputs is held to
+Gate: rowlist_harness.check_rows, unchanged.  The agreement with ge2e_loss_fwd_bwd_labeled_masked on the same inputs is held to
 factor=2 (two fp32 results are compared); a batch in which nothing counts is held to exact zeros.  Inputs:
-test_gpu_masked.inputs (unit rows centre[label] + 0.5 noise, seeded), w = 10, b = -5.  Every seeded draw is checked on the
+rowlist_cases.inputs (unit rows centre[label] + 0.5 noise, seeded), w = 10, b = -5.  Every seeded draw is checked on the
 numpy reference, before anything is launched, to hold what its case is named for.  `-s` prints every figure before it is
 asserted.
 """
@@ -20,80 +20,12 @@ import numpy as np
 import pytest
 import torch
 
-import masked_ref as mr
-from guarded import Buf, IntBuf, Workspace
-from test_gpu_masked import KEYS, LOSS_CASES, check_masked, draw, inputs, loss_case, mixed_draw
-from test_gpu_masked import run as run_masked
-from test_gpu_ragged import BIAS, DEV, EPS, EPS_COS, VAR, VARIANTS, W, batch_of, check, same_bits
+from capi import GF, lib  # noqa: F401
+from rowlist_cases import LOSS_CASES, draw, inputs, loss_case, mixed_draw, reference
+from rowlist_harness import BIAS, DEV, KEYS, VARIANTS, W, batch_of, check_masked, check_rows, poisoned, run_masked, same_bits
+from rowlist_harness import run_wide as run
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def lib():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from speaker_embedding_ge2e_loss_amd import _lib
-    return _lib.load()
-
-
-@pytest.fixture(scope="module")
-def GF(lib):
-    from speaker_embedding_ge2e_loss_amd import functional
-    return functional
-
-
-# ---- the call ------------------------------------------------------------------------------------------------------------------
-def run(lib, E, labels, N, variant, want_grad=True, pattern=0xFF, want_per=True, want_active=True, w=W, b=BIAS):
-    """One ge2e_loss_fwd_bwd_labeled_wide call on guarded buffers.  E (B, R, D) float32 (rows that do not count may hold
-    NaN or Inf), labels (B, R) int32 -> numpy outputs, `active` among them."""
-    E = np.ascontiguousarray(E, dtype=np.float32)
-    labels = np.ascontiguousarray(labels, dtype=np.int32)
-    B, R, D = E.shape
-    what = f"wide B{B} N{N} R{R} D{D} {variant} {'fwd+bwd' if want_grad else 'fwd'} fill {pattern:#04x}"
-    e, lab, wb, bb = Buf(E.shape, E), IntBuf(labels.shape, labels), Buf((1,), [w]), Buf((1,), [b])
-    outs = {"loss": Buf((B,))}
-    if want_per:
-        outs["per"] = Buf((B, R))
-    if want_grad:
-        outs.update(dE=Buf(E.shape), dw=Buf((B,)), db=Buf((B,)))
-    act = IntBuf((B, 2)) if want_active else None
-    nbytes = int(lib.ge2e_workspace_bytes_labeled_wide(B, N, R, D, VAR[variant]))
-    assert nbytes > 0 and nbytes % 256 == 0
-    ws = Workspace(nbytes, pattern)
-    ptr = lambda k: outs[k].ptr if k in outs else None  # noqa: E731
-    code = lib.ge2e_loss_fwd_bwd_labeled_wide(e.ptr, lab.ptr, B, N, R, D, wb.ptr, bb.ptr, EPS_COS, EPS, VAR[variant],
-                                              ptr("loss"), ptr("per"), ptr("dE"), ptr("dw"), ptr("db"),
-                                              act.ptr if act else None, ws.ptr, nbytes, None)
-    torch.cuda.synchronize()
-    assert code == 0, f"{what} returned {code}"
-    ws.check(what)
-    res = {k: v.get(f"{what} {k}") for k, v in outs.items()}       # guards intact, every element written and finite
-    if act:
-        res["active"] = act.get(what + " active")
-    for k, v in (("E", e), ("labels", lab), ("w", wb), ("b", bb)):
-        assert v.guards_intact(), f"{what}: guard of {k} overwritten"
-    assert same_bits(e.get(what + " E", finite=False), E), f"{what}: E was modified"
-    assert np.array_equal(lab.get(what + " labels", written=False), labels), f"{what}: the labels were modified"
-    return res
-
-
-def reference(E, labels, N, variant):
-    """The fp64 reference of one batch, finite and read-only, with the labels beside the index tables."""
-    ref = mr.masked_loss(E, labels, N, W, BIAS, variant=variant)
-    ref["index"]["labels"] = np.asarray(labels)
-    for k in KEYS:
-        assert np.isfinite(ref[k]).all()
-        ref[k].setflags(write=False)
-    return ref
-
-
-def poisoned(E, idx):
-    """E with NaN and +-Inf, in turn, on every row that does not count."""
-    bad = E.copy()
-    rest = np.flatnonzero(~idx["active_row"])
-    bad[rest] = np.array([np.nan, np.inf, -np.inf], dtype=np.float32)[np.arange(len(rest)) % 3][:, None]
-    return bad
 
 
 def whole_check(lib, E, labels, N, variant, ref, what, against_masked=True, noper=False):
@@ -125,8 +57,8 @@ def whole_check(lib, E, labels, N, variant, ref, what, against_masked=True, nope
             for k in KEYS:
                 assert same_bits(parent[k], full[k]), f"{what}: {k} is not the masked entry's zero"
         else:
-            check({k: full[k][0] for k in KEYS}, {k: parent[k][0].astype(np.float64) for k in KEYS},
-                  what + " vs the masked entry", factor=2)
+            check_rows({k: full[k][0] for k in KEYS}, {k: parent[k][0].astype(np.float64) for k in KEYS},
+                       what + " vs the masked entry", factor=2)
     return full
 
 
@@ -297,7 +229,7 @@ def test_python_surface(GF):
     rawm = GF.loss_fwd_bwd_labeled(em.detach(), lab32, wm.detach(), bm.detach(), num_speakers=N, need_per=True, masked=True)
     masked = {k: np.asarray(v, dtype=np.float64) for k, v in grads(em, wm, bm, lm, rawm.per[0].cpu().numpy()).items()}
     assert torch.equal(am, active)
-    check(got, masked, "wide vs masked=True", factor=2)
+    check_rows(got, masked, "wide vs masked=True", factor=2)
 
     # the module, with return_active
     mod = GE2ELoss(HParams(DEV))
@@ -318,7 +250,7 @@ def test_python_surface(GF):
     l2, a2 = GF.ge2e_loss_labeled(e2, lab64, w2, b2, num_speakers=N, wide=True, return_active=True)
     l2.backward()
     assert torch.equal(a2, active) and torch.equal(l2, loss) and torch.equal(e2.grad, e.grad)
-    check(grads(e2, w2, b2, l2, got["per"]), masked, "int64 labels vs masked=True", factor=2)
+    check_rows(grads(e2, w2, b2, l2, got["per"]), masked, "int64 labels vs masked=True", factor=2)
 
     # host labels with arbitrary ids, a lone speaker, negative ids on the rows to ignore
     ids = np.sort(np.random.default_rng(9).choice(10 ** 6, size=N, replace=False))
@@ -327,7 +259,7 @@ def test_python_surface(GF):
     l3, a3 = GF.ge2e_loss_labeled(e3, host, w3, b3, wide=True, return_active=True)
     l3.backward()
     assert torch.equal(a3, active)
-    check(grads(e3, w3, b3, l3, got["per"]), masked, "host labels vs masked=True", factor=2)
+    check_rows(grads(e3, w3, b3, l3, got["per"]), masked, "host labels vs masked=True", factor=2)
     check_masked(dict(grads(e3, w3, b3, l3, got["per"]), active=a3.cpu().numpy()), ref, "host labels")
     with pytest.raises(ValueError, match="masked=False"):
         GF.ge2e_loss_labeled(e3.detach(), host, w3.detach(), b3.detach(), wide=True, masked=False)

@@ -9,233 +9,26 @@ sentinel guards, outputs poisoned, the workspace exactly ge2e_workspace_bytes_la
 (ge2e_label_index_masked_workspace_bytes) bytes between guard bands, filled with 0xFF bytes in one run and 0x00 in another
 (the two must agree bit for bit), every guard intact afterwards, inputs unmodified.
 
-Gate: test_gpu_ragged.check, unchanged: the arithmetic is the same kernel's.  A batch in which nothing counts is held to
+Gate: rowlist_harness.check_rows, unchanged: the arithmetic is the same kernel's.  A batch in which nothing counts is held to
 exact zeros.  Inputs: unit rows centre[label] + 0.5 noise, seeded (rows that are ignored get a centre of their own);
 w = 10, b = -5.  Every seeded random draw is checked on the numpy reference, before anything is launched, to hold at least
 2 active speakers, a lone speaker, an absent speaker and an ignored row.  `-s` prints every figure before it is asserted.
 """
-import functools
-
 import numpy as np
 import pytest
 import torch
 
 import masked_ref as mr
-from guarded import Buf, IntBuf, Workspace
-from test_gpu_labeled import run as run_labeled
-from test_gpu_ragged import BIAS, DEV, EPS, EPS_COS, VAR, VARIANTS, W, batch_of, check, same_bits
-from test_gpu_ragged import run as run_ragged
+from capi import GF, lib  # noqa: F401
+from rowlist_cases import INDEX_CASES, LOSS_CASES, RANDOM_INDEX_CASES, draw, inputs, loss_case, mixed_draw
+from rowlist_harness import (BIAS, DEV, KEYS, VARIANTS, W, batch_of, check_masked, ragged_on_compacted, run_index, run_labeled,
+                             same_bits)
+from rowlist_harness import run_masked as run
 
 pytestmark = pytest.mark.gpu
 
-I32_MIN, I32_MAX = -2 ** 31, 2 ** 31 - 1
-KEYS = ("loss", "per", "dE", "dw", "db")
-
-
-@pytest.fixture(scope="module")
-def lib():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from speaker_embedding_ge2e_loss_amd import _lib
-    return _lib.load()
-
-
-@pytest.fixture(scope="module")
-def GF(lib):
-    from speaker_embedding_ge2e_loss_amd import functional
-    return functional
-
-
-# ---- inputs and references ---------------------------------------------------------------------------------------------------
-def inputs(labels, N, D, seed):
-    """Unit rows centre[class] + 0.5 noise, float32 (R, D); class = the label where 0 <= label < N, one more class otherwise."""
-    labels = np.asarray(labels, dtype=np.int64)
-    rng = np.random.default_rng(seed)
-    cls = np.where((labels >= 0) & (labels < N), labels, N)
-    centre = rng.standard_normal((N + 1, D))
-    x = centre[cls] + 0.5 * rng.standard_normal((len(labels), D))
-    x /= np.linalg.norm(x, axis=1, keepdims=True)
-    return np.ascontiguousarray(x, dtype=np.float32)
-
-
-def mixed_draw(idx, N):
-    """Whether a draw holds what every random case must: >= 2 active speakers, a lone one, an absent one, an ignored row."""
-    hist = np.bincount(idx["labels"][(idx["labels"] >= 0) & (idx["labels"] < N)], minlength=N)
-    return (idx["active"][0] >= 2 and bool((hist == 1).any()) and bool((hist == 0).any())
-            and bool(((idx["labels"] < 0) | (idx["labels"] >= N)).any()))
-
-
-def draw(N, R, n_active, n_lone, n_ignored, seed, spread=None):
-    """Seeded labels (R,): `n_active` speakers share the rows that are left (each >= 2), `n_lone` speakers have one row,
-    `n_ignored` rows carry labels outside [0, N); the speakers are drawn from range(N) (or from `spread`), rows shuffled."""
-    rng = np.random.default_rng(seed)
-    ids = rng.choice(N if spread is None else spread, size=n_active + n_lone, replace=False)
-    rows = R - n_lone - n_ignored
-    assert rows >= 2 * n_active and n_active + n_lone < N
-    counts = np.full(n_active, 2)
-    for _ in range(rows - 2 * n_active):
-        counts[rng.integers(n_active)] += 1
-    outside = rng.choice(np.array([-1, N, N + 5, -7, I32_MIN, I32_MAX]), size=n_ignored)
-    lab = np.concatenate([np.repeat(ids[:n_active], counts), ids[n_active:], outside])
-    return lab[rng.permutation(R)].astype(np.int32)
-
-
-def _loss_cases():
-    big = np.array([4] * 130 + [0, 1, 2, 6, -1, 8, 9], dtype=np.int32)           # one speaker of 130 rows among lone ones
-    return {
-        # name: (labels, N, D, random draw?)
-        "nact1_D5": (np.array([3, 1, 3, -1], dtype=np.int32), 5, 5, False),      # one pair, one lone row, one ignored row
-        "nact0": (np.array([0, 1, 2, -1, 7, 4, 3], dtype=np.int32), 4, 6, False),
-        "nact17_of_N40_D36": (draw(40, 75, 17, 4, 5, 1), 40, 36, True),
-        "ract33_in_R48": (draw(12, 48, 5, 6, 9, 2), 12, 20, True),
-        "ract32_in_R45": (draw(12, 45, 6, 4, 9, 3), 12, 16, True),
-        "one_of_130_among_lone_D8": (big[np.random.default_rng(4).permutation(len(big))], 8, 8, False),
-        "N1251_bound_R80": (draw(1251, 80, 23, 9, 6, 5), 1251, 16, True),
-    }
-
-
-LOSS_CASES = _loss_cases()
-
-
-@functools.lru_cache(maxsize=None)
-def loss_case(name, variant):
-    """(E, labels, N, fp64 reference) of one batch: computed once, shared, read-only."""
-    labels, N, D, random = LOSS_CASES[name]
-    E = inputs(labels, N, D, 4000 + len(labels) + D)
-    ref = mr.masked_loss(E, labels, N, W, BIAS, variant=variant)
-    ref["index"]["labels"] = labels
-    assert not random or mixed_draw(ref["index"], N), f"{name}: the draw does not hold every kind of row"
-    for v in [E] + [ref[k] for k in KEYS]:
-        assert np.isfinite(v).all()
-        v.setflags(write=False)
-    return E, labels, N, ref
-
-
-# ---- the calls ---------------------------------------------------------------------------------------------------------------
-def run_index(lib, labels, N, pattern=0xFF):
-    """One ge2e_label_index_masked call on guarded buffers: labels (B, R) int32 -> dict of offsets, order, speakers, active."""
-    labels = np.ascontiguousarray(labels, dtype=np.int32)
-    B, R = labels.shape
-    what = f"label_index_masked B{B} N{N} R{R} fill {pattern:#04x}"
-    lab = IntBuf(labels.shape, labels)
-    outs = {"offsets": IntBuf((B, N + 1)), "order": IntBuf((B, R)), "speakers": IntBuf((B, N)), "active": IntBuf((B, 2))}
-    nbytes = int(lib.ge2e_label_index_masked_workspace_bytes(B, N, R))
-    assert nbytes % 256 == 0
-    ws = Workspace(nbytes, pattern)
-    code = lib.ge2e_label_index_masked(lab.ptr, B, N, R, outs["offsets"].ptr, outs["order"].ptr, outs["speakers"].ptr,
-                                       outs["active"].ptr, ws.ptr if nbytes else None, nbytes, None)
-    torch.cuda.synchronize()
-    assert code == 0, f"{what} returned {code}"
-    ws.check(what)
-    res = {k: v.get(f"{what} {k}") for k, v in outs.items()}                  # guards intact, no sentinel poison left
-    assert lab.guards_intact() and np.array_equal(lab.get(what + " labels", written=False), labels), f"{what}: labels modified"
-    return res
-
-
-def run(lib, E, labels, N, variant, want_grad=True, pattern=0xFF, want_per=True, want_active=True, w=W, b=BIAS):
-    """One ge2e_loss_fwd_bwd_labeled_masked call on guarded buffers.  E (B, R, D) float32 (rows that do not count may hold
-    NaN), labels (B, R) int32 -> numpy outputs, `active` among them."""
-    E = np.ascontiguousarray(E, dtype=np.float32)
-    labels = np.ascontiguousarray(labels, dtype=np.int32)
-    B, R, D = E.shape
-    what = f"masked B{B} N{N} R{R} D{D} {variant} {'fwd+bwd' if want_grad else 'fwd'} fill {pattern:#04x}"
-    e, lab, wb, bb = Buf(E.shape, E), IntBuf(labels.shape, labels), Buf((1,), [w]), Buf((1,), [b])
-    outs = {"loss": Buf((B,))}
-    if want_per:
-        outs["per"] = Buf((B, R))
-    if want_grad:
-        outs.update(dE=Buf(E.shape), dw=Buf((B,)), db=Buf((B,)))
-    act = IntBuf((B, 2)) if want_active else None
-    nbytes = int(lib.ge2e_workspace_bytes_labeled_masked(B, N, R, D, VAR[variant]))
-    assert nbytes > 0 and nbytes % 256 == 0
-    ws = Workspace(nbytes, pattern)
-    ptr = lambda k: outs[k].ptr if k in outs else None  # noqa: E731
-    code = lib.ge2e_loss_fwd_bwd_labeled_masked(e.ptr, lab.ptr, B, N, R, D, wb.ptr, bb.ptr, EPS_COS, EPS, VAR[variant],
-                                                ptr("loss"), ptr("per"), ptr("dE"), ptr("dw"), ptr("db"),
-                                                act.ptr if act else None, ws.ptr, nbytes, None)
-    torch.cuda.synchronize()
-    assert code == 0, f"{what} returned {code}"
-    ws.check(what)
-    res = {k: v.get(f"{what} {k}") for k, v in outs.items()}       # guards intact, every element written and finite
-    if act:
-        res["active"] = act.get(what + " active")
-    for k, v in (("E", e), ("labels", lab), ("w", wb), ("b", bb)):
-        assert v.guards_intact(), f"{what}: guard of {k} overwritten"
-    assert same_bits(e.get(what + " E", finite=False), E), f"{what}: E was modified"
-    assert np.array_equal(lab.get(what + " labels", written=False), labels), f"{what}: the labels were modified"
-    return res
-
-
-def is_zero(a, plus):
-    a = np.atleast_1d(np.asarray(a))
-    return not a.any() and not (plus and np.signbit(a).any())
-
-
-def check_masked(o, ref, what, quiet=False, plus=True):
-    """One batch against masked_ref: `active` exactly, the rows that do not count exactly 0, and test_gpu_ragged.check.
-    `plus`: the zeros are +0, as the kernel writes them (False where autograd has scaled them by a negative gradient)."""
-    idx = ref["index"]
-    if "active" in o:
-        assert o["active"].tolist() == idx["active"].tolist(), f"{what}: active {o['active']} vs {idx['active']}"
-    rest = ~idx["active_row"]
-    for k in ("per", "dE"):
-        if k in o:
-            assert is_zero(o[k][rest], plus), f"{what}: {k} is not 0 on a row that does not count"
-    if idx["active"][0] == 0:
-        for k in KEYS:
-            if k in o:
-                assert is_zero(o[k], plus), f"{what}: {k} is not 0 though nothing counts"
-        return
-    check({k: o[k] for k in KEYS if k in o}, ref, what, quiet=quiet)
-
-
-def ragged_on_compacted(lib, E, ref, variant, w=W, b=BIAS):
-    """ge2e_loss_fwd_bwd_ragged on the rows that count, per and dE scattered back (zeros elsewhere): what the masked call
-    must return bit for bit."""
-    idx = ref["index"]
-    n_act, r_act = (int(v) for v in idx["active"])
-    rows = idx["order"][:r_act]
-    want = run_ragged(lib, np.ascontiguousarray(E[rows])[None], idx["offsets"][:n_act + 1][None], variant, True, 0xFF, w=w, b=b)
-    out = {k: want[k] for k in ("loss", "dw", "db")}
-    for k in ("per", "dE"):
-        back = np.zeros((1,) + E.shape[:1] + want[k].shape[2:], dtype=np.float32)
-        back[0, rows] = want[k][0]
-        out[k] = back
-    return out
-
 
 # ---- 1. the index kernel: exact integer equality with numpy ----------------------------------------------------------------
-def _index_cases():
-    rng = np.random.default_rng(21)
-    n600 = np.concatenate([np.repeat([0, 255, 256, 511, 512, 599], [2, 3, 2, 4, 2, 3]), [1, 254, 257, 510, 513, 598, 600, -1]])
-    # runs of ignored rows across the 256-row chunks and the 64-row waves, valid rows of 3 speakers in between
-    runs = rng.integers(0, 3, 2500)
-    for lo, hi in ((60, 70), (250, 262), (500, 520), (700, 1100), (1279, 1281), (1530, 1800), (2490, 2500)):
-        runs[lo:hi] = rng.choice([-1, 3, I32_MAX], size=hi - lo)
-    # the second batch: nine lone speakers and 31 labels outside the bound, nothing counts
-    b3 = np.stack([draw(9, 40, 3, 2, 4, 31), np.concatenate([np.arange(9), 9 + np.arange(31) % 9]), draw(9, 40, 1, 5, 7, 32)])
-    return {
-        "every_row_ignored": (4, np.array([[-1, 4, 100, -1, I32_MIN, 4, I32_MAX]])),
-        "every_speaker_lone": (8, rng.permutation(8)[None]),
-        "wild_values_among_valid": (5, np.array([[2, -1, 0, 5, I32_MIN, 2, I32_MAX, 0, 4, 2, 5, -1, 3, 3]])),
-        "N1": (1, np.array([[0, 0, -1, 0, 1]])),
-        "N1_lone": (1, np.array([[1, 0, -1]])),
-        "R1": (3, np.array([[2]])),
-        "N600_across_the_scan_rounds": (600, n600[rng.permutation(len(n600))][None]),
-        "N1100_R300": (1100, draw(1100, 300, 40, 60, 30, 22)[None]),           # counters in the workspace, most absent
-        "N5000_R64": (5000, draw(5000, 64, 11, 20, 9, 23)[None]),
-        "R2500_ignored_runs": (3, runs[None]),
-        "B3_own_nact_one_empty": (9, b3),
-        "B515_past_the_grid": (3, rng.integers(-1, 4, (515, 7))),
-        "B3_N1100": (1100, np.stack([draw(1100, 90, 10 * i + 1, 7, 5, 24 + i) for i in range(3)])),
-    }
-
-
-INDEX_CASES = _index_cases()
-# the batches of the seeded random cases that are drawn to hold >= 2 active speakers, a lone one, an absent one, an ignored row
-RANDOM_INDEX_CASES = {"N1100_R300": (0,), "N5000_R64": (0,), "B3_own_nact_one_empty": (0,), "B3_N1100": (1, 2)}
-
-
 @pytest.mark.parametrize("name", list(INDEX_CASES))
 def test_label_index_masked_is_the_numpy_reference(lib, name):
     N, labels = INDEX_CASES[name]
@@ -255,16 +48,16 @@ def test_label_index_masked_is_the_numpy_reference(lib, name):
     if name == "B515_past_the_grid":
         hist = np.stack([np.bincount(row[(row >= 0) & (row < N)], minlength=N) for row in labels])
         assert (ref["active"][:, 0] >= 2).any() and (hist == 1).any() and (hist == 0).any() and (labels < 0).any() and (labels >= N).any()
-    got = run_index(lib, labels, N, 0xFF)
+    got = run_index(lib, labels, N, 0xFF, masked=True)
     print(f"{name}: B {B} N {N} R {R} active {ref['active'][:4].tolist()}: " +
           ", ".join(f"{k} differs at {int((got[k] != ref[k]).sum())}" for k in ref))
     for k in ref:
         assert np.array_equal(got[k], ref[k]), f"{name}: {k}"
-    again = run_index(lib, labels, N, 0x00)
+    again = run_index(lib, labels, N, 0x00, masked=True)
     for k in ref:
         assert np.array_equal(got[k], again[k]), f"{name}: {k}: two launches differ"
     if B > 1:     # the batch at index i sits at index B-1-i of the flipped stack
-        flipped = run_index(lib, labels[::-1], N, 0xFF)
+        flipped = run_index(lib, labels[::-1], N, 0xFF, masked=True)
         for k in ref:
             assert np.array_equal(flipped[k][::-1], got[k]), f"{name}: {k}: a batch depends on its position"
 
@@ -358,7 +151,7 @@ def test_position_independence_in_a_stack_of_601(lib):
         assert np.array_equal(o[k][0].view(np.uint32), o[k][600].view(np.uint32)), f"{k}: position 0 and 600 differ"
     for i in (0, 5, 99, 300, 511, 512, 600):
         check_masked(batch_of(o, i), mr.masked_loss(E[i], labels[i], N, W, BIAS), f"B601 batch {i}")
-    ind = run_index(lib, labels, N)
+    ind = run_index(lib, labels, N, masked=True)
     for k in ind:
         assert np.array_equal(ind[k][0], ind[k][600]), f"index {k}: position 0 and 600 differ"
     assert np.array_equal(ind["active"], o["active"])

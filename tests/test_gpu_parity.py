@@ -9,81 +9,12 @@ import numpy as np
 import pytest
 import torch
 
+from capi import functional as GF  # noqa: F401
 from conftest import golden_names, load_golden, rel_fro
+from dense_harness import check_dense, impls_for, run_hip
 from oracle import ge2e_oracle as orc
 
 pytestmark = pytest.mark.gpu
-
-TOL = {  # impl -> (loss rtol, dE rel-fro / relative max-abs, dw rtol, cos atol)
-    "generic": (5e-6, 1e-5, 2e-5, 2e-6),
-    "fused_f32": (5e-6, 1e-5, 2e-5, 2e-6),
-    "fused_split": (2e-5, 2e-5, 5e-5, 5e-6),
-    "tiled": (2e-5, 2e-5, 5e-5, 5e-6),
-    "team": (2e-5, 2e-5, 5e-5, 5e-6),
-    "wave": (5e-6, 1e-5, 2e-5, 2e-6),
-    "auto": (1e-4, 1e-4, 1e-4, 1e-5),
-}
-
-
-@pytest.fixture(scope="module")
-def GF():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from speaker_embedding_ge2e_loss_amd import functional
-    return functional
-
-
-def impls_for(GF, B, N, M, D, variant="softmax"):
-    out = []
-    for name in ("generic", "fused_f32", "fused_split", "tiled", "team", "wave"):
-        try:
-            GF.resolve_impl(B, N, M, D, variant, name)
-            out.append(name)
-        except RuntimeError:
-            pass
-    assert out, "no implementation accepts this shape"
-    return out + ["auto"]
-
-
-def run_hip(GF, E, w, b, variant="softmax", impl="auto", eps=1e-6):
-    dev = torch.device("cuda:0")
-    e = torch.as_tensor(E, device=dev)
-    wt = torch.tensor(float(w), device=dev)
-    bt = torch.tensor(float(b), device=dev)
-    # poison every output first: a kernel that skips rows must not pass on stale allocator memory
-    shp = tuple(e.shape) if e.dim() == 4 else (1,) + tuple(e.shape)
-    nan = lambda *s: torch.full(s, float("nan"), device=dev)  # noqa: E731
-    out = GF.LossOutputs(loss=nan(shp[0]), per=nan(*shp[:3]), dE=nan(*shp), dw=nan(shp[0]), db=nan(shp[0]))
-    o = GF.loss_fwd_bwd(e, wt, bt, variant=variant, impl=impl, eps=eps, out=out)
-    torch.cuda.synchronize()
-    squeeze = (lambda t: t[0]) if e.dim() == 3 else (lambda t: t)
-    return {k: squeeze(getattr(o, k)).cpu().numpy() for k in ("loss", "per", "dE", "dw", "db")}
-
-
-def check(o, ref, impl, what="", strict=False):
-    """strict = the BASELINE configs and the reference's own fixtures: the stated gate with no per-row floors --
-    db atol 1e-4 flat, dw rtol + 1e-5.  The floors that scale with the row count are for fuzz / ragged shapes only, where
-    dw and db are sums of thousands of terms of both signs that cancel to ~0."""
-    lt, gt, wt, _ = TOL[impl]
-    loss_ref = np.asarray(ref["loss"], np.float64)
-    # loss is a sum of NM terms of size ~|S|: fp32 noise floor scales with that, not with |loss|
-    floor = 3e-7 * np.abs(np.asarray(ref["per"], np.float64)).sum(axis=(-1, -2))
-    nm = int(np.prod(np.asarray(ref["per"]).shape[-2:]))   # rows per batch: an absolute fp32 floor per row (log(1 + tiny) at N = 1)
-    assert np.all(np.abs(o["loss"] - loss_ref) <= lt * np.abs(loss_ref) + floor + 1e-6 + 2e-7 * nm), \
-        f"{what} loss {o['loss']} vs {loss_ref}"
-    assert np.allclose(o["per"], ref["per"], rtol=20 * lt, atol=2e-5), f"{what} per"
-    scale = max(1.0, float(np.abs(ref["dE"]).max()))
-    # (a gradient that vanishes -- one speaker: p_jj = 1 - O(eps) -- is held to an absolute bound instead)
-    assert rel_fro(o["dE"], ref["dE"]) <= gt or np.abs(o["dE"] - ref["dE"]).max() <= 1e-8, \
-        f"{what} dE rel-fro {rel_fro(o['dE'], ref['dE'])}"
-    assert np.abs(o["dE"] - ref["dE"]).max() <= 4 * gt * scale, f"{what} dE max-abs"
-    dw_ref = np.asarray(ref["dw"], np.float64)
-    # dw = sum G (cos + eps) cancels when the rows' terms have both signs: an absolute floor per row beside the relative bound
-    rowfloor = 0.0 if strict else 1.0
-    assert np.all(np.abs(o["dw"] - dw_ref) <= wt * np.abs(dw_ref) + 1e-5 + 1e-7 * nm * rowfloor), f"{what} dw {o['dw']} vs {dw_ref}"
-    # db cancels row by row: an fp32 floor per row -- for the non-BASELINE shapes only
-    assert np.allclose(o["db"], ref["db"], rtol=0, atol=1e-4 + 3e-7 * nm * rowfloor), f"{what} db {o['db']} vs {ref['db']}"
-
 
 @pytest.mark.parametrize("name", golden_names())
 def test_golden_vectors(GF, name):
@@ -98,7 +29,7 @@ def test_golden_vectors(GF, name):
             assert np.abs(o["dE"] - ref["dE"]).max() <= 1e-5 * np.abs(ref["dE"]).max()
             assert np.allclose(o["loss"], ref["loss"], rtol=1e-5)
             continue
-        check(o, ref, impl, f"{name}/{impl}", strict=True)
+        check_dense(o, ref, impl, f"{name}/{impl}", strict=True)
         # and against the reference's own fp32 run, at the north-star tolerance
         assert np.allclose(o["loss"], g["loss"], rtol=1e-4, atol=1e-5)
         assert rel_fro(o["dE"], g["dE"]) <= 1e-4
@@ -119,7 +50,7 @@ def test_baseline_configs_vs_oracle(GF, cfg, kind):
     E = orc.synth_embeddings((B, N, M, D), kind, seed=1234)
     ref = orc.closed_form(E, 10.0, -5.0, variant=variant)
     for impl in impls_for(GF, B, N, M, D, variant):
-        check(run_hip(GF, E, 10.0, -5.0, variant, impl), ref, impl, f"{cfg}/{kind}/{impl}", strict=True)
+        check_dense(run_hip(GF, E, 10.0, -5.0, variant, impl), ref, impl, f"{cfg}/{kind}/{impl}", strict=True)
 
 
 def test_config5_large(GF):
@@ -128,7 +59,7 @@ def test_config5_large(GF):
     E = orc.synth_embeddings((B, N, M, D), "clustered", seed=5)
     ref = orc.closed_form(E, 10.0, -5.0)
     o = run_hip(GF, E, 10.0, -5.0, impl="auto")
-    check(o, ref, "auto", "cfg5", strict=True)
+    check_dense(o, ref, "auto", "cfg5", strict=True)
 
 
 def test_config5_benched_launch_sampled(GF):
@@ -146,8 +77,8 @@ def test_config5_benched_launch_sampled(GF):
     assert bool(torch.isfinite(o.loss).all()) and bool(torch.isfinite(o.dE).all())
     for i in (0, B // 2 - 1, B - 1):
         ref = orc.closed_form(e[i].cpu().numpy(), 10.0, -5.0)
-        check({k: getattr(o, k)[i].cpu().numpy() for k in ("loss", "per", "dE", "dw", "db")}, ref, "auto", f"cfg5 B={B} batch {i}",
-              strict=True)
+        check_dense({k: getattr(o, k)[i].cpu().numpy() for k in ("loss", "per", "dE", "dw", "db")}, ref, "auto", f"cfg5 B={B} batch {i}",
+                    strict=True)
 
 
 @pytest.mark.parametrize("shape", [(2, 1, 2, 1), (1, 2, 2, 3), (3, 5, 3, 7), (2, 7, 4, 65), (1, 65, 2, 33),
@@ -176,7 +107,7 @@ def test_ragged_shapes(GF, shape, variant):
     if shape[3] % 8 == 0 and (shape[1] > 64 or shape[3] > 256):
         assert "tiled" in impls and GF.resolve_impl(*shape, variant, "auto") == "tiled", impls
     for impl in impls:
-        check(run_hip(GF, E, 7.5, -2.0, variant, impl), ref, impl, f"{shape}/{variant}/{impl}")
+        check_dense(run_hip(GF, E, 7.5, -2.0, variant, impl), ref, impl, f"{shape}/{variant}/{impl}")
 
 
 @pytest.mark.parametrize("w,b", [(-3.0, 0.5), (0.0, 1.0), (1.0, 0.0), (40.0, -20.0)])
@@ -185,7 +116,7 @@ def test_w_b_values_no_clamp(GF, w, b):
     E = orc.synth_embeddings((2, 12, 5, 96), "unit", seed=3)
     ref = orc.closed_form(E, w, b)
     for impl in impls_for(GF, 2, 12, 5, 96):
-        check(run_hip(GF, E, w, b, impl=impl), ref, impl, f"w={w}")
+        check_dense(run_hip(GF, E, w, b, impl=impl), ref, impl, f"w={w}")
 
 
 def test_large_w_stays_finite(GF):
@@ -414,7 +345,7 @@ def test_tiled_more_than_64_utterances_per_speaker(GF, variant):
     B, N, M, D = 3, 130, 70, 128
     E = orc.synth_embeddings((B, N, M, D), "unit", seed=70)
     ref = orc.closed_form(E, 9.0, -4.0, variant=variant)
-    check(run_hip(GF, E, 9.0, -4.0, variant, "tiled"), ref, "tiled", f"M=70 {variant}")
+    check_dense(run_hip(GF, E, 9.0, -4.0, variant, "tiled"), ref, "tiled", f"M=70 {variant}")
 
 
 def test_cos_sim_through_the_walked_dma_tiles(GF):
@@ -445,7 +376,7 @@ def test_tiled_fused_similarity_and_row_pass(GF, shape, variant):
     B, N, M, D = shape
     E = orc.synth_embeddings(shape, "raw", seed=N + M)
     ref = orc.closed_form(E, 7.5, -2.0, variant=variant)
-    check(run_hip(GF, E, 7.5, -2.0, variant, "tiled"), ref, "tiled", f"{shape}/{variant}")
+    check_dense(run_hip(GF, E, 7.5, -2.0, variant, "tiled"), ref, "tiled", f"{shape}/{variant}")
     # forward only (dE = NULL) through the same kernel
     dev = torch.device("cuda:0")
     e = torch.as_tensor(E, device=dev)
@@ -467,7 +398,7 @@ def test_tiled_dma_contractions_at_ragged_tile_edges(GF, variant):
     o = run_hip(GF, E, 7.5, -2.0, variant, "tiled")
     for i in (0, 23, 47):
         ref = orc.closed_form(E[i], 7.5, -2.0, variant=variant)
-        check({k: v[i] for k, v in o.items()}, ref, "tiled", f"dma ragged {variant} batch {i}")
+        check_dense({k: v[i] for k, v in o.items()}, ref, "tiled", f"dma ragged {variant} batch {i}")
 
 
 @pytest.mark.parametrize("shape", [(64, 10, 256), (4, 5, 256), (3, 64, 10, 256)])

@@ -2,8 +2,8 @@
 
 bounds_cases.PLAN_CASES has one entry per kernel name ("atom") the other tables miss (tests/test_plan_cases.py keeps the
 four tables' union equal to ge2e_plan_atoms on the CPU).  Each entry runs through the implementation it names and is
-compared with oracle.closed_form in fp64 by test_gpu_parity.check(strict=False) at that implementation's row of
-test_gpu_parity.TOL; forward-only entries (team_fwd) are held to the loss and per lines of that gate.  Every case first asks
+compared with oracle.closed_form in fp64 by dense_harness.check_dense(strict=False) at that implementation's row of
+dense_harness.TOL; forward-only entries (team_fwd) are held to the loss and per lines of that gate.  Every case first asks
 ge2e_loss_plan ON THIS MACHINE and requires the atom in the answer, so it cannot pass by running another kernel.
 
 Small entries (B N M D <= 6e6: every team, team_fwd and fused entry) take the route of tests/test_gpu_bounds.py: the
@@ -25,20 +25,12 @@ import pytest
 import torch
 
 import bounds_cases as bc
+from capi import lib  # noqa: F401
+from dense_harness import FILLS, PLANS_JSON, TOL, call_loss, check_dense, check_forward, current_plans
+from guarded import same_bits
 from oracle import ge2e_oracle as orc
-from test_gpu_bounds import FILLS, call_loss, check_forward, same_bits
-from test_gpu_parity import TOL, check
-from test_plan_cases import PLANS_JSON, current_plans
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def lib():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from speaker_embedding_ge2e_loss_amd import _lib
-    return _lib.load()
 
 
 def errors(o, ref):
@@ -62,7 +54,7 @@ def run_small(lib, case):
     assert set(o) == ({"loss", "per", "dE", "dw", "db"} if grad else {"loss", "per"})
     print(f"{bc.plan_id(case)}: {errors(o, ref)}   TOL[{impl}] = {TOL[impl]}")
     if grad:
-        check(o, ref, impl, atom, strict=False)
+        check_dense(o, ref, impl, atom, strict=False)
     else:
         check_forward(o, ref, impl, atom)
 
@@ -87,7 +79,7 @@ def run_on_device_inputs(case):
         assert np.isfinite(ref[k]).all(), f"{atom}: reference {k}"
     print(f"{bc.plan_id(case)}: {errors(got, ref)}   TOL[{impl}] = {TOL[impl]}")
     for i in range(B):                                  # every batch
-        check({k: v[i] for k, v in got.items()}, {k: ref[k][i] for k in got}, impl, f"{atom} batch {i}", strict=False)
+        check_dense({k: v[i] for k, v in got.items()}, {k: ref[k][i] for k in got}, impl, f"{atom} batch {i}", strict=False)
 
 
 @pytest.mark.parametrize("case", bc.PLAN_CASES, ids=bc.plan_id)

@@ -5,7 +5,7 @@ without a GPU, to reach every instantiation of the wide rows kernel, every cut o
 speakers.
 
 Reference, never the code under test: tests/masked_ref.py (torch autograd in float64).  Every C call goes through the
-guarded buffers of tests/guarded.py.  Gate: test_gpu_ragged.check, unchanged, through test_gpu_masked.check_masked; the
+guarded buffers of tests/guarded.py.  Gate: rowlist_harness.check_rows, unchanged, through rowlist_harness.check_masked; the
 wide entry against the masked one at factor 2 (two fp32 results); the masked entry against the ragged one bit for bit.
 A batch of a contrast case that falls under the tie rule of test_gpu_fuzz.py (rowlist_cases.ties) skips its dE / dw / db
 comparisons only, never the forward.  `-s` prints every figure before it is asserted; profiles/rowlist_inputs_gate.txt
@@ -15,14 +15,10 @@ import os
 
 import numpy as np
 import pytest
-import torch
 
 import rowlist_cases as rc
-from test_gpu_labeled_wide import poisoned
-from test_gpu_labeled_wide import run as run_wide
-from test_gpu_masked import KEYS, check_masked, ragged_on_compacted
-from test_gpu_masked import run as run_masked
-from test_gpu_ragged import batch_of, check, same_bits
+from capi import lib  # noqa: F401
+from rowlist_harness import KEYS, batch_of, check_masked, check_rows, poisoned, ragged_on_compacted, run_masked, run_wide, same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -30,14 +26,6 @@ pytestmark = pytest.mark.gpu
 # suite runs and what tests/test_rowlist_cases.py checks)
 CASES = rc.cases(int(os.environ.get("GE2E_ROWLIST_FUZZ_N", rc.N_DEFAULT)), int(os.environ.get("GE2E_ROWLIST_FUZZ_SEED", rc.SEED_DEFAULT)))
 FORWARD = ("loss", "per", "active")
-
-
-@pytest.fixture(scope="module")
-def lib():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from speaker_embedding_ge2e_loss_amd import _lib
-    return _lib.load()
 
 
 @pytest.mark.parametrize("case", CASES, ids=rc.case_id)
@@ -68,8 +56,8 @@ def test_random_row_lists(lib, case):
         o_wide, o_masked = ({k: batch_of(o, i)[k] for k in keep} for o in (full, masked))
         check_masked(o_wide, refs[i], f"[fuzz wide] {name} batch {i}")
         check_masked(o_masked, refs[i], f"[fuzz masked] {name} batch {i}")
-        check({k: o_wide[k] for k in keep if k != "active"}, {k: np.asarray(o_masked[k], np.float64) for k in keep if k != "active"},
-              f"[fuzz wide-vs-masked] {name} batch {i}", factor=2)
+        check_rows({k: o_wide[k] for k in keep if k != "active"}, {k: np.asarray(o_masked[k], np.float64) for k in keep if k != "active"},
+                   f"[fuzz wide-vs-masked] {name} batch {i}", factor=2)
         want = ragged_on_compacted(lib, E[i], refs[i], variant, w=w, b=b)
         for k in KEYS:
             assert same_bits(masked[k][i:i + 1], want[k]), f"{name} batch {i}: masked {k} is not the ragged entry's on the compacted batch"

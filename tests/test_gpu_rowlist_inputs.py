@@ -4,35 +4,25 @@ rows among ragged counts.  tests/rowlist_cases.py builds the inputs; tests/test_
 to what they are named for.
 
 References, never the code under test: the golden files' float64 numbers; tests/masked_ref.py (torch autograd in float64).
-Every C call goes through the guarded buffers of tests/guarded.py (the `run` helpers of test_gpu_labeled_wide.py,
-test_gpu_masked.py and test_gpu_ragged.py).
+Every C call goes through the guarded buffers of tests/guarded.py (run_wide, run_masked and run_ragged of
+tests/rowlist_harness.py).
 
-Gates.  Golden vectors: test_gpu_ragged.check(strict=True) on the fixture's rows, as test_gpu_ragged.py holds the ragged
-entry; g8_degenerate as it is held there.  Degenerate rows: the two-part rule of `two_part` below.  The wide entry against
+Gates.  Golden vectors: rowlist_harness.check_rows(strict=True) on the fixture's rows, as test_gpu_ragged.py holds the ragged
+entry; g8_degenerate as it is held there.  Degenerate rows: the two-part rule of rowlist_harness.two_part.  The wide entry against
 the masked one: the same rules at factor 2 (two fp32 results); the masked entry against ge2e_loss_fwd_bwd_ragged on the
 compacted rows: bit for bit.  The rows that do not count: exact +0, whatever they hold.  `-s` prints every figure before it
 is asserted; profiles/rowlist_inputs_gate.txt keeps the worst of them.
 """
 import numpy as np
 import pytest
-import torch
 
 import rowlist_cases as rc
+from capi import lib  # noqa: F401
 from conftest import golden_names
-from test_gpu_labeled_wide import run as run_wide
-from test_gpu_masked import KEYS, check_masked, is_zero, ragged_on_compacted
-from test_gpu_masked import run as run_masked
-from test_gpu_ragged import BIAS, GT, LT, VARIANTS, W, batch_of, check, same_bits
+from rowlist_harness import (BIAS, KEYS, VARIANTS, W, batch_of, check_masked, check_rows, is_zero, ragged_on_compacted, run_masked,
+                             run_wide, same_bits, two_part)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def lib():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from speaker_embedding_ge2e_loss_amd import _lib
-    return _lib.load()
 
 
 def as_ref(o):
@@ -62,11 +52,11 @@ def test_golden_vectors_as_row_lists(lib, name):
     E, labels, N, ref, w, b = rc.golden_rows(name)
     idx, counted = ref["index"], ref["counted"]
 
-    def on_fixture_rows(o):     # the outputs of the fixture's rows in the fixture's order: what check(strict=True) is worded for
+    def on_fixture_rows(o):     # the outputs of the fixture's rows in the fixture's order: what check_rows(strict=True) is worded for
         return dict(o, per=o["per"][counted], dE=o["dE"][counted])
 
     fixture = on_fixture_rows(ref)
-    rule = g8_rule if "degenerate" in name else (lambda o, r, what, factor=1.0: check(o, r, what, strict=True, factor=factor))
+    rule = g8_rule if "degenerate" in name else (lambda o, r, what, factor=1.0: check_rows(o, r, what, strict=True, factor=factor))
     masked = run_masked(lib, E[None], labels[None], N, "softmax", True, 0xFF, w=w, b=b)
     got = {"wide": batch_of(run_wide(lib, E[None], labels[None], N, "softmax", True, 0xFF, w=w, b=b), 0), "masked": batch_of(masked, 0)}
     for entry, o in got.items():
@@ -79,27 +69,6 @@ def test_golden_vectors_as_row_lists(lib, name):
 
 
 # ---- 2. degenerate rows with ragged counts ----------------------------------------------------------------------------------------
-def two_part(o, ref, deg, active_row, what, factor=1.0):
-    """The gate where one speaker's gradients are 1e6 to 1e9 times the others':
-      loss rtol 1e-5, and dE on the degenerate speaker's rows max-abs <= 1e-5 max|dE_ref| (the rule of g8_degenerate);
-      every other speaker's rows at the ordinary row bound of test_gpu_ragged.check, max-abs <= 4e-5 max(1, max|dE_ref| over
-      THOSE rows), so that the large entries cannot hide them, and per there at check's per bound: these rows get terms of
-      ordinary size only."""
-    rest = active_row & ~deg
-    dref = np.asarray(ref["dE"], np.float64)
-    top, plain = float(np.abs(dref).max()), max(1.0, float(np.abs(dref[rest]).max()))
-    derr, rerr = float(np.abs(o["dE"][deg] - dref[deg]).max()), float(np.abs(o["dE"][rest] - dref[rest]).max())
-    lerr, lref = abs(float(o["loss"]) - float(ref["loss"])), abs(float(ref["loss"]))
-    per_ref = np.asarray(ref["per"], np.float64)[rest]
-    pshare = float((np.abs(o["per"][rest] - per_ref) / (factor * (2e-5 + 20 * LT * np.abs(per_ref)))).max())
-    print(f"{what}: loss {lerr:.3e} / {factor * 1e-5 * lref:.3e}  per worst share {pshare:.3f}"
-          f"  dE degenerate rows max-abs {derr:.3e} / {factor * 1e-5 * top:.3e}  other rows max-abs {rerr:.3e} / {factor * 4 * GT * plain:.3e}")
-    assert lerr <= factor * 1e-5 * lref, f"{what}: loss {float(o['loss'])} vs {float(ref['loss'])}"
-    assert derr <= factor * 1e-5 * top, f"{what}: dE of the degenerate speaker's rows {derr} of {top}"
-    assert rerr <= factor * 4 * GT * plain, f"{what}: dE of the other speakers' rows {rerr}"
-    assert pshare <= 1.0, f"{what}: per of the other speakers' rows"
-
-
 @pytest.mark.parametrize("variant", VARIANTS)
 @pytest.mark.parametrize("kind", list(rc.DEG_KINDS))
 def test_degenerate_rows_among_ragged_counts(lib, kind, variant):

@@ -5,22 +5,15 @@ import numpy as np
 import pytest
 import torch
 
+from capi import functional as GF  # noqa: F401
 from conftest import rel_fro
+from dense_harness import check_dense, run_hip
 from oracle import ge2e_oracle as orc
-from test_gpu_parity import check, run_hip
 import bench
 
 BENCH_B = bench.CONFIGS["cfg2"]["B"]      # batches per launch of the metric config's bench line
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def GF():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from speaker_embedding_ge2e_loss_amd import functional
-    return functional
 
 
 TEAM_IMPLS = ("team",)
@@ -45,7 +38,7 @@ def test_many_batches_per_team_full_size(GF, impl):
         assert np.allclose(ot["loss"][i], ref["loss"], rtol=2e-5)
         assert rel_fro(ot["dE"][i], ref["dE"]) < 2e-5
         assert np.allclose(ot["per"][i], ref["per"], rtol=1e-4, atol=1e-4)
-        check({k: v[i] for k, v in ot.items()}, ref, impl, f"batch {i}", strict=True)
+        check_dense({k: v[i] for k, v in ot.items()}, ref, impl, f"batch {i}", strict=True)
 
 
 @pytest.mark.parametrize("shape", [(40, 23, 7, 128), (70, 9, 5, 64), (3, 32, 16, 64), (33, 64, 2, 192), (5, 17, 4, 256)])
@@ -93,7 +86,7 @@ def test_small_d_full_members(GF, shape, impl):
     for i in range(B):
         assert rel_fro(o["dE"][i], ref["dE"][i]) < 2e-5, i
     if N == 64 and M == 10:      # the metric's (N, M): the flat gate of the BASELINE configs (db atol 1e-4, dw rtol + 1e-5)
-        check(o, ref, impl, f"{shape}/{impl}", strict=True)
+        check_dense(o, ref, impl, f"{shape}/{impl}", strict=True)
 
 
 def test_fallback_when_no_team_forms(GF):

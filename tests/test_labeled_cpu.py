@@ -3,30 +3,23 @@ ge2e_loss_fwd_bwd_labeled / ge2e_workspace_bytes_labeled and functional.dense_la
 workspace size, every error code and the order of the checks, the handling of host labels -- all before anything is
 launched."""
 import ctypes
-import os
 import re
 
 import numpy as np
 import pytest
 import torch
 
+from capi import built_lib as lib  # noqa: F401
+from capi import header_text
 from speaker_embedding_ge2e_loss_amd import _lib, build
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMS = ("ge2e_label_index_workspace_bytes", "ge2e_label_index", "ge2e_workspace_bytes_labeled", "ge2e_loss_fwd_bwd_labeled")
 ERR_NULL, ERR_SHAPE, ERR_WORKSPACE, ERR_VARIANT, ERR_ALIGN = -1, -2, -3, -4, -6
 GRID = 512           # the ragged kernel's grid cap: one workspace slice per workgroup
 
 
-@pytest.fixture(scope="module")
-def lib():
-    build.build(verbose=False)
-    return _lib.load()
-
-
 def test_header_library_and_binding_have_the_four_symbols(lib):
-    text = open(os.path.join(ROOT, "include", "ge2e_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text = header_text()
     raw = ctypes.CDLL(build.LIB_PATH)
     for s in SYMS:
         assert re.search(r"\b%s\s*\(" % s, text), f"{s} not declared in include/ge2e_hip.h"

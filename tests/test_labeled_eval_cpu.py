@@ -10,28 +10,22 @@ import numpy as np
 import pytest
 import torch
 
+from capi import built_lib as lib  # noqa: F401
+from capi import header_text
 import labeled_eval_ref as ler
 from conftest import golden_names, load_golden
 from oracle import ge2e_oracle as orc
 from speaker_embedding_ge2e_loss_amd import _lib, build
 from speaker_embedding_ge2e_loss_amd import evaluation as EV
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMS = ("ge2e_cos_sim_labeled_workspace_bytes", "ge2e_cos_sim_labeled", "ge2e_eer_counts_labeled")
 ERR_NULL, ERR_SHAPE, ERR_WORKSPACE, ERR_ALIGN = -1, -2, -3, -6
 Z = np.load(os.path.join(os.path.dirname(__file__), "golden", "callers", "eer.npz"))
 EER_CASES = sorted({k.split(".")[0] for k in Z.files})
 
 
-@pytest.fixture(scope="module")
-def lib():
-    build.build(verbose=False)
-    return _lib.load()
-
-
 def test_header_library_and_binding_have_the_symbols(lib):
-    text = open(os.path.join(ROOT, "include", "ge2e_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text = header_text()
     raw = ctypes.CDLL(build.LIB_PATH)
     for s in SYMS:
         assert re.search(r"\b%s\s*\(" % s, text), f"{s} not declared in include/ge2e_hip.h"

@@ -4,34 +4,27 @@ declared, exported and bound, the ABI version unmoved, the error codes and their
 it cannot do without and the wide entry's, the float64 reference of tests/labeled_grad_ref.py held to the references that
 exist (labeled_eval_ref.cos_ref, masked_ref.masked_loss), and the argument errors raised before any device is needed."""
 import ctypes
-import os
 import re
 
 import numpy as np
 import pytest
 import torch
 
+from capi import built_lib as lib  # noqa: F401
+from capi import header_text
 import labeled_eval_ref as ler
 import labeled_grad_ref as lgr
 import masked_ref as mr
+from rowlist_cases import LOSS_CASES, inputs
 from speaker_embedding_ge2e_loss_amd import _lib, build
-from test_gpu_masked import LOSS_CASES, inputs
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMS = ("ge2e_cos_sim_labeled_bwd_workspace_bytes", "ge2e_cos_sim_labeled_bwd", "ge2e_calc_loss_labeled",
         "ge2e_calc_loss_labeled_bwd")
 ERR_NULL, ERR_SHAPE, ERR_WORKSPACE, ERR_VARIANT, ERR_ALIGN = -1, -2, -3, -4, -6
 
 
-@pytest.fixture(scope="module")
-def lib():
-    build.build(verbose=False)
-    return _lib.load()
-
-
 def test_header_library_and_binding_have_the_symbols(lib):
-    text = open(os.path.join(ROOT, "include", "ge2e_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text = header_text()
     raw = ctypes.CDLL(build.LIB_PATH)
     for s in SYMS:
         assert re.search(r"\b%s\s*\(" % s, text), f"{s} not declared in include/ge2e_hip.h"

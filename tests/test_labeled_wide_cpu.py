@@ -4,28 +4,21 @@ error codes in the masked entry's order (the argument table of test_masked_cpu.p
 workspace between the one plane it cannot do without and the sum of the planes the header lists, and the argument errors
 that are raised before any device is needed."""
 import ctypes
-import os
 import re
 
 import pytest
 import torch
 
+from capi import built_lib as lib  # noqa: F401
+from capi import header_text
 from speaker_embedding_ge2e_loss_amd import _lib, build
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMS = ("ge2e_workspace_bytes_labeled_wide", "ge2e_loss_fwd_bwd_labeled_wide")
 ERR_NULL, ERR_SHAPE, ERR_WORKSPACE, ERR_VARIANT, ERR_ALIGN = -1, -2, -3, -4, -6
 
 
-@pytest.fixture(scope="module")
-def lib():
-    build.build(verbose=False)
-    return _lib.load()
-
-
 def test_header_library_and_binding_have_the_two_symbols(lib):
-    text = open(os.path.join(ROOT, "include", "ge2e_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text = header_text()
     raw = ctypes.CDLL(build.LIB_PATH)
     for s in SYMS:
         assert re.search(r"\b%s\s*\(" % s, text), f"{s} not declared in include/ge2e_hip.h"

@@ -17,15 +17,14 @@ printed) and lists every kernel name there is (ge2e_plan_atoms).  Here:
 """
 import ctypes
 import json
-import os
 
 import numpy as np
 import pytest
 
 import bounds_cases as bc
+from capi import built_lib as lib  # noqa: F401
+from dense_harness import PLANS_JSON, current_plans
 from speaker_embedding_ge2e_loss_amd import _lib, build
-
-PLANS_JSON = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "plans.json")
 
 # The scan.  N to 1024 (tiled's limit) around 8 (a team), 16 (AUTO's team / cos thresholds), 64, 128, 256 and the wave
 # kernels' speaker counts; M 2..17 one by one (the wave kernels' M, 10 | 11: prep and team registers, 16 | 17: team) and
@@ -38,12 +37,6 @@ BS = (1, 2, 3, 24, 25, 32, 47, 48, 65, 96, 191, 192, 224, 256, 257, 4096)
 AUTO_BS = (1, 207, 208, 256, 257, 383, 384, 4096)
 COMBOS = ((0, 0), (0, 1), (1, 0), (1, 1))      # (variant, want_grad)
 EXPLICIT = ("generic", "fused_f32", "fused_split", "tiled", "team", "wave")
-
-
-@pytest.fixture(scope="module")
-def lib():
-    build.build(verbose=False)
-    return _lib.load()
 
 
 @pytest.fixture(scope="module")
@@ -140,11 +133,6 @@ def test_committed_plans_are_the_plans_computed_here(lib):
     with open(PLANS_JSON) as f:
         committed = json.load(f)
     assert committed == current_plans(lib)
-
-
-def current_plans(lib):
-    plans = bc.table_plans(lib)
-    return {what: ",".join(plan) for t in ("LOSS_CASES", "PLAN_CASES") for what, plan in plans[t]}
 
 
 def test_plan_queries_answer_like_snprintf_and_refuse_what_the_call_refuses(lib):

@@ -2,26 +2,20 @@
 ge2e_loss_fwd_bwd_ragged / ge2e_workspace_bytes_ragged / functional.ragged_offsets: declared, exported and bound, a sane
 workspace size, every error code and the order of the checks -- all before anything is launched."""
 import ctypes
-import os
 import re
 
 import numpy as np
 import pytest
 import torch
 
+from capi import built_lib as lib  # noqa: F401
+from capi import header_text
 import ragged_ref as rr
 from oracle import ge2e_oracle as orc
 from speaker_embedding_ge2e_loss_amd import _lib, build
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMS = ("ge2e_workspace_bytes_ragged", "ge2e_loss_fwd_bwd_ragged")
 ERR_NULL, ERR_SHAPE, ERR_WORKSPACE, ERR_VARIANT, ERR_ALIGN = -1, -2, -3, -4, -6
-
-
-@pytest.fixture(scope="module")
-def lib():
-    build.build(verbose=False)
-    return _lib.load()
 
 
 # (contrast with one speaker has no other speaker to take the max over: the definition -- and every kernel -- says 0 for
@@ -47,8 +41,7 @@ def test_reference_helper_is_the_dense_loss_at_equal_counts(shape, variant):
 
 
 def test_header_library_and_binding_have_both_symbols(lib):
-    text = open(os.path.join(ROOT, "include", "ge2e_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text = header_text()
     raw = ctypes.CDLL(build.LIB_PATH)
     for s in SYMS:
         assert re.search(r"\b%s\s*\(" % s, text), f"{s} not declared in include/ge2e_hip.h"
