@@ -335,6 +335,65 @@ int ge2e_calc_loss_labeled_bwd(const float* sim, const int* col, const int* acti
                                float* d_sim /* [B][R][N] */, void* stream);
 
 /*
+ * ENROLMENT AND VERIFICATION: a speaker bank filled from one set of rows, and other rows scored against it.  Every cosine
+ * above is the training-time similarity: the centroids come from the very rows that are scored and the own column is the
+ * leave-one-out centroid.  A held-out trial row is no part of the model it is compared with: nothing here leaves one out.
+ * A BANK is two caller-owned device buffers for the speaker ids 0 .. K-1, sums [K][D] float32 and cnt [K] int32, zeroed
+ * once by the caller.  Rows are taken as given (the encoder's output is L2-normalised, s2:34; nothing is normalised on the
+ * way in).  No batch dimension.
+ *
+ * ge2e_enroll_accumulate.  E [R][D], labels [R] int32, rows in any order, labels of ANY content.  A row is valid iff
+ * 0 <= label < K; every other row is ignored and never read: it may hold NaN.  For a speaker s with m >= 1 valid rows in
+ * this call (ONE row enrols: not the masked loss's "at least 2") the partial sum starts from 0 and adds the speaker's rows
+ * in ascending row index; then, once, sums[s] = sums[s] + partial and cnt[s] += m.  A speaker without a valid row in this
+ * call is not touched: its sums row keeps its bits, whatever they are.  Two launches: the masked index kernel with the
+ * activity threshold 1, then one wave per active speaker (up to min(K, R) of them).  Exactly one wave touches a speaker per
+ * launch, no floating-point atomics, every sum has a fixed order: the same bits on every launch, and the same for every
+ * row order that keeps each speaker's own rows in their order.  Workspace (ge2e_enroll_workspace_bytes, 256-byte aligned):
+ * the index tables of one batch -- offsets [K+1], order [R], speakers [K], active [2] -- and, above 1024 speakers, the
+ * index kernel's K counters, each part 256-byte aligned; no initialisation, and the result does not depend on what it held.
+ * Checked on the host before anything is launched, in this order: GE2E_ERR_NULL (E, labels, sums or cnt), GE2E_ERR_SHAPE
+ * (K, R or D < 1), GE2E_ERR_WORKSPACE, GE2E_ERR_ALIGN (E or sums not 16-byte aligned).
+ *
+ * ge2e_enroll_finalize.  models [K][D]: for cnt[s] > 0 the unit centroid c / max(|c|, eps_cos), c = sums[s] / cnt[s], in
+ * the centroid kernels' arithmetic; for cnt[s] <= 0 the row is written as +0 and sums[s] is never read.  EVERY element is
+ * written.  One launch (one wave per speaker), no workspace.  Checks: GE2E_ERR_NULL (sums, cnt or models), GE2E_ERR_SHAPE
+ * (K or D < 1).
+ *
+ * ge2e_verify_scores.  E [R][D] the trial rows, models [K][D] and cnt [K] as above.  A speaker k is ENROLLED iff cnt[k] > 0.
+ * labels NULL: every row is scored; scores is required, counts and trials must be NULL.  With labels [R]: a row with
+ * label < 0 is ignored (never read: it may hold NaN; its score row is +0), every other row is scored, and its TARGET is
+ * `label` if label < K and that speaker is enrolled; otherwise it has none (an unknown speaker: an impostor against
+ * everybody).  Outputs:
+ *   scores [R][K]   (e_r . models[k]) / max(|e_r|, eps_cos) + eps for an enrolled k, +0 for any other: every element is
+ *                   written.  NULL: the matrix is never materialised (counts only)
+ *   counts [T][2]   [t][0] = #{(r, k) : r scored, k enrolled, k != target(r), scores[r][k] > thr[t]},
+ *                   [t][1] = #{r : r has a target, scores[r][target(r)] > thr[t]}.  fp32 strict `>`, NaN accepts nothing;
+ *                   thresholds non-decreasing, T <= 4096, as for ge2e_eer_counts.  Or NULL
+ *   trials [2]      {impostor scores counted, target scores counted}: the denominators of FAR and FRR, tallied where
+ *                   the values are binned, NaN included.  Or NULL
+ * A zeroing launch when counts or trials are wanted, then one rows kernel (one workgroup per 64 rows in the caller's
+ * order; exact fp32 on the matrix core; every wave streams the model tiles from L2).  No workspace, enqueue-only, static shapes: fit for a HIP
+ * graph.  Integer atomics only: the same bits every launch, and a row's scores do not depend on where it stands in E.
+ * Checked on the host before anything is launched, in this order: GE2E_ERR_NULL (E, models or cnt NULL; both scores and
+ * counts NULL; counts or trials without labels), GE2E_ERR_SHAPE (K, R or D < 1; T < 0 or T > 4096; counts without
+ * thresholds or with T = 0; counts or trials with R * K > 2^31 - 1), GE2E_ERR_ALIGN (E or models not 16-byte aligned).
+ */
+size_t ge2e_enroll_workspace_bytes(int K, int R, int D);   /* 0 for a bad shape */
+int ge2e_enroll_accumulate(const float* E, const int* labels, int K, int R, int D,
+                           float* sums /* [K][D] */, int* cnt /* [K] */,
+                           void* workspace, size_t workspace_bytes, void* stream);
+int ge2e_enroll_finalize(const float* sums, const int* cnt, int K, int D, float eps_cos,
+                         float* models /* [K][D] */, void* stream);
+int ge2e_verify_scores(const float* E, const int* labels /* [R] or NULL */, const float* models, const int* cnt,
+                       int K, int R, int D, float eps_cos, float eps,
+                       const float* thresholds, int T,       /* NULL / 0: no counts */
+                       float* scores,   /* [R][K] or NULL */
+                       int* counts,     /* [T][2] or NULL */
+                       int* trials,     /* [2]    or NULL */
+                       void* stream);
+
+/*
  * The same, fed with the encoder's RAW output (s2_model_GE2E_loss_speach_embed.py:34 +
  * s4_train_embed_model.py:186-192 folded into the loss kernel's load and store stages):
  *   Y   [B][N*M][D]  the encoder's projection BEFORE its L2-normalisation, rows in the encoder's own (permuted) order
@@ -505,6 +564,14 @@ int ge2e_selftest_team_grid(const float* E, int B, int N, int M, int D, const fl
                             float eps_cos, float eps, int variant, float* loss, float* per_emb_loss, float* dE,
                             float* dw, float* db, void* workspace, size_t workspace_bytes, void* stream,
                             int max_workgroups);
+
+/* ge2e_verify_scores with the form of its rows kernel chosen by the caller: 0 = as the product call chooses (2), 1 = the
+ * model tiles staged in LDS once per workgroup (up to T = 2730; above that there is no room beside the histograms and the
+ * call streams), 2 = every wave streams them from L2.  Same arguments, checks and results (bit for bit); for the tests of
+ * both forms and for tools/bench_enroll_verify.py, which measured 2 faster than 1. */
+int ge2e_selftest_verify_form(const float* E, const int* labels, const float* models, const int* cnt, int K, int R, int D,
+                              float eps_cos, float eps, const float* thresholds, int T, float* scores, int* counts,
+                              int* trials, void* stream, int form);
 
 #ifdef __cplusplus
 }

@@ -62,6 +62,13 @@ PROTOTYPES = {
     "ge2e_calc_loss_labeled": (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _fp, _fp, _fp]),
     "ge2e_calc_loss_labeled_bwd": (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _fp, _fp, _fp,
                                              _fp]),
+    "ge2e_enroll_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
+    "ge2e_enroll_accumulate": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, C.c_size_t, _fp]),
+    "ge2e_enroll_finalize": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_float, _fp, _fp]),
+    "ge2e_verify_scores": (C.c_int, [_fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _fp, C.c_int,
+                                     _fp, _fp, _fp, _fp]),
+    "ge2e_selftest_verify_form": (C.c_int, [_fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _fp,
+                                            C.c_int, _fp, _fp, _fp, _fp, C.c_int]),
     "ge2e_raw_supported": (C.c_int, [C.c_int] * 3),
     "ge2e_loss_fwd_bwd_raw": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, C.c_float, C.c_float,
                                         C.c_int, _fp, _fp, _fp, _fp, _fp, _fp]),

@@ -13,6 +13,7 @@
 #include "ge2e_labeled_eval.hpp"
 #include "ge2e_labeled_wide.hpp"
 #include "ge2e_labeled_helpers.hpp"
+#include "ge2e_enroll.hpp"
 #include "ge2e_helpers.hpp"
 #include "ge2e_fused.hpp"
 #include "ge2e_selftest.hpp"
@@ -447,6 +448,60 @@ int ge2e_eer_counts_labeled(const float* sim, const int* col, const int* active,
     if (!sim || !col || !active || !thresholds || !counts) return GE2E_ERR_NULL;
     if (B < 1 || N < 1 || R < 1 || T < 1 || T > 4096) return GE2E_ERR_SHAPE;
     return (int)launch_eer_counts_labeled(sim, col, active, B, N, R, thresholds, T, counts, (hipStream_t)stream);
+}
+
+// ENROLMENT AND VERIFICATION (include/ge2e_hip.h, csrc/ge2e_enroll.hip).  The bank has no batch dimension: the index kernel
+// runs on one batch, with the activity threshold 1.
+size_t ge2e_enroll_workspace_bytes(int K, int R, int D) {
+    return (K >= 1 && R >= 1 && D >= 1) ? enroll_layout(K, R).total : 0;
+}
+
+int ge2e_enroll_accumulate(const float* E, const int* labels, int K, int R, int D, float* sums, int* cnt, void* workspace,
+                           size_t workspace_bytes, void* stream) {
+    if (!E || !labels || !sums || !cnt) return GE2E_ERR_NULL;
+    if (K < 1 || R < 1 || D < 1) return GE2E_ERR_SHAPE;
+    const IndexTables L = enroll_layout(K, R);
+    if (!workspace_ok(workspace, workspace_bytes, L.total)) return GE2E_ERR_WORKSPACE;
+    if (!aligned16(E) || !aligned16(sums)) return GE2E_ERR_ALIGN;
+    char* ws = (char*)workspace;
+    int* offsets = (int*)(ws + L.off);
+    int* order = (int*)(ws + L.order);
+    int* speakers = (int*)(ws + L.speakers);
+    int* active = (int*)(ws + L.active);
+    const hipError_t err = launch_label_index_masked(labels, 1, K, R, offsets, order, speakers, active, (int*)(ws + L.index),
+                                                     (hipStream_t)stream, true);
+    if (err != hipSuccess) return (int)err;
+    return (int)launch_enroll_accumulate(E, offsets, order, speakers, active, K, R, D, sums, cnt, (hipStream_t)stream);
+}
+
+int ge2e_enroll_finalize(const float* sums, const int* cnt, int K, int D, float eps_cos, float* models, void* stream) {
+    if (!sums || !cnt || !models) return GE2E_ERR_NULL;
+    if (K < 1 || D < 1) return GE2E_ERR_SHAPE;
+    return (int)launch_enroll_finalize(sums, cnt, K, D, eps_cos, models, (hipStream_t)stream);
+}
+
+int ge2e_selftest_verify_form(const float* E, const int* labels, const float* models, const int* cnt, int K, int R, int D,
+                              float eps_cos, float eps, const float* thresholds, int T, float* scores, int* counts, int* trials,
+                              void* stream, int form) {
+    if (!E || !models || !cnt || (!scores && !counts) || (!labels && (counts || trials))) return GE2E_ERR_NULL;
+    if (K < 1 || R < 1 || D < 1 || T < 0 || T > 4096 || (counts && (!thresholds || T == 0)) ||
+        ((counts || trials) && (long long)R * K > 2147483647LL) || form < VERIFY_AUTO || form > VERIFY_STREAMED)
+        return GE2E_ERR_SHAPE;
+    if (!aligned16(E) || !aligned16(models)) return GE2E_ERR_ALIGN;
+    ProblemVerify p{};
+    p.E = E; p.labels = labels; p.models = models; p.cnt = cnt;
+    p.thr = counts ? thresholds : nullptr;
+    p.scores = scores; p.counts = counts; p.trials = trials;
+    p.K = K; p.R = R; p.D = D;
+    p.T = counts ? T : 0;
+    p.eps_cos = eps_cos; p.eps = eps;
+    return (int)launch_verify_scores(p, (VerifyForm)form, (hipStream_t)stream);
+}
+
+int ge2e_verify_scores(const float* E, const int* labels, const float* models, const int* cnt, int K, int R, int D, float eps_cos,
+                       float eps, const float* thresholds, int T, float* scores, int* counts, int* trials, void* stream) {
+    return ge2e_selftest_verify_form(E, labels, models, cnt, K, R, D, eps_cos, eps, thresholds, T, scores, counts, trials, stream,
+                                     VERIFY_AUTO);
 }
 
 // The DIFFERENTIABLE labelled helpers (include/ge2e_hip.h).  ge2e_cos_sim_labeled_bwd: stateless like every entry -- the

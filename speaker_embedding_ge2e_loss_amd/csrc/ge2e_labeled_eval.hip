@@ -33,6 +33,7 @@
 
 #include <algorithm>
 
+#include "ge2e_counting_dev.hpp"
 #include "ge2e_rows_dev.hpp"
 
 namespace ge2e {
@@ -43,55 +44,8 @@ constexpr int kTile = 64, kWaveRows = kTile / kWaves;   // sorted positions per 
 constexpr int kAcc = 4;                                 // column tiles (accumulators) in flight per wave
 constexpr int kMaxCentroidBlocks = 8192, kMaxRowBlocks = 1 << 20;
 
-// ---- the counting epilogue, shared by the fused kernel and ge2e_eer_counts_labeled ---------------------------------
-// LDS: hist [2][T+1] (false accepts, own accepts), then the T thresholds.
-__device__ __forceinline__ void counting_begin(int* hist, float* thr_lds, const float* thr, int T) {
-    for (int t = threadIdx.x; t < 2 * (T + 1); t += kThreads) hist[t] = 0;
-    for (int t = threadIdx.x; t < T; t += kThreads) thr_lds[t] = thr[t];
-    __syncthreads();
-}
-// v is binned by the number of thresholds below it (the first t with !(v > thr[t]); NaN: 0); bin 0 is above no threshold
-__device__ __forceinline__ void count_value(float v, bool own, int* hist, const float* thr_lds, int T) {
-    if (!(v > thr_lds[0])) return;   // bin 0 (most other-speaker cosines, and NaN): nothing to search, nothing to record
-    int lo = 1, hi = T;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (v > thr_lds[mid]) lo = mid + 1; else hi = mid;
-    }
-    if (lo > 0) atomicAdd(&hist[(own ? T + 1 : 0) + lo], 1);
-}
-// counts[t][a] += number of recorded values whose bin is > t.  Every thread owns a run of bins; a suffix scan over the
-// runs' totals (lanes, then waves), then each run from its end.  Called by all threads after a barrier.
-__device__ __forceinline__ void counting_end(const int* hist, int T, int* counts, int (*wtot)[kWaves]) {
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const int per = (T + kThreads - 1) / kThreads;
-    const int lo = min(1 + (int)threadIdx.x * per, T + 1), hi = min(lo + per, T + 1);   // bins lo .. hi-1 of 1 .. T
-    int own[2], suf[2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a) {
-        int s = 0;
-        for (int u = lo; u < hi; ++u) s += hist[a * (T + 1) + u];
-        own[a] = s;
-        int v = s;
-#pragma unroll
-        for (int d = 1; d < kWave; d <<= 1) {
-            const int t = __shfl_down(v, d);
-            if (lane + d < kWave) v += t;
-        }
-        suf[a] = v;                                      // this run and every later run of the wave
-        if (lane == 0) wtot[a][wid] = v;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int a = 0; a < 2; ++a) {
-        int run = suf[a] - own[a];
-        for (int i = wid + 1; i < kWaves; ++i) run += wtot[a][i];
-        for (int u = hi - 1; u >= lo; --u) {
-            run += hist[a * (T + 1) + u];
-            if (run) atomicAdd(&counts[(size_t)(u - 1) * 2 + a], run);
-        }
-    }
-}
+// (the counting epilogue -- counting_begin, count_value, counting_end -- is in ge2e_counting_dev.hpp)
+static_assert(kThreads == kCountThreads, "the counting helpers are written for this workgroup");
 
 // ---- kernel 1: centroids ---------------------------------------------------------------------------------------------
 // kLoss: the labelled loss's wide route (ge2e_labeled_wide.hip) runs the same kernel for its SS, CH, CST and spk.  It keeps

@@ -111,7 +111,10 @@ __device__ __forceinline__ void index_batch(const int* lab, int N, int R, int* o
 //      row index, so order is a permutation of 0..R-1 whatever the labels hold.
 // Whether a row is active is read from the cursors before any of the chunk moves (one barrier): cursors only grow from a
 // value >= 0, so the answer is the same for every chunk.
+// kMinRows: the activity threshold, the valid rows a speaker needs to be active: 2 for the loss and the training-time
+// evaluation (a lone row has no leave-one-out centroid), 1 for enrolment (ge2e_enroll.hip), where every valid row counts.
 // cnt: N counters (LDS or workspace); wtot: 2 kWaves ints of LDS; tail: one int of LDS.
+template <int kMinRows>
 __device__ __forceinline__ void index_batch_masked(const int* lab, int N, int R, int* offs, int* ord, int* spkr, int* act,
                                                    int* cnt, int* wtot, int* tail) {
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -130,7 +133,7 @@ __device__ __forceinline__ void index_batch_masked(const int* lab, int N, int R,
     for (long long j0 = 0; j0 < N; j0 += kThreads) {
         const long long j = j0 + tid;
         const int c = j < N ? cnt[j] : 0;
-        const int f = c >= 2 ? 1 : 0, a = f ? c : 0;
+        const int f = c >= kMinRows ? 1 : 0, a = f ? c : 0;
         const int incf = wave_inclusive_scan(f, lane), inca = wave_inclusive_scan(a, lane);
         if (lane == kWave - 1) { wtot[wid] = incf; wtot[kWaves + wid] = inca; }
         __syncthreads();
@@ -199,6 +202,7 @@ __device__ __forceinline__ void index_batch_masked(const int* lab, int N, int R,
     }
 }
 
+template <int kMinRows>
 __global__ __launch_bounds__(kThreads) void ge2e_label_index_masked_kernel(const int* labels, int B, int N, int R,
                                                                             int* offsets, int* order, int* speakers,
                                                                             int* active, int* ws) {
@@ -212,7 +216,7 @@ __global__ __launch_bounds__(kThreads) void ge2e_label_index_masked_kernel(const
         int* spkr = speakers + (size_t)bi * N;
         int* act = active + (size_t)bi * 2;
         int* cnt = N <= kLabelLdsSpeakers ? lds_cnt : ws + (size_t)blockIdx.x * N;
-        index_batch_masked(lab, N, R, offs, ord, spkr, act, cnt, wtot, &tail);
+        index_batch_masked<kMinRows>(lab, N, R, offs, ord, spkr, act, cnt, wtot, &tail);
         // (index_batch_masked ends on a barrier: counters, wtot and tail are free for the next batch of this workgroup)
     }
 }
@@ -246,9 +250,13 @@ hipError_t launch_label_index(const int* labels, int B, int N, int R, int* offse
 size_t label_index_masked_workspace_bytes(int B, int N, int R) { return label_index_workspace_bytes(B, N, R); }
 
 hipError_t launch_label_index_masked(const int* labels, int B, int N, int R, int* offsets, int* order, int* speakers,
-                                     int* active, int* ws, hipStream_t stream) {
-    hipLaunchKernelGGL(ge2e_label_index_masked_kernel, dim3(ragged_grid(B)), dim3(kThreads), 0, stream, labels, B, N, R,
-                       offsets, order, speakers, active, ws);
+                                     int* active, int* ws, hipStream_t stream, bool lone_speakers) {
+    if (lone_speakers)
+        hipLaunchKernelGGL(ge2e_label_index_masked_kernel<1>, dim3(ragged_grid(B)), dim3(kThreads), 0, stream, labels, B, N, R,
+                           offsets, order, speakers, active, ws);
+    else
+        hipLaunchKernelGGL(ge2e_label_index_masked_kernel<2>, dim3(ragged_grid(B)), dim3(kThreads), 0, stream, labels, B, N, R,
+                           offsets, order, speakers, active, ws);
     return hipGetLastError();
 }
 

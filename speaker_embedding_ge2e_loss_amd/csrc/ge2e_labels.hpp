@@ -13,10 +13,11 @@ size_t label_index_workspace_bytes(int B, int N, int R);      // 0 while the cou
 hipError_t launch_label_index(const int* labels, int B, int N, int R, int* offsets, int* order, int* ws, hipStream_t stream);
 
 // The masked form: labels of any content.  speakers [B][N], active [B][2] = {active speakers, active rows}; the same
-// workspace rule.
+// workspace rule.  A speaker is active from two valid rows on; with `lone_speakers` (enrolment, ge2e_enroll.hip) from one,
+// and then up to min(N, R) speakers are active, not speaker_capacity's R / 2.
 size_t label_index_masked_workspace_bytes(int B, int N, int R);
 hipError_t launch_label_index_masked(const int* labels, int B, int N, int R, int* offsets, int* order, int* speakers,
-                                     int* active, int* ws, hipStream_t stream);
+                                     int* active, int* ws, hipStream_t stream, bool lone_speakers = false);
 
 // R rows hold at most R / 2 speakers of two rows each: the NA that the kernels behind the masked index kernel lay their
 // per-speaker planes out for, max(1, min(N, R / 2)).

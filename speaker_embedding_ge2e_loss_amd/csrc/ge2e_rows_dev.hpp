@@ -220,6 +220,40 @@ __device__ __forceinline__ TileRows<kSteps> tile_rows(const float* E, const floa
     t.cosd = part[2] * t.rne * t.rnu;
     return t;
 }
+// The same builder without the leave-one-out part, for rows that are scored against models they are no part of
+// (ge2e_enroll.hip): the lane's row is `row` of E where row_ok, and is not read otherwise.  Only the row's norm is taken,
+// on the same fragments and with the same two lane swaps; pp = row, j = -1, and rnu, ku, cosd are 0.
+template <int kSteps>
+__device__ __forceinline__ TileRows<kSteps> tile_rows_plain(const float* E, int row, bool row_ok, int D, float eps_cos) {
+    const int q = (threadIdx.x & 63) >> 4;
+    TileRows<kSteps> t;
+    t.row_ok = row_ok;
+    t.pp = t.row = row_ok ? row : 0;
+    t.j = -1;
+    t.rnu = t.ku = t.cosd = 0.f;
+    t.pe = E + (size_t)t.row * D;
+    float ee = 0.f;
+    if constexpr (kSteps > 0) {
+#pragma unroll
+        for (int s = 0; s < kSteps; ++s) t.eh[s] = load4(t.pe, 16 * s + 4 * q, D, row_ok, true);
+#pragma unroll
+        for (int s = 0; s < kSteps; ++s)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) ee += t.eh[s][i] * t.eh[s][i];
+    } else {
+        const bool vecD = (D & 3) == 0;
+        for (int s = 0; s < (D + 15) >> 4; ++s) {
+            const v4f e = load4(t.pe, 16 * s + 4 * q, D, row_ok, vecD);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) ee += e[i] * e[i];
+        }
+    }
+    auto a = GE2E_SWAP16(__float_as_uint(ee));   // (q0 + q1) + (q2 + q3) in every lane, as in tile_rows
+    const float h = __uint_as_float(a[0]) + __uint_as_float(a[1]);
+    auto b = GE2E_SWAP32(__float_as_uint(h));
+    unit_stats(__uint_as_float(b[0]) + __uint_as_float(b[1]), eps_cos, t.rne, t.ke);
+    return t;
+}
 // The cos tiles on the matrix core: unit centroids x the wave's rows, K = D, kAcc column tiles of 16 speakers (independent
 // accumulators) at a time.  After each group epi(kt0, acc): acc[a][g] is the product of the lane's row with centroid
 // (kt0 + a) 16 + 4 q + g, before the row norm; tiles past the last one and centroids past n_act hold what must be dropped.

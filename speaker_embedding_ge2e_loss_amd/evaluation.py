@@ -117,3 +117,89 @@ def evaluate_labeled(model, loader, num_speakers=None, device="cuda:0", threshol
                 print("\nEER : %0.2f (thres:%0.2f, FAR:%0.2f, FRR:%0.2f)" % (r["EER"], r["thres"], r["FAR"], r["FRR"]))
             results.append(r)
     return results
+
+
+# ---- enrolment and verification: models from one set of utterances, trials from another (ge2e_verify_scores) -------------
+
+class SpeakerBank:
+    """A bank of ``num_speakers`` speaker models of dimension ``dim`` on ``device``: the per-speaker sums and counts that
+    `functional.enroll_accumulate` fills, and the unit models made from them.  ``enroll`` may be called any number of times;
+    ``models()`` finalises lazily and is invalidated by ``enroll``.  Ids are bank indices 0 .. num_speakers - 1; rows with
+    any other id are ignored on enrolment."""
+
+    def __init__(self, num_speakers: int, dim: int, device="cuda:0"):
+        self.device = torch.device(device)
+        self.sums = torch.zeros(int(num_speakers), int(dim), dtype=torch.float32, device=self.device)
+        self.cnt = torch.zeros(int(num_speakers), dtype=torch.int32, device=self.device)
+        self._models = None
+
+    def enroll(self, emb: torch.Tensor, ids) -> None:
+        self._models = None
+        GF.enroll_accumulate(self.sums, self.cnt, emb, ids)
+
+    def models(self) -> torch.Tensor:
+        if self._models is None:
+            self._models = GF.enroll_finalize(self.sums, self.cnt)
+        return self._models
+
+    def score(self, emb: torch.Tensor) -> torch.Tensor:
+        """(R, D) -> scores (R, num_speakers): the cosine of every row with every enrolled model (+ eps), 0 elsewhere."""
+        return GF.verify_scores(emb, self.models(), self.cnt).scores
+
+    def verify(self, emb: torch.Tensor, ids, thresholds=THRESHOLDS, need_scores: bool = True) -> GF.VerifyOutputs:
+        """Labelled trials: scores, accept counts per threshold and the numbers of impostor and target trials."""
+        return GF.verify_scores(emb, self.models(), self.cnt, labels=ids, thresholds=thresholds, need_scores=need_scores)
+
+
+def eer_from_trial_counts(counts, n_imp: int, n_tgt: int, thresholds=THRESHOLDS):
+    """The sweep of `eer_from_labeled_counts` (s5:50-98) over held-out trials: counts (T, 2) = [impostor accepts, target
+    accepts], FAR = fa / n_imp, FRR = (n_tgt - ta) / n_tgt; a zero denominator gives 0."""
+    n_imp, n_tgt = int(n_imp), int(n_tgt)
+    diff, EER, EER_thres, EER_FAR, EER_FRR = 1, 0, 0, 0, 0  # s5:50-54
+    for thres, (fa, ta) in zip(thresholds, counts):
+        fa, ta = int(fa), int(ta)
+        FAR = fa / n_imp if n_imp > 0 else 0
+        FRR = (n_tgt - ta) / n_tgt if n_tgt > 0 else 0
+        if diff > abs(FAR - FRR):             # s5:93-98
+            diff = abs(FAR - FRR)
+            EER = (FAR + FRR) / 2
+            EER_thres = thres
+            EER_FAR = FAR
+            EER_FRR = FRR
+    return {"EER": EER, "thres": EER_thres, "FAR": EER_FAR, "FRR": EER_FRR}
+
+
+def evaluate_enrolled(model, enroll_loader, trial_loader, num_speakers: int, device="cuda:0", thresholds=THRESHOLDS,
+                      verbose: bool = True):
+    """Speaker verification as it is used: both loaders yield (mel, speaker_ids), the ids being bank indices in
+    [0, num_speakers).  Every enrolment batch goes into one `SpeakerBank`; every trial batch is scored against it with
+    ``need_scores=False`` -- no score matrix is materialised -- and its counts and trial numbers are added on the device in
+    int64; ONE read-back at the end.  Returns ONE result over the whole trial set: the dict of `eer_from_trial_counts`
+    with ``n_imp`` and ``n_tgt`` added."""
+    T = len(thresholds)
+    bank = None
+    total = None
+    with torch.no_grad():
+        for mel, speaker_ids in enroll_loader:
+            emb = model(mel.to(device)).contiguous().float()
+            if bank is None:
+                bank = SpeakerBank(num_speakers, emb.shape[1], emb.device)
+            bank.enroll(emb, speaker_ids)
+        if bank is None:
+            raise ValueError("the enrolment loader is empty")
+        thr = torch.tensor(list(thresholds), dtype=torch.float64).to(torch.float32)
+        if bool((thr[1:] < thr[:-1]).any()):
+            raise ValueError("thresholds must be non-decreasing")
+        thr = thr.to(bank.device)              # uploaded once: a device table is taken as it is
+        for mel, speaker_ids in trial_loader:
+            emb = model(mel.to(device)).contiguous().float()
+            out = bank.verify(emb, speaker_ids, thresholds=thr, need_scores=False)
+            part = torch.cat([out.counts.reshape(-1), out.trials]).to(torch.int64)
+            total = part if total is None else total + part
+    back = total.cpu().numpy() if total is not None else [0] * (2 * T + 2)   # the one read-back
+    n_imp, n_tgt = int(back[2 * T]), int(back[2 * T + 1])
+    r = eer_from_trial_counts([(back[2 * t], back[2 * t + 1]) for t in range(T)], n_imp, n_tgt, thresholds)
+    r["n_imp"], r["n_tgt"] = n_imp, n_tgt
+    if verbose:
+        print("\nEER : %0.2f (thres:%0.2f, FAR:%0.2f, FRR:%0.2f)" % (r["EER"], r["thres"], r["FAR"], r["FRR"]))
+    return r

@@ -180,6 +180,7 @@ _ENTRIES = {
     "labeled_wide": _Entry("ge2e_loss_fwd_bwd_labeled_wide", "ge2e_workspace_bytes_labeled_wide", ("labeled_wide",)),
     "labeled_eval": _Entry("ge2e_cos_sim_labeled", "ge2e_cos_sim_labeled_workspace_bytes", ("labeled_eval",)),
     "labeled_cos_bwd": _Entry("ge2e_cos_sim_labeled_bwd", "ge2e_cos_sim_labeled_bwd_workspace_bytes", ("labeled_cos_bwd",)),
+    "enroll": _Entry("ge2e_enroll_accumulate", "ge2e_enroll_workspace_bytes", ("enroll",)),
 }
 
 
@@ -820,6 +821,108 @@ def calc_loss_labeled(sim: torch.Tensor, col: torch.Tensor, active: torch.Tensor
     loss, per = _CalcLossLabeledFunction.apply(s.contiguous().float(), col.contiguous(), active.contiguous(), float(eps),
                                                variant)
     return (loss[0], per[0]) if squeeze else (loss, per)
+
+
+# ---- enrolment and verification: a speaker bank and held-out trials (csrc/ge2e_enroll.hip) --------------------------------
+
+@dataclass
+class VerifyOutputs:
+    scores: Optional[torch.Tensor]      # (R, K) float32: 0 on ignored rows and on speakers that are not enrolled
+    counts: Optional[torch.Tensor]      # (T, 2) int32: [impostor accepts, target accepts] per threshold
+    trials: Optional[torch.Tensor]      # (2,) int32: impostor and target scores counted (the denominators of FAR and FRR)
+
+
+def _bank_rows(embeddings: torch.Tensor, D: int, dev: torch.device) -> torch.Tensor:
+    _require_cuda(embeddings, "embeddings")
+    e = embeddings.detach()
+    if e.dim() != 2 or e.shape[0] < 1 or e.shape[1] != D:
+        raise ValueError(f"embeddings must be (R, {D}) with R >= 1, got {tuple(e.shape)}")
+    if e.dtype != torch.float32 or not e.is_contiguous() or e.device != dev:
+        raise TypeError(f"embeddings must be contiguous torch.float32 on {dev}")
+    return e
+
+
+def _bank_labels(labels, K: int, R: int, dev: torch.device) -> torch.Tensor:
+    """(R,) int32 bank indices on `dev`.  A device tensor (torch.int32 / torch.int64) is taken as it is; a host sequence of
+    ints is copied, NOT compacted: the ids are bank indices.  64-bit ids are clamped into [-1, K] before they are narrowed,
+    so that 2**32 + 3 stays outside the bank."""
+    if torch.is_tensor(labels) and labels.device.type != "cpu":
+        if labels.device != dev:
+            raise RuntimeError(f"labels are on {labels.device}, the bank on {dev}: raw pointers cross the C ABI, all on one device")
+        lab, _ = _device_labels(labels, K, True, "labels")
+    else:
+        raw = labels if torch.is_tensor(labels) else torch.as_tensor(labels)
+        if raw.is_floating_point() or raw.is_complex() or raw.dtype == torch.bool:
+            raise TypeError(f"labels must be integers, got {raw.dtype}")
+        lab = raw.to(torch.int64).clamp(-1, K).to(torch.int32).to(dev)
+    if lab.dim() != 1 or lab.shape[0] != R:
+        raise ValueError(f"labels must be ({R},), got {tuple(lab.shape)}")
+    return lab.contiguous()
+
+
+def _check_bank(sums: torch.Tensor, cnt: torch.Tensor):
+    _require_cuda(sums, "sums")
+    if sums.dim() != 2 or sums.dtype != torch.float32 or not sums.is_contiguous():
+        raise TypeError("sums must be a contiguous (K, D) torch.float32 tensor")
+    K, D = sums.shape
+    if cnt.dtype != torch.int32 or tuple(cnt.shape) != (K,) or cnt.device != sums.device or not cnt.is_contiguous():
+        raise TypeError(f"cnt must be a contiguous ({K},) torch.int32 tensor on {sums.device}")
+    return K, D, sums.device
+
+
+def enroll_accumulate(sums: torch.Tensor, cnt: torch.Tensor, embeddings: torch.Tensor, labels, *,
+                      workspace: Optional[torch.Tensor] = None) -> None:
+    """ge2e_enroll_accumulate, IN PLACE on the caller's bank ``sums`` (K, D) float32 / ``cnt`` (K,) int32 (zeroed once by
+    the caller): every row of ``embeddings`` (R, D) whose label is in [0, K) is added to its speaker, rows in any order,
+    every other row is ignored and never read.  One row enrols a speaker; a speaker without a row in this call is not
+    touched.  Two launches on the current stream, no host sync for device labels.  ``labels``: a device torch.int32 /
+    torch.int64 tensor, or a host sequence of ints (copied, not compacted: the ids are bank indices)."""
+    K, D, dev = _check_bank(sums, cnt)
+    e = _bank_rows(embeddings, D, dev)
+    R = e.shape[0]
+    with _on_device(dev):
+        lab = _bank_labels(labels, K, R, dev)
+    _launch_rows("enroll", e, (K, R, D), workspace, e.data_ptr(), lab.data_ptr(), K, R, D, sums.data_ptr(), cnt.data_ptr())
+
+
+def enroll_finalize(sums: torch.Tensor, cnt: torch.Tensor, eps_cos: float = EPS_COS) -> torch.Tensor:
+    """ge2e_enroll_finalize -> ``models`` (K, D): the unit centroid of every enrolled speaker (cnt > 0), +0 elsewhere."""
+    K, D, dev = _check_bank(sums, cnt)
+    models = torch.empty(K, D, dtype=torch.float32, device=dev)
+    _launch("ge2e_enroll_finalize", dev, sums.data_ptr(), cnt.data_ptr(), K, D, float(eps_cos), models.data_ptr(),
+            _stream_ptr(sums))
+    return models
+
+
+def verify_scores(embeddings: torch.Tensor, models: torch.Tensor, cnt: torch.Tensor, labels=None, thresholds=None,
+                  need_scores: bool = True, eps: float = SMALL_ERR, eps_cos: float = EPS_COS) -> VerifyOutputs:
+    """ge2e_verify_scores on the current stream: the trial rows ``embeddings`` (R, D) against ``models`` (K, D) of a bank
+    whose ``cnt`` (K,) says who is enrolled.  No leave-one-out: a trial row is no part of a model.  Without ``labels``
+    every row is scored and only ``scores`` (R, K) comes back.  With ``labels`` (as `enroll_accumulate` takes them) a row
+    with a negative label is ignored (never read, its scores are 0), a row whose label is an enrolled speaker has that
+    speaker as its target and every other row is an impostor against everybody; ``trials`` (2,) counts the impostor and
+    target scores, and with ``thresholds`` (as `cos_sim_labeled` takes them) ``counts`` (T, 2) holds the accepts per
+    threshold.  ``need_scores=False``: the matrix is never materialised."""
+    _check_bank(models, cnt)
+    K, D = models.shape
+    dev = models.device
+    e = _bank_rows(embeddings, D, dev)
+    R = e.shape[0]
+    if labels is None and (thresholds is not None or not need_scores):
+        raise ValueError("counts are about targets and impostors: thresholds / need_scores=False need labels")
+    if thresholds is None and not need_scores:
+        raise ValueError("nothing to compute: need_scores=False without thresholds")
+    with _on_device(dev):
+        lab = _bank_labels(labels, K, R, dev) if labels is not None else None
+        thr = _threshold_table(thresholds, dev, device_ok=True) if thresholds is not None else None
+    T = thr.numel() if thr is not None else 0
+    i32 = dict(dtype=torch.int32, device=dev)
+    out = VerifyOutputs(scores=torch.empty(R, K, dtype=torch.float32, device=dev) if need_scores else None,
+                        counts=torch.empty(T, 2, **i32) if T else None,
+                        trials=torch.empty(2, **i32) if lab is not None else None)
+    _launch("ge2e_verify_scores", dev, e.data_ptr(), _ptr(lab), models.data_ptr(), cnt.data_ptr(), K, R, D, float(eps_cos),
+            float(eps), _ptr(thr), T, _ptr(out.scores), _ptr(out.counts), _ptr(out.trials), _stream_ptr(e))
+    return out
 
 
 # ---- the reference's static helpers (s3:33-38, 41-80, 95-112, 114-127), differentiable like the originals ----------
