@@ -394,6 +394,46 @@ int ge2e_verify_scores(const float* E, const int* labels /* [R] or NULL */, cons
                        void* stream);
 
 /*
+ * SPEAKER IDENTIFICATION (csrc/ge2e_identify.hip): "who is this row?" -- the best k_top enrolled speakers of every trial
+ * row, without the score matrix [R][K] ever being materialised.  Inputs as for ge2e_verify_scores: E [R][D] the trial rows,
+ * models [K][D] and cnt [K] (speaker k is ENROLLED iff cnt[k] > 0), optional labels [R] int32, and k_top with
+ * 1 <= k_top <= GE2E_IDENTIFY_MAX_TOP.
+ * Which rows are scored, and their targets: without labels every row is scored and no row has a target.  With labels a row
+ * with label < 0 is ignored: it is never read and may hold NaN.  Every other row is scored; its TARGET is `label` if
+ * label < K and that speaker is enrolled; otherwise it has none.
+ * The score of (r, k) for an enrolled k is ge2e_verify_scores' score, (e_r . models[k]) / max(|e_r|, eps_cos) + eps, with
+ * the same bits (the same fmaf chain).  A speaker that is not enrolled is never a candidate.
+ * The order of candidates is total: candidate a stands before b iff score_a > score_b as fp32 values; -0 and +0 are equal;
+ * a NaN score stands behind every number; where the scores are equal, or both NaN, the lower speaker index stands first.
+ * Outputs:
+ *   idx [R][k_top]    int32, required: the first k_top candidates of the row in that order.  Positions past the number of
+ *                     enrolled speakers hold -1; ignored rows hold all -1.  Every element is written
+ *   score [R][k_top]  float32 or NULL: the candidates' scores; -inf wherever idx is -1.  Every element is written.  (A
+ *                     NaN score comes back as the quiet NaN 0x7fc00000 and a -0 score as +0.)
+ *   rank [R]          int32 or NULL (needs labels): the target's position 0 .. k_top-1 in the row's list, k_top when the
+ *                     row has a target that is not in the list, -1 for a row without target and for an ignored row
+ *   hist [k_top + 1]  int32 or NULL (needs labels): hist[j] = number of rows whose rank is j, hist[k_top] = rows whose
+ *                     target is outside the list; its sum is the number of rows with a target.  Integer atomics only
+ * The result is a function of the inputs alone: the same bits on every launch and whatever the workspace held, and it does
+ * not depend on how the bank axis was split.
+ * Launches: [a zeroing launch for hist,] the rows kernel -- one workgroup per (64 trial rows, slice of the bank); the number
+ * of slices S = clamp(ceil(W / ceil(R / 64)), 1, ceil(K / 64)) is a function of (K, R) alone, W = 512, a slice being
+ * ceil(ceil(K / 64) / S) groups of 64 speakers -- and the merge kernel, one wave per row.  Enqueue-only, no allocation, no
+ * state, grids from the shapes alone: fit for a HIP graph.  Workspace (ge2e_identify_workspace_bytes, 256-byte aligned):
+ * the rows' partial lists [S][R][k_top] of 8 bytes and nothing else; no initialisation.
+ * Checked on the host before anything is launched, in this order: GE2E_ERR_NULL (E, models, cnt or idx NULL; rank or hist
+ * without labels), GE2E_ERR_SHAPE (K, R or D < 1; k_top < 1 or > GE2E_IDENTIFY_MAX_TOP), GE2E_ERR_WORKSPACE (NULL, too
+ * small, or not 256-byte aligned), GE2E_ERR_ALIGN (E or models not 16-byte aligned).
+ */
+#define GE2E_IDENTIFY_MAX_TOP 32
+size_t ge2e_identify_workspace_bytes(int K, int R, int D, int k_top);     /* 0 for a bad shape */
+int ge2e_identify(const float* E, const int* labels /* [R] or NULL */, const float* models, const int* cnt,
+                  int K, int R, int D, int k_top, float eps_cos, float eps,
+                  int* idx /* [R][k_top] */, float* score /* [R][k_top] or NULL */,
+                  int* rank /* [R] or NULL */, int* hist /* [k_top+1] or NULL */,
+                  void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * The same, fed with the encoder's RAW output (s2_model_GE2E_loss_speach_embed.py:34 +
  * s4_train_embed_model.py:186-192 folded into the loss kernel's load and store stages):
  *   Y   [B][N*M][D]  the encoder's projection BEFORE its L2-normalisation, rows in the encoder's own (permuted) order
@@ -572,6 +612,15 @@ int ge2e_selftest_team_grid(const float* E, int B, int N, int M, int D, const fl
 int ge2e_selftest_verify_form(const float* E, const int* labels, const float* models, const int* cnt, int K, int R, int D,
                               float eps_cos, float eps, const float* thresholds, int T, float* scores, int* counts,
                               int* trials, void* stream, int form);
+
+/* ge2e_identify with the number of bank slices forced to `slices` (clamped to 1 .. ceil(K / 64), and so that tiles x slices
+ * stays a launchable grid; slices that would start past the bank are not made); 0 = the product's choice.  The workspace
+ * must be ge2e_selftest_identify_workspace_bytes(K, R, D, k_top, slices).  Same checks and results (bit for bit): for the
+ * tests of the split and for tools/bench_identify.py. */
+size_t ge2e_selftest_identify_workspace_bytes(int K, int R, int D, int k_top, int slices);
+int ge2e_selftest_identify_slices(const float* E, const int* labels, const float* models, const int* cnt, int K, int R, int D,
+                                  int k_top, float eps_cos, float eps, int* idx, float* score, int* rank, int* hist,
+                                  void* workspace, size_t workspace_bytes, void* stream, int slices);
 
 #ifdef __cplusplus
 }

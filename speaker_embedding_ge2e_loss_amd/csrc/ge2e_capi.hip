@@ -14,6 +14,7 @@
 #include "ge2e_labeled_wide.hpp"
 #include "ge2e_labeled_helpers.hpp"
 #include "ge2e_enroll.hpp"
+#include "ge2e_identify.hpp"
 #include "ge2e_helpers.hpp"
 #include "ge2e_fused.hpp"
 #include "ge2e_selftest.hpp"
@@ -502,6 +503,41 @@ int ge2e_verify_scores(const float* E, const int* labels, const float* models, c
                        float eps, const float* thresholds, int T, float* scores, int* counts, int* trials, void* stream) {
     return ge2e_selftest_verify_form(E, labels, models, cnt, K, R, D, eps_cos, eps, thresholds, T, scores, counts, trials, stream,
                                      VERIFY_AUTO);
+}
+
+// SPEAKER IDENTIFICATION (include/ge2e_hip.h, csrc/ge2e_identify.hip).  The product call is the selftest entry with the
+// split left to identify_split.
+size_t ge2e_selftest_identify_workspace_bytes(int K, int R, int D, int k_top, int slices) {
+    if (K < 1 || R < 1 || D < 1 || k_top < 1 || k_top > GE2E_IDENTIFY_MAX_TOP) return 0;
+    return identify_workspace_bytes(R, k_top, identify_split(K, R, slices).slices);
+}
+
+size_t ge2e_identify_workspace_bytes(int K, int R, int D, int k_top) {
+    return ge2e_selftest_identify_workspace_bytes(K, R, D, k_top, 0);
+}
+
+int ge2e_selftest_identify_slices(const float* E, const int* labels, const float* models, const int* cnt, int K, int R, int D,
+                                  int k_top, float eps_cos, float eps, int* idx, float* score, int* rank, int* hist,
+                                  void* workspace, size_t workspace_bytes, void* stream, int slices) {
+    if (!E || !models || !cnt || !idx || (!labels && (rank || hist))) return GE2E_ERR_NULL;
+    if (K < 1 || R < 1 || D < 1 || k_top < 1 || k_top > GE2E_IDENTIFY_MAX_TOP) return GE2E_ERR_SHAPE;
+    const IdentifySplit split = identify_split(K, R, slices);
+    if (!workspace_ok(workspace, workspace_bytes, identify_workspace_bytes(R, k_top, split.slices))) return GE2E_ERR_WORKSPACE;
+    if (!aligned16(E) || !aligned16(models)) return GE2E_ERR_ALIGN;
+    ProblemIdentify p{};
+    p.E = E; p.labels = labels; p.models = models; p.cnt = cnt;
+    p.idx = idx; p.score = score; p.rank = rank; p.hist = hist;
+    p.part = (unsigned long long*)workspace;
+    p.K = K; p.R = R; p.D = D; p.k_top = k_top;
+    p.eps_cos = eps_cos; p.eps = eps;
+    return (int)launch_identify(p, split, (hipStream_t)stream);
+}
+
+int ge2e_identify(const float* E, const int* labels, const float* models, const int* cnt, int K, int R, int D, int k_top,
+                  float eps_cos, float eps, int* idx, float* score, int* rank, int* hist, void* workspace,
+                  size_t workspace_bytes, void* stream) {
+    return ge2e_selftest_identify_slices(E, labels, models, cnt, K, R, D, k_top, eps_cos, eps, idx, score, rank, hist, workspace,
+                                         workspace_bytes, stream, 0);
 }
 
 // The DIFFERENTIABLE labelled helpers (include/ge2e_hip.h).  ge2e_cos_sim_labeled_bwd: stateless like every entry -- the

@@ -150,6 +150,11 @@ class SpeakerBank:
         """Labelled trials: scores, accept counts per threshold and the numbers of impostor and target trials."""
         return GF.verify_scores(emb, self.models(), self.cnt, labels=ids, thresholds=thresholds, need_scores=need_scores)
 
+    def identify(self, emb: torch.Tensor, k: int = 1, ids=None) -> GF.IdentifyOutputs:
+        """(R, D) -> the best ``k`` enrolled speakers of every row and their scores; with ``ids`` also the position of each
+        row's own speaker among them and the histogram of those positions (`identification_rates` takes it)."""
+        return GF.identify(emb, self.models(), self.cnt, k=k, labels=ids)
+
 
 def eer_from_trial_counts(counts, n_imp: int, n_tgt: int, thresholds=THRESHOLDS):
     """The sweep of `eer_from_labeled_counts` (s5:50-98) over held-out trials: counts (T, 2) = [impostor accepts, target
@@ -202,4 +207,45 @@ def evaluate_enrolled(model, enroll_loader, trial_loader, num_speakers: int, dev
     r["n_imp"], r["n_tgt"] = n_imp, n_tgt
     if verbose:
         print("\nEER : %0.2f (thres:%0.2f, FAR:%0.2f, FRR:%0.2f)" % (r["EER"], r["thres"], r["FAR"], r["FRR"]))
+    return r
+
+
+# ---- identification: who is this row?  (ge2e_identify) ---------------------------------------------------------------------
+
+def identification_rates(hist):
+    """hist (k + 1,) of `functional.identify` (or a sum of them) -> the cumulative top-1 .. top-k identification rates,
+    cumsum(hist[:k]) / hist.sum(): the share of the rows with a target whose target stands among the first j.  A zero
+    denominator gives 0."""
+    h = [int(v) for v in (hist.tolist() if hasattr(hist, "tolist") else hist)]
+    total, run, rates = sum(h), 0, []
+    for v in h[:-1]:
+        run += v
+        rates.append(run / total if total > 0 else 0)
+    return rates
+
+
+def evaluate_identification(model, enroll_loader, trial_loader, num_speakers: int, k: int = 5, device="cuda:0",
+                            verbose: bool = True):
+    """Closed- or open-set identification over two loaders, in `evaluate_enrolled`'s shape: both yield (mel, speaker_ids),
+    the ids being bank indices in [0, num_speakers).  Every enrolment batch goes into one `SpeakerBank`; every trial batch
+    is identified against it, its ``hist`` added on the device in int64; ONE read-back at the end.  Returns ONE result
+    over the whole trial set: {"rates": top-1 .. top-k, "hist": [...], "n_tgt": rows with an enrolled target}."""
+    bank = None
+    total = None
+    with torch.no_grad():
+        for mel, speaker_ids in enroll_loader:
+            emb = model(mel.to(device)).contiguous().float()
+            if bank is None:
+                bank = SpeakerBank(num_speakers, emb.shape[1], emb.device)
+            bank.enroll(emb, speaker_ids)
+        if bank is None:
+            raise ValueError("the enrolment loader is empty")
+        for mel, speaker_ids in trial_loader:
+            emb = model(mel.to(device)).contiguous().float()
+            part = bank.identify(emb, k=k, ids=speaker_ids).hist.to(torch.int64)
+            total = part if total is None else total + part
+    hist = [int(v) for v in total.cpu().numpy()] if total is not None else [0] * (int(k) + 1)   # the one read-back
+    r = {"rates": identification_rates(hist), "hist": hist, "n_tgt": sum(hist)}
+    if verbose:
+        print("\ntop-1 : %0.4f   top-%d : %0.4f   (%d trials)" % (r["rates"][0], len(r["rates"]), r["rates"][-1], r["n_tgt"]))
     return r

@@ -181,6 +181,7 @@ _ENTRIES = {
     "labeled_eval": _Entry("ge2e_cos_sim_labeled", "ge2e_cos_sim_labeled_workspace_bytes", ("labeled_eval",)),
     "labeled_cos_bwd": _Entry("ge2e_cos_sim_labeled_bwd", "ge2e_cos_sim_labeled_bwd_workspace_bytes", ("labeled_cos_bwd",)),
     "enroll": _Entry("ge2e_enroll_accumulate", "ge2e_enroll_workspace_bytes", ("enroll",)),
+    "identify": _Entry("ge2e_identify", "ge2e_identify_workspace_bytes", ("identify",)),
 }
 
 
@@ -922,6 +923,49 @@ def verify_scores(embeddings: torch.Tensor, models: torch.Tensor, cnt: torch.Ten
                         trials=torch.empty(2, **i32) if lab is not None else None)
     _launch("ge2e_verify_scores", dev, e.data_ptr(), _ptr(lab), models.data_ptr(), cnt.data_ptr(), K, R, D, float(eps_cos),
             float(eps), _ptr(thr), T, _ptr(out.scores), _ptr(out.counts), _ptr(out.trials), _stream_ptr(e))
+    return out
+
+
+# ---- identification: the best k enrolled speakers of every trial row (csrc/ge2e_identify.hip) -----------------------------
+
+IDENTIFY_MAX_TOP = 32    # GE2E_IDENTIFY_MAX_TOP
+
+
+@dataclass
+class IdentifyOutputs:
+    indices: torch.Tensor               # (R, k) int32: the best k enrolled speakers, best first; -1 past the enrolled count
+    #                                     and on ignored rows
+    scores: Optional[torch.Tensor]      # (R, k) float32: their scores, -inf where indices is -1
+    rank: Optional[torch.Tensor]        # (R,) int32: the target's position, k if it is outside the list, -1 without target
+    hist: Optional[torch.Tensor]        # (k + 1,) int32: rows per rank; [k] = target outside the list
+
+
+def identify(embeddings: torch.Tensor, models: torch.Tensor, cnt: torch.Tensor, k: int = 1, labels=None,
+             need_scores: bool = True, eps: float = SMALL_ERR, eps_cos: float = EPS_COS,
+             workspace: Optional[torch.Tensor] = None) -> IdentifyOutputs:
+    """ge2e_identify on the current stream: for every trial row of ``embeddings`` (R, D) the best ``k`` enrolled speakers
+    of the bank ``models`` (K, D) / ``cnt`` (K,), by `verify_scores`' score (the same bits), equal scores in index order,
+    NaN last.  The (R, K) score matrix is never materialised and the bank axis is split over workgroups where R alone
+    would not fill the chip.  With ``labels`` (as `verify_scores` takes them) a row with a negative label is ignored
+    (never read, all -1), a row whose label is an enrolled speaker has that speaker as its target, and ``rank`` (R,) /
+    ``hist`` (k + 1,) come back as well; without labels they are None.  ``need_scores=False``: ``scores`` is None."""
+    _check_bank(models, cnt)
+    K, D = models.shape
+    dev = models.device
+    e = _bank_rows(embeddings, D, dev)
+    R = e.shape[0]
+    k = int(k)
+    if not 1 <= k <= IDENTIFY_MAX_TOP:
+        raise ValueError(f"k must be in 1 .. {IDENTIFY_MAX_TOP}, got {k}")
+    with _on_device(dev):
+        lab = _bank_labels(labels, K, R, dev) if labels is not None else None
+    i32 = dict(dtype=torch.int32, device=dev)
+    out = IdentifyOutputs(indices=torch.empty(R, k, **i32),
+                          scores=torch.empty(R, k, dtype=torch.float32, device=dev) if need_scores else None,
+                          rank=torch.empty(R, **i32) if lab is not None else None,
+                          hist=torch.empty(k + 1, **i32) if lab is not None else None)
+    _launch_rows("identify", e, (K, R, D, k), workspace, e.data_ptr(), _ptr(lab), models.data_ptr(), cnt.data_ptr(), K, R, D, k,
+                 float(eps_cos), float(eps), out.indices.data_ptr(), _ptr(out.scores), _ptr(out.rank), _ptr(out.hist))
     return out
 
 
