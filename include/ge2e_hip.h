@@ -434,6 +434,61 @@ int ge2e_identify(const float* E, const int* labels /* [R] or NULL */, const flo
                   void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * ADAPTIVE SCORE NORMALISATION, AS-norm (csrc/ge2e_snorm.hip): verification scores normalised with statistics of the
+ * enrolment model and of the trial row, each taken against a COHORT of impostor models.  A cohort is a bank's finalised
+ * form: cohort [C][D] float32 and ccnt [C] int32, 1 <= C <= GE2E_COHORT_MAX; cohort speaker c is a MEMBER iff ccnt[c] > 0,
+ * and the model row of a non-member is never used: it may hold NaN.  The score of (row x, member c) is ge2e_verify_scores'
+ * score, (x . cohort[c]) / max(|x|, eps_cos) + eps, with the same bits.
+ *
+ * ge2e_cohort_stats.  X [R][D]; sel [R] int32 or NULL with sel_min: a row is SCORED iff sel == NULL or sel[r] >= sel_min
+ * (trial rows pass (labels, 0), a bank's own models pass (cnt, 1)).  A row that is not scored is never read and gets
+ * {+0, 1}.  n = min(n_top, number of members); for n = 0 the row gets {+0, 1} as well, with which normalising is the
+ * identity.  Otherwise the n largest member scores are taken, in ge2e_identify's order (fp32 `>`, -0 equal to +0, a NaN
+ * behind every number).  Only the MULTISET of those n values matters -- with v the n-th largest value: every score > v and
+ * n - #{> v} copies of v -- so ties at the boundary need no index rule.
+ *   stats [R][2]   {mean, max(std, eps_std)}: mean = sum / n; std the population one (ddof = 0), two-pass, from the
+ *                  deviations from that mean.  A NaN among the n gives NaN for both.  Every element is written
+ * Launches: per chunk of chunk_rows(C) rows -- a multiple of 64 and a function of C alone, floor(32 MiB / (4 C)) rounded
+ * down to 64 rows and at least 64 -- a rows kernel (the verify rows kernel's shape, the cohort axis split over workgroups as
+ * ge2e_identify splits its bank -- a function of C and the chunk's rows alone; the chunk's scores go into the workspace
+ * as 32-bit keys, [chunk][C]) and a select kernel (one workgroup per row: an exact radix selection of the n-th largest key,
+ * then the sum and the deviations in a fixed order).  The matrix [R][C] is never materialised.  Enqueue-only, no allocation,
+ * no state, no synchronisation, grids from the shapes alone: fit for a HIP graph.  LDS integer atomics only, every sum in
+ * an order fixed by the shapes: the same bits on every launch and whatever the workspace held, a row's statistics do not
+ * depend on where it stands in X, and the chunking does not change them.  Workspace (ge2e_cohort_stats_workspace_bytes,
+ * 256-byte aligned): the keys of one chunk, min(chunk_rows(C), R rounded up to 64) x C x 4 bytes -- at most 32 MiB plus
+ * rounding whatever R is; no initialisation.
+ * Checked on the host before anything is launched, in this order: GE2E_ERR_NULL (X, cohort, ccnt or stats), GE2E_ERR_SHAPE
+ * (C < 1 or > GE2E_COHORT_MAX; R, D or n_top < 1), GE2E_ERR_WORKSPACE (NULL, too small, or not 256-byte aligned),
+ * GE2E_ERR_ALIGN (X or cohort not 16-byte aligned).
+ *
+ * ge2e_verify_scores_normed.  ge2e_verify_scores with row_stats [R][2] and model_stats [K][2] ({mean, spread}, as
+ * ge2e_cohort_stats writes them): the same rules for which rows are scored, their targets, +0 on ignored rows and on
+ * columns that are not enrolled, counts, trials.  The statistics of an ignored row and of a speaker that is not enrolled
+ * are never read and may hold NaN.  With v the verify score of (r, k),
+ *   out = 0.5f * ( fl(fl(v - mu_k) * fl(1 / sd_k)) + fl(fl(v - mu_r) * fl(1 / sd_r)) ),
+ * every operation rounded on its own in fp32, the reciprocal correctly rounded, nothing contracted into an fma.  counts are
+ * taken on `out` (fp32 strict `>`; a NaN accepts nothing and is still tallied in trials).  Nothing is clamped here:
+ * ge2e_cohort_stats did.  With both tables {0, 1} the output has ge2e_verify_scores' bits.  A zeroing launch when counts
+ * or trials are wanted, then one rows kernel (streamed form); no workspace; fit for a HIP graph.
+ * Checks, in this order: GE2E_ERR_NULL (E, models, cnt, row_stats or model_stats NULL; both scores and counts NULL; counts
+ * or trials without labels), GE2E_ERR_SHAPE and GE2E_ERR_ALIGN as for ge2e_verify_scores.
+ */
+#define GE2E_COHORT_MAX 65536
+size_t ge2e_cohort_stats_workspace_bytes(int C, int R, int D, int n_top);   /* 0 for a bad shape */
+int ge2e_cohort_stats(const float* X, const int* sel /* [R] or NULL */, int sel_min, const float* cohort, const int* ccnt,
+                      int C, int R, int D, int n_top, float eps_cos, float eps, float eps_std,
+                      float* stats /* [R][2] */, void* workspace, size_t workspace_bytes, void* stream);
+int ge2e_verify_scores_normed(const float* E, const int* labels /* [R] or NULL */, const float* models, const int* cnt,
+                              int K, int R, int D, float eps_cos, float eps,
+                              const float* row_stats /* [R][2] */, const float* model_stats /* [K][2] */,
+                              const float* thresholds, int T,       /* NULL / 0: no counts */
+                              float* scores,   /* [R][K] or NULL */
+                              int* counts,     /* [T][2] or NULL */
+                              int* trials,     /* [2]    or NULL */
+                              void* stream);
+
+/*
  * The same, fed with the encoder's RAW output (s2_model_GE2E_loss_speach_embed.py:34 +
  * s4_train_embed_model.py:186-192 folded into the loss kernel's load and store stages):
  *   Y   [B][N*M][D]  the encoder's projection BEFORE its L2-normalisation, rows in the encoder's own (permuted) order
@@ -621,6 +676,14 @@ size_t ge2e_selftest_identify_workspace_bytes(int K, int R, int D, int k_top, in
 int ge2e_selftest_identify_slices(const float* E, const int* labels, const float* models, const int* cnt, int K, int R, int D,
                                   int k_top, float eps_cos, float eps, int* idx, float* score, int* rank, int* hist,
                                   void* workspace, size_t workspace_bytes, void* stream, int slices);
+
+/* ge2e_cohort_stats with the chunk forced to `chunk_rows` rows (rounded up to a multiple of 64; <= 0 = the product's choice),
+ * so that a small R crosses chunk boundaries.  The workspace must be ge2e_selftest_cohort_stats_workspace_bytes(C, R, D,
+ * n_top, chunk_rows).  Same checks and results (bit for bit): for the tests of the chunking and for tools/bench_snorm.py. */
+size_t ge2e_selftest_cohort_stats_workspace_bytes(int C, int R, int D, int n_top, int chunk_rows);
+int ge2e_selftest_cohort_stats_chunk(const float* X, const int* sel, int sel_min, const float* cohort, const int* ccnt, int C,
+                                     int R, int D, int n_top, float eps_cos, float eps, float eps_std, float* stats,
+                                     void* workspace, size_t workspace_bytes, void* stream, int chunk_rows);
 
 #ifdef __cplusplus
 }

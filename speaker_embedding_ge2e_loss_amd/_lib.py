@@ -75,6 +75,14 @@ PROTOTYPES = {
     "ge2e_selftest_identify_workspace_bytes": (C.c_size_t, [C.c_int] * 5),
     "ge2e_selftest_identify_slices": (C.c_int, [_fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
                                                 _fp, _fp, _fp, _fp, _fp, C.c_size_t, _fp, C.c_int]),
+    "ge2e_cohort_stats_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
+    "ge2e_cohort_stats": (C.c_int, [_fp, _fp, C.c_int, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
+                                    C.c_float, _fp, _fp, C.c_size_t, _fp]),
+    "ge2e_verify_scores_normed": (C.c_int, [_fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _fp, _fp,
+                                            _fp, C.c_int, _fp, _fp, _fp, _fp]),
+    "ge2e_selftest_cohort_stats_workspace_bytes": (C.c_size_t, [C.c_int] * 5),
+    "ge2e_selftest_cohort_stats_chunk": (C.c_int, [_fp, _fp, C.c_int, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                                                   C.c_float, C.c_float, _fp, _fp, C.c_size_t, _fp, C.c_int]),
     "ge2e_raw_supported": (C.c_int, [C.c_int] * 3),
     "ge2e_loss_fwd_bwd_raw": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, C.c_float, C.c_float,
                                         C.c_int, _fp, _fp, _fp, _fp, _fp, _fp]),

@@ -15,6 +15,7 @@
 #include "ge2e_labeled_helpers.hpp"
 #include "ge2e_enroll.hpp"
 #include "ge2e_identify.hpp"
+#include "ge2e_snorm.hpp"
 #include "ge2e_helpers.hpp"
 #include "ge2e_fused.hpp"
 #include "ge2e_selftest.hpp"
@@ -538,6 +539,62 @@ int ge2e_identify(const float* E, const int* labels, const float* models, const 
                   size_t workspace_bytes, void* stream) {
     return ge2e_selftest_identify_slices(E, labels, models, cnt, K, R, D, k_top, eps_cos, eps, idx, score, rank, hist, workspace,
                                          workspace_bytes, stream, 0);
+}
+
+// SCORE NORMALISATION (include/ge2e_hip.h, csrc/ge2e_snorm.hip).  The product call is the selftest entry with the chunk
+// left to cohort_chunk_rows.
+size_t ge2e_selftest_cohort_stats_workspace_bytes(int C, int R, int D, int n_top, int chunk_rows) {
+    if (C < 1 || C > GE2E_COHORT_MAX || R < 1 || D < 1 || n_top < 1) return 0;
+    return cohort_workspace_bytes(C, R, cohort_chunk_rows(C, chunk_rows));
+}
+
+size_t ge2e_cohort_stats_workspace_bytes(int C, int R, int D, int n_top) {
+    return ge2e_selftest_cohort_stats_workspace_bytes(C, R, D, n_top, 0);
+}
+
+int ge2e_selftest_cohort_stats_chunk(const float* X, const int* sel, int sel_min, const float* cohort, const int* ccnt, int C,
+                                     int R, int D, int n_top, float eps_cos, float eps, float eps_std, float* stats,
+                                     void* workspace, size_t workspace_bytes, void* stream, int chunk_rows) {
+    if (!X || !cohort || !ccnt || !stats) return GE2E_ERR_NULL;
+    if (C < 1 || C > GE2E_COHORT_MAX || R < 1 || D < 1 || n_top < 1) return GE2E_ERR_SHAPE;
+    const int chunk = cohort_chunk_rows(C, chunk_rows);
+    if (!workspace_ok(workspace, workspace_bytes, cohort_workspace_bytes(C, R, chunk))) return GE2E_ERR_WORKSPACE;
+    if (!aligned16(X) || !aligned16(cohort)) return GE2E_ERR_ALIGN;
+    ProblemCohort p{};
+    p.X = X; p.sel = sel; p.cohort = cohort; p.ccnt = ccnt;
+    p.stats = stats;
+    p.keys = (unsigned*)workspace;
+    p.C = C; p.R = R; p.D = D; p.n_top = n_top; p.sel_min = sel_min;
+    p.eps_cos = eps_cos; p.eps = eps; p.eps_std = eps_std;
+    return (int)launch_cohort_stats(p, chunk, (hipStream_t)stream);
+}
+
+int ge2e_cohort_stats(const float* X, const int* sel, int sel_min, const float* cohort, const int* ccnt, int C, int R, int D,
+                      int n_top, float eps_cos, float eps, float eps_std, float* stats, void* workspace, size_t workspace_bytes,
+                      void* stream) {
+    return ge2e_selftest_cohort_stats_chunk(X, sel, sel_min, cohort, ccnt, C, R, D, n_top, eps_cos, eps, eps_std, stats, workspace,
+                                            workspace_bytes, stream, 0);
+}
+
+int ge2e_verify_scores_normed(const float* E, const int* labels, const float* models, const int* cnt, int K, int R, int D,
+                              float eps_cos, float eps, const float* row_stats, const float* model_stats,
+                              const float* thresholds, int T, float* scores, int* counts, int* trials, void* stream) {
+    if (!E || !models || !cnt || !row_stats || !model_stats || (!scores && !counts) || (!labels && (counts || trials)))
+        return GE2E_ERR_NULL;
+    if (K < 1 || R < 1 || D < 1 || T < 0 || T > 4096 || (counts && (!thresholds || T == 0)) ||
+        ((counts || trials) && (long long)R * K > 2147483647LL))
+        return GE2E_ERR_SHAPE;
+    if (!aligned16(E) || !aligned16(models)) return GE2E_ERR_ALIGN;
+    ProblemVerifyNormed pn{};
+    ProblemVerify& p = pn.v;
+    p.E = E; p.labels = labels; p.models = models; p.cnt = cnt;
+    p.thr = counts ? thresholds : nullptr;
+    p.scores = scores; p.counts = counts; p.trials = trials;
+    p.K = K; p.R = R; p.D = D;
+    p.T = counts ? T : 0;
+    p.eps_cos = eps_cos; p.eps = eps;
+    pn.row_stats = row_stats; pn.model_stats = model_stats;
+    return (int)launch_verify_scores_normed(pn, (hipStream_t)stream);
 }
 
 // The DIFFERENTIABLE labelled helpers (include/ge2e_hip.h).  ge2e_cos_sim_labeled_bwd: stateless like every entry -- the

@@ -132,9 +132,12 @@ class SpeakerBank:
         self.sums = torch.zeros(int(num_speakers), int(dim), dtype=torch.float32, device=self.device)
         self.cnt = torch.zeros(int(num_speakers), dtype=torch.int32, device=self.device)
         self._models = None
+        self._cohort = None          # (cohort bank, n_top, eps_std) of set_cohort
+        self._model_stats = None     # the models' (mean, spread) against the cohort: lazily, as _models
 
     def enroll(self, emb: torch.Tensor, ids) -> None:
         self._models = None
+        self._model_stats = None
         GF.enroll_accumulate(self.sums, self.cnt, emb, ids)
 
     def models(self) -> torch.Tensor:
@@ -142,13 +145,54 @@ class SpeakerBank:
             self._models = GF.enroll_finalize(self.sums, self.cnt)
         return self._models
 
-    def score(self, emb: torch.Tensor) -> torch.Tensor:
-        """(R, D) -> scores (R, num_speakers): the cosine of every row with every enrolled model (+ eps), 0 elsewhere."""
-        return GF.verify_scores(emb, self.models(), self.cnt).scores
+    def set_cohort(self, cohort_bank: "SpeakerBank", n_top: int = 300, eps_std: float = 1e-5) -> None:
+        """The cohort of impostor speakers that ``normalize=True`` scores against: another bank of the same dimension on
+        the same device, a disjoint set of speakers.  The statistics of this bank's models against it are computed on the
+        first normalised call and again after every ``enroll`` (of this bank) or ``set_cohort``; the cohort's own models
+        are read when they are needed, so the cohort bank may still be enrolled into."""
+        if not isinstance(cohort_bank, SpeakerBank):
+            raise TypeError("cohort_bank must be a SpeakerBank")
+        if cohort_bank.sums.shape[1] != self.sums.shape[1] or cohort_bank.device != self.device:
+            raise ValueError(f"the cohort must have dimension {self.sums.shape[1]} on {self.device}")
+        if int(n_top) < 1:
+            raise ValueError(f"n_top must be at least 1, got {n_top}")
+        self._cohort = (cohort_bank, int(n_top), float(eps_std))
+        self._model_stats = None
 
-    def verify(self, emb: torch.Tensor, ids, thresholds=THRESHOLDS, need_scores: bool = True) -> GF.VerifyOutputs:
-        """Labelled trials: scores, accept counts per threshold and the numbers of impostor and target trials."""
-        return GF.verify_scores(emb, self.models(), self.cnt, labels=ids, thresholds=thresholds, need_scores=need_scores)
+    def _stats(self, rows: torch.Tensor, select, select_min: int) -> torch.Tensor:
+        if self._cohort is None:
+            raise ValueError("normalize=True needs a cohort: call set_cohort first")
+        bank, n_top, eps_std = self._cohort
+        return GF.cohort_stats(rows, bank.models(), bank.cnt, n_top=n_top, select=select, select_min=select_min, eps_std=eps_std)
+
+    def model_stats(self) -> torch.Tensor:
+        """(num_speakers, 2): mean and spread of every enrolled model's best cohort scores; (0, 1) where nobody is enrolled."""
+        if self._cohort is None:
+            raise ValueError("normalize=True needs a cohort: call set_cohort first")
+        if self._model_stats is None:
+            self._model_stats = self._stats(self.models(), self.cnt, 1)
+        return self._model_stats
+
+    def score(self, emb: torch.Tensor, normalize: bool = False) -> torch.Tensor:
+        """(R, D) -> scores (R, num_speakers): the cosine of every row with every enrolled model (+ eps), 0 elsewhere.
+        ``normalize=True``: AS-norm against the cohort of ``set_cohort``."""
+        if not normalize:
+            return GF.verify_scores(emb, self.models(), self.cnt).scores
+        model_stats = self.model_stats()
+        return GF.verify_scores_normed(emb, self.models(), self.cnt, self._stats(emb, None, 0), model_stats).scores
+
+    def verify(self, emb: torch.Tensor, ids, thresholds=THRESHOLDS, need_scores: bool = True,
+               normalize: bool = False) -> GF.VerifyOutputs:
+        """Labelled trials: scores, accept counts per threshold and the numbers of impostor and target trials.
+        ``normalize=True``: scores and counts of the AS-normalised scores (``thresholds`` are then on that scale)."""
+        if not normalize:
+            return GF.verify_scores(emb, self.models(), self.cnt, labels=ids, thresholds=thresholds, need_scores=need_scores)
+        model_stats = self.model_stats()
+        K = self.cnt.shape[0]
+        with torch.cuda.device(self.device):
+            lab = GF._bank_labels(ids, K, emb.shape[0], self.device)
+        return GF.verify_scores_normed(emb, self.models(), self.cnt, self._stats(emb, lab, 0), model_stats, labels=lab,
+                                       thresholds=thresholds, need_scores=need_scores)
 
     def identify(self, emb: torch.Tensor, k: int = 1, ids=None) -> GF.IdentifyOutputs:
         """(R, D) -> the best ``k`` enrolled speakers of every row and their scores; with ``ids`` also the position of each
@@ -175,12 +219,16 @@ def eer_from_trial_counts(counts, n_imp: int, n_tgt: int, thresholds=THRESHOLDS)
 
 
 def evaluate_enrolled(model, enroll_loader, trial_loader, num_speakers: int, device="cuda:0", thresholds=THRESHOLDS,
-                      verbose: bool = True):
+                      verbose: bool = True, cohort=None, n_top: int = 300):
     """Speaker verification as it is used: both loaders yield (mel, speaker_ids), the ids being bank indices in
     [0, num_speakers).  Every enrolment batch goes into one `SpeakerBank`; every trial batch is scored against it with
     ``need_scores=False`` -- no score matrix is materialised -- and its counts and trial numbers are added on the device in
     int64; ONE read-back at the end.  Returns ONE result over the whole trial set: the dict of `eer_from_trial_counts`
-    with ``n_imp`` and ``n_tgt`` added."""
+    with ``n_imp`` and ``n_tgt`` added.  ``cohort`` (a `SpeakerBank` of impostor speakers): every trial batch is
+    AS-normalised against it over its ``n_top`` best; ``thresholds`` must then be passed, on the normalised scale -- the
+    reference's table 0.5 .. 0.99 is one of cosines."""
+    if cohort is not None and thresholds is THRESHOLDS:
+        raise ValueError("thresholds must be passed with a cohort: the default table is one of cosines, not of normalised scores")
     T = len(thresholds)
     bank = None
     total = None
@@ -196,9 +244,11 @@ def evaluate_enrolled(model, enroll_loader, trial_loader, num_speakers: int, dev
         if bool((thr[1:] < thr[:-1]).any()):
             raise ValueError("thresholds must be non-decreasing")
         thr = thr.to(bank.device)              # uploaded once: a device table is taken as it is
+        if cohort is not None:
+            bank.set_cohort(cohort, n_top=n_top)
         for mel, speaker_ids in trial_loader:
             emb = model(mel.to(device)).contiguous().float()
-            out = bank.verify(emb, speaker_ids, thresholds=thr, need_scores=False)
+            out = bank.verify(emb, speaker_ids, thresholds=thr, need_scores=False, normalize=cohort is not None)
             part = torch.cat([out.counts.reshape(-1), out.trials]).to(torch.int64)
             total = part if total is None else total + part
     back = total.cpu().numpy() if total is not None else [0] * (2 * T + 2)   # the one read-back

@@ -182,6 +182,7 @@ _ENTRIES = {
     "labeled_cos_bwd": _Entry("ge2e_cos_sim_labeled_bwd", "ge2e_cos_sim_labeled_bwd_workspace_bytes", ("labeled_cos_bwd",)),
     "enroll": _Entry("ge2e_enroll_accumulate", "ge2e_enroll_workspace_bytes", ("enroll",)),
     "identify": _Entry("ge2e_identify", "ge2e_identify_workspace_bytes", ("identify",)),
+    "cohort": _Entry("ge2e_cohort_stats", "ge2e_cohort_stats_workspace_bytes", ("cohort",)),
 }
 
 
@@ -966,6 +967,92 @@ def identify(embeddings: torch.Tensor, models: torch.Tensor, cnt: torch.Tensor, 
                           hist=torch.empty(k + 1, **i32) if lab is not None else None)
     _launch_rows("identify", e, (K, R, D, k), workspace, e.data_ptr(), _ptr(lab), models.data_ptr(), cnt.data_ptr(), K, R, D, k,
                  float(eps_cos), float(eps), out.indices.data_ptr(), _ptr(out.scores), _ptr(out.rank), _ptr(out.hist))
+    return out
+
+
+# ---- score normalisation against a cohort, AS-norm (csrc/ge2e_snorm.hip) ---------------------------------------------------
+
+COHORT_MAX = 65536       # GE2E_COHORT_MAX
+EPS_STD = 1e-5
+
+
+def cohort_stats(rows: torch.Tensor, cohort_models: torch.Tensor, cohort_cnt: torch.Tensor, n_top: int = 300, select=None,
+                 select_min: int = 0, eps: float = SMALL_ERR, eps_cos: float = EPS_COS, eps_std: float = EPS_STD,
+                 workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ge2e_cohort_stats on the current stream -> ``stats`` (R, 2) float32: for every row of ``rows`` (R, D) the mean and the
+    population spread (at least ``eps_std``) of its ``n_top`` best scores against the members of the cohort
+    ``cohort_models`` (C, D) / ``cohort_cnt`` (C,) -- a finalised bank; a member has cnt > 0 -- by `verify_scores`' score.
+    ``select`` (R,) with ``select_min``: only the rows with select >= select_min are scored; the others are never read and
+    get (0, 1), as every row does when the cohort has no member.  Trial rows pass their labels and 0, a bank's own models
+    its ``cnt`` and 1.  The (R, C) matrix is never materialised: at most 32 MiB of it at a time."""
+    _check_bank(cohort_models, cohort_cnt)
+    C, D = cohort_models.shape
+    dev = cohort_models.device
+    x = _bank_rows(rows, D, dev)
+    R = x.shape[0]
+    n_top = int(n_top)
+    if n_top < 1:
+        raise ValueError(f"n_top must be at least 1, got {n_top}")
+    if C > COHORT_MAX:
+        raise ValueError(f"a cohort holds at most {COHORT_MAX} speakers, got {C}")
+    with _on_device(dev):
+        sel = _selector(select, R, dev) if select is not None else None
+    stats =torch.empty(R, 2, dtype=torch.float32, device=dev)
+    _launch_rows("cohort", x, (C, R, D, n_top), workspace, x.data_ptr(), _ptr(sel), int(select_min), cohort_models.data_ptr(),
+                 cohort_cnt.data_ptr(), C, R, D, n_top, float(eps_cos), float(eps), float(eps_std), stats.data_ptr())
+    return stats
+
+
+def _selector(select, R: int, dev: torch.device) -> torch.Tensor:
+    """(R,) int32 on `dev`: a device torch.int32 tensor (a bank's cnt, a label vector) is taken as it is; 64-bit and host
+    integers are clamped into the int32 range before they are narrowed, so that their order against select_min stays."""
+    if torch.is_tensor(select) and select.device.type != "cpu" and select.device != dev:
+        raise RuntimeError(f"select is on {select.device}, the cohort on {dev}: raw pointers cross the C ABI, all on one device")
+    raw = select if torch.is_tensor(select) else torch.as_tensor(select)
+    if raw.is_floating_point() or raw.is_complex() or raw.dtype == torch.bool:
+        raise TypeError(f"select must be integers, got {raw.dtype}")
+    if raw.dim() != 1 or raw.shape[0] != R:
+        raise ValueError(f"select must be ({R},), got {tuple(raw.shape)}")
+    if raw.dtype != torch.int32:
+        raw = raw.to(torch.int64).clamp(-2 ** 31, 2 ** 31 - 1).to(torch.int32)
+    return raw.to(dev).contiguous()
+
+
+def _check_stats(t: torch.Tensor, n: int, dev: torch.device, name: str) -> torch.Tensor:
+    if not torch.is_tensor(t) or t.dtype != torch.float32 or tuple(t.shape) != (n, 2) or t.device != dev or not t.is_contiguous():
+        raise TypeError(f"{name} must be a contiguous ({n}, 2) torch.float32 tensor on {dev}")
+    return t
+
+
+def verify_scores_normed(embeddings: torch.Tensor, models: torch.Tensor, cnt: torch.Tensor, row_stats: torch.Tensor,
+                         model_stats: torch.Tensor, labels=None, thresholds=None, need_scores: bool = True,
+                         eps: float = SMALL_ERR, eps_cos: float = EPS_COS) -> VerifyOutputs:
+    """ge2e_verify_scores_normed on the current stream: `verify_scores` whose every score v of (row r, enrolled speaker k)
+    becomes 0.5 ((v - mu_k) / sd_k + (v - mu_r) / sd_r) before it is stored and counted, with ``row_stats`` (R, 2) and
+    ``model_stats`` (K, 2) the (mean, spread) pairs of `cohort_stats` for the trial rows and for the bank's models.  The
+    same arguments, outputs and rules otherwise; with both tables (0, 1) the same bits."""
+    _check_bank(models, cnt)
+    K, D = models.shape
+    dev = models.device
+    e = _bank_rows(embeddings, D, dev)
+    R = e.shape[0]
+    _check_stats(row_stats, R, dev, "row_stats")
+    _check_stats(model_stats, K, dev, "model_stats")
+    if labels is None and (thresholds is not None or not need_scores):
+        raise ValueError("counts are about targets and impostors: thresholds / need_scores=False need labels")
+    if thresholds is None and not need_scores:
+        raise ValueError("nothing to compute: need_scores=False without thresholds")
+    with _on_device(dev):
+        lab = _bank_labels(labels, K, R, dev) if labels is not None else None
+        thr = _threshold_table(thresholds, dev, device_ok=True) if thresholds is not None else None
+    T = thr.numel() if thr is not None else 0
+    i32 = dict(dtype=torch.int32, device=dev)
+    out = VerifyOutputs(scores=torch.empty(R, K, dtype=torch.float32, device=dev) if need_scores else None,
+                        counts=torch.empty(T, 2, **i32) if T else None,
+                        trials=torch.empty(2, **i32) if lab is not None else None)
+    _launch("ge2e_verify_scores_normed", dev, e.data_ptr(), _ptr(lab), models.data_ptr(), cnt.data_ptr(), K, R, D,
+            float(eps_cos), float(eps), row_stats.data_ptr(), model_stats.data_ptr(), _ptr(thr), T, _ptr(out.scores),
+            _ptr(out.counts), _ptr(out.trials), _stream_ptr(e))
     return out
 
 
