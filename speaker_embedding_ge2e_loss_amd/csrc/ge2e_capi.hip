@@ -482,10 +482,14 @@ int ge2e_enroll_finalize(const float* sums, const int* cnt, int K, int D, float 
     return (int)launch_enroll_finalize(sums, cnt, K, D, eps_cos, models, (hipStream_t)stream);
 }
 
-int ge2e_selftest_verify_form(const float* E, const int* labels, const float* models, const int* cnt, int K, int R, int D,
-                              float eps_cos, float eps, const float* thresholds, int T, float* scores, int* counts, int* trials,
-                              void* stream, int form) {
-    if (!E || !models || !cnt || (!scores && !counts) || (!labels && (counts || trials))) return GE2E_ERR_NULL;
+// The checks, the launch description and the launch of every verification call: ge2e_verify_scores[_normed] and the selftest
+// entry.  `normed`: the two tables of {mean, spread} are wanted (and the streamed form is taken).
+static int verify_call(const float* E, const int* labels, const float* models, const int* cnt, int K, int R, int D,
+                       float eps_cos, float eps, bool normed, const float* row_stats, const float* model_stats,
+                       const float* thresholds, int T, float* scores, int* counts, int* trials, void* stream, int form) {
+    if (!E || !models || !cnt || (normed && (!row_stats || !model_stats)) || (!scores && !counts) ||
+        (!labels && (counts || trials)))
+        return GE2E_ERR_NULL;
     if (K < 1 || R < 1 || D < 1 || T < 0 || T > 4096 || (counts && (!thresholds || T == 0)) ||
         ((counts || trials) && (long long)R * K > 2147483647LL) || form < VERIFY_AUTO || form > VERIFY_STREAMED)
         return GE2E_ERR_SHAPE;
@@ -494,10 +498,18 @@ int ge2e_selftest_verify_form(const float* E, const int* labels, const float* mo
     p.E = E; p.labels = labels; p.models = models; p.cnt = cnt;
     p.thr = counts ? thresholds : nullptr;
     p.scores = scores; p.counts = counts; p.trials = trials;
+    if (normed) { p.row_stats = row_stats; p.model_stats = model_stats; }
     p.K = K; p.R = R; p.D = D;
     p.T = counts ? T : 0;
     p.eps_cos = eps_cos; p.eps = eps;
     return (int)launch_verify_scores(p, (VerifyForm)form, (hipStream_t)stream);
+}
+
+int ge2e_selftest_verify_form(const float* E, const int* labels, const float* models, const int* cnt, int K, int R, int D,
+                              float eps_cos, float eps, const float* thresholds, int T, float* scores, int* counts, int* trials,
+                              void* stream, int form) {
+    return verify_call(E, labels, models, cnt, K, R, D, eps_cos, eps, false, nullptr, nullptr, thresholds, T, scores, counts,
+                       trials, stream, form);
 }
 
 int ge2e_verify_scores(const float* E, const int* labels, const float* models, const int* cnt, int K, int R, int D, float eps_cos,
@@ -579,22 +591,8 @@ int ge2e_cohort_stats(const float* X, const int* sel, int sel_min, const float* 
 int ge2e_verify_scores_normed(const float* E, const int* labels, const float* models, const int* cnt, int K, int R, int D,
                               float eps_cos, float eps, const float* row_stats, const float* model_stats,
                               const float* thresholds, int T, float* scores, int* counts, int* trials, void* stream) {
-    if (!E || !models || !cnt || !row_stats || !model_stats || (!scores && !counts) || (!labels && (counts || trials)))
-        return GE2E_ERR_NULL;
-    if (K < 1 || R < 1 || D < 1 || T < 0 || T > 4096 || (counts && (!thresholds || T == 0)) ||
-        ((counts || trials) && (long long)R * K > 2147483647LL))
-        return GE2E_ERR_SHAPE;
-    if (!aligned16(E) || !aligned16(models)) return GE2E_ERR_ALIGN;
-    ProblemVerifyNormed pn{};
-    ProblemVerify& p = pn.v;
-    p.E = E; p.labels = labels; p.models = models; p.cnt = cnt;
-    p.thr = counts ? thresholds : nullptr;
-    p.scores = scores; p.counts = counts; p.trials = trials;
-    p.K = K; p.R = R; p.D = D;
-    p.T = counts ? T : 0;
-    p.eps_cos = eps_cos; p.eps = eps;
-    pn.row_stats = row_stats; pn.model_stats = model_stats;
-    return (int)launch_verify_scores_normed(pn, (hipStream_t)stream);
+    return verify_call(E, labels, models, cnt, K, R, D, eps_cos, eps, true, row_stats, model_stats, thresholds, T, scores,
+                       counts, trials, stream, VERIFY_STREAMED);
 }
 
 // The DIFFERENTIABLE labelled helpers (include/ge2e_hip.h).  ge2e_cos_sim_labeled_bwd: stateless like every entry -- the

@@ -10,6 +10,11 @@ namespace ge2e {
 
 constexpr int kCountThreads = 256, kCountWaves = kCountThreads / kWave;
 
+// The zeroing launch in front of a call that adds into integer outputs: a[0 .. n) = 0 and b[0 .. nb) = 0, nb <= 256; a
+// pointer whose count is 0 is not touched.  One kernel for every such call (ge2e_labeled_eval.hip); a launch, not a memset
+// node: the calls are captured into graphs as launches.  (Hidden: the library's symbol table stays as it was.)
+__attribute__((visibility("hidden"))) hipError_t launch_zero_ints(int* a, size_t n, int* b, int nb, hipStream_t stream);
+
 // LDS: hist [2][T+1] (false accepts, own accepts), then the T thresholds.
 __device__ __forceinline__ void counting_begin(int* hist, float* thr_lds, const float* thr, int T) {
     for (int t = threadIdx.x; t < 2 * (T + 1); t += kCountThreads) hist[t] = 0;

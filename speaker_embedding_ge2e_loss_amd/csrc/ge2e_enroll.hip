@@ -6,10 +6,11 @@
 //               valid row on), one WAVE per compact speaker k: the speaker's rows E[order[p]], p = off[k] .. off[k+1]-1,
 //               summed from 0 in ascending p (ascending row index: the sort is stable), then ONE read-modify-write of
 //               sums[speakers[k]] and cnt[speakers[k]].  The row indices of up to 64 positions come with one coalesced
-//               load and are handed out with v_readlane, as in labeled_eval_centroids_kernel.  Exactly one wave touches a
-//               speaker per launch and a speaker without a valid row is touched by none: no atomics, a fixed order.
-//   finalize    one wave per speaker: models[s] = c / max(|c|, eps_cos), c = sums[s] / cnt[s], in the centroid kernel's
-//               arithmetic (unit_stats, then s / m * rn); +0 where cnt[s] <= 0, and sums[s] is not read there.
+//               load and are handed out with v_readlane: speaker_sum (ge2e_rows_dev.hpp), the step that
+//               labeled_eval_centroids_kernel runs.  Exactly one wave touches a speaker per launch and a speaker without a
+//               valid row is touched by none: no atomics, a fixed order.
+//   finalize    one wave per speaker: models[s] = c / max(|c|, eps_cos), c = sums[s] / cnt[s], with the centroid kernel's
+//               own steps (mean_sq, unit_stats, unit_scale: s / m * rn); +0 where cnt[s] <= 0, and sums[s] is not read there.
 //   rows        one 256-thread workgroup per 64 trial rows IN THE CALLER'S ORDER (no sort, no index kernel), 16 rows per
 //               wave.  Row norms on the MFMA's own row fragments (tile_rows_plain), then models . E^T over K = D on
 //               v_mfma_f32_16x16x4_f32 with the operand map of ge2e_rows_dev.hpp: a lane ends with four consecutive columns
@@ -26,9 +27,15 @@
 //                           figures can be taken again.
 //               Both walk k in the same order, lane group q taking the elements 16 s + 4 q .. + 3 of step s: an output
 //               element is the same fmaf chain either way, whatever its workgroup, wave or lane.
-//               Epilogue: x 1 / |e_r|, + eps, 0 where cnt[k] <= 0, a 16-byte store where K % 4 == 0 and scores is aligned;
-//               with counts every value of an enrolled column is binned (ge2e_counting_dev.hpp) as own where k is the
-//               row's target and as impostor otherwise, and tallied in trials.  Integer atomics only.
+//               Epilogue: x 1 / |e_r|, + eps (raw_score, ge2e_bank_dev.hpp), 0 where cnt[k] <= 0, a 16-byte store where
+//               K % 4 == 0 and scores is aligned; with counts every value of an enrolled column is binned
+//               (ge2e_counting_dev.hpp) as own where k is the row's target and as impostor otherwise, and tallied in
+//               trials.  Integer atomics only.
+//   normed      ge2e_verify_scores_normed (AS-norm, ge2e_snorm.hip has the statistics) is the SAME rows kernel, streamed,
+//               with kNormed: the score v of an enrolled column becomes 0.5 ((v - mu_k) (1 / sd_k) + (v - mu_r) (1 / sd_r)),
+//               every operation rounded on its own (no contraction), and that value is stored and counted.  mu_r and
+//               1 / sd_r are read once per tile and only for a scored row, model_stats[k] only for an enrolled column.
+//               Everything else -- labels, targets, ignored rows, counting, tallies, barriers -- is the one text.
 // Every index read from memory is clamped or range-checked where it is read (active, offsets, order, speakers; a label
 // indexes cnt only after 0 <= label < K): whatever labels, cnt and the workspace hold, no access leaves the buffers.
 #include "ge2e_enroll.hpp"
@@ -37,15 +44,13 @@
 
 #include <algorithm>
 
+#include "ge2e_bank_dev.hpp"
 #include "ge2e_counting_dev.hpp"
-#include "ge2e_rows_dev.hpp"
 
 namespace ge2e {
 
 namespace {
-constexpr int kThreads = 256, kWaves = kThreads / kWave;
-constexpr int kTile = 64, kWaveRows = kTile / kWaves;   // trial rows per workgroup / per wave
-constexpr int kAcc = 4;                                 // column tiles (accumulators) in flight per wave
+using namespace tile_geom;                              // kThreads, kWaves, kTile, kWaveRows, kAcc
 constexpr int kGroup = 16 * kAcc;                       // models per group
 constexpr int kChunk = 64;                              // elements of k per staged tile: four MFMA steps of 16
 constexpr int kStageFloats = kGroup * kChunk;           // one staging buffer, 16 KiB
@@ -71,24 +76,10 @@ __global__ __launch_bounds__(kThreads) void enroll_accumulate_kernel(const float
         if (r1 == r0) continue;
         const int sp = clampi(speakers[k], 0, K - 1);
         float* S = sums + (size_t)sp * D;
-        // a lane owns 4 (vecD) or 1 element of every stretch of 256 / 64; rows in ascending position
-        const int stretch = vecD ? 4 * kWave : kWave;
-        for (int d0 = 0; d0 < D; d0 += stretch) {
-            const int d = d0 + (vecD ? 4 * lane : lane);
+        for (int d0 = 0; d0 < D; d0 += wave_stretch(vecD)) {
+            const int d = wave_elem(d0, lane, vecD);
             const bool ok = d < D;
-            v4f s = {0.f, 0.f, 0.f, 0.f};
-            for (int c0 = r0; c0 < r1; c0 += kWave) {
-                const int pp = c0 + lane;
-                const int idx = pp < r1 ? clampi(order[pp], 0, R - 1) : 0;   // one coalesced load for up to 64 rows
-                const int n = min(kWave, r1 - c0);
-                for (int i = 0; i < n; ++i) {
-                    const float* er = E + (size_t)__builtin_amdgcn_readlane(idx, i) * D;
-                    if (ok) {
-                        if (vecD) s += *reinterpret_cast<const v4f*>(er + d);
-                        else s[0] += er[d];
-                    }
-                }
-            }
+            const v4f s = speaker_sum(E, order, r0, r1, R, D, d, ok, vecD);
             if (ok) {   // the bank takes the partial sum once
                 if (vecD) *reinterpret_cast<v4f*>(S + d) = *reinterpret_cast<const v4f*>(S + d) + s;
                 else S[d] = S[d] + s[0];
@@ -102,7 +93,6 @@ __global__ __launch_bounds__(kThreads) void enroll_finalize_kernel(const float* 
                                                                     int K, int D, float eps_cos, float* __restrict__ models) {
     const int lane = threadIdx.x & 63;
     const bool vecD = (D & 3) == 0 && (((uintptr_t)sums | (uintptr_t)models) & 15) == 0;
-    const int stretch = vecD ? 4 * kWave : kWave;
     const int nwaves = gridDim.x * kWaves;
     const v4f zero4 = {0.f, 0.f, 0.f, 0.f};
     for (int sp = blockIdx.x * kWaves + (threadIdx.x >> 6); sp < K; sp += nwaves) {
@@ -110,8 +100,8 @@ __global__ __launch_bounds__(kThreads) void enroll_finalize_kernel(const float* 
         const float* S = sums + (size_t)sp * D;
         float* M = models + (size_t)sp * D;
         if (m <= 0) {
-            for (int d0 = 0; d0 < D; d0 += stretch) {
-                const int d = d0 + (vecD ? 4 * lane : lane);
+            for (int d0 = 0; d0 < D; d0 += wave_stretch(vecD)) {
+                const int d = wave_elem(d0, lane, vecD);
                 if (d < D) {
                     if (vecD) *reinterpret_cast<v4f*>(M + d) = zero4;
                     else M[d] = 0.f;
@@ -121,51 +111,42 @@ __global__ __launch_bounds__(kThreads) void enroll_finalize_kernel(const float* 
         }
         const float fm = (float)m;
         float sq = 0.f;
-        for (int d0 = 0; d0 < D; d0 += stretch) {
-            const int d = d0 + (vecD ? 4 * lane : lane);
+        for (int d0 = 0; d0 < D; d0 += wave_stretch(vecD)) {
+            const int d = wave_elem(d0, lane, vecD);
             if (d < D) {
-                if (vecD) {
-                    const v4f s = *reinterpret_cast<const v4f*>(S + d);
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) { const float c = s[t] / fm; sq += c * c; }
-                } else {
-                    const float c = S[d] / fm;
-                    sq += c * c;
-                }
+                v4f s = {0.f, 0.f, 0.f, 0.f};
+                if (vecD) s = *reinterpret_cast<const v4f*>(S + d);
+                else s[0] = S[d];
+                sq = mean_sq(sq, s, fm, vecD);
             }
         }
         sq = wave_sum(sq);
         float rn, kap;
         unit_stats(sq, eps_cos, rn, kap);
-        for (int d0 = 0; d0 < D; d0 += stretch) {
-            const int d = d0 + (vecD ? 4 * lane : lane);
-            if (d < D) {
-                if (vecD) {
-                    const v4f s = *reinterpret_cast<const v4f*>(S + d);
-                    v4f c;
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) c[t] = s[t] / fm * rn;
-                    *reinterpret_cast<v4f*>(M + d) = c;
-                } else {
-                    M[d] = S[d] / fm * rn;
-                }
-            }
-        }
+        unit_scale(S, M, D, fm, rn, vecD);
     }
 }
 
 // ---- verification ------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kThreads) void verify_zero_kernel(int* counts, int n, int* trials) {
-    for (int i = blockIdx.x * kThreads + threadIdx.x; i < n; i += gridDim.x * kThreads) counts[i] = 0;
-    if (trials && blockIdx.x == 0 && threadIdx.x < 2) trials[threadIdx.x] = 0;
+// 0.5 ((v - mu_k) rs_k + (v - mu_r) rs_r), rs = the correctly rounded 1 / sd: five roundings, nothing fused.
+__device__ __forceinline__ float snorm_value(float v, float mu_k, float rs_k, float mu_r, float rs_r) {
+#pragma clang fp contract(off)
+    const float a = (v - mu_k) * rs_k;
+    const float b = (v - mu_r) * rs_r;
+    return 0.5f * (a + b);
+}
+__device__ __forceinline__ float snorm_recip(float sd) {
+#pragma clang fp contract(off)
+    return 1.0f / sd;
 }
 
 // The slots of a staged tile: model sp (0 .. 63 of the group), 16-byte slot c (0 .. 15 of the chunk).
 __device__ __forceinline__ int stage_at(int sp, int c) { return sp * kChunk + ((c ^ (sp & 15)) << 2); }
 
 // kSteps: the form of the row fragments (ge2e_rows_dev.hpp): > 0 in registers (D a multiple of 4 and at most 16 kSteps), 0
-// for any D.  kStaged: the model tiles come through LDS.
-template <int kSteps, bool kStaged>
+// for any D.  kStaged: the model tiles come through LDS.  kNormed: the score is normalised with p.row_stats and
+// p.model_stats before it is stored and counted (streamed form only).
+template <int kSteps, bool kStaged, bool kNormed>
 __global__ __launch_bounds__(kThreads) void verify_rows_kernel(ProblemVerify p, int tiles) {
     extern __shared__ __attribute__((aligned(16))) int lds[];
     __shared__ int wtot[2][kWaves];
@@ -193,6 +174,13 @@ __global__ __launch_bounds__(kThreads) void verify_rows_kernel(ProblemVerify p, 
         const bool row_ok = in && lab >= 0;
         int tgt = -1;
         if (labelled && row_ok && lab < K && p.cnt[lab] > 0) tgt = lab;
+        [[maybe_unused]] float mu_r = 0.f, rs_r = 1.f;   // (an ignored row's statistics are not read)
+        if constexpr (kNormed) {
+            if (row_ok) {
+                mu_r = p.row_stats[(size_t)r * 2];
+                rs_r = snorm_recip(p.row_stats[(size_t)r * 2 + 1]);
+            }
+        }
 
         // the ignored rows: the whole score row is +0 (one wave per row; the row of E is not read)
         if (p.scores && labelled) {
@@ -220,7 +208,12 @@ __global__ __launch_bounds__(kThreads) void verify_rows_kernel(ProblemVerify p, 
                 for (int g = 0; g < 4; ++g) {
                     const int c = c0 + g;
                     const bool enrolled = c < K && p.cnt[c] > 0;
-                    v[g] = enrolled ? acc[a][g] * t.rne + eps : 0.f;
+                    v[g] = enrolled ? raw_score(acc[a][g], t.rne, eps) : 0.f;
+                    if constexpr (kNormed) {   // (the statistics of a speaker that is not enrolled are not read)
+                        if (enrolled)
+                            v[g] = snorm_value(v[g], p.model_stats[(size_t)c * 2], snorm_recip(p.model_stats[(size_t)c * 2 + 1]),
+                                               mu_r, rs_r);
+                    }
                     if (labelled && enrolled) {
                         const bool own = c == tgt;
                         if (T) count_value(v[g], own, hist, thr_lds, T);
@@ -345,20 +338,19 @@ bool verify_staged_fits(int T) { return verify_lds_bytes(T, true) <= kLdsLimit; 
 hipError_t launch_verify_scores(const ProblemVerify& p, VerifyForm form, hipStream_t stream) {
     const int T = p.counts ? p.T : 0;
     if (p.counts || p.trials) {
-        const int n = 2 * T;
-        hipLaunchKernelGGL(verify_zero_kernel, dim3(std::max(1, std::min((n + kThreads - 1) / kThreads, 64))), dim3(kThreads), 0,
-                           stream, p.counts, n, p.trials);
-        const hipError_t err = hipGetLastError();
+        const hipError_t err = launch_zero_ints(p.counts, (size_t)2 * T, p.trials, p.trials ? 2 : 0, stream);
         if (err != hipSuccess) return err;
     }
     const int tiles = (p.R + kTile - 1) / kTile;
     const unsigned grid = (unsigned)std::min(tiles, kMaxRowBlocks);
-    const bool staged = form == VERIFY_STAGED && verify_staged_fits(T);
+    const bool normed = p.row_stats != nullptr;
+    const bool staged = form == VERIFY_STAGED && !normed && verify_staged_fits(T);
     const size_t lds = verify_lds_bytes(T, staged);
     dispatch_tile_steps(p.D, [&](auto ks) {
         constexpr int kSteps = decltype(ks)::value;
-        if (staged) hipLaunchKernelGGL((verify_rows_kernel<kSteps, true>), dim3(grid), dim3(kThreads), lds, stream, p, tiles);
-        else hipLaunchKernelGGL((verify_rows_kernel<kSteps, false>), dim3(grid), dim3(kThreads), lds, stream, p, tiles);
+        if (normed) hipLaunchKernelGGL((verify_rows_kernel<kSteps, false, true>), dim3(grid), dim3(kThreads), lds, stream, p, tiles);
+        else if (staged) hipLaunchKernelGGL((verify_rows_kernel<kSteps, true, false>), dim3(grid), dim3(kThreads), lds, stream, p, tiles);
+        else hipLaunchKernelGGL((verify_rows_kernel<kSteps, false, false>), dim3(grid), dim3(kThreads), lds, stream, p, tiles);
     });
     return hipGetLastError();
 }

@@ -20,7 +20,7 @@ hipError_t launch_enroll_accumulate(const float* E, const int* off, const int* o
 hipError_t launch_enroll_finalize(const float* sums, const int* cnt, int K, int D, float eps_cos, float* models,
                                   hipStream_t stream);
 
-// Launch-time description of ge2e_verify_scores.  Every pointer is a device pointer.
+// Launch-time description of ge2e_verify_scores and ge2e_verify_scores_normed.  Every pointer is a device pointer.
 struct ProblemVerify {
     const float* E;        // [R][D] trial rows, in the caller's order
     const int* labels;     // [R] or null
@@ -30,6 +30,8 @@ struct ProblemVerify {
     float* scores;         // [R][K] or null
     int* counts;           // [T][2] or null
     int* trials;           // [2] or null
+    const float* row_stats;     // [R][2] {mean, spread} of the trial rows, or null: the plain call
+    const float* model_stats;   // [K][2] of the models; with row_stats
     int K, R, D, T;
     float eps_cos, eps;
 };
@@ -37,7 +39,8 @@ struct ProblemVerify {
 // measured), or staged in LDS once per workgroup (where T leaves room for the buffers beside the histograms).
 enum VerifyForm { VERIFY_AUTO = 0, VERIFY_STAGED = 1, VERIFY_STREAMED = 2 };
 bool verify_staged_fits(int T);   // the staging buffers and the histograms fit the LDS of one launch
-// A zeroing launch where counts or trials are wanted, then the rows kernel.
+// A zeroing launch where counts or trials are wanted, then the rows kernel.  With row_stats the scores are normalised
+// (ge2e_verify_scores_normed), in the streamed form whatever `form` says.
 hipError_t launch_verify_scores(const ProblemVerify& p, VerifyForm form, hipStream_t stream);
 
 }  // namespace ge2e

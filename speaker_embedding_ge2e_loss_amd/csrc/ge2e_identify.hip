@@ -2,12 +2,12 @@
 // best k_top enrolled speakers of every trial row, the position of the row's target among them and the histogram of those
 // positions.  The score matrix [R][K] is never materialised.
 //   A CANDIDATE of a scored row is an enrolled speaker k (cnt[k] > 0) with ge2e_verify_scores' score, the same fmaf chain
-//   (tile_cosines on models + k0 D) and the same epilogue expression.  The order of candidates is total: a stands before b
+//   (tile_cosines on models + k0 D) and the same epilogue function (raw_score, ge2e_bank_dev.hpp).  The order of candidates is total: a stands before b
 //   iff score_a > score_b as fp32 values, -0 and +0 being equal and a NaN standing behind every number; where the scores are
 //   equal, or both NaN, the lower speaker index stands first.  One 64-bit KEY per candidate implements it with one unsigned
 //   compare (a larger key stands first):
-//     high word  the score's bits made monotone (-0 taken as +0; b ^ 0x80000000 for b >= 0, ~b otherwise), 1 for a NaN:
-//                -inf gives 0x007fffff, so a NaN stands behind it and in front of
+//     high word  score_key (ge2e_bank_dev.hpp): the score's bits made monotone (-0 taken as +0; b ^ 0x80000000 for b >= 0,
+//                ~b otherwise), 1 for a NaN: -inf gives 0x007fffff, so a NaN stands behind it and in front of
 //     key 0      the empty slot (index -1, score -inf), which no candidate's key equals;
 //     low word   ~index: of two equal scores the lower index has the larger key.
 //   A returned NaN score is the quiet NaN 0x7fc00000 and a returned -0 is +0: the key does not carry the difference.
@@ -24,7 +24,7 @@
 //           (keys are distinct: they carry the index), lane t keeps round t's.  Decodes idx / score, finds the target,
 //           writes rank and counts it in the workgroup's LDS histogram; one integer atomic per workgroup and non-empty bin.
 //           It always runs, also for S = 1: one output path.
-//   zero    hist, only when hist is wanted.
+//   zero    hist, only when hist is wanted (launch_zero_ints).
 // The k_top best of the bank are among the k_top best of their slices and the order is total, so the result does not depend
 // on the split; the lists' contents depend on nothing but the candidates, so it does not depend on what the workspace held.
 // Every index read from memory is range-checked where it is read (a label indexes cnt only after 0 <= label < K).
@@ -34,33 +34,24 @@
 
 #include <algorithm>
 
-#include "ge2e_rows_dev.hpp"
+#include "ge2e_bank_dev.hpp"
+#include "ge2e_counting_dev.hpp"
 
 namespace ge2e {
 
 namespace {
 typedef unsigned long long u64;
-constexpr int kThreads = 256, kWaves = kThreads / kWave;
-constexpr int kTile = 64, kWaveRows = kTile / kWaves;   // trial rows per workgroup / per wave
-constexpr int kAcc = 4;                                 // column tiles (accumulators) in flight per wave
+using namespace tile_geom;                              // kThreads, kWaves, kTile, kWaveRows, kAcc
 constexpr int kListStride = kIdentifyMaxTop + 1;        // keys between two rows' lists in LDS (odd: 16 rows, 16 bank pairs)
 constexpr int kMaxMergeBlocks = 1024;
 static_assert(16 * kAcc == kIdentifyGroup, "a slice starts on a group of the rows kernel");
 static_assert(kIdentifyMaxTop <= 32, "the merge kernel reads a list with half a wave");
 
-__device__ __forceinline__ u64 make_key(float v, int c) {
-    unsigned b = __float_as_uint(v);
-    if (b == 0x80000000u) b = 0u;
-    unsigned hi = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-    if (v != v) hi = 1u;
-    return ((u64)hi << 32) | (unsigned)~c;
-}
+__device__ __forceinline__ u64 make_key(float v, int c) { return ((u64)score_key(v) << 32) | (unsigned)~c; }
 __device__ __forceinline__ int key_index(u64 key) { return key ? (int)~(unsigned)key : -1; }
-__device__ __forceinline__ float key_score(u64 key) {
+__device__ __forceinline__ float key_score(u64 key) {   // (the empty slot: -inf)
     const unsigned hi = (unsigned)(key >> 32);
-    if (hi == 0u) return -INFINITY;
-    if (hi == 1u) return __uint_as_float(0x7fc00000u);
-    return __uint_as_float((hi & 0x80000000u) ? (hi & 0x7fffffffu) : ~hi);
+    return hi == 0u ? -INFINITY : key_to_score(hi);
 }
 
 // The lanes of a wave see each other's LDS stores: the wave runs in lockstep and LDS returns in order; this keeps the
@@ -95,12 +86,8 @@ __device__ __forceinline__ u64 list_insert(volatile u64* L, int k, u64 key) {
     return L[k - 1];
 }
 
-__global__ __launch_bounds__(64) void identify_zero_kernel(int* hist, int n) {
-    for (int i = threadIdx.x; i < n; i += 64) hist[i] = 0;
-}
-
-// kSteps: the form of the row fragments (ge2e_rows_dev.hpp).  Workgroup b: tile b % tiles, slice b / tiles -- workgroups
-// that run together read the same slice of the models.
+// kSteps: the form of the row fragments (ge2e_rows_dev.hpp).  Workgroup b: a tile of the rows and a slice of the models
+// (slice_frame, ge2e_bank_dev.hpp).
 template <int kSteps>
 __global__ __launch_bounds__(kThreads) void identify_rows_kernel(ProblemIdentify p, int tiles, int slice_models) {
     __shared__ u64 lists[kTile * kListStride];
@@ -108,11 +95,9 @@ __global__ __launch_bounds__(kThreads) void identify_rows_kernel(ProblemIdentify
     const int l15 = lane & 15, q = lane >> 4;
     const int D = p.D, R = p.R, K = p.K, k_top = p.k_top;
     const float eps = p.eps;
-    const int tile = (int)(blockIdx.x % (unsigned)tiles), slice = (int)(blockIdx.x / (unsigned)tiles);
-    const int k0 = slice * slice_models;                       // (the host counts non-empty slices only: k0 < K)
-    const int n_models = min(slice_models, K - k0);
-    const int p0 = tile * kTile + wid * kWaveRows;
-    if (p0 >= R) return;    // (the whole wave; waves share nothing and meet at no barrier) the online case: R = 16 is one wave
+    SliceFrame f;
+    if (!slice_frame(tiles, slice_models, K, R, f)) return;    // (the online case: R = 16 is one wave)
+    const int slice = f.slice, k0 = f.k0, n_models = f.n_models, p0 = f.p0;
     const int r = p0 + l15;
     const bool in = r < R;
     const int lab = (p.labels && in) ? p.labels[r] : 0;
@@ -136,8 +121,7 @@ __global__ __launch_bounds__(kThreads) void identify_rows_kernel(ProblemIdentify
             for (int g = 0; g < 4; ++g) {
                 const int c = c0 + g;
                 const bool cand = row_ok && c < k0 + n_models && p.cnt[c] > 0;
-                const float v = acc[a][g] * t.rne + eps;
-                key[g] = cand ? make_key(v, c) : 0;
+                key[g] = cand ? make_key(raw_score(acc[a][g], t.rne, eps), c) : 0;
                 win |= key[g] > thr;
             }
             if (__ballot(win) == 0) continue;   // (the whole wave: almost always, once the lists have filled)
@@ -222,8 +206,7 @@ __global__ __launch_bounds__(kThreads) void identify_merge_kernel(ProblemIdentif
 
 hipError_t launch_identify(const ProblemIdentify& p, IdentifySplit split, hipStream_t stream) {
     if (p.hist) {
-        hipLaunchKernelGGL(identify_zero_kernel, dim3(1), dim3(64), 0, stream, p.hist, p.k_top + 1);
-        const hipError_t err = hipGetLastError();
+        const hipError_t err = launch_zero_ints(p.hist, (size_t)p.k_top + 1, nullptr, 0, stream);
         if (err != hipSuccess) return err;
     }
     const int tiles = (p.R + kTile - 1) / kTile;

@@ -39,9 +39,7 @@
 namespace ge2e {
 
 namespace {
-constexpr int kThreads = 256, kWaves = kThreads / kWave;
-constexpr int kTile = 64, kWaveRows = kTile / kWaves;   // sorted positions per workgroup / per wave
-constexpr int kAcc = 4;                                 // column tiles (accumulators) in flight per wave
+using namespace tile_geom;   // kThreads, kWaves, kTile, kWaveRows, kAcc
 constexpr int kMaxCentroidBlocks = 8192, kMaxRowBlocks = 1 << 20;
 
 // (the counting epilogue -- counting_begin, count_value, counting_end -- is in ge2e_counting_dev.hpp)
@@ -78,54 +76,22 @@ __global__ __launch_bounds__(kThreads) void labeled_eval_centroids_kernel(Proble
             p.spk[(size_t)bi * R + pp] = k;
             if constexpr (!kLoss) p.col[(size_t)bi * R + row] = k;
         }
-        // the sums: a lane owns 4 (vecD) or 1 element of every stretch of 256 / 64; rows in ascending position
+        // the sums (speaker_sum, ge2e_rows_dev.hpp: rows in ascending position), stored once, and |c|^2 on the way
         float sq = 0.f;
-        const int stretch = vecD ? 4 * kWave : kWave;
-        for (int d0 = 0; d0 < D; d0 += stretch) {
-            const int d = d0 + (vecD ? 4 * lane : lane);
+        for (int d0 = 0; d0 < D; d0 += wave_stretch(vecD)) {
+            const int d = wave_elem(d0, lane, vecD);
             const bool ok = d < D;
-            v4f s = {0.f, 0.f, 0.f, 0.f};
-            for (int c0 = r0; c0 < r1; c0 += kWave) {
-                const int pp = c0 + lane;
-                const int idx = pp < r1 ? clampi(ord[pp], 0, R - 1) : 0;   // one coalesced load for up to 64 rows
-                const int cnt = min(kWave, r1 - c0);
-                for (int i = 0; i < cnt; ++i) {
-                    const float* er = E + (size_t)__builtin_amdgcn_readlane(idx, i) * D;
-                    if (ok) {
-                        if (vecD) s += *reinterpret_cast<const v4f*>(er + d);
-                        else s[0] += er[d];
-                    }
-                }
-            }
+            const v4f s = speaker_sum(E, ord, r0, r1, R, D, d, ok, vecD);
             if (ok) {
-                if (vecD) {
-                    *reinterpret_cast<v4f*>(SS + d) = s;
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) { const float c = s[t] / fm; sq += c * c; }
-                } else {
-                    SS[d] = s[0];
-                    const float c = s[0] / fm;
-                    sq += c * c;
-                }
+                if (vecD) *reinterpret_cast<v4f*>(SS + d) = s;
+                else SS[d] = s[0];
+                sq = mean_sq(sq, s, fm, vecD);
             }
         }
         sq = wave_sum(sq);
         float rn, kap;
         unit_stats(sq, p.eps_cos, rn, kap);
-        for (int d0 = 0; d0 < D; d0 += stretch) {   // (every lane reads back what it wrote itself)
-            const int d = d0 + (vecD ? 4 * lane : lane);
-            if (d < D) {
-                if (vecD) {
-                    const v4f s = *reinterpret_cast<const v4f*>(SS + d);
-                    v4f c;
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) c[t] = s[t] / fm * rn;
-                    *reinterpret_cast<v4f*>(CH + d) = c;
-                } else {
-                    CH[d] = SS[d] / fm * rn;
-                }
-            }
-        }
+        unit_scale(SS, CH, D, fm, rn, vecD);   // (every lane reads back what it wrote itself)
         if (lane == 0) {
             float* cs = p.CST + ((size_t)bi * NA + k) * 4;
             cs[CS_RN] = rn; cs[CS_KAP] = kap; cs[CS_M] = fm; cs[CS_M1] = fm - 1.f;
@@ -220,10 +186,13 @@ __global__ __launch_bounds__(kThreads) void labeled_eval_rows_kernel(ProblemLabe
     }
 }
 
-// ---- ge2e_eer_counts_labeled -------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kThreads) void zero_counts_kernel(int* counts, size_t n) {
-    for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += (size_t)gridDim.x * kThreads) counts[i] = 0;
+// ---- the zeroing launch of every call that counts (launch_zero_ints, ge2e_counting_dev.hpp) --------------------------------
+__global__ __launch_bounds__(kThreads) void zero_ints_kernel(int* a, size_t n, int* b, int nb) {
+    for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += (size_t)gridDim.x * kThreads) a[i] = 0;
+    if (blockIdx.x == 0 && (int)threadIdx.x < nb) b[threadIdx.x] = 0;
 }
+
+// ---- ge2e_eer_counts_labeled -------------------------------------------------------------------------------------------
 
 // One workgroup per (batch, tile of 64 rows in the caller's order), one wave per row, lanes over the columns < n_act.
 __global__ __launch_bounds__(kThreads) void eer_counts_labeled_kernel(const float* __restrict__ sim, const int* __restrict__ col,
@@ -268,6 +237,12 @@ __global__ __launch_bounds__(kThreads) void eer_counts_labeled_kernel(const floa
 }
 }  // namespace
 
+hipError_t launch_zero_ints(int* a, size_t n, int* b, int nb, hipStream_t stream) {
+    const size_t blocks = std::min<size_t>((n + kThreads - 1) / kThreads, 1024);
+    hipLaunchKernelGGL(zero_ints_kernel, dim3((unsigned)std::max<size_t>(blocks, 1)), dim3(kThreads), 0, stream, a, n, b, nb);
+    return hipGetLastError();
+}
+
 hipError_t launch_labeled_centroids(const ProblemLabeledEval& p, bool loss_stats, hipStream_t stream) {
     const long long waves = (long long)p.B * p.NA;
     const long long cblocks = (waves + kWaves - 1) / kWaves;
@@ -293,10 +268,7 @@ hipError_t launch_labeled_eval(const ProblemLabeledEval& p, hipStream_t stream) 
 
 hipError_t launch_eer_counts_labeled(const float* sim, const int* col, const int* active, int B, int N, int R,
                                      const float* thr, int T, int* counts, hipStream_t stream) {
-    const size_t n = (size_t)B * T * 2;
-    hipLaunchKernelGGL(zero_counts_kernel, dim3((unsigned)std::min<size_t>((n + kThreads - 1) / kThreads, 1024)),
-                       dim3(kThreads), 0, stream, counts, n);
-    hipError_t err = hipGetLastError();
+    hipError_t err = launch_zero_ints(counts, (size_t)B * T * 2, nullptr, 0, stream);
     if (err != hipSuccess) return err;
     const int tiles = (R + kTile - 1) / kTile;
     const unsigned grid = (unsigned)std::min<long long>((long long)B * tiles, kMaxRowBlocks);

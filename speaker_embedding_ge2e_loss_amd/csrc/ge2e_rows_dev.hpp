@@ -1,7 +1,9 @@
 // Device helpers of the exact kernels, written once: ge2e_generic.hip, ge2e_f64.hip, ge2e_ragged.hip,
-// ge2e_labeled_wide.hip and ge2e_labeled_eval.hip.  The statistic indices, the 16-byte fragment loads of the fp32 MFMA, the
-// row-loss step (row_scan, row_loss), the leave-one-out gradient term (loo_term) and the cosine-tile stage of the two
-// labelled row kernels (tile_rows, tile_cosines).  Algebra: oracle/ge2e_oracle.py:closed_form and the header of
+// ge2e_labeled_wide.hip, ge2e_labeled_eval.hip and the bank kernels (ge2e_enroll.hip, ge2e_identify.hip, ge2e_snorm.hip).
+// The statistic indices, the 16-byte fragment loads of the fp32 MFMA, the row-loss step (row_scan, row_loss), the
+// leave-one-out gradient term (loo_term), the cosine-tile stage of the row kernels (tile_rows, tile_rows_plain,
+// tile_cosines) with the geometry of a workgroup that runs it (tile_geom), and the speaker sum and the unit scaling of the
+// centroid and enrolment kernels (speaker_sum, mean_sq, unit_scale).  Algebra: oracle/ge2e_oracle.py:closed_form and the header of
 // ge2e_generic.hip.  The operand order and the parentheses of every expression are part of the results: the kernels agree
 // bit for bit with what they computed when each carried its own copy (tools/output_digest.py).
 #pragma once
@@ -313,6 +315,73 @@ __device__ __forceinline__ void tile_cosines(const TileRows<kSteps>& t, const fl
             }
         }
         epi(kt0, acc);
+    }
+}
+
+// The workgroup of a row kernel built on tile_rows / tile_cosines, whose lane map these describe: four waves, one MFMA tile
+// of 16 rows each.  (`using namespace tile_geom` in the kernels' files.)
+namespace tile_geom {
+constexpr int kThreads = 256, kWaves = kThreads / kWave;
+constexpr int kTile = 64, kWaveRows = kTile / kWaves;   // rows (sorted positions) per workgroup / per wave
+constexpr int kAcc = 4;                                 // column tiles (accumulators) in flight per wave
+}  // namespace tile_geom
+
+// ---- a speaker's sum and its unit form: one wave per speaker --------------------------------------------------------------
+// A lane owns 4 (vecD: D % 4 == 0 and 16-byte aligned rows) or 1 element of every stretch of 256 / 64 elements of a row:
+// the elements from wave_elem(d0, lane, vecD) on, for d0 = 0, wave_stretch(vecD), ...
+__device__ __forceinline__ int wave_stretch(bool vecD) { return vecD ? 4 * kWave : kWave; }
+__device__ __forceinline__ int wave_elem(int d0, int lane, bool vecD) { return d0 + (vecD ? 4 * lane : lane); }
+// The lane's elements d .. (`ok`: d < D) of the sum of the rows E[order[p]], p = r0 .. r1 - 1, from 0 in ascending p.  The
+// row indices of up to 64 positions come with ONE coalesced load, clamped to [0, R - 1], and are handed out with v_readlane:
+// no dependent order[p] -> row pair per row.  Called by the whole wave.
+__device__ __forceinline__ v4f speaker_sum(const float* E, const int* order, int r0, int r1, int R, int D, int d, bool ok,
+                                           bool vecD) {
+    const int lane = threadIdx.x & 63;
+    v4f s = {0.f, 0.f, 0.f, 0.f};
+    for (int c0 = r0; c0 < r1; c0 += kWave) {
+        const int pp = c0 + lane;
+        const int idx = pp < r1 ? clampi(order[pp], 0, R - 1) : 0;
+        const int n = min(kWave, r1 - c0);
+        for (int i = 0; i < n; ++i) {
+            const float* er = E + (size_t)__builtin_amdgcn_readlane(idx, i) * D;
+            if (ok) {
+                if (vecD) s += *reinterpret_cast<const v4f*>(er + d);
+                else s[0] += er[d];
+            }
+        }
+    }
+    return s;
+}
+// sq + the squares of the lane's elements of the centroid c = s / fm.  The roundings are spelled out, because they are part of
+// the results and were the optimiser's choice while each kernel carried its own copy (packed multiplies for the four, one fma
+// for the single element): the four squares are rounded and added on in turn, nothing fused; the single one is fused.
+__device__ __forceinline__ float mean_sq(float sq, const v4f& s, float fm, bool vecD) {
+    if (vecD) {
+#pragma clang fp contract(off)
+#pragma unroll
+        for (int t = 0; t < 4; ++t) { const float c = s[t] / fm; sq = sq + c * c; }
+    } else {
+        const float c = s[0] / fm;
+        sq = fmaf(c, c, sq);
+    }
+    return sq;
+}
+// U = S / fm * rn over the D elements of a speaker: the unit centroid from the sum, the count and 1 / |c| (unit_stats)
+__device__ __forceinline__ void unit_scale(const float* S, float* U, int D, float fm, float rn, bool vecD) {
+    const int lane = threadIdx.x & 63;
+    for (int d0 = 0; d0 < D; d0 += wave_stretch(vecD)) {
+        const int d = wave_elem(d0, lane, vecD);
+        if (d < D) {
+            if (vecD) {
+                const v4f s = *reinterpret_cast<const v4f*>(S + d);
+                v4f c;
+#pragma unroll
+                for (int t = 0; t < 4; ++t) c[t] = s[t] / fm * rn;
+                *reinterpret_cast<v4f*>(U + d) = c;
+            } else {
+                U[d] = S[d] / fm * rn;
+            }
+        }
     }
 }
 

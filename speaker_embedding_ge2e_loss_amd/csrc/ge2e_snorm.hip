@@ -1,15 +1,16 @@
-// ge2e_cohort_stats / ge2e_verify_scores_normed: adaptive score normalisation (AS-norm) against a cohort.  A COHORT is a
-// bank's finalised form, cohort [C][D] and ccnt [C]; speaker c is a MEMBER iff ccnt[c] > 0.  The score of (row, member) is
-// ge2e_verify_scores' score with the same bits: tile_rows_plain / tile_cosines and the same epilogue expression.
+// ge2e_cohort_stats: the statistics of adaptive score normalisation (AS-norm) against a cohort.  A COHORT is a bank's
+// finalised form, cohort [C][D] and ccnt [C]; speaker c is a MEMBER iff ccnt[c] > 0.  The score of (row, member) is
+// ge2e_verify_scores' score with the same bits: tile_rows_plain / tile_cosines and raw_score (ge2e_bank_dev.hpp), the very
+// functions the verify kernel calls.
 //   rows     one 256-thread workgroup per (64 rows of a CHUNK of rows, slice of the cohort), 16 rows per wave, the verify rows
 //            kernel's shape.  A chunk is a few tiles of rows (21 at C = 5 994), far fewer than the chip has CUs, and a
 //            workgroup that walked the whole cohort alone set the call's time whatever the chunk held (measured: 0.9 ms per
 //            chunk of 320, 1 344 or 5 568 rows alike), so the cohort axis is split as ge2e_identify splits its bank
-//            (identify_split: at least 512 workgroups where the cohort has the groups for it).  An output element is the
-//            same fmaf chain whatever the split.  Every score goes into the workspace [chunk][C] as a 32-bit KEY, identify's monotone map: -0 taken as +0, b ^ 0x80000000
-//            for b >= 0 and ~b otherwise, 1 for a NaN (behind every number: -inf is 0x007fffff) and 0 for a column that is
-//            no member, which no member's key equals.  A 16-byte store where C % 4 == 0.  Rows that are not scored are
-//            neither loaded nor written.
+//            (identify_split and slice_frame: at least 512 workgroups where the cohort has the groups for it).  An output
+//            element is the same fmaf chain whatever the split.  Every score goes into the workspace [chunk][C] as a 32-bit
+//            KEY, score_key (ge2e_bank_dev.hpp: the high word of identify's key), and 0 for a column that is no member,
+//            which no member's key equals.  A 16-byte store where C % 4 == 0.  Rows that are not scored are neither
+//            loaded nor written.
 //   select   one workgroup per row of the chunk.  A row that is not scored, or a cohort without members, gets {+0, 1}.
 //            Otherwise an exact radix selection of the n-th largest key, n = min(n_top, members): four passes over eight
 //            bits from the top, each an LDS histogram (integer atomics) of the keys that carry the prefix found so far, a
@@ -23,8 +24,7 @@
 //            Both forms visit the keys in the same order: the same bits.
 //   chunk    the host loops over chunks of chunk_rows(C) rows, rows then select, all on one stream and one workspace of at
 //            most 32 MiB: the matrix [R][C] never exists.  A row's keys and its statistics do not depend on its chunk.
-//   normed   ge2e_verify_scores' streamed rows kernel with another epilogue: v -> 0.5 ((v - mu_k) (1 / sd_k) + (v - mu_r)
-//            (1 / sd_r)), every operation rounded on its own (no contraction), then stored and counted as verify does.
+//   normed   ge2e_verify_scores_normed, which takes these statistics, is the verify rows kernel itself (ge2e_enroll.hip).
 // No index is read from memory anywhere here: sel and ccnt are compared, never used as an offset.
 #include "ge2e_snorm.hpp"
 
@@ -32,50 +32,33 @@
 
 #include <algorithm>
 
-#include "ge2e_counting_dev.hpp"
+#include "ge2e_bank_dev.hpp"
 #include "ge2e_identify.hpp"
-#include "ge2e_rows_dev.hpp"
 
 namespace ge2e {
 
 namespace {
-constexpr int kThreads = 256, kWaves = kThreads / kWave;
-constexpr int kTile = 64, kWaveRows = kTile / kWaves;   // rows per workgroup / per wave
-constexpr int kAcc = 4;                                 // column tiles (accumulators) in flight per wave
+using namespace tile_geom;   // kThreads, kWaves, kTile, kWaveRows, kAcc
 constexpr int kMaxRowBlocks = 1 << 20;
 constexpr int kBins = 256, kRadixBits = 8;
-static_assert(kThreads == kCountThreads, "the counting helpers are written for this workgroup");
 static_assert(kBins == kThreads, "the suffix scan gives bin t to thread t");
 
 typedef unsigned v4u __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ unsigned make_key32(float v) {
-    unsigned b = __float_as_uint(v);
-    if (b == 0x80000000u) b = 0u;
-    const unsigned k = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-    return v != v ? 1u : k;
-}
-__device__ __forceinline__ float key_value(unsigned k) {
-    if (k == 1u) return __uint_as_float(0x7fc00000u);
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
-
 // ---- cohort scores of a chunk of rows ---------------------------------------------------------------------------------------
-// Workgroup b: tile b % tiles of the chunk's rows, slice b / tiles of the cohort (slice_models columns, a multiple of 64) --
-// workgroups that run together read the same slice of the cohort.
+// Workgroup b: a tile of the chunk's rows and a slice of the cohort (slice_frame, ge2e_bank_dev.hpp).
 template <int kSteps>
 __global__ __launch_bounds__(kThreads) void cohort_rows_kernel(ProblemCohort p, int row0, int nrows, int tiles, int slice_models) {
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
     const int l15 = lane & 15, q = lane >> 4;
     const int D = p.D, C = p.C;
     const bool vecC = (C & 3) == 0;   // (the workspace is 256-byte aligned and a row of it C keys long)
     const float eps = p.eps;
     {
-        const int tile = (int)(blockIdx.x % (unsigned)tiles), slice = (int)(blockIdx.x / (unsigned)tiles);
-        const int k0 = slice * slice_models;                  // (the host counts non-empty slices only: k0 < C)
-        const int n_models = min(slice_models, C - k0);
-        if (tile * kTile + wid * kWaveRows >= nrows) return;  // (the whole wave; waves share nothing and meet at no barrier)
-        const int i = tile * kTile + wid * kWaveRows + l15;   // the row's place in the chunk
+        SliceFrame f;
+        if (!slice_frame(tiles, slice_models, C, nrows, f)) return;
+        const int k0 = f.k0, n_models = f.n_models;
+        const int i = f.p0 + l15;                             // the row's place in the chunk
         const int r = row0 + i;
         const bool row_ok = i < nrows && (!p.sel || p.sel[r] >= p.sel_min);
         const TileRows<kSteps> t = tile_rows_plain<kSteps>(p.X, r, row_ok, D, p.eps_cos);
@@ -91,8 +74,7 @@ __global__ __launch_bounds__(kThreads) void cohort_rows_kernel(ProblemCohort p, 
                 for (int g = 0; g < 4; ++g) {
                     const int c = c0 + g;
                     const bool member = c < C && p.ccnt[c] > 0;
-                    const float v = acc[a][g] * t.rne + eps;
-                    key[g] = member ? make_key32(v) : 0u;
+                    key[g] = member ? score_key(raw_score(acc[a][g], t.rne, eps)) : 0u;
                 }
                 if (vecC) {
                     *reinterpret_cast<v4u*>(kr + c0) = key;
@@ -191,13 +173,13 @@ __global__ __launch_bounds__(kThreads) void cohort_select_kernel(ProblemCohort p
             continue;
         }
         const unsigned vkey = prefix;                         // the n-th largest key, taken `want` times
-        const float v = key_value(vkey), fn = (float)n, copies = (float)want;
+        const float v = key_to_score(vkey), fn = (float)n, copies = (float)want;
         float s = 0.f;
-        each_key([&](unsigned k) { if (k > vkey) s += key_value(k); });
+        each_key([&](unsigned k) { if (k > vkey) s += key_to_score(k); });
         const float mean = (block_sum(s, part) + copies * v) / fn;
         float d2 = 0.f;
         each_key([&](unsigned k) {
-            if (k > vkey) { const float d = key_value(k) - mean; d2 += d * d; }
+            if (k > vkey) { const float d = key_to_score(k) - mean; d2 += d * d; }
         });
         const float dv = v - mean;
         const float sd = sqrtf((block_sum(d2, part) + copies * (dv * dv)) / fn);
@@ -208,116 +190,6 @@ __global__ __launch_bounds__(kThreads) void cohort_select_kernel(ProblemCohort p
     }
 }
 
-// ---- normalised verification ---------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kThreads) void snorm_zero_kernel(int* counts, int n, int* trials) {
-    for (int i = blockIdx.x * kThreads + threadIdx.x; i < n; i += gridDim.x * kThreads) counts[i] = 0;
-    if (trials && blockIdx.x == 0 && threadIdx.x < 2) trials[threadIdx.x] = 0;
-}
-
-// 0.5 ((v - mu_k) rs_k + (v - mu_r) rs_r), rs = the correctly rounded 1 / sd: five roundings, nothing fused.
-__device__ __forceinline__ float snorm_value(float v, float mu_k, float rs_k, float mu_r, float rs_r) {
-#pragma clang fp contract(off)
-    const float a = (v - mu_k) * rs_k;
-    const float b = (v - mu_r) * rs_r;
-    return 0.5f * (a + b);
-}
-__device__ __forceinline__ float snorm_recip(float sd) {
-#pragma clang fp contract(off)
-    return 1.0f / sd;
-}
-
-template <int kSteps>
-__global__ __launch_bounds__(kThreads) void verify_normed_rows_kernel(ProblemVerifyNormed pn, int tiles) {
-    extern __shared__ __attribute__((aligned(16))) int lds[];
-    __shared__ int wtot[2][kWaves];
-    const ProblemVerify& p = pn.v;
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const int l15 = lane & 15, q = lane >> 4;
-    const int D = p.D, R = p.R, K = p.K;
-    const int T = p.counts ? p.T : 0;
-    int* hist = lds;
-    float* thr_lds = reinterpret_cast<float*>(hist + 2 * (T + 1));
-    const bool vecK = p.scores && (K & 3) == 0 && ((uintptr_t)p.scores & 15) == 0;
-    const bool labelled = p.labels != nullptr;
-    const float eps = p.eps;
-    const v4f zero4 = {0.f, 0.f, 0.f, 0.f};
-
-    for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-        const int p0 = tile * kTile + wid * kWaveRows;
-        const int r = p0 + l15;
-        const bool in = r < R;
-        const int lab = (labelled && in) ? p.labels[r] : 0;
-        const bool row_ok = in && lab >= 0;
-        int tgt = -1;
-        if (labelled && row_ok && lab < K && p.cnt[lab] > 0) tgt = lab;
-        float mu_r = 0.f, rs_r = 1.f;   // (an ignored row's statistics are not read)
-        if (row_ok) {
-            mu_r = pn.row_stats[(size_t)r * 2];
-            rs_r = snorm_recip(pn.row_stats[(size_t)r * 2 + 1]);
-        }
-
-        // the ignored rows: the whole score row is +0 (one wave per row; the row of E is not read)
-        if (p.scores && labelled) {
-            const unsigned long long okmask = __ballot(row_ok);
-            for (int i = 0; i < kWaveRows && p0 + i < R; ++i) {
-                if ((okmask >> i) & 1) continue;
-                float* zr = p.scores + (size_t)(p0 + i) * K;
-                if (vecK) for (int c = 4 * lane; c < K; c += 4 * kWave) *reinterpret_cast<v4f*>(zr + c) = zero4;
-                else for (int c = lane; c < K; c += kWave) zr[c] = 0.f;
-            }
-        }
-        if (T) counting_begin(hist, thr_lds, p.thr, T);
-
-        const TileRows<kSteps> t = tile_rows_plain<kSteps>(p.E, r, row_ok, D, p.eps_cos);
-        float* cr = p.scores ? p.scores + (size_t)t.row * K : nullptr;
-        int n_imp = 0, n_tgt = 0;
-        // epilogue: the lane holds columns c0 .. c0+3 of row l15
-        auto epi = [&](int kt0, const v4f (&acc)[kAcc]) {
-#pragma unroll
-            for (int a = 0; a < kAcc; ++a) {
-                const int c0 = (kt0 + a) * 16 + 4 * q;
-                if (!row_ok || c0 >= K) continue;
-                v4f v;
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const int c = c0 + g;
-                    const bool enrolled = c < K && p.cnt[c] > 0;
-                    v[g] = 0.f;
-                    if (enrolled) {   // (the statistics of a speaker that is not enrolled are not read)
-                        const float raw = acc[a][g] * t.rne + eps;
-                        const float mu_k = pn.model_stats[(size_t)c * 2];
-                        const float rs_k = snorm_recip(pn.model_stats[(size_t)c * 2 + 1]);
-                        v[g] = snorm_value(raw, mu_k, rs_k, mu_r, rs_r);
-                        if (labelled) {
-                            const bool own = c == tgt;
-                            if (T) count_value(v[g], own, hist, thr_lds, T);
-                            if (own) ++n_tgt; else ++n_imp;
-                        }
-                    }
-                }
-                if (cr) store4(cr, c0, K, v, vecK);
-            }
-        };
-        tile_cosines<kSteps, kAcc>(t, p.models, K, D, epi);
-
-        if (labelled && p.trials) {   // the tallies of the wave: one integer atomic each
-#pragma unroll
-            for (int d = kWave / 2; d >= 1; d >>= 1) {
-                n_imp += __shfl_down(n_imp, d);
-                n_tgt += __shfl_down(n_tgt, d);
-            }
-            if (lane == 0) {
-                if (n_imp) atomicAdd(&p.trials[0], n_imp);
-                if (n_tgt) atomicAdd(&p.trials[1], n_tgt);
-            }
-        }
-        if (T) {
-            __syncthreads();
-            counting_end(hist, T, p.counts, wtot);
-            __syncthreads();   // hist and wtot are reused by the workgroup's next tile
-        }
-    }
-}
 }  // namespace
 
 hipError_t launch_cohort_stats(const ProblemCohort& p, int chunk_rows, hipStream_t stream) {
@@ -345,26 +217,6 @@ hipError_t launch_cohort_stats(const ProblemCohort& p, int chunk_rows, hipStream
         if (err != hipSuccess) return err;
     }
     return hipSuccess;
-}
-
-hipError_t launch_verify_scores_normed(const ProblemVerifyNormed& pn, hipStream_t stream) {
-    const ProblemVerify& p = pn.v;
-    const int T = p.counts ? p.T : 0;
-    if (p.counts || p.trials) {
-        const int n = 2 * T;
-        hipLaunchKernelGGL(snorm_zero_kernel, dim3(std::max(1, std::min((n + kThreads - 1) / kThreads, 64))), dim3(kThreads), 0,
-                           stream, p.counts, n, p.trials);
-        const hipError_t err = hipGetLastError();
-        if (err != hipSuccess) return err;
-    }
-    const int tiles = (p.R + kTile - 1) / kTile;
-    const unsigned grid = (unsigned)std::min(tiles, kMaxRowBlocks);
-    const size_t lds = (size_t)(3 * T + 2) * sizeof(int);
-    dispatch_tile_steps(p.D, [&](auto ks) {
-        constexpr int kSteps = decltype(ks)::value;
-        hipLaunchKernelGGL((verify_normed_rows_kernel<kSteps>), dim3(grid), dim3(kThreads), lds, stream, pn, tiles);
-    });
-    return hipGetLastError();
 }
 
 }  // namespace ge2e

@@ -1,10 +1,9 @@
-// Layout + launchers of adaptive score normalisation (see ge2e_snorm.hip): the mean and the spread of the n best cohort
-// scores of every row, and verification scores normalised with them before they are counted.
+// Layout + launcher of adaptive score normalisation (see ge2e_snorm.hip): the mean and the spread of the n best cohort
+// scores of every row.  (The verification scores normalised with them are ge2e_enroll.hip's rows kernel.)
 #pragma once
 #include <algorithm>
 
 #include "ge2e_common.hpp"
-#include "ge2e_enroll.hpp"
 
 namespace ge2e {
 
@@ -37,14 +36,5 @@ struct ProblemCohort {
 };
 // Per chunk of rows: the rows kernel (cohort scores as keys into the workspace), the select kernel (one workgroup per row).
 hipError_t launch_cohort_stats(const ProblemCohort& p, int chunk_rows, hipStream_t stream);
-
-// ge2e_verify_scores_normed: ge2e_verify_scores' description and the two tables of {mean, spread}.
-struct ProblemVerifyNormed {
-    ProblemVerify v;
-    const float* row_stats;     // [R][2]
-    const float* model_stats;   // [K][2]
-};
-// A zeroing launch where counts or trials are wanted, then the rows kernel (streamed form).
-hipError_t launch_verify_scores_normed(const ProblemVerifyNormed& p, hipStream_t stream);
 
 }  // namespace ge2e

@@ -905,11 +905,20 @@ def verify_scores(embeddings: torch.Tensor, models: torch.Tensor, cnt: torch.Ten
     speaker as its target and every other row is an impostor against everybody; ``trials`` (2,) counts the impostor and
     target scores, and with ``thresholds`` (as `cos_sim_labeled` takes them) ``counts`` (T, 2) holds the accepts per
     threshold.  ``need_scores=False``: the matrix is never materialised."""
+    return _verify(embeddings, models, cnt, None, labels, thresholds, need_scores, eps, eps_cos)
+
+
+def _verify(embeddings, models, cnt, stats, labels, thresholds, need_scores, eps, eps_cos) -> VerifyOutputs:
+    """`verify_scores` (``stats`` None) and `verify_scores_normed` (``stats`` = (row_stats, model_stats)): the checks, the
+    labels and thresholds, the outputs and the launch."""
     _check_bank(models, cnt)
     K, D = models.shape
     dev = models.device
     e = _bank_rows(embeddings, D, dev)
     R = e.shape[0]
+    if stats is not None:
+        _check_stats(stats[0], R, dev, "row_stats")
+        _check_stats(stats[1], K, dev, "model_stats")
     if labels is None and (thresholds is not None or not need_scores):
         raise ValueError("counts are about targets and impostors: thresholds / need_scores=False need labels")
     if thresholds is None and not need_scores:
@@ -922,8 +931,10 @@ def verify_scores(embeddings: torch.Tensor, models: torch.Tensor, cnt: torch.Ten
     out = VerifyOutputs(scores=torch.empty(R, K, dtype=torch.float32, device=dev) if need_scores else None,
                         counts=torch.empty(T, 2, **i32) if T else None,
                         trials=torch.empty(2, **i32) if lab is not None else None)
-    _launch("ge2e_verify_scores", dev, e.data_ptr(), _ptr(lab), models.data_ptr(), cnt.data_ptr(), K, R, D, float(eps_cos),
-            float(eps), _ptr(thr), T, _ptr(out.scores), _ptr(out.counts), _ptr(out.trials), _stream_ptr(e))
+    tables = () if stats is None else (stats[0].data_ptr(), stats[1].data_ptr())
+    _launch("ge2e_verify_scores" if stats is None else "ge2e_verify_scores_normed", dev, e.data_ptr(), _ptr(lab),
+            models.data_ptr(), cnt.data_ptr(), K, R, D, float(eps_cos), float(eps), *tables, _ptr(thr), T, _ptr(out.scores),
+            _ptr(out.counts), _ptr(out.trials), _stream_ptr(e))
     return out
 
 
@@ -997,7 +1008,7 @@ def cohort_stats(rows: torch.Tensor, cohort_models: torch.Tensor, cohort_cnt: to
         raise ValueError(f"a cohort holds at most {COHORT_MAX} speakers, got {C}")
     with _on_device(dev):
         sel = _selector(select, R, dev) if select is not None else None
-    stats =torch.empty(R, 2, dtype=torch.float32, device=dev)
+    stats = torch.empty(R, 2, dtype=torch.float32, device=dev)
     _launch_rows("cohort", x, (C, R, D, n_top), workspace, x.data_ptr(), _ptr(sel), int(select_min), cohort_models.data_ptr(),
                  cohort_cnt.data_ptr(), C, R, D, n_top, float(eps_cos), float(eps), float(eps_std), stats.data_ptr())
     return stats
@@ -1031,29 +1042,7 @@ def verify_scores_normed(embeddings: torch.Tensor, models: torch.Tensor, cnt: to
     becomes 0.5 ((v - mu_k) / sd_k + (v - mu_r) / sd_r) before it is stored and counted, with ``row_stats`` (R, 2) and
     ``model_stats`` (K, 2) the (mean, spread) pairs of `cohort_stats` for the trial rows and for the bank's models.  The
     same arguments, outputs and rules otherwise; with both tables (0, 1) the same bits."""
-    _check_bank(models, cnt)
-    K, D = models.shape
-    dev = models.device
-    e = _bank_rows(embeddings, D, dev)
-    R = e.shape[0]
-    _check_stats(row_stats, R, dev, "row_stats")
-    _check_stats(model_stats, K, dev, "model_stats")
-    if labels is None and (thresholds is not None or not need_scores):
-        raise ValueError("counts are about targets and impostors: thresholds / need_scores=False need labels")
-    if thresholds is None and not need_scores:
-        raise ValueError("nothing to compute: need_scores=False without thresholds")
-    with _on_device(dev):
-        lab = _bank_labels(labels, K, R, dev) if labels is not None else None
-        thr = _threshold_table(thresholds, dev, device_ok=True) if thresholds is not None else None
-    T = thr.numel() if thr is not None else 0
-    i32 = dict(dtype=torch.int32, device=dev)
-    out = VerifyOutputs(scores=torch.empty(R, K, dtype=torch.float32, device=dev) if need_scores else None,
-                        counts=torch.empty(T, 2, **i32) if T else None,
-                        trials=torch.empty(2, **i32) if lab is not None else None)
-    _launch("ge2e_verify_scores_normed", dev, e.data_ptr(), _ptr(lab), models.data_ptr(), cnt.data_ptr(), K, R, D,
-            float(eps_cos), float(eps), row_stats.data_ptr(), model_stats.data_ptr(), _ptr(thr), T, _ptr(out.scores),
-            _ptr(out.counts), _ptr(out.trials), _stream_ptr(e))
-    return out
+    return _verify(embeddings, models, cnt, (row_stats, model_stats), labels, thresholds, need_scores, eps, eps_cos)
 
 
 # ---- the reference's static helpers (s3:33-38, 41-80, 95-112, 114-127), differentiable like the originals ----------

@@ -4,7 +4,7 @@ bit for bit on one GPU:
     GE2E_HIP_LIB=$PWD/speaker_embedding_ge2e_loss_amd/libge2e_hip_parent.so python tools/output_digest.py > a.txt
     python tools/output_digest.py > b.txt && diff a.txt b.txt
 
-(tools/build_rev.sh builds the other revision's library.)  Two sections:
+(tools/build_rev.sh builds the other revision's library.)  Three sections:
 
   1. the fp32 matrix-core implementations: loss | per | dE | dw | db per (implementation, shape, variant), with and
      without the gradient.  A pair the library refuses prints SKIP.
@@ -18,6 +18,17 @@ bit for bit on one GPU:
        (room for 12 beside it: the 16-byte stores of cos); a speaker of 68 rows that crosses a tile; one speaker
        alone (the other arm of contrast's N > 1)
        masked forms: ignored rows and lone speakers, and, of three batches, one without an active speaker
+  3. the bank kernels, one line per call over every output: enroll_accumulate twice into one bank (sums | cnt after each;
+     the second call leaves speakers untouched) and enroll_finalize; verify_scores without labels, with labels and
+     thresholds, counts only, and both forms of the rows kernel through ge2e_selftest_verify_form; identify at k = 1, 5 and
+     32 with and without labels; cohort_stats at two n_top with and without select; verify_scores_normed with labels and
+     thresholds.  Banks of (K, D, R) as the tests have them:
+       D = 36, 100, 256: the rows kernels' 4, 8 and 16 register-resident steps; D = 7 and 260: the plain loop
+       K = 15, 16, 17, 67, 130: either side of the 16-model tile, of the group of 64 and of two groups; R = 1 .. 130: one
+       wave with one row, a last wave with one row, three tiles
+       speakers with 65, 64 and 1 rows in a call (the 64-index chunk of the speaker sum), speakers 4 mod 8 never enrolled
+       (cnt = 0); labels with ignored rows (-1), a target that is not enrolled, and ids K and K + 5 past the bank
+       cohorts of 2048, 2049 and 6145 at D = 36, R = 40: the three forms of the select kernel
 
 Exit status 1 if one of the fp32 matrix-core implementations appears in no line.
 """
@@ -30,6 +41,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from oracle import ge2e_oracle as orc  # noqa: E402
+from speaker_embedding_ge2e_loss_amd import _lib  # noqa: E402
 from speaker_embedding_ge2e_loss_amd import functional as GF  # noqa: E402
 
 IMPLS = ("fused_f32", "fused_split", "tiled", "team")
@@ -60,6 +72,12 @@ BOUND = {"big": None, "small": 12, "one": None}  # num_speakers of the masked fo
 ROW_CASES = [("big", 64), ("big", 128), ("big", 256), ("big", 260), ("big", 37), ("small", 64), ("small", 37), ("one", 64)]
 B_ROWS = 3
 THRESHOLDS = [0.02 * i - 0.2 for i in range(50)]
+# section 3: (K, D, R, cohort size) -- the banks of tests/enroll_cases.py with the cohorts of tests/snorm_cases.py
+BANK_CASES = [(1, 36, 1, 1), (15, 100, 16, 15), (16, 256, 17, 17), (17, 7, 63, 67), (67, 260, 64, 130), (130, 36, 65, 300),
+              (130, 256, 130, 300), (16, 100, 130, 67)]
+ENROLL_ROWS = ((65, 1, 2, 64, 0, 3, 0, 5), (0, 3, 0, 1, 0, 0, 2, 4))   # rows per speaker (id mod 8) in the two calls
+SELECT_COHORTS = (2048, 2049, 6145)                                   # at D = 36, R = 40
+N_TOPS = (5, 64)
 
 
 def digest(o, names=("loss", "per", "dE", "dw", "db")):
@@ -151,11 +169,101 @@ def exact_section(dev, w, b):
         print(f"eer_counts_labeled {tag}", hashlib.sha256(n.cpu().contiguous().numpy().tobytes()).hexdigest())
 
 
+def line(tag, *tensors):
+    torch.cuda.synchronize()
+    h = hashlib.sha256()
+    for t in tensors:
+        h.update(b"|")
+        if t is not None:
+            h.update(t.detach().cpu().contiguous().numpy().tobytes())
+    print(tag, h.hexdigest())
+
+
+def unit_rows(rng, centre, cls, dev):
+    x = centre[cls] + 0.5 * rng.standard_normal((len(cls), centre.shape[1]))
+    return torch.as_tensor((x / np.linalg.norm(x, axis=1, keepdims=True)).astype(np.float32), device=dev)
+
+
+def make_cohort(rng, C, D, dev):
+    """Unit models; member iff c % 8 != 4 (cnt 1 .. 3, else 0 or -1)."""
+    c = np.arange(C)
+    ccnt = np.where(c % 8 != 4, 1 + c % 3, -(c % 2)).astype(np.int32)
+    return unit_rows(rng, rng.standard_normal((C, D)), c, dev), torch.as_tensor(ccnt, device=dev)
+
+
+def cohort_lines(tag, rows, select, cohort, ccnt):
+    for n_top in N_TOPS:
+        line(f"{tag} n_top={n_top}", GF.cohort_stats(rows, cohort, ccnt, n_top=n_top))
+        line(f"{tag} n_top={n_top} select", GF.cohort_stats(rows, cohort, ccnt, n_top=n_top, select=select, select_min=0))
+
+
+def bank_section(dev):
+    lib = _lib.load()
+    thr = torch.as_tensor(THRESHOLDS, dtype=torch.float64).to(torch.float32).to(dev)
+    T = thr.numel()
+    for K, D, R, C in BANK_CASES:
+        tag = f"K={K} D={D} R={R}"
+        rng = np.random.default_rng(100000 * K + 1000 * D + R)
+        centre = rng.standard_normal((K + 1, D))
+        sums, cnt = torch.zeros(K, D, device=dev), torch.zeros(K, dtype=torch.int32, device=dev)
+        for i, pattern in enumerate(ENROLL_ROWS):
+            lab = np.concatenate([np.repeat(np.arange(K), [pattern[s % 8] for s in range(K)]), [-1, K, K + 5]])
+            lab = lab[rng.permutation(len(lab))]
+            e = unit_rows(rng, centre, np.clip(lab, 0, K), dev)
+            GF.enroll_accumulate(sums, cnt, e, torch.as_tensor(lab.astype(np.int32), device=dev))
+            line(f"enroll_accumulate {i + 1} {tag}", sums, cnt)
+        models = GF.enroll_finalize(sums, cnt)
+        line(f"enroll_finalize {tag}", models)
+        # the trials: enrolled speakers in turn; rows 1 and (from 17 rows on) R - 1 ignored, row 3 the id K + 5, row 5 the
+        # id K, row 6 a speaker that is not enrolled
+        n = cnt.cpu().numpy()
+        enrolled, absent = np.flatnonzero(n > 0), np.flatnonzero(n <= 0)
+        lab = enrolled[np.arange(R) % len(enrolled)]
+        for pos, v in ((1, -1), (3, K + 5), (5, K), (6, int(absent[0]) if len(absent) else K + 5)) + (((R - 1, -1),) if R >= 17 else ()):
+            if pos < R:
+                lab[pos] = v
+        e = unit_rows(rng, centre, np.clip(lab, 0, K), dev)
+        lab = torch.as_tensor(lab.astype(np.int32), device=dev)
+        line(f"verify_scores {tag}", GF.verify_scores(e, models, cnt).scores)
+        o = GF.verify_scores(e, models, cnt, labels=lab, thresholds=thr)
+        line(f"verify_scores labels {tag}", o.scores, o.counts, o.trials)
+        o = GF.verify_scores(e, models, cnt, labels=lab, thresholds=thr, need_scores=False)
+        line(f"verify_scores counts only {tag}", o.counts, o.trials)
+        for form, name in ((1, "staged"), (2, "streamed")):
+            scores = torch.empty(R, K, device=dev)
+            counts, trials = torch.empty(T, 2, dtype=torch.int32, device=dev), torch.empty(2, dtype=torch.int32, device=dev)
+            with torch.cuda.device(dev):
+                _lib.check(lib.ge2e_selftest_verify_form(
+                    e.data_ptr(), lab.data_ptr(), models.data_ptr(), cnt.data_ptr(), K, R, D, GF.EPS_COS, GF.SMALL_ERR,
+                    thr.data_ptr(), T, scores.data_ptr(), counts.data_ptr(), trials.data_ptr(),
+                    torch.cuda.current_stream(dev).cuda_stream, form), "ge2e_selftest_verify_form")
+            line(f"verify_form {name} {tag}", scores, counts, trials)
+        for k in (1, 5, 32):
+            o = GF.identify(e, models, cnt, k=k)
+            line(f"identify k={k} {tag}", o.indices, o.scores)
+            o = GF.identify(e, models, cnt, k=k, labels=lab)
+            line(f"identify k={k} labels {tag}", o.indices, o.scores, o.rank, o.hist)
+        cohort, ccnt = make_cohort(rng, C, D, dev)
+        cohort_lines(f"cohort_stats C={C} {tag}", e, lab, cohort, ccnt)
+        rs = GF.cohort_stats(e, cohort, ccnt, n_top=N_TOPS[0], select=lab, select_min=0)
+        ms = GF.cohort_stats(models, cohort, ccnt, n_top=N_TOPS[0], select=cnt, select_min=1)
+        o = GF.verify_scores_normed(e, models, cnt, rs, ms, labels=lab, thresholds=thr)
+        line(f"verify_scores_normed C={C} {tag}", ms, o.scores, o.counts, o.trials)
+    D, R = 36, 40
+    for C in SELECT_COHORTS:
+        rng = np.random.default_rng(C)
+        cohort, ccnt = make_cohort(rng, C, D, dev)
+        e = unit_rows(rng, rng.standard_normal((1, D)), np.zeros(R, dtype=np.int64), dev)
+        select = torch.as_tensor((np.arange(R) % 7 - 1).astype(np.int32), device=dev)    # every seventh row is not scored
+        cohort_lines(f"cohort_stats C={C} D={D} R={R}", e, select, cohort, ccnt)
+
+
 def main():
     dev = torch.device("cuda:0")
     w, b = torch.tensor(7.5, device=dev), torch.tensor(-2.0, device=dev)
     missing = fused_section(dev, w, b)
     exact_section(dev, w, b)
+    bank_section(dev)
     if missing:
         print("no line for:", " ".join(missing))
     return 1 if missing else 0
