@@ -119,6 +119,41 @@ IndexTables labeled_tables(int B, int N, int R, int D, bool masked) {
     return index_tables(ragged_workspace_bytes(B, masked ? speaker_capacity(N, R) : N, R, D), B, N, R, masked);
 }
 
+// The prologue of every entry that starts with an index kernel, behind the entry's own checks: the four tables inside the
+// call's checked workspace (L: where; the plain form has no speakers and no active) and the launch.  The masked forms write
+// speakers and active into the caller's buffers where the caller gives some.  Handed back: the tables the kernels behind
+// read, and the launch's error.
+enum IndexForm { INDEX_PLAIN, INDEX_MASKED, INDEX_LONE_SPEAKERS };
+struct IndexPtrs { int *offsets, *order, *speakers, *active; hipError_t err; };
+IndexPtrs run_label_index(IndexForm form, const int* labels, int B, int N, int R, const IndexTables& L, void* workspace,
+                          int* speakers, int* active, void* stream) {
+    char* ws = (char*)workspace;
+    IndexPtrs t = {(int*)(ws + L.off), (int*)(ws + L.order), nullptr, nullptr, hipSuccess};
+    if (form == INDEX_PLAIN) {
+        t.err = launch_label_index(labels, B, N, R, t.offsets, t.order, (int*)(ws + L.index), (hipStream_t)stream);
+        return t;
+    }
+    t.speakers = speakers ? speakers : (int*)(ws + L.speakers);
+    t.active = active ? active : (int*)(ws + L.active);
+    t.err = launch_label_index_masked(labels, B, N, R, t.offsets, t.order, t.speakers, t.active, (int*)(ws + L.index),
+                                      (hipStream_t)stream, form == INDEX_LONE_SPEAKERS);
+    return t;
+}
+
+// What the wide loss and the cosine backward share of a ProblemLabeledWide: the tables, the planes of the layout on the
+// checked workspace (`partials`: with the tile partials, which the cosine backward has no room for) and the shape.
+void wide_problem_tables(ProblemLabeledWide& p, const IndexPtrs& t, void* workspace, const LabeledWideLayout& L, bool partials,
+                         int B, int N, int R, int D) {
+    char* ws = (char*)workspace;
+    p.off = t.offsets; p.order = t.order; p.active = t.active;
+    p.CH = (float*)(ws + L.ch); p.SS = (float*)(ws + L.ss); p.GC = (float*)(ws + L.gc); p.DUS = (float*)(ws + L.dus);
+    p.GCP = (float*)(ws + L.gcp); p.CST = (float*)(ws + L.cstat); p.A = (float*)(ws + L.a);
+    p.RST = (float*)(ws + L.rowstat); p.spk = (int*)(ws + L.spk);
+    if (partials) p.PART = (float*)(ws + L.part);
+    p.B = B; p.N = N; p.R = R; p.D = D;
+    p.NA = speaker_capacity(N, R);
+}
+
 // AUTO at shapes both accept (measured at N=64, M=10, D=256, interleaved in one process, tools/compare_impls.py,
 // profiles/r02_team_vs_fused_split_by_B.txt): the eight-CU team kernel wins everywhere (28 us vs 117 us at B = 1,
 // 96 vs 133 us at B = 128, 245 vs 298 us at B = 384, 612 vs 619 us at B = 1024, 2.32 vs 2.40 ms at B = 4096, and it moves
@@ -328,26 +363,30 @@ size_t ge2e_workspace_bytes_labeled(int B, int N, int R, int D, int variant) {
     return ragged_shape_ok(B, N, R, D) ? labeled_tables(B, N, R, D, false).total : 0;
 }
 
-int ge2e_loss_fwd_bwd_labeled(const float* E, const int* labels, int B, int N, int R, int D, const float* w, const float* b,
-                              float eps_cos, float eps, int variant, float* loss, float* per_row_loss, float* dE, float* dw,
-                              float* db, void* workspace, size_t workspace_bytes, void* stream) {
+// Both labelled losses on the ragged kernel.  `masked` (labels of ANY content, include/ge2e_hip.h): N is a bound in the shape
+// rule, the masked index kernel runs, and its `active` gives the ragged kernel's masked instantiation its extents.
+static int labeled_loss(bool masked, const float* E, const int* labels, int B, int N, int R, int D, const float* w,
+                        const float* b, float eps_cos, float eps, int variant, float* loss, float* per_row_loss, float* dE,
+                        float* dw, float* db, int* active, void* workspace, size_t workspace_bytes, void* stream) {
     if (!labels || !loss_ptrs_ok(E, w, b, loss, dE, dw, db)) return GE2E_ERR_NULL;
     IndexTables L{};
-    if (const int code = loss_checks(ragged_shape_ok(B, N, R, D), variant, [&] { return (L = labeled_tables(B, N, R, D, false)).total; },
-                                     workspace, workspace_bytes, E, dE))
+    if (const int code = loss_checks(masked ? masked_shape_ok(B, N, R, D) : ragged_shape_ok(B, N, R, D), variant,
+                                     [&] { return (L = labeled_tables(B, N, R, D, masked)).total; }, workspace, workspace_bytes, E, dE))
         return code;
-    char* ws = (char*)workspace;
-    int* offsets = (int*)(ws + L.off);
-    int* order = (int*)(ws + L.order);
-    const hipError_t err = launch_label_index(labels, B, N, R, offsets, order, (int*)(ws + L.index), (hipStream_t)stream);
-    if (err != hipSuccess) return (int)err;
+    const IndexPtrs t = run_label_index(masked ? INDEX_MASKED : INDEX_PLAIN, labels, B, N, R, L, workspace, nullptr, active, stream);
+    if (t.err != hipSuccess) return (int)t.err;
     const ProblemRagged p = ragged_problem(make_problem_io<ProblemRagged>(E, w, b, eps_cos, eps, variant, loss, per_row_loss, dE, dw, db),
-                                           offsets, order, nullptr, 0, B, N, R, D, workspace);
+                                           t.offsets, t.order, t.active, masked ? speaker_capacity(N, R) : 0, B, N, R, D, workspace);
     return (int)launch_ragged(p, (hipStream_t)stream);
 }
 
-// The labelled loss on labels of ANY content (include/ge2e_hip.h): the masked index kernel's `active` gives the ragged
-// kernel's masked instantiation its extents.
+int ge2e_loss_fwd_bwd_labeled(const float* E, const int* labels, int B, int N, int R, int D, const float* w, const float* b,
+                              float eps_cos, float eps, int variant, float* loss, float* per_row_loss, float* dE, float* dw,
+                              float* db, void* workspace, size_t workspace_bytes, void* stream) {
+    return labeled_loss(false, E, labels, B, N, R, D, w, b, eps_cos, eps, variant, loss, per_row_loss, dE, dw, db, nullptr, workspace,
+                        workspace_bytes, stream);
+}
+
 size_t ge2e_workspace_bytes_labeled_masked(int B, int N, int R, int D, int variant) {
     (void)variant;
     return masked_shape_ok(B, N, R, D) ? labeled_tables(B, N, R, D, true).total : 0;
@@ -357,21 +396,8 @@ int ge2e_loss_fwd_bwd_labeled_masked(const float* E, const int* labels, int B, i
                                      const float* b, float eps_cos, float eps, int variant, float* loss, float* per_row_loss,
                                      float* dE, float* dw, float* db, int* active, void* workspace, size_t workspace_bytes,
                                      void* stream) {
-    if (!labels || !loss_ptrs_ok(E, w, b, loss, dE, dw, db)) return GE2E_ERR_NULL;
-    IndexTables L{};
-    if (const int code = loss_checks(masked_shape_ok(B, N, R, D), variant, [&] { return (L = labeled_tables(B, N, R, D, true)).total; },
-                                     workspace, workspace_bytes, E, dE))
-        return code;
-    char* ws = (char*)workspace;
-    int* offsets = (int*)(ws + L.off);
-    int* order = (int*)(ws + L.order);
-    if (!active) active = (int*)(ws + L.active);
-    const hipError_t err = launch_label_index_masked(labels, B, N, R, offsets, order, (int*)(ws + L.speakers), active,
-                                                     (int*)(ws + L.index), (hipStream_t)stream);
-    if (err != hipSuccess) return (int)err;
-    const ProblemRagged p = ragged_problem(make_problem_io<ProblemRagged>(E, w, b, eps_cos, eps, variant, loss, per_row_loss, dE, dw, db),
-                                           offsets, order, active, speaker_capacity(N, R), B, N, R, D, workspace);
-    return (int)launch_ragged(p, (hipStream_t)stream);
+    return labeled_loss(true, E, labels, B, N, R, D, w, b, eps_cos, eps, variant, loss, per_row_loss, dE, dw, db, active, workspace,
+                        workspace_bytes, stream);
 }
 
 // The masked labelled loss on many workgroups per batch (include/ge2e_hip.h, csrc/ge2e_labeled_wide.hip): the masked
@@ -390,20 +416,10 @@ int ge2e_loss_fwd_bwd_labeled_wide(const float* E, const int* labels, int B, int
     if (const int code = loss_checks(masked_shape_ok(B, N, R, D), variant, [&] { return (L = labeled_wide_layout(B, N, R, D)).t.total; },
                                      workspace, workspace_bytes, E, dE))
         return code;
-    char* ws = (char*)workspace;
-    int* offsets = (int*)(ws + L.t.off);
-    int* order = (int*)(ws + L.t.order);
-    if (!active) active = (int*)(ws + L.t.active);
-    const hipError_t err = launch_label_index_masked(labels, B, N, R, offsets, order, (int*)(ws + L.t.speakers), active,
-                                                     (int*)(ws + L.t.index), (hipStream_t)stream);
-    if (err != hipSuccess) return (int)err;
+    const IndexPtrs t = run_label_index(INDEX_MASKED, labels, B, N, R, L.t, workspace, nullptr, active, stream);
+    if (t.err != hipSuccess) return (int)t.err;
     ProblemLabeledWide p = make_problem_io<ProblemLabeledWide>(E, w, b, eps_cos, eps, variant, loss, per_row_loss, dE, dw, db);
-    p.off = offsets; p.order = order; p.active = active;
-    p.CH = (float*)(ws + L.ch); p.SS = (float*)(ws + L.ss); p.GC = (float*)(ws + L.gc); p.DUS = (float*)(ws + L.dus);
-    p.GCP = (float*)(ws + L.gcp); p.CST = (float*)(ws + L.cstat); p.A = (float*)(ws + L.a);
-    p.RST = (float*)(ws + L.rowstat); p.spk = (int*)(ws + L.spk); p.PART = (float*)(ws + L.part);
-    p.B = B; p.N = N; p.R = R; p.D = D;
-    p.NA = speaker_capacity(N, R);
+    wide_problem_tables(p, t, workspace, L, true, B, N, R, D);
     p.log_eps = log_eps_of(p.eps);
     return (int)launch_labeled_wide(p, (hipStream_t)stream);
 }
@@ -423,25 +439,21 @@ int ge2e_cos_sim_labeled(const float* E, const int* labels, int B, int N, int R,
     const LabeledEvalLayout L = labeled_eval_layout(B, N, R, D);
     if (!workspace_ok(workspace, workspace_bytes, L.t.total)) return GE2E_ERR_WORKSPACE;
     if (!aligned16(E)) return GE2E_ERR_ALIGN;
+    const IndexPtrs t = run_label_index(INDEX_MASKED, labels, B, N, R, L.t, workspace, speakers, active, stream);
+    if (t.err != hipSuccess) return (int)t.err;
     char* ws = (char*)workspace;
-    if (!col) col = (int*)(ws + L.t.extra);
-    if (!speakers) speakers = (int*)(ws + L.t.speakers);
-    if (!active) active = (int*)(ws + L.t.active);
     ProblemLabeledEval p{};
     p.E = E;
-    p.off = (int*)(ws + L.t.off);
-    p.order = (int*)(ws + L.t.order);
-    p.active = active;
+    p.off = t.offsets;
+    p.order = t.order;
+    p.active = t.active;
     p.thr = counts ? thresholds : nullptr;
-    p.cos = cos; p.col = col; p.counts = counts;
+    p.cos = cos; p.col = col ? col : (int*)(ws + L.t.extra); p.counts = counts;
     p.CH = (float*)(ws + L.ch); p.SS = (float*)(ws + L.ss); p.CST = (float*)(ws + L.cstat); p.spk = (int*)(ws + L.spk);
     p.B = B; p.N = N; p.R = R; p.D = D;
     p.NA = speaker_capacity(N, R);
     p.T = counts ? T : 0;
     p.eps_cos = eps_cos; p.eps = eps;
-    const hipError_t err = launch_label_index_masked(labels, B, N, R, (int*)(ws + L.t.off), (int*)(ws + L.t.order), speakers,
-                                                     active, (int*)(ws + L.t.index), (hipStream_t)stream);
-    if (err != hipSuccess) return (int)err;
     return (int)launch_labeled_eval(p, (hipStream_t)stream);
 }
 
@@ -465,15 +477,9 @@ int ge2e_enroll_accumulate(const float* E, const int* labels, int K, int R, int 
     const IndexTables L = enroll_layout(K, R);
     if (!workspace_ok(workspace, workspace_bytes, L.total)) return GE2E_ERR_WORKSPACE;
     if (!aligned16(E) || !aligned16(sums)) return GE2E_ERR_ALIGN;
-    char* ws = (char*)workspace;
-    int* offsets = (int*)(ws + L.off);
-    int* order = (int*)(ws + L.order);
-    int* speakers = (int*)(ws + L.speakers);
-    int* active = (int*)(ws + L.active);
-    const hipError_t err = launch_label_index_masked(labels, 1, K, R, offsets, order, speakers, active, (int*)(ws + L.index),
-                                                     (hipStream_t)stream, true);
-    if (err != hipSuccess) return (int)err;
-    return (int)launch_enroll_accumulate(E, offsets, order, speakers, active, K, R, D, sums, cnt, (hipStream_t)stream);
+    const IndexPtrs t = run_label_index(INDEX_LONE_SPEAKERS, labels, 1, K, R, L, workspace, nullptr, nullptr, stream);
+    if (t.err != hipSuccess) return (int)t.err;
+    return (int)launch_enroll_accumulate(E, t.offsets, t.order, t.speakers, t.active, K, R, D, sums, cnt, (hipStream_t)stream);
 }
 
 int ge2e_enroll_finalize(const float* sums, const int* cnt, int K, int D, float eps_cos, float* models, void* stream) {
@@ -609,21 +615,11 @@ int ge2e_cos_sim_labeled_bwd(const float* E, const int* labels, const float* g_c
     const LabeledWideLayout L = labeled_wide_layout(B, N, R, D, false);
     if (!workspace_ok(workspace, workspace_bytes, L.t.total)) return GE2E_ERR_WORKSPACE;
     if (!aligned16(E) || !aligned16(dE)) return GE2E_ERR_ALIGN;
-    char* ws = (char*)workspace;
-    int* offsets = (int*)(ws + L.t.off);
-    int* order = (int*)(ws + L.t.order);
-    if (!active) active = (int*)(ws + L.t.active);
-    const hipError_t err = launch_label_index_masked(labels, B, N, R, offsets, order, (int*)(ws + L.t.speakers), active,
-                                                     (int*)(ws + L.t.index), (hipStream_t)stream);
-    if (err != hipSuccess) return (int)err;
+    const IndexPtrs t = run_label_index(INDEX_MASKED, labels, B, N, R, L.t, workspace, nullptr, active, stream);
+    if (t.err != hipSuccess) return (int)t.err;
     ProblemLabeledWide p{};
     p.E = E; p.dE = dE;
-    p.off = offsets; p.order = order; p.active = active;
-    p.CH = (float*)(ws + L.ch); p.SS = (float*)(ws + L.ss); p.GC = (float*)(ws + L.gc); p.DUS = (float*)(ws + L.dus);
-    p.GCP = (float*)(ws + L.gcp); p.CST = (float*)(ws + L.cstat); p.A = (float*)(ws + L.a);
-    p.RST = (float*)(ws + L.rowstat); p.spk = (int*)(ws + L.spk);
-    p.B = B; p.N = N; p.R = R; p.D = D;
-    p.NA = speaker_capacity(N, R);
+    wide_problem_tables(p, t, workspace, L, false, B, N, R, D);
     p.eps_cos = eps_cos;
     return (int)launch_labeled_cos_grad(p, g_cos, (hipStream_t)stream);
 }

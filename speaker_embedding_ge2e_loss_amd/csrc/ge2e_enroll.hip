@@ -36,8 +36,8 @@
 //               every operation rounded on its own (no contraction), and that value is stored and counted.  mu_r and
 //               1 / sd_r are read once per tile and only for a scored row, model_stats[k] only for an enrolled column.
 //               Everything else -- labels, targets, ignored rows, counting, tallies, barriers -- is the one text.
-// Every index read from memory is clamped or range-checked where it is read (active, offsets, order, speakers; a label
-// indexes cnt only after 0 <= label < K): whatever labels, cnt and the workspace hold, no access leaves the buffers.
+// Every index read from memory is clamped or range-checked where it is read (active, offsets and order through the index
+// reader of ge2e_rows_dev.hpp; speakers; a label indexes cnt only after 0 <= label < K): no access leaves the buffers.
 #include "ge2e_enroll.hpp"
 
 #include <math.h>
@@ -69,23 +69,22 @@ __global__ __launch_bounds__(kThreads) void enroll_accumulate_kernel(const float
     const bool vecD = (D & 3) == 0;
     const int nwaves = gridDim.x * kWaves;
     for (int k = blockIdx.x * kWaves + (threadIdx.x >> 6); k < NA; k += nwaves) {
-        const int n_act = clampi(active[0], 0, NA);
-        const int r_act = clampi(active[1], 0, R);
+        const int n_act = index_n_act(active, 0, NA);   // (one batch)
         if (k >= n_act) continue;
-        const int r0 = clampi(off[k], 0, r_act), r1 = max(clampi(off[k + 1], 0, r_act), r0);
-        if (r1 == r0) continue;
+        const IndexSpan span = index_span(off, k, index_r_act(active, 0, R, n_act));
+        if (span.r1 == span.r0) continue;
         const int sp = clampi(speakers[k], 0, K - 1);
         float* S = sums + (size_t)sp * D;
         for (int d0 = 0; d0 < D; d0 += wave_stretch(vecD)) {
             const int d = wave_elem(d0, lane, vecD);
             const bool ok = d < D;
-            const v4f s = speaker_sum(E, order, r0, r1, R, D, d, ok, vecD);
+            const v4f s = speaker_sum(E, order, span, R, D, d, ok, vecD);
             if (ok) {   // the bank takes the partial sum once
                 if (vecD) *reinterpret_cast<v4f*>(S + d) = *reinterpret_cast<const v4f*>(S + d) + s;
                 else S[d] = S[d] + s[0];
             }
         }
-        if (lane == 0) cnt[sp] += r1 - r0;
+        if (lane == 0) cnt[sp] += span.r1 - span.r0;
     }
 }
 

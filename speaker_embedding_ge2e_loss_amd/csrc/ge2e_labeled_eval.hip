@@ -22,8 +22,7 @@
 //              it (binary search on the fp32 table in LDS, the comparison is fp32 `>`; bin 0 counts for no threshold and
 //              is not recorded), LDS histograms [2][T+1], a suffix sum, INTEGER atomics into counts: exact, so the same
 //              bits every launch.  No floating-point atomics anywhere.
-// n_act and r_act are clamped to [0, NA] and [0, R] where they are read, every offset to [0, r_act], every row index to
-// [0, R-1], every speaker id to [0, n_act-1]: whatever the memory holds, no access leaves the buffers.
+// The index tables are read through a batch's IndexView (ge2e_rows_dev.hpp has the contract).
 // An active row's bits depend on that row, on its speaker's rows in their order and on the other speakers' rows in their
 // order: the sums have a fixed order, every output element of an MFMA is the same fmaf chain over k, and nothing looks
 // at blockIdx beyond choosing the work.
@@ -60,28 +59,24 @@ __global__ __launch_bounds__(kThreads) void labeled_eval_centroids_kernel(Proble
             int* c = p.counts + (size_t)bi * 2 * p.T;
             for (int t = lane; t < 2 * p.T; t += kWave) c[t] = 0;
         }
-        const int n_act = clampi(p.active[(size_t)bi * 2], 0, NA);
-        const int r_act = clampi(p.active[(size_t)bi * 2 + 1], 0, R);
-        if (k >= n_act) continue;
-        const int* offs = p.off + (size_t)bi * ((size_t)p.N + 1);
-        const int r0 = clampi(offs[k], 0, r_act), r1 = max(clampi(offs[k + 1], 0, r_act), r0);
-        const int* ord = p.order + (size_t)bi * R;
+        const IndexView ix = index_view(p, bi);
+        if (k >= ix.n_act) continue;
+        const IndexSpan sp = ix.span(k);
         const float* E = p.E + (size_t)bi * R * D;
         float* SS = p.SS + ((size_t)bi * NA + k) * D;
         float* CH = p.CH + ((size_t)bi * NA + k) * D;
-        const float fm = (float)(r1 - r0);
+        const float fm = (float)(sp.r1 - sp.r0);
 
-        for (int pp = r0 + lane; pp < r1; pp += kWave) {
-            const int row = clampi(ord[pp], 0, R - 1);
+        for (int pp = sp.r0 + lane; pp < sp.r1; pp += kWave) {
             p.spk[(size_t)bi * R + pp] = k;
-            if constexpr (!kLoss) p.col[(size_t)bi * R + row] = k;
+            if constexpr (!kLoss) p.col[(size_t)bi * R + ix.row_at(pp)] = k;
         }
         // the sums (speaker_sum, ge2e_rows_dev.hpp: rows in ascending position), stored once, and |c|^2 on the way
         float sq = 0.f;
         for (int d0 = 0; d0 < D; d0 += wave_stretch(vecD)) {
             const int d = wave_elem(d0, lane, vecD);
             const bool ok = d < D;
-            const v4f s = speaker_sum(E, ord, r0, r1, R, D, d, ok, vecD);
+            const v4f s = speaker_sum(E, ix.order, sp, R, D, d, ok, vecD);
             if (ok) {
                 if (vecD) *reinterpret_cast<v4f*>(SS + d) = s;
                 else SS[d] = s[0];
@@ -119,9 +114,8 @@ __global__ __launch_bounds__(kThreads) void labeled_eval_rows_kernel(ProblemLabe
     const long long items = (long long)p.B * tiles;
     for (long long item = blockIdx.x; item < items; item += gridDim.x) {
         const int bi = (int)(item / tiles), tile = (int)(item - (long long)bi * tiles);
-        const int n_act = clampi(p.active[(size_t)bi * 2], 0, NA);       // the same two words for every thread
-        const int r_act = clampi(p.active[(size_t)bi * 2 + 1], 0, R);
-        const int* ord = p.order + (size_t)bi * R;
+        const IndexView ix = index_view(p, bi);
+        const int n_act = ix.n_act, r_act = ix.r_act;
         const float* E = p.E + (size_t)bi * R * D;
         const float* CHb = p.CH + (size_t)bi * NA * D;
         const float* SSb = p.SS + (size_t)bi * NA * D;
@@ -134,7 +128,7 @@ __global__ __launch_bounds__(kThreads) void labeled_eval_rows_kernel(ProblemLabe
             const int pp = p0 + i;
             if (pp >= R) break;
             if (pp < r_act) continue;
-            const int row = clampi(ord[pp], 0, R - 1);
+            const int row = ix.row_at(pp);
             if (lane == 0) p.col[(size_t)bi * R + row] = -1;
             if (cosb) {
                 float* cr = cosb + (size_t)row * N;
@@ -149,7 +143,7 @@ __global__ __launch_bounds__(kThreads) void labeled_eval_rows_kernel(ProblemLabe
         if (p0 < r_act) {   // uniform over the wave
             const int nrow = min(kWaveRows, r_act - p0);
             // ---- row norms and the leave-one-out cosine of the wave's 16 positions (ge2e_rows_dev.hpp) ----
-            const TileRows<kSteps> t = tile_rows<kSteps>(E, SSb, CSTb, ord, p.spk + (size_t)bi * R, p0, nrow, n_act, R, D, eps_cos);
+            const TileRows<kSteps> t = tile_rows<kSteps>(E, SSb, CSTb, ix, p0, nrow, D, eps_cos);
             float* cr = cosb ? cosb + (size_t)t.row * N : nullptr;
             // ---- cos tiles on the matrix core: unit centroids x rows, K = D; kAcc column tiles at a time ----
             const int KT = (n_act + 15) >> 4;
@@ -207,7 +201,7 @@ __global__ __launch_bounds__(kThreads) void eer_counts_labeled_kernel(const floa
     const long long items = (long long)B * tiles;
     for (long long item = blockIdx.x; item < items; item += gridDim.x) {
         const int bi = (int)(item / tiles), tile = (int)(item - (long long)bi * tiles);
-        const int n_act = clampi(active[(size_t)bi * 2], 0, N);
+        const int n_act = index_n_act(active, (size_t)bi, N);   // (the caller's active: N is the bound)
         if (n_act == 0) continue;
         counting_begin(hist, thr_lds, thr, T);
         for (int i = wid; i < kTile; i += kWaves) {

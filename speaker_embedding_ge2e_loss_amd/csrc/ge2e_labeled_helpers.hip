@@ -30,7 +30,7 @@ __global__ __launch_bounds__(kThreads) void calc_loss_labeled_kernel(const float
     const int lane = threadIdx.x & 63;
     const size_t rows = (size_t)B * R, nwaves = (size_t)gridDim.x * kWaves;
     for (size_t r = (size_t)blockIdx.x * kWaves + (threadIdx.x >> 6); r < rows; r += nwaves) {
-        const int n_act = clampi(active[(r / R) * 2], 0, N);
+        const int n_act = index_n_act(active, r / R, N);   // (the caller's active: N is the bound)
         const int j = own_column(col, r, n_act);
         if (j < 0) {   // uniform over the wave
             if (lane == 0) per[r] = 0.f;
@@ -76,7 +76,7 @@ __global__ __launch_bounds__(kThreads) void calc_loss_labeled_bwd_kernel(const f
     const size_t rows = (size_t)B * R, nwaves = (size_t)gridDim.x * kWaves;
     for (size_t r = (size_t)blockIdx.x * kWaves + (threadIdx.x >> 6); r < rows; r += nwaves) {
         const size_t bi = r / R;
-        const int n_act = clampi(active[bi * 2], 0, N);
+        const int n_act = index_n_act(active, bi, N);
         const int j = own_column(col, r, n_act);
         float* out = dS + r * N;
         if (j < 0) {   // uniform over the wave

@@ -27,10 +27,9 @@
 // and gc, speakers, de as they are (launch_labeled_wide_backward: one copy for both entries).
 // No floating-point atomics, no integer ones either; every sum has a fixed order that depends on the shapes and on the
 // batch's own labels only, never on the batch's place in the stack or on which workgroup took the work.  Grids are sized
-// from R and NA = speaker_capacity(N, R); n_act and r_act are read on the device and clamped to [0, NA] and [0, R] where
-// they are read, every offset to [0, r_act], every row index to [0, R-1], every speaker id to [0, n_act-1]: whatever the
-// workspace and the labels hold, no access leaves the buffers and no loop is unbounded.  Rows that do not count are
-// never read.  Every barrier is reached by the whole workgroup (the conditions around them are uniform).
+// from R and NA = speaker_capacity(N, R); n_act and r_act are read on the device, and every table through a batch's
+// IndexView (ge2e_rows_dev.hpp has the contract), here with r_act = 0 where n_act = 0: nothing counts without a speaker.
+// Rows that do not count are never read.  Every barrier is reached by the whole workgroup (the conditions are uniform).
 #include "ge2e_labeled_wide.hpp"
 
 #include <math.h>
@@ -65,13 +64,16 @@ __device__ __forceinline__ void store_own(float* row, int d, const v4f& v, bool 
     else row[d] = v[0];
 }
 
-// The batch's extents: the same two words for every thread that works on the batch.  Nothing counts without a speaker.
-struct Extents { int n_act, r_act; };
-__device__ __forceinline__ Extents extents(const ProblemLabeledWide& p, int bi) {
-    Extents x;
-    x.n_act = clampi(p.active[(size_t)bi * 2], 0, p.NA);
-    x.r_act = x.n_act > 0 ? clampi(p.active[(size_t)bi * 2 + 1], 0, p.R) : 0;
-    return x;
+constexpr bool kRowsNeedSpeaker = true;   // every batch's IndexView here: nothing counts without a speaker
+
+// The batch's planes as the two rows kernels read and write them.
+struct RowPlanes {
+    const float *E, *CH, *SS, *CST;
+    float *A, *RST;
+};
+__device__ __forceinline__ RowPlanes row_planes(const ProblemLabeledWide& p, int bi, int NAp) {
+    const size_t b = (size_t)bi, R = (size_t)p.R, NA = (size_t)p.NA, D = (size_t)p.D;
+    return {p.E + b * R * D, p.CH + b * NA * D, p.SS + b * NA * D, p.CST + b * NA * 4, p.A + b * R * NAp, p.RST + b * R * 8};
 }
 
 // ---- rows: phases B0, B1, B2 ---------------------------------------------------------------------------------------------
@@ -92,22 +94,15 @@ __global__ __launch_bounds__(kThreads) void wide_rows_kernel(ProblemLabeledWide 
     const long long items = (long long)p.B * tiles;
     for (long long item = blockIdx.x; item < items; item += gridDim.x) {
         const int bi = (int)(item / tiles), tile = (int)(item - (long long)bi * tiles);
-        const Extents x = extents(p, bi);
-        const int n_act = x.n_act, r_act = x.r_act;
-        const int* ord = p.order + (size_t)bi * R;
-        const int* spk = p.spk + (size_t)bi * R;
-        const float* E = p.E + (size_t)bi * R * D;
-        const float* CHb = p.CH + (size_t)bi * NA * D;
-        const float* SSb = p.SS + (size_t)bi * NA * D;
-        const float* CSTb = p.CST + (size_t)bi * NA * 4;
-        float* Ab = p.A + (size_t)bi * R * NAp;
-        float* RSTb = p.RST + (size_t)bi * R * 8;
+        const IndexView ix = index_view(p, bi, kRowsNeedSpeaker);
+        const int n_act = ix.n_act, r_act = ix.r_act;
+        const RowPlanes b = row_planes(p, bi, NAp);
         const int p0 = tile * kTile + wid * kWaveRows;
 
         // the positions that do not count: per = 0
         if (p.per && lane < kWaveRows) {
             const int pp = p0 + lane;
-            if (pp < R && pp >= r_act) p.per[(size_t)bi * R + clampi(ord[pp], 0, R - 1)] = 0.f;
+            if (pp < R && pp >= r_act) p.per[(size_t)bi * R + ix.row_at(pp)] = 0.f;
         }
         if (tile * kTile >= r_act) continue;   // uniform over the workgroup
 
@@ -115,17 +110,17 @@ __global__ __launch_bounds__(kThreads) void wide_rows_kernel(ProblemLabeledWide 
         const int nrow = wave_active ? min(kWaveRows, r_act - p0) : 0;
         if (wave_active) {
             // ---- B0: row norms and the leave-one-out cosine of the wave's 16 positions (ge2e_rows_dev.hpp) ----
-            const TileRows<kSteps> t = tile_rows<kSteps>(E, SSb, CSTb, ord, spk, p0, nrow, n_act, R, D, eps_cos);
+            const TileRows<kSteps> t = tile_rows<kSteps>(b.E, b.SS, b.CST, ix, p0, nrow, D, eps_cos);
             if (t.row_ok && q == 0) {
-                float* rs = RSTb + (size_t)t.pp * 8;
+                float* rs = b.RST + (size_t)t.pp * 8;
                 const v4f st = {t.rne, t.ke, t.rnu, t.ku};
                 *reinterpret_cast<v4f*>(rs) = st;
                 rs[RS_COSD] = t.cosd;
             }
             // ---- B1: cos tiles on the matrix core: unit centroids x rows, K = D; kAcc column tiles at a time ----
-            float* ar = Ab + (size_t)t.pp * NAp;
+            float* ar = b.A + (size_t)t.pp * NAp;
             const int KT = (n_act + 15) >> 4;
-            tile_cosines<kSteps, kAcc>(t, CHb, n_act, D, [&](int kt0, const v4f (&acc)[kAcc]) {
+            tile_cosines<kSteps, kAcc>(t, b.CH, n_act, D, [&](int kt0, const v4f (&acc)[kAcc]) {
                 // the lane holds columns c0 .. c0+3 of row l15: the cosine before eps, the own column replaced
 #pragma unroll
                 for (int a = 0; a < kAcc; ++a) {
@@ -150,9 +145,9 @@ __global__ __launch_bounds__(kThreads) void wide_rows_kernel(ProblemLabeledWide 
         for (int it = 0; 4 * it < nrow; ++it) {   // uniform over the wave
             const bool ok = 4 * it + q < nrow;
             const int r = p0 + (ok ? 4 * it + q : 0);
-            const int j = clampi(spk[r], 0, n_act - 1);
-            float* Arow = Ab + (size_t)r * NAp;
-            float* rs = RSTb + (size_t)r * 8;
+            const int j = ix.speaker_at(r);
+            float* Arow = b.A + (size_t)r * NAp;
+            float* rs = b.RST + (size_t)r * 8;
             const float cosd = rs[RS_COSD];
             const float sjj = w * (cosd + eps) + bias;
             float mx, best, dwr = 0.f, dbr = 0.f;
@@ -165,7 +160,7 @@ __global__ __launch_bounds__(kThreads) void wide_rows_kernel(ProblemLabeledWide 
                 db_acc += dbr;
                 if (l15 == 0) {
                     loss_acc += rl.per;
-                    if (p.per) p.per[(size_t)bi * R + clampi(ord[r], 0, R - 1)] = rl.per;
+                    if (p.per) p.per[(size_t)bi * R + ix.row_at(r)] = rl.per;
                     rs[RS_AD] = rl.ad; rs[RS_COEF] = rl.coef;
                 }
             }
@@ -208,29 +203,22 @@ __global__ __launch_bounds__(kThreads) void labeled_cos_grad_rows_kernel(Problem
     const long long items = (long long)p.B * tiles;
     for (long long item = blockIdx.x; item < items; item += gridDim.x) {
         const int bi = (int)(item / tiles), tile = (int)(item - (long long)bi * tiles);
-        const Extents x = extents(p, bi);
-        const int n_act = x.n_act, r_act = x.r_act;
+        const IndexView ix = index_view(p, bi, kRowsNeedSpeaker);
+        const int n_act = ix.n_act, r_act = ix.r_act;
         const int p0 = tile * kTile + wid * kWaveRows;
         if (p0 >= r_act) continue;   // uniform over the wave; no barrier in this kernel
-        const int* ord = p.order + (size_t)bi * R;
-        const int* spk = p.spk + (size_t)bi * R;
-        const float* E = p.E + (size_t)bi * R * D;
-        const float* CHb = p.CH + (size_t)bi * NA * D;
-        const float* SSb = p.SS + (size_t)bi * NA * D;
-        const float* CSTb = p.CST + (size_t)bi * NA * 4;
-        float* Ab = p.A + (size_t)bi * R * NAp;
-        float* RSTb = p.RST + (size_t)bi * R * 8;
+        const RowPlanes b = row_planes(p, bi, NAp);
         const int nrow = min(kWaveRows, r_act - p0);
 
-        const TileRows<kSteps> t = tile_rows<kSteps>(E, SSb, CSTb, ord, spk, p0, nrow, n_act, R, D, eps_cos);
-        float* rs = RSTb + (size_t)t.pp * 8;
+        const TileRows<kSteps> t = tile_rows<kSteps>(b.E, b.SS, b.CST, ix, p0, nrow, D, eps_cos);
+        float* rs = b.RST + (size_t)t.pp * 8;
         if (t.row_ok && q == 0) {
             const v4f st = {t.rne, t.ke, t.rnu, t.ku};
             *reinterpret_cast<v4f*>(rs) = st;
             rs[RS_COSD] = t.cosd;
         }
         const float* gr = g_cos + ((size_t)bi * R + t.row) * N;   // (!row_ok: the wave's first row, an active one)
-        float* ar = Ab + (size_t)t.pp * NAp;
+        float* ar = b.A + (size_t)t.pp * NAp;
         const int KT = (n_act + 15) >> 4;
         // the lane's four words of g_cos in every tile of the group that starts at tile kt0
         v4f gnext[kAcc];
@@ -248,7 +236,7 @@ __global__ __launch_bounds__(kThreads) void labeled_cos_grad_rows_kernel(Problem
         };
         load_g(0);
         float coef = 0.f;
-        tile_cosines<kSteps, kAcc>(t, CHb, n_act, D, [&](int kt0, const v4f (&acc)[kAcc]) {
+        tile_cosines<kSteps, kAcc>(t, b.CH, n_act, D, [&](int kt0, const v4f (&acc)[kAcc]) {
             v4f gc[kAcc];
 #pragma unroll
             for (int a = 0; a < kAcc; ++a) gc[a] = gnext[a];
@@ -285,8 +273,8 @@ __global__ __launch_bounds__(kThreads) void wide_sums_kernel(ProblemLabeledWide 
     const long long nwaves = (long long)gridDim.x * kWaves;
     for (long long wv = (long long)blockIdx.x * kWaves + (threadIdx.x >> 6); wv < p.B; wv += nwaves) {
         const int bi = (int)wv;
-        const Extents x = extents(p, bi);
-        const int nt = min((x.r_act + kTile - 1) / kTile, tiles);
+        const int r_act = index_r_act(p.active, (size_t)bi, p.R, index_n_act(p.active, (size_t)bi, p.NA), kRowsNeedSpeaker);
+        const int nt = min((r_act + kTile - 1) / kTile, tiles);
         float l = 0.f, a = 0.f, c = 0.f;
         for (int t = lane; t < nt; t += kWave) {
             const float* pt = p.PART + ((size_t)bi * tiles + t) * 4;
@@ -310,7 +298,7 @@ __global__ __launch_bounds__(kThreads) void wide_sums_kernel(ProblemLabeledWide 
 __global__ __launch_bounds__(kThreads) void wide_gc_kernel(ProblemLabeledWide p, int S, int KTc, int DB) {
     const int lane = threadIdx.x & 63;
     const int l15 = lane & 15, q = lane >> 4;
-    const int D = p.D, R = p.R, NA = p.NA;
+    const int D = p.D, NA = p.NA;
     const int NAp = (NA + 3) & ~3;
     const v4f zero4 = {0.f, 0.f, 0.f, 0.f};
     const long long per_batch = (long long)S * KTc * DB;
@@ -321,17 +309,14 @@ __global__ __launch_bounds__(kThreads) void wide_gc_kernel(ProblemLabeledWide p,
         const int piece = (int)(rem / ((long long)KTc * DB));
         rem -= (long long)piece * KTc * DB;
         const int kt = (int)(rem / DB), db = (int)(rem - (long long)kt * DB);
-        const Extents x = extents(p, bi);
-        const int n_act = x.n_act, r_act = x.r_act;
+        const IndexView ix = index_view(p, bi, kRowsNeedSpeaker);
+        const int n_act = ix.n_act, r_act = ix.r_act;
         const int k_base = kt * 16 * kGcTiles;
         if (k_base >= n_act) continue;   // uniform over the wave
         // the piece's rows: whole blocks of 64, the same cut for every wave of the batch
         const int len = ((r_act + S - 1) / S + kWave - 1) / kWave * kWave;
         const int r_begin = min(piece * len, r_act), r_end = min(r_begin + len, r_act);
-        const int* ord = p.order + (size_t)bi * R;
-        const float* E = p.E + (size_t)bi * R * D;
-        const float* Ab = p.A + (size_t)bi * R * NAp;
-        const float* RSTb = p.RST + (size_t)bi * R * 8;
+        const RowPlanes pl = row_planes(p, bi, NAp);
         int ka[kGcTiles], dcol[kAcc];
         bool ka_ok[kGcTiles], d_ok[kAcc];
 #pragma unroll
@@ -350,7 +335,7 @@ __global__ __launch_bounds__(kThreads) void wide_gc_kernel(ProblemLabeledWide p,
 #pragma unroll
             for (int t = 0; t < kAcc; ++t) acc[u][t] = zero4;
         for (int rb = r_begin; rb < r_end; rb += kWave) {
-            const int idx = clampi(ord[min(rb + lane, r_end - 1)], 0, R - 1);   // one coalesced load for 64 positions
+            const int idx = ix.row_at(min(rb + lane, r_end - 1));   // one coalesced load for 64 positions
             // kGcAhead steps at a time: all their loads, then all their MFMAs (left alone, the scheduler sinks every load
             // to the step that uses it and a step waits out a round trip to L2)
 #pragma unroll
@@ -365,9 +350,9 @@ __global__ __launch_bounds__(kThreads) void wide_gc_kernel(ProblemLabeledWide p,
                     const int row = q == 0 ? i0 : q == 1 ? i1 : q == 2 ? i2 : i3;
                     r_ok[i] = rb + 4 * s + q < r_end;
                     const int r = min(rb + 4 * s + q, r_end - 1);
-                    rne[i] = RSTb[(size_t)r * 8 + RS_RNE];
-                    const float* ar = Ab + (size_t)r * NAp;
-                    const float* er = E + (size_t)row * D;
+                    rne[i] = pl.RST[(size_t)r * 8 + RS_RNE];
+                    const float* ar = pl.A + (size_t)r * NAp;
+                    const float* er = pl.E + (size_t)row * D;
 #pragma unroll
                     for (int u = 0; u < kGcTiles; ++u) ra[i][u] = ar[ka[u]];
 #pragma unroll
@@ -412,12 +397,9 @@ __global__ __launch_bounds__(kThreads) void wide_speakers_kernel(ProblemLabeledW
     const long long total = (long long)p.B * NA, nwaves = (long long)gridDim.x * kWaves;
     for (long long wv = (long long)blockIdx.x * kWaves + (threadIdx.x >> 6); wv < total; wv += nwaves) {
         const int bi = (int)(wv / NA), k = (int)(wv - (long long)bi * NA);
-        const Extents x = extents(p, bi);
-        if (k >= x.n_act) continue;
-        const int r_act = x.r_act;
-        const int* offs = p.off + (size_t)bi * ((size_t)p.N + 1);
-        const int r0 = clampi(offs[k], 0, r_act), r1 = max(clampi(offs[k + 1], 0, r_act), r0);
-        const int* ord = p.order + (size_t)bi * R;
+        const IndexView ix = index_view(p, bi, kRowsNeedSpeaker);
+        if (k >= ix.n_act) continue;
+        const auto [r0, r1] = ix.span(k);
         const float* E = p.E + (size_t)bi * R * D;
         const float* RSTb = p.RST + (size_t)bi * R * 8;
         const size_t at = ((size_t)bi * NA + k) * D;
@@ -465,7 +447,7 @@ __global__ __launch_bounds__(kThreads) void wide_speakers_kernel(ProblemLabeledW
             v4f dus = {0.f, 0.f, 0.f, 0.f};
             for (int c0 = r0; c0 < r1; c0 += kWave) {
                 const int pp = c0 + lane;
-                const int idx = pp < r1 ? clampi(ord[pp], 0, R - 1) : 0;   // one coalesced load for up to 64 rows
+                const int idx = pp < r1 ? ix.row_at(pp) : 0;   // one coalesced load for up to 64 rows
                 const int cnt = min(kWave, r1 - c0);
                 for (int i = 0; i < cnt; ++i) {
                     const float* er = E + (size_t)__builtin_amdgcn_readlane(idx, i) * D;
@@ -500,15 +482,14 @@ __global__ __launch_bounds__(kThreads) void wide_de_kernel(ProblemLabeledWide p,
         const int bi = (int)(item / per_batch);
         const long long rem = item - (long long)bi * per_batch;
         const int tile = (int)(rem / DB), db = (int)(rem - (long long)tile * DB);
-        const Extents x = extents(p, bi);
-        const int n_act = x.n_act, r_act = x.r_act;
-        const int* ord = p.order + (size_t)bi * R;
+        const IndexView ix = index_view(p, bi, kRowsNeedSpeaker);
+        const int n_act = ix.n_act, r_act = ix.r_act;
         float* dE = p.dE + (size_t)bi * R * D;
         const int p0 = tile * kTile + wid * kWaveRows;
         const int pp = p0 + l15;
         if (p0 >= R) continue;   // uniform over the wave; no barrier in this kernel
         const bool in_R = pp < R, row_ok = pp < r_act;
-        const int my_row = clampi(ord[in_R ? pp : p0], 0, R - 1);
+        const int my_row = ix.row_at(in_R ? pp : p0);
         float* out = dE + (size_t)my_row * D;
         if (p0 >= r_act) {   // uniform over the wave: nothing counts here
             if (in_R) {
@@ -521,7 +502,7 @@ __global__ __launch_bounds__(kThreads) void wide_de_kernel(ProblemLabeledWide p,
             continue;
         }
         const int my_pp = row_ok ? pp : p0;   // (p0 is an active position: readable)
-        const int sp = clampi(p.spk[(size_t)bi * R + my_pp], 0, n_act - 1);
+        const int sp = ix.speaker_at(my_pp);
         const float* pa = p.A + ((size_t)bi * R + my_pp) * NAp;
         const float* CHb = p.CH + (size_t)bi * NA * D;
         v4f acc[kAcc];
@@ -605,25 +586,31 @@ __global__ __launch_bounds__(kThreads) void wide_de_kernel(ProblemLabeledWide p,
 unsigned blocks_for(long long items, long long per_block = 1) {
     return (unsigned)std::max<long long>(1, std::min<long long>((items + per_block - 1) / per_block, kMaxBlocks));
 }
-}  // namespace
 
-hipError_t launch_labeled_wide(const ProblemLabeledWide& p, hipStream_t stream) {
+// The front of both chains: the centroid launch (what labeled_eval_centroids_kernel<true> reads and writes, from the wide
+// problem), then the chain's rows kernel, one workgroup per (batch, tile): rows(ks, grid, tiles) launches its instantiation.
+template <class Rows>
+hipError_t launch_wide_front(const ProblemLabeledWide& p, hipStream_t stream, Rows&& rows) {
     ProblemLabeledEval c{};
     c.E = p.E; c.off = p.off; c.order = p.order; c.active = p.active;
     c.CH = p.CH; c.SS = p.SS; c.CST = p.CST; c.spk = p.spk;
     c.B = p.B; c.N = p.N; c.R = p.R; c.D = p.D; c.NA = p.NA;
     c.eps_cos = p.eps_cos; c.eps = p.eps;
-    hipError_t err = launch_labeled_centroids(c, true, stream);
+    const hipError_t err = launch_labeled_centroids(c, true, stream);
+    if (err != hipSuccess) return err;
+    const int tiles = wide_tiles(p.R);
+    dispatch_tile_steps(p.D, [&](auto ks) { rows(ks, dim3(blocks_for((long long)p.B * tiles)), tiles); });
+    return hipGetLastError();
+}
+}  // namespace
+
+hipError_t launch_labeled_wide(const ProblemLabeledWide& p, hipStream_t stream) {
+    hipError_t err = launch_wide_front(p, stream, [&](auto ks, dim3 grid, int tiles) {
+        hipLaunchKernelGGL((wide_rows_kernel<decltype(ks)::value>), grid, dim3(kThreads), 0, stream, p, tiles);
+    });
     if (err != hipSuccess) return err;
 
-    const int tiles = wide_tiles(p.R);
-    const unsigned rgrid = blocks_for((long long)p.B * tiles);
-    dispatch_tile_steps(p.D, [&](auto ks) {
-        hipLaunchKernelGGL((wide_rows_kernel<decltype(ks)::value>), dim3(rgrid), dim3(kThreads), 0, stream, p, tiles);
-    });
-    if ((err = hipGetLastError()) != hipSuccess) return err;
-
-    hipLaunchKernelGGL(wide_sums_kernel, dim3(blocks_for(p.B, kWaves)), dim3(kThreads), 0, stream, p, tiles);
+    hipLaunchKernelGGL(wide_sums_kernel, dim3(blocks_for(p.B, kWaves)), dim3(kThreads), 0, stream, p, wide_tiles(p.R));
     if ((err = hipGetLastError()) != hipSuccess || !p.dE) return err;
 
     return launch_labeled_wide_backward(p, stream);
@@ -643,20 +630,10 @@ hipError_t launch_labeled_wide_backward(const ProblemLabeledWide& p, hipStream_t
 }
 
 hipError_t launch_labeled_cos_grad(const ProblemLabeledWide& p, const float* g_cos, hipStream_t stream) {
-    ProblemLabeledEval c{};
-    c.E = p.E; c.off = p.off; c.order = p.order; c.active = p.active;
-    c.CH = p.CH; c.SS = p.SS; c.CST = p.CST; c.spk = p.spk;
-    c.B = p.B; c.N = p.N; c.R = p.R; c.D = p.D; c.NA = p.NA;
-    c.eps_cos = p.eps_cos; c.eps = p.eps;
-    hipError_t err = launch_labeled_centroids(c, true, stream);
-    if (err != hipSuccess) return err;
-    const int tiles = wide_tiles(p.R);
-    const unsigned rgrid = blocks_for((long long)p.B * tiles);
-    dispatch_tile_steps(p.D, [&](auto ks) {
-        hipLaunchKernelGGL((labeled_cos_grad_rows_kernel<decltype(ks)::value>), dim3(rgrid), dim3(kThreads), 0, stream, p,
-                           g_cos, tiles);
+    const hipError_t err = launch_wide_front(p, stream, [&](auto ks, dim3 grid, int tiles) {
+        hipLaunchKernelGGL((labeled_cos_grad_rows_kernel<decltype(ks)::value>), grid, dim3(kThreads), 0, stream, p, g_cos, tiles);
     });
-    if ((err = hipGetLastError()) != hipSuccess) return err;
+    if (err != hipSuccess) return err;
     return launch_labeled_wide_backward(p, stream);
 }
 

@@ -30,6 +30,29 @@ __device__ __forceinline__ int wave_inclusive_scan(int v, int lane) {
     return v;
 }
 
+// Step 3's grouping, for both forms: the lanes of a wave that hold the same key find each other with ballots.  rank = the
+// equal keys in lower lanes, group = how many there are, lead = the lowest of them.  Called by the whole wave; a lane that
+// is not `valid` joins no group.
+struct KeyGroup { int rank, group, lead; };
+__device__ __forceinline__ KeyGroup wave_group_by_key(int key, bool valid, int lane) {
+    KeyGroup g = {0, 0, lane};
+    bool todo = valid;
+    for (;;) {   // one round per distinct key of the wave; every lane of the wave takes every round
+        const unsigned long long open = __ballot(todo);
+        if (!open) break;
+        const int first = __ffsll((long long)open) - 1;
+        const bool same = todo && key == __shfl(key, first);
+        const unsigned long long m = __ballot(same);
+        if (same) {
+            g.rank = __popcll(m & ((1ull << lane) - 1ull));
+            g.group = __popcll(m);
+            g.lead = first;
+            todo = false;
+        }
+    }
+    return g;
+}
+
 // One batch.  cnt: N counters (LDS or workspace); wtot: kWaves ints of LDS.
 __device__ __forceinline__ void index_batch(const int* lab, int N, int R, int* offs, int* ord, int* cnt, int* wtot) {
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -68,30 +91,16 @@ __device__ __forceinline__ void index_batch(const int* lab, int N, int R, int* o
         const long long r = r0 + tid;
         const bool valid = r < R;
         const int l = valid ? label_at(r) : -1;
-        int rank = 0, group = 0, lead = lane;
-        bool todo = valid;
-        for (;;) {   // one round per distinct label of the wave; every lane of the wave takes every round
-            const unsigned long long open = __ballot(todo);
-            if (!open) break;
-            const int first = __ffsll((long long)open) - 1;
-            const bool same = todo && l == __shfl(l, first);
-            const unsigned long long g = __ballot(same);
-            if (same) {
-                rank = __popcll(g & ((1ull << lane) - 1ull));
-                group = __popcll(g);
-                lead = first;
-                todo = false;
-            }
-        }
+        const KeyGroup g = wave_group_by_key(l, valid, lane);
         for (int w = 0; w < kWaves; ++w) {
             if (wid == w) {
                 int base = 0;
-                if (valid && rank == 0) {   // one lane per label: nobody else touches this cursor now
+                if (valid && g.rank == 0) {   // one lane per label: nobody else touches this cursor now
                     base = cnt[l];
-                    cnt[l] = base + group;
+                    cnt[l] = base + g.group;
                 }
-                base = __shfl(base, lead);
-                if (valid) ord[base + rank] = (int)r;
+                base = __shfl(base, g.lead);
+                if (valid) ord[base + g.rank] = (int)r;
             }
             __syncthreads();
         }
@@ -170,32 +179,18 @@ __device__ __forceinline__ void index_batch_masked(const int* lab, int N, int R,
             key = (l >= 0 && l < N && cnt[l] >= 0) ? l : N;
         }
         __syncthreads();   // every key of the chunk is decided before a cursor moves
-        int rank = 0, group = 0, lead = lane;
-        bool todo = valid;
-        for (;;) {   // one round per distinct key of the wave; every lane of the wave takes every round
-            const unsigned long long open = __ballot(todo);
-            if (!open) break;
-            const int first = __ffsll((long long)open) - 1;
-            const bool same = todo && key == __shfl(key, first);
-            const unsigned long long g = __ballot(same);
-            if (same) {
-                rank = __popcll(g & ((1ull << lane) - 1ull));
-                group = __popcll(g);
-                lead = first;
-                todo = false;
-            }
-        }
+        const KeyGroup g = wave_group_by_key(key, valid, lane);
         for (int w = 0; w < kWaves; ++w) {
             if (wid == w) {
                 int base = 0;
-                if (valid && rank == 0) {   // one lane per key: nobody else touches this cursor now
+                if (valid && g.rank == 0) {   // one lane per key: nobody else touches this cursor now
                     int* cur = key < N ? &cnt[key] : tail;
                     base = *cur;
-                    *cur = base + group;
+                    *cur = base + g.group;
                 }
-                base = __shfl(base, lead);
+                base = __shfl(base, g.lead);
                 // (the clamp holds only for labels that change between the two reads: otherwise the positions are exact)
-                if (valid) ord[min(max(base + rank, 0), R - 1)] = (int)r;
+                if (valid) ord[min(max(base + g.rank, 0), R - 1)] = (int)r;
             }
             __syncthreads();
         }

@@ -1,9 +1,10 @@
 // Device helpers of the exact kernels, written once: ge2e_generic.hip, ge2e_f64.hip, ge2e_ragged.hip,
 // ge2e_labeled_wide.hip, ge2e_labeled_eval.hip and the bank kernels (ge2e_enroll.hip, ge2e_identify.hip, ge2e_snorm.hip).
-// The statistic indices, the 16-byte fragment loads of the fp32 MFMA, the row-loss step (row_scan, row_loss), the
-// leave-one-out gradient term (loo_term), the cosine-tile stage of the row kernels (tile_rows, tile_rows_plain,
-// tile_cosines) with the geometry of a workgroup that runs it (tile_geom), and the speaker sum and the unit scaling of the
-// centroid and enrolment kernels (speaker_sum, mean_sq, unit_scale).  Algebra: oracle/ge2e_oracle.py:closed_form and the header of
+// The statistic indices, the reader of the label index tables (IndexView), the 16-byte fragment loads of the fp32 MFMA, the
+// row-loss step (row_scan, row_loss), the leave-one-out gradient term (loo_term), the cosine-tile stage of the row kernels
+// (tile_rows, tile_rows_plain, tile_cosines) with the geometry of a workgroup that runs it (tile_geom), and the speaker sum
+// and the unit scaling of the centroid and enrolment kernels (speaker_sum, mean_sq, unit_scale).  Algebra:
+// oracle/ge2e_oracle.py:closed_form and the header of
 // ge2e_generic.hip.  The operand order and the parentheses of every expression are part of the results: the kernels agree
 // bit for bit with what they computed when each carried its own copy (tools/output_digest.py).
 #pragma once
@@ -19,11 +20,47 @@ constexpr int CS_RN = 0, CS_KAP = 1, CS_M = 2, CS_M1 = 3;
 
 typedef float v4f __attribute__((ext_vector_type(4)));
 
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
+
+// ---- the one reader of the index tables ----------------------------------------------------------------------------------
+// An index kernel (ge2e_labels.hip) has left offsets [B][N+1], order [B][R] and active [B][2] = {n_act, r_act}; the centroid
+// kernel adds spk [B][R], the compact speaker of every sorted position.  Every kernel behind them reads the tables here
+// and nowhere else, under ONE contract: n_act and r_act are clamped to [0, n_bound] and [0, R] where they are read, every
+// offset to [0, r_act], every row index to [0, R-1], every speaker id to [0, n_act-1]: whatever the memory holds, no
+// access leaves the buffers and no loop over them is unbounded.  n_bound: the speakers the reader's planes are laid out for
+// (speaker_capacity, enroll_capacity), or the caller's N where active is the caller's.  (ge2e_ragged.hip is no client: its
+// gather trusts the permutation the index kernel writes, and its offsets may be the caller's.)
+__device__ __forceinline__ int index_n_act(const int* active, size_t bi, int n_bound) { return clampi(active[bi * 2], 0, n_bound); }
+// `rows_need_speaker`: r_act = 0 where n_act = 0 (the wide route, whose kernels ask r_act alone whether there is work); the
+// evaluation kernels ask n_act first and take r_act as it stands.
+__device__ __forceinline__ int index_r_act(const int* active, size_t bi, int R, int n_act, bool rows_need_speaker = false) {
+    return (rows_need_speaker && n_act == 0) ? 0 : clampi(active[bi * 2 + 1], 0, R);
+}
+struct IndexSpan { int r0, r1; };   // the sorted positions r0 .. r1 - 1 of a compact speaker (r1 >= r0 whatever off holds)
+__device__ __forceinline__ IndexSpan index_span(const int* off, int k, int r_act) {   // off: the batch's; k < n_act
+    const int r0 = clampi(off[k], 0, r_act);
+    return {r0, max(clampi(off[k + 1], 0, r_act), r0)};
+}
+__device__ __forceinline__ int index_row(const int* order, int p, int R) { return clampi(order[p], 0, R - 1); }   // p < R
+// One batch's tables and extents, of a launch description that carries them (ProblemLabeledEval, ProblemLabeledWide).
+struct IndexView {
+    const int *off, *order, *spk;   // the batch's offsets [N+1], order [R], spk [R]
+    int R, n_act, r_act;
+    __device__ __forceinline__ IndexSpan span(int k) const { return index_span(off, k, r_act); }
+    __device__ __forceinline__ int row_at(int p) const { return index_row(order, p, R); }
+    __device__ __forceinline__ int speaker_at(int p) const { return clampi(spk[p], 0, n_act - 1); }   // p < r_act
+};
+template <class P>
+__device__ __forceinline__ IndexView index_view(const P& p, int bi, bool rows_need_speaker = false) {
+    const size_t b = (size_t)bi;
+    const int n_act = index_n_act(p.active, b, p.NA);
+    const int r_act = index_r_act(p.active, b, p.R, n_act, rows_need_speaker);
+    return {p.off + b * ((size_t)p.N + 1), p.order + b * p.R, p.spk + b * p.R, p.R, n_act, r_act};
+}
+
 __device__ __forceinline__ v4f mfma_f32(float a, float b, v4f c) {
     return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
 
 // Elements k .. k+3 of a row of `len` floats (k a multiple of 4), zero where the row is absent or ends.  `vec`: the row
 // starts 16-byte aligned and len is a multiple of 4, so the four are there together or not at all.
@@ -172,18 +209,17 @@ struct TileRows {
 // fragments: index, speaker and m - 1 come with one load each for the whole wave (no dependent chain per row), lane group q
 // holds the elements d0 + 4 q .. + 3 of every step, and the four groups' partial sums meet through two lane swaps in a
 // fixed order.  The lanes past the wave's last row point at its first one (an active row: readable) and zero what they
-// load.  ord, spk: the batch's; every index is clamped where it is read.
+// load.  ix: the batch's tables, which clamp every index where it is read.
 template <int kSteps>
-__device__ __forceinline__ TileRows<kSteps> tile_rows(const float* E, const float* SSb, const float* CSTb, const int* ord,
-                                                      const int* spk, int p0, int nrow, int n_act, int R, int D,
-                                                      float eps_cos) {
+__device__ __forceinline__ TileRows<kSteps> tile_rows(const float* E, const float* SSb, const float* CSTb, const IndexView& ix,
+                                                      int p0, int nrow, int D, float eps_cos) {
     constexpr bool kHold = kSteps > 0;
     const int l15 = threadIdx.x & 15, q = (threadIdx.x & 63) >> 4;
     TileRows<kSteps> t;
     t.row_ok = l15 < nrow;
     t.pp = p0 + (t.row_ok ? l15 : 0);
-    t.row = clampi(ord[t.pp], 0, R - 1);
-    const int sp = clampi(spk[t.pp], 0, n_act - 1);
+    t.row = ix.row_at(t.pp);
+    const int sp = ix.speaker_at(t.pp);
     t.j = t.row_ok ? sp : -1;
     const float fm1 = CSTb[(size_t)sp * 4 + CS_M1];
     t.pe = E + (size_t)t.row * D;
@@ -331,16 +367,16 @@ constexpr int kAcc = 4;                                 // column tiles (accumul
 // the elements from wave_elem(d0, lane, vecD) on, for d0 = 0, wave_stretch(vecD), ...
 __device__ __forceinline__ int wave_stretch(bool vecD) { return vecD ? 4 * kWave : kWave; }
 __device__ __forceinline__ int wave_elem(int d0, int lane, bool vecD) { return d0 + (vecD ? 4 * lane : lane); }
-// The lane's elements d .. (`ok`: d < D) of the sum of the rows E[order[p]], p = r0 .. r1 - 1, from 0 in ascending p.  The
-// row indices of up to 64 positions come with ONE coalesced load, clamped to [0, R - 1], and are handed out with v_readlane:
-// no dependent order[p] -> row pair per row.  Called by the whole wave.
-__device__ __forceinline__ v4f speaker_sum(const float* E, const int* order, int r0, int r1, int R, int D, int d, bool ok,
+// The lane's elements d .. (`ok`: d < D) of the sum of the rows E[order[p]], p = r0 .. r1 - 1 (a speaker's span), from 0 in
+// ascending p.  The row indices of up to 64 positions come with ONE coalesced load (index_row) and are handed out with
+// v_readlane: no dependent order[p] -> row pair per row.  order: the batch's.  Called by the whole wave.
+__device__ __forceinline__ v4f speaker_sum(const float* E, const int* order, IndexSpan sp, int R, int D, int d, bool ok,
                                            bool vecD) {
-    const int lane = threadIdx.x & 63;
+    const int lane = threadIdx.x & 63, r0 = sp.r0, r1 = sp.r1;
     v4f s = {0.f, 0.f, 0.f, 0.f};
     for (int c0 = r0; c0 < r1; c0 += kWave) {
         const int pp = c0 + lane;
-        const int idx = pp < r1 ? clampi(order[pp], 0, R - 1) : 0;
+        const int idx = pp < r1 ? index_row(order, pp, R) : 0;
         const int n = min(kWave, r1 - c0);
         for (int i = 0; i < n; ++i) {
             const float* er = E + (size_t)__builtin_amdgcn_readlane(idx, i) * D;

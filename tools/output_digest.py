@@ -4,7 +4,7 @@ bit for bit on one GPU:
     GE2E_HIP_LIB=$PWD/speaker_embedding_ge2e_loss_amd/libge2e_hip_parent.so python tools/output_digest.py > a.txt
     python tools/output_digest.py > b.txt && diff a.txt b.txt
 
-(tools/build_rev.sh builds the other revision's library.)  Three sections:
+(tools/build_rev.sh builds the other revision's library.)  Four sections:
 
   1. the fp32 matrix-core implementations: loss | per | dE | dw | db per (implementation, shape, variant), with and
      without the gradient.  A pair the library refuses prints SKIP.
@@ -29,6 +29,11 @@ bit for bit on one GPU:
        speakers with 65, 64 and 1 rows in a call (the 64-index chunk of the speaker sum), speakers 4 mod 8 never enrolled
        (cnt = 0); labels with ignored rows (-1), a target that is not enrolled, and ids K and K + 5 past the bank
        cohorts of 2048, 2049 and 6145 at D = 36, R = 40: the three forms of the select kernel
+  4. the index tables themselves, one line per call: label_index (offsets | order) and label_index_masked (offsets | order |
+     speakers | active) at the smallest shapes that reach every path of the two kernels: B 1, N 67, R 300; B 3, N 1100,
+     R 2200 (counters in the workspace, not in LDS); B 515, N 2, R 5 (past the grid); N 3, R 2500 with runs across 256-row
+     chunks; and, masked only, a seeded draw at N 1100, R 300 with ignored rows, a lone and an absent speaker.  (The
+     lone-speaker instantiation is reached by section 3's enroll_accumulate lines.)
 
 Exit status 1 if one of the fp32 matrix-core implementations appears in no line.
 """
@@ -258,12 +263,40 @@ def bank_section(dev):
         cohort_lines(f"cohort_stats C={C} D={D} R={R}", e, select, cohort, ccnt)
 
 
+def index_cases():
+    """name -> (N, labels (B, R)): the shapes of the index tests (tests/test_gpu_labeled.py), every label inside [0, N)."""
+    rng = np.random.default_rng(11)
+    runs = np.concatenate([np.zeros(700), np.arange(900) % 3, np.full(300, 2), rng.integers(0, 3, 350), np.ones(250)])
+    return {
+        "B=1 N=67 R=300": (67, rng.integers(0, 67, (1, 300))),
+        "B=3 N=1100 R=2200": (1100, np.stack([rng.permutation(np.repeat(np.arange(1100), 2)) for _ in range(3)])),
+        "B=515 N=2 R=5": (2, rng.integers(0, 2, (515, 5))),
+        "B=1 N=3 R=2500 runs": (3, runs[None]),
+    }
+
+
+def index_section(dev):
+    for tag, (N, labels) in index_cases().items():
+        lab = torch.as_tensor(labels.astype(np.int32), device=dev)
+        line(f"label_index {tag}", *GF.label_index(lab, N))
+        line(f"label_index_masked {tag}", *GF.label_index_masked(lab, N))
+    # the masked form alone: ignored rows (negative, N and past it), a lone and an absent speaker among seeded draws
+    N, R = 1100, 300
+    rng = np.random.default_rng(N + R)
+    labels = rng.integers(0, 120, (2, R))                # about 2.5 rows a speaker: lone ones and absent ones among them
+    labels[:, ::17] = -1
+    labels[0, 5], labels[0, 6], labels[1, 7] = N, N + 5, -2147483648
+    labels[0, 100:103] = [N - 1, N - 1, 700]             # the last speaker active, 700 alone, 701 .. 1098 absent
+    line(f"label_index_masked B=2 N={N} R={R} draw", *GF.label_index_masked(torch.as_tensor(labels.astype(np.int32), device=dev), N))
+
+
 def main():
     dev = torch.device("cuda:0")
     w, b = torch.tensor(7.5, device=dev), torch.tensor(-2.0, device=dev)
     missing = fused_section(dev, w, b)
     exact_section(dev, w, b)
     bank_section(dev)
+    index_section(dev)
     if missing:
         print("no line for:", " ".join(missing))
     return 1 if missing else 0
