@@ -1,9 +1,11 @@
 // The coefficients of a row's gradient in the fp32 loss kernels, written once (row_coeffs, row_own_o, row_c4_share): the two
-// one-workgroup-per-batch kernels and the three row kernels of ge2e_tiled.hip.  Algebra: oracle/ge2e_oracle.py:closed_form
+// one-workgroup-per-batch kernels and the three row kernels of ge2e_tiled.hip, which also take their leave-one-out own-column
+// cosine from here (own_column_cos).  Algebra: oracle/ge2e_oracle.py:closed_form
 // and the header of ge2e_fused_f32.hip.  The operand order and the parentheses of every expression are part of the
 // results: the kernels agree bit for bit with what they computed when each carried its own copy.
 #pragma once
 #include "ge2e_common.hpp"
+#include "ge2e_dev.hpp"
 
 namespace ge2e {
 
@@ -28,6 +30,20 @@ __device__ __forceinline__ RowCoeffs row_coeffs(float ad, float coef, float rne,
 __device__ __forceinline__ float row_own_o(float rne, float rnu, float ku, float cosd, float inv_m1, float sj) {
     const float rho = rnu * inv_m1;
     return rho * (rne + ku * cosd * rho) * sj / rne;
+}
+// The own-speaker column of a row without a second pass over the speaker's rows (ge2e_tiled.hip): the cosine with the
+// leave-one-out centroid u = (s_j - e) / (M - 1) from the row scalars rst = (1/|e|, kappa_e, |e|^2, .), the speaker scalars
+// cs = (., ., |s_j| scale, |s_j|^2) of the preparation pass and xo = e-hat . c-hat_j, the own column of the similarity.
+struct OwnCos { float cosd, rnu, ku; };
+__device__ __forceinline__ OwnCos own_column_cos(const float4& rst, const float4& cs, float xo, float inv_m1, float eps_cos) {
+    OwnCos o;
+    const float rne = rst.x, ee = rst.z;
+    const float es = xo * cs.z / rne;
+    const float eu = (es - ee) * inv_m1;
+    const float uu = fmaxf((cs.w - 2.0f * es + ee) * (inv_m1 * inv_m1), 0.0f);
+    unit_stats_fast(uu, eps_cos, o.rnu, o.ku);
+    o.cosd = eu * rne * o.rnu;
+    return o;
 }
 // c4': the row's share of the c-hat_j coefficient of the speaker's KJ row, (beta |s_j| + kap_j alpha xo) / (M - 1)
 __device__ __forceinline__ float row_c4_share(const RowCoeffs& rc, float inv_m1, float sj, float kap, float xo) {

@@ -4,7 +4,7 @@ bit for bit on one GPU:
     GE2E_HIP_LIB=$PWD/speaker_embedding_ge2e_loss_amd/libge2e_hip_parent.so python tools/output_digest.py > a.txt
     python tools/output_digest.py > b.txt && diff a.txt b.txt
 
-(tools/build_rev.sh builds the other revision's library.)  Four sections:
+(tools/build_rev.sh builds the other revision's library.)  Five sections:
 
   1. the fp32 matrix-core implementations: loss | per | dE | dw | db per (implementation, shape, variant), with and
      without the gradient.  A pair the library refuses prints SKIP.
@@ -34,8 +34,17 @@ bit for bit on one GPU:
      R 2200 (counters in the workspace, not in LDS); B 515, N 2, R 5 (past the grid); N 3, R 2500 with runs across 256-row
      chunks; and, masked only, a seeded draw at N 1100, R 300 with ignored rows, a lone and an absent speaker.  (The
      lone-speaker instantiation is reached by section 3's enroll_accumulate lines.)
+  5. the tiled pipeline where section 1 does not reach (its shapes have sim, gc and ge on the 128 x 128 tile and the DMA-fed
+     tile only inside simrows).  Every line prints the plan the library answers (ge2e_loss_plan, ge2e_cos_sim_plan).
+     The five tiled PLAN_CASES of tests/bounds_cases.py, inputs made on the device from a seed as tests/test_gpu_plans.py
+     makes them, loss | per | dE | dw | db with the gradient and forward only:
+       (48, 257, 2, 288)  gc<C2>: the register-staged 256 x 256 tile (N M = 514 is no multiple of 32); sim<C3> walks 288 tiles
+       (48, 272, 2, 264)  gc<C3>/1, 192 tiles     (65, 272, 2, 264)  gc<C3>/2, 520 tiles: a walk of more than one round
+       (32, 528, 2, 264)  gc<C3>/4, 768 tiles     (25, 800, 3, 264)  gc<C3>/8, 1600 tiles; ge<C3> walks 500
+     ge2e_cos_sim on its matrix-core route (prep, sim<C1>, tiled_cos) at (1, 16, 3, 64), (2, 65, 3, 128), (1, 300, 3, 768).
 
-Exit status 1 if one of the fp32 matrix-core implementations appears in no line.
+Exit status 1 if one of the fp32 matrix-core implementations appears in no line, or if the plan of a line of section 5 is
+not the one its table claims.
 """
 import hashlib
 import os
@@ -44,7 +53,9 @@ import sys
 import numpy as np
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+import bounds_cases as bc  # noqa: E402
 from oracle import ge2e_oracle as orc  # noqa: E402
 from speaker_embedding_ge2e_loss_amd import _lib  # noqa: E402
 from speaker_embedding_ge2e_loss_amd import functional as GF  # noqa: E402
@@ -83,6 +94,13 @@ BANK_CASES = [(1, 36, 1, 1), (15, 100, 16, 15), (16, 256, 17, 17), (17, 7, 63, 6
 ENROLL_ROWS = ((65, 1, 2, 64, 0, 3, 0, 5), (0, 3, 0, 1, 0, 0, 2, 4))   # rows per speaker (id mod 8) in the two calls
 SELECT_COHORTS = (2048, 2049, 6145)                                   # at D = 36, R = 40
 N_TOPS = (5, 64)
+# section 5: the five tiled PLAN_CASES of tests/bounds_cases.py (the atom a case is named for and every kernel PLAN_TILES
+# counts more than 0 tiles for must be in the plan of its fwd+bwd line) ...
+TILED_PLAN_CASES = [c for c in bc.PLAN_CASES if c[1] == "tiled"]
+# ... and ge2e_cos_sim where its contraction runs on the matrix cores, with the plan the line must print
+TILED_COS_CASES = [((1, 16, 3, 64), ["tiled_prep<10,1>", "tiled_sim<C1>", "tiled_cos"]),
+                   ((2, 65, 3, 128), ["tiled_prep<10,1>", "tiled_sim<C1>", "tiled_cos"]),
+                   ((1, 300, 3, 768), ["tiled_prep<10,3>", "tiled_sim<C1>", "tiled_cos"])]
 
 
 def digest(o, names=("loss", "per", "dE", "dw", "db")):
@@ -290,6 +308,34 @@ def index_section(dev):
     line(f"label_index_masked B=2 N={N} R={R} draw", *GF.label_index_masked(torch.as_tensor(labels.astype(np.int32), device=dev), N))
 
 
+def tiled_section(dev, w, b):
+    """Returns the lines whose plan, asked of the library under test, lacks an atom the tables claim for them."""
+    wrong = []
+    for case in TILED_PLAN_CASES:
+        atom, impl, B, N, M, D, variant, _ = case
+        g = torch.Generator(device=dev).manual_seed(B + N + M + D)
+        e = torch.nn.functional.normalize(torch.randn(B, N, M, D, generator=g, device=dev), dim=-1)
+        for grad in (True, False):
+            plan = _lib.loss_plan(B, N, M, D, variant, impl, grad)
+            tag = f"tiled plan {(B, N, M, D)} {variant} {'fwd+bwd' if grad else 'fwd'} [{' '.join(plan)}]"
+            walked = [k for k, n in bc.PLAN_TILES[atom].items() if n > 0]
+            if grad and not all(any(a.startswith(k) for a in plan) for k in [atom] + walked):
+                wrong.append(tag)
+            o = GF.loss_fwd_bwd(e, w, b, variant=variant, impl=impl, need_grad=grad, need_per=True)
+            torch.cuda.synchronize()
+            print(tag, digest(o))
+        del e, o
+    for shape, atoms in TILED_COS_CASES:
+        plan = _lib.cos_sim_plan(*shape)
+        tag = f"tiled cos_sim {shape} [{' '.join(plan)}]"
+        if plan != atoms:
+            wrong.append(tag)
+        e = torch.as_tensor(orc.synth_embeddings(shape, "raw", seed=sum(shape)), device=dev)
+        with torch.no_grad():
+            line(tag, GF.cos_sim(e))
+    return wrong
+
+
 def main():
     dev = torch.device("cuda:0")
     w, b = torch.tensor(7.5, device=dev), torch.tensor(-2.0, device=dev)
@@ -297,9 +343,12 @@ def main():
     exact_section(dev, w, b)
     bank_section(dev)
     index_section(dev)
+    wrong = tiled_section(dev, w, b)
     if missing:
         print("no line for:", " ".join(missing))
-    return 1 if missing else 0
+    for tag in wrong:
+        print("plan is not the one claimed:", tag)
+    return 1 if missing or wrong else 0
 
 
 if __name__ == "__main__":
