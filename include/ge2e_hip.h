@@ -601,6 +601,46 @@ int ge2e_eer_counts(const float* sim, int B, int N, int M, const float* threshol
 int ge2e_sample_batch(const void* store, int store_is_f64, const long long* spk_offsets, const int* utter_idx,
                       const int* clip_start, int N, int M, int T, int L, int F, float* out, void* stream);
 
+/*
+ * ENCODER INFERENCE (csrc/ge2e_encoder.hip): the forward pass of the d-vector encoder (s2:7-35) for inference -- L stacked
+ * LSTM layers of H units over the T frames of a window of n_mels mel channels, the LAST frame's top hidden state through one
+ * Linear [D][H], divided by its L2 norm -- from mel windows to embeddings in ONE launch.  Forward only, float32, exact fp32
+ * on the matrix core (v_mfma_f32_16x16x4_f32).  Supported: H = 128 or 256, 1 <= L <= 4, 1 <= n_mels <= 256, 1 <= D <= 256,
+ * any T >= 1 and R >= 1; everything else is GE2E_ERR_IMPL and nothing is launched.
+ *
+ * ge2e_encoder_pack, once per set of weights.  flat_params: the parameters in torch's own layout as one float32 buffer --
+ * per layer l, in order, weight_ih [4H][I_l] (I_0 = n_mels, I_l = H above), weight_hh [4H][H], bias_ih [4H], bias_hh [4H],
+ * gate order i, f, g, o; then projection.weight [D][H] and projection.bias [D].  packed (ge2e_encoder_packed_bytes, 16-byte
+ * aligned; every byte is written): per layer the matrix [pad16(I_l) + H][4H] in the MFMA's B-fragment order -- the input's k
+ * zero-padded to a multiple of 16, i.e. to whole groups of four K-steps, of which a lane fetches 16 contiguous bytes -- with
+ * the gate columns permuted so that i, f, g, o of one hidden unit fall into the same lane and register slot of four
+ * accumulator tiles, followed by the 4H sums bias_ih + bias_hh in the same column order; then the projection likewise,
+ * [H][pad16(D)] and pad16(D) biases, zero past D.  One launch.  Checks, in this order: GE2E_ERR_NULL (flat_params or
+ * packed), GE2E_ERR_SHAPE (n_mels, D or L < 1), GE2E_ERR_IMPL, GE2E_ERR_ALIGN (packed not 16-byte aligned).
+ *
+ * ge2e_encode.  mel [frames][n_mels] float32; row r is the T frames from frame row_start[r] (int64, device) on, or from
+ * frame r T where row_start is NULL (mel is then [R][T][n_mels]).  Rows may overlap: the sliding windows of a long utterance
+ * are encoded without being materialised.  0 <= row_start[r] and row_start[r] + T <= frames are the caller's guarantee;
+ * frames outside every row are never read.  out [R][D]: y / |y| of the projection y for normalize != 0 -- no epsilon, as
+ * s2:34: a zero y gives NaN -- and y itself for normalize == 0.  Exactly the R D elements of out are written.
+ * One launch of ceil(R / 32) workgroups of 512 threads; a workgroup owns 32 rows for all T steps and all L layers (time
+ * outside, layers inside), c in registers, h in LDS (4 L 32 H bytes), the weights streamed from L2 every step; rows past R
+ * in the last tile compute on zeros and are never stored.  No workspace, no allocation, no synchronisation, everything on
+ * `stream`, grid from the shape alone: fit for a HIP graph.  The bits of an output row depend on that row's frames and the
+ * weights ALONE: not on R, on the row's position, or on the tile it fell into.
+ * Checked on the host before anything is launched, in this order: GE2E_ERR_NULL (packed, mel or out), GE2E_ERR_SHAPE (R, T,
+ * n_mels, D or L < 1), GE2E_ERR_IMPL (H, L, n_mels or D unsupported), GE2E_ERR_ALIGN (packed, mel or out not 16-byte aligned).
+ *
+ * ge2e_encode_plan (diagnostics, no GPU): "encode<H>/tiles", the instantiation and its grid ceil(R / 32), snprintf-style as
+ * ge2e_loss_plan; < 0: GE2E_ERR_SHAPE or GE2E_ERR_IMPL as the call itself.  (These names are no part of ge2e_plan_atoms.)
+ */
+size_t ge2e_encoder_packed_bytes(int n_mels, int H, int L, int D);   /* 0 for an unsupported shape */
+int ge2e_encoder_pack(const float* flat_params, int n_mels, int H, int L, int D, float* packed, void* stream);
+int ge2e_encode(const float* packed, const float* mel, const long long* row_start /* [R] or NULL */,
+                int R, int T, int n_mels, int H, int L, int D, int normalize,
+                float* out /* [R][D] */, void* stream);
+int ge2e_encode_plan(int R, int T, int n_mels, int H, int L, int D, char* buf, size_t buf_bytes);
+
 /* ---- diagnostics (tests only): which kernels a call launches ---------------------------------------------------------
  * Below ge2e_resolve_impl every launcher chooses again among kernels and template instantiations.  These queries print
  * that choice -- made by the very functions the launchers switch on -- without a GPU and without launching anything:

@@ -83,6 +83,10 @@ PROTOTYPES = {
     "ge2e_selftest_cohort_stats_workspace_bytes": (C.c_size_t, [C.c_int] * 5),
     "ge2e_selftest_cohort_stats_chunk": (C.c_int, [_fp, _fp, C.c_int, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
                                                    C.c_float, C.c_float, _fp, _fp, C.c_size_t, _fp, C.c_int]),
+    "ge2e_encoder_packed_bytes": (C.c_size_t, [C.c_int] * 4),
+    "ge2e_encoder_pack": (C.c_int, [_fp] + [C.c_int] * 4 + [_fp, _fp]),
+    "ge2e_encode": (C.c_int, [_fp, _fp, _fp] + [C.c_int] * 7 + [_fp, _fp]),
+    "ge2e_encode_plan": (C.c_int, [C.c_int] * 6 + [C.c_char_p, C.c_size_t]),
     "ge2e_raw_supported": (C.c_int, [C.c_int] * 3),
     "ge2e_loss_fwd_bwd_raw": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, C.c_float, C.c_float,
                                         C.c_int, _fp, _fp, _fp, _fp, _fp, _fp]),
@@ -189,6 +193,11 @@ def loss_plan(B: int, N: int, M: int, D: int, variant: str = "softmax", impl: st
 def cos_sim_plan(B: int, N: int, M: int, D: int) -> list[str]:
     """... ge2e_cos_sim on a workspace of ge2e_cos_sim_workspace_bytes would launch."""
     return _plan(load().ge2e_cos_sim_plan, B, N, M, D)
+
+
+def encode_plan(R: int, T: int, n_mels: int, H: int, L: int, D: int) -> list[str]:
+    """... ge2e_encode would launch: ["encode<H>/tiles"]."""
+    return _plan(load().ge2e_encode_plan, R, T, n_mels, H, L, D)
 
 
 def plan_atoms() -> list[str]:

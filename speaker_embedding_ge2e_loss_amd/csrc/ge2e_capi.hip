@@ -14,6 +14,7 @@
 #include "ge2e_labeled_wide.hpp"
 #include "ge2e_labeled_helpers.hpp"
 #include "ge2e_enroll.hpp"
+#include "ge2e_encoder.hpp"
 #include "ge2e_identify.hpp"
 #include "ge2e_snorm.hpp"
 #include "ge2e_helpers.hpp"
@@ -638,6 +639,36 @@ int ge2e_calc_loss_labeled_bwd(const float* sim, const int* col, const int* acti
     if (B < 1 || N < 1 || R < 1) return GE2E_ERR_SHAPE;
     if (!variant_ok(variant)) return GE2E_ERR_VARIANT;
     return (int)launch_calc_loss_labeled_bwd(sim, col, active, B, N, R, eps, variant, g_loss, g_per, d_sim, (hipStream_t)stream);
+}
+
+// ENCODER INFERENCE (include/ge2e_hip.h, csrc/ge2e_encoder.hip): the weights packed once, then mel windows to d-vectors in
+// one launch.
+size_t ge2e_encoder_packed_bytes(int n_mels, int H, int L, int D) {
+    return encoder_supported(n_mels, H, L, D) ? encoder_packed_floats(n_mels, H, L, D) * sizeof(float) : 0;
+}
+
+int ge2e_encoder_pack(const float* flat_params, int n_mels, int H, int L, int D, float* packed, void* stream) {
+    if (!flat_params || !packed) return GE2E_ERR_NULL;
+    if (n_mels < 1 || D < 1 || L < 1) return GE2E_ERR_SHAPE;
+    if (!encoder_supported(n_mels, H, L, D)) return GE2E_ERR_IMPL;
+    if (!aligned16(packed)) return GE2E_ERR_ALIGN;
+    return (int)launch_encoder_pack(flat_params, n_mels, H, L, D, packed, (hipStream_t)stream);
+}
+
+int ge2e_encode(const float* packed, const float* mel, const long long* row_start, int R, int T, int n_mels, int H, int L,
+                int D, int normalize, float* out, void* stream) {
+    if (!packed || !mel || !out) return GE2E_ERR_NULL;
+    if (R < 1 || T < 1 || n_mels < 1 || D < 1 || L < 1) return GE2E_ERR_SHAPE;
+    if (!encoder_supported(n_mels, H, L, D)) return GE2E_ERR_IMPL;
+    if (!aligned16(packed) || !aligned16(mel) || !aligned16(out)) return GE2E_ERR_ALIGN;
+    const ProblemEncode p = {packed, mel, row_start, out, R, T, n_mels, L, D, normalize != 0};
+    return (int)launch_encode(p, H, (hipStream_t)stream);
+}
+
+int ge2e_encode_plan(int R, int T, int n_mels, int H, int L, int D, char* buf, size_t buf_bytes) {
+    if (R < 1 || T < 1 || n_mels < 1 || D < 1 || L < 1) return GE2E_ERR_SHAPE;
+    if (!encoder_supported(n_mels, H, L, D)) return GE2E_ERR_IMPL;
+    return plan_string_encode(R, H, buf, buf_bytes);
 }
 
 // ---- diagnostics: the launch plan of a call, from the launchers' own decision functions (ge2e_plan.hpp); no GPU needed ----

@@ -1,0 +1,289 @@
+// ge2e_encoder_pack / ge2e_encode: the d-vector encoder's forward pass for inference (s2:7-35: stacked LSTM over the frames of
+// a window, the last frame's top hidden state through one Linear, L2-normalised), mel windows to embeddings in ONE launch.
+//   tile      one 512-thread workgroup owns 32 rows (windows) for all T steps and all L layers; no workgroup waits for
+//             another.  Time is the outer loop, layers the inner one.  Wave w owns the hidden units w H/8 .. (w+1) H/8 - 1 of
+//             every layer (UB = H / 128 blocks of 16 units) and both 16-row halves of the tile.
+//   operands  v_mfma_f32_16x16x4_f32, exact fp32 (ge2e_rows_dev.hpp has the operand map): A[i = l15][k = q] is the
+//             activation of row l15, B[k = q][j = l15] the weight of gate column l15, C[i = 4 q + v][j = l15].  The k index
+//             is permuted the same way in both operands: over the four steps of a GROUP of 16 k, lane group q takes
+//             k = 16 g + 4 q + i in step i, so a lane fetches 16 contiguous bytes per operand and group.
+//   packed    per layer the matrix [pad16(I) + H][4 H] (rows: the input's k, zero-padded to a multiple of 16, then the
+//             recurrent k) as [group][column tile][lane][4]: one coalesced 1 KiB line per wave, group and tile.  Column
+//             tile pc = (w UB + ub) 4 + gate holds the gate's columns of the 16 units of block ub of wave w, so i, f, g, o of
+//             one unit land in the same lane and register slot of four accumulators and the cell update runs in
+//             registers.  Then the 4 H biases b_ih + b_hh in the same column order.  The projection likewise:
+//             [H][pad16(D)] and pad16(D) biases, zero past D.
+//   state     c in registers (UB x 2 x 4 per layer), h of every layer in LDS [L][32][H]; x_t and the weights come from
+//             global memory (L2) one group ahead of the MFMAs that use them.  Two barriers per layer-step: the old h of the
+//             layer is read by every wave before any wave overwrites it.
+//   epilogue  projection of the top layer's h into LDS [32][pad16(D)] (over the h planes), then one wave per four rows:
+//             sum of squares in a fixed order, y / sqrt(ss) (no epsilon, s2:34: a zero row gives NaN) or y itself, stored.
+// Every K chain has a fixed order and MFMA rows are independent: the bits of an output row depend on that row's frames and
+// the weights alone.  Pad rows of the last tile compute on zeros and are never stored.
+#include "ge2e_encoder.hpp"
+
+#include <math.h>
+#include <stdio.h>
+
+#include "ge2e_rows_dev.hpp"
+
+namespace ge2e {
+
+namespace {
+
+// The row of torch's [4 H][..] gate matrices (gate order i, f, g, o) behind column l15 of packed column tile pc.
+__device__ __forceinline__ int enc_gate_row(int pc, int l15, int H) {
+    const int UB = H / 128, NT = 4 * UB;
+    const int w = pc / NT, j = pc % NT;
+    return (j & 3) * H + (w * UB + (j >> 2)) * 16 + l15;
+}
+
+__global__ __launch_bounds__(256) void encoder_pack_kernel(const float* __restrict__ flat, int n_mels, int H, int L, int D,
+                                                            float* __restrict__ packed, size_t total) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += stride) {
+        size_t off = 0;
+        const float* src = flat;
+        float val = 0.f;
+        bool done = false;
+        for (int l = 0; l < L && !done; ++l) {
+            const int I = l ? H : n_mels, Ip = enc_pad16(I), C = 4 * H, CT = C / 16;
+            const size_t lf = enc_layer_floats(I, H);
+            if (idx < off + lf) {
+                const size_t local = idx - off, wsz = (size_t)(Ip + H) * C;
+                const float *w_ih = src, *w_hh = w_ih + (size_t)C * I, *b_ih = w_hh + (size_t)C * H, *b_hh = b_ih + C;
+                if (local < wsz) {
+                    const int i = (int)(local & 3), lane = (int)((local >> 2) & 63);
+                    const int rest = (int)(local >> 8), pc = rest % CT, g = rest / CT;
+                    const int k = 16 * g + 4 * (lane >> 4) + i, row = enc_gate_row(pc, lane & 15, H);
+                    if (k < Ip) val = k < I ? w_ih[(size_t)row * I + k] : 0.f;
+                    else val = w_hh[(size_t)row * H + (k - Ip)];
+                } else {
+                    const int b = (int)(local - wsz), row = enc_gate_row(b >> 4, b & 15, H);
+                    val = b_ih[row] + b_hh[row];
+                }
+                done = true;
+            }
+            off += lf;
+            src += (size_t)C * (I + H + 2);
+        }
+        if (!done) {
+            const int Dp = enc_pad16(D), DT = Dp / 16;
+            const size_t local = idx - off, wsz = (size_t)H * Dp;
+            const float *wp = src, *bp = src + (size_t)D * H;
+            if (local < wsz) {
+                const int i = (int)(local & 3), lane = (int)((local >> 2) & 63);
+                const int rest = (int)(local >> 8), dt = rest % DT, g = rest / DT;
+                const int k = 16 * g + 4 * (lane >> 4) + i, d = dt * 16 + (lane & 15);
+                val = d < D ? wp[(size_t)d * H + k] : 0.f;
+            } else {
+                const int d = (int)(local - wsz);
+                val = d < D ? bp[d] : 0.f;
+            }
+        }
+        packed[idx] = val;
+    }
+}
+
+__device__ __forceinline__ float enc_sigmoid(float z) { return 1.0f / (1.0f + expf(-z)); }   // finite at z = +-100 and beyond
+
+template <int H>
+__global__ __launch_bounds__(kEncThreads) void encode_kernel(ProblemEncode p) {
+    extern __shared__ __attribute__((aligned(16))) float enc_lds[];
+    constexpr int UB = H / 128, NT = 4 * UB, CT = H / 4, GH = H / 16;
+    static_assert(H == 128 || H == 256, "a wave owns one or two blocks of 16 units");
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int l15 = lane & 15, q = lane >> 4;
+    const int L = p.L, T = p.T, n_mels = p.n_mels, D = p.D, R = p.R;
+    const int Dp = enc_pad16(D), DT = Dp / 16, G0 = enc_pad16(n_mels) / 16;
+    const bool vecX = (n_mels & 3) == 0;
+    const v4f zero4 = {0.f, 0.f, 0.f, 0.f};
+    float* hs = enc_lds;                                   // [L][32][H]
+
+    for (int i = threadIdx.x; i < L * kEncTile * H; i += kEncThreads) hs[i] = 0.f;
+
+    // the lane's two rows as the A operand: rows l15 and 16 + l15 of the tile
+    const float* xrow[2];
+    bool xok[2];
+#pragma unroll
+    for (int rt = 0; rt < 2; ++rt) {
+        const long long r = (long long)blockIdx.x * kEncTile + rt * 16 + l15;
+        xok[rt] = r < R;
+        const long long f0 = !xok[rt] ? 0 : (p.row_start ? p.row_start[r] : r * T);
+        xrow[rt] = p.mel + (size_t)f0 * n_mels;
+    }
+    v4f c[kEncMaxLayers][UB][2];
+#pragma unroll
+    for (int l = 0; l < kEncMaxLayers; ++l)
+#pragma unroll
+        for (int ub = 0; ub < UB; ++ub) c[l][ub][0] = c[l][ub][1] = zero4;
+    __syncthreads();
+
+    // The wave's column tiles against both row halves over G groups of 16 k, in NCG chunks of TPC tiles per group.  `bw`:
+    // the lane's slot of the wave's first tile in group 0 (tiles 256 floats apart, groups `gstride`); `afrag(g, rt)`: the
+    // lane's four activations.  The weights of the next chunk and the activations of the next group are fetched before
+    // the MFMAs of the current chunk.
+    auto contract = [&](auto tpc_c, auto ncg_c, const float* bw, size_t gstride, int G, auto&& afrag, v4f (&acc)[NT][2]) {
+        constexpr int TPC = decltype(tpc_c)::value, NCG = decltype(ncg_c)::value;
+        v4f bn[TPC], an[2];
+#pragma unroll
+        for (int j = 0; j < TPC; ++j) bn[j] = *reinterpret_cast<const v4f*>(bw + (size_t)j * 256);
+        an[0] = afrag(0, 0);
+        an[1] = afrag(0, 1);
+#pragma clang loop unroll(disable)
+        for (int g = 0; g < G; ++g) {
+            const v4f ac[2] = {an[0], an[1]};
+            const bool more = g + 1 < G;
+            if (more) {
+                an[0] = afrag(g + 1, 0);
+                an[1] = afrag(g + 1, 1);
+            }
+            static_for<0, NCG>([&](auto uc) {
+                constexpr int u = decltype(uc)::value;
+                v4f bc[TPC];
+#pragma unroll
+                for (int j = 0; j < TPC; ++j) bc[j] = bn[j];
+                if (u + 1 < NCG || more) {
+                    const float* nb = u + 1 < NCG ? bw + (size_t)g * gstride + (size_t)(u + 1) * TPC * 256
+                                                  : bw + (size_t)(g + 1) * gstride;
+#pragma unroll
+                    for (int j = 0; j < TPC; ++j) bn[j] = *reinterpret_cast<const v4f*>(nb + (size_t)j * 256);
+                }
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int j = 0; j < TPC; ++j) {
+                        acc[u * TPC + j][0] = mfma_f32(ac[0][i], bc[j][i], acc[u * TPC + j][0]);
+                        acc[u * TPC + j][1] = mfma_f32(ac[1][i], bc[j][i], acc[u * TPC + j][1]);
+                    }
+            });
+        }
+    };
+
+    for (int t = 0; t < T; ++t) {
+        const float* wl = p.packed;
+        static_for<0, kEncMaxLayers>([&](auto lc) {
+            constexpr int l = decltype(lc)::value;
+            if (l < L) {
+                const int Gin = l == 0 ? G0 : GH, G = Gin + GH;
+                const float* bias = wl + (size_t)G * 16 * 4 * H;
+                v4f acc[NT][2];
+#pragma unroll
+                for (int j = 0; j < NT; ++j) {
+                    const float b = bias[(wid * NT + j) * 16 + l15];
+                    acc[j][0] = acc[j][1] = v4f{b, b, b, b};
+                }
+                const float* hown = hs + (size_t)l * kEncTile * H;
+                const float* hbelow = hs + (size_t)(l > 0 ? l - 1 : 0) * kEncTile * H;
+                auto afrag = [&](int g, int rt) -> v4f {
+                    if (g < Gin) {
+                        if constexpr (l == 0) return load4(xrow[rt] + (size_t)t * n_mels, 16 * g + 4 * q, n_mels, xok[rt], vecX);
+                        else return *reinterpret_cast<const v4f*>(hbelow + (rt * 16 + l15) * H + 16 * g + 4 * q);
+                    }
+                    return *reinterpret_cast<const v4f*>(hown + (rt * 16 + l15) * H + 16 * (g - Gin) + 4 * q);
+                };
+                contract(std::integral_constant<int, 4>{}, std::integral_constant<int, UB>{}, wl + ((size_t)wid * NT * 64 + lane) * 4, (size_t)CT * 256, G,
+                         afrag, acc);
+                // the cell update, in registers: the lane holds i, f, g, o of unit l15 of block ub for the rows 4 q + v
+                v4f hnew[UB][2];
+#pragma unroll
+                for (int ub = 0; ub < UB; ++ub)
+#pragma unroll
+                    for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+                        for (int v = 0; v < 4; ++v) {
+                            const float ig = enc_sigmoid(acc[4 * ub + 0][rt][v]), fg = enc_sigmoid(acc[4 * ub + 1][rt][v]);
+                            const float gg = tanhf(acc[4 * ub + 2][rt][v]), og = enc_sigmoid(acc[4 * ub + 3][rt][v]);
+                            const float cn = fg * c[l][ub][rt][v] + ig * gg;
+                            c[l][ub][rt][v] = cn;
+                            hnew[ub][rt][v] = og * tanhf(cn);
+                        }
+                __syncthreads();   // every wave has read the layer's old h
+                float* hw = hs + (size_t)l * kEncTile * H;
+#pragma unroll
+                for (int ub = 0; ub < UB; ++ub)
+#pragma unroll
+                    for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+                        for (int v = 0; v < 4; ++v)
+                            hw[(rt * 16 + 4 * q + v) * H + (wid * UB + ub) * 16 + l15] = hnew[ub][rt][v];
+                __syncthreads();   // ... and the new one is there for the layer above and for the next step
+                wl = bias + 4 * H;
+            }
+        });
+    }
+
+    // projection of the top layer's h: column tiles wid and wid + 8 of pad16(D) / 16
+    const float* wp = p.packed + enc_layer_floats(n_mels, H) + (size_t)(L - 1) * enc_layer_floats(H, H);
+    const float* pbias = wp + (size_t)H * Dp;
+    const float* htop = hs + (size_t)(L - 1) * kEncTile * H;
+    v4f y[2][2];
+#pragma unroll
+    for (int jt = 0; jt < 2; ++jt) {
+        const int dt = wid + 8 * jt;
+        y[jt][0] = y[jt][1] = zero4;
+        if (dt < DT) {   // (uniform over the wave)
+            const float b = pbias[dt * 16 + l15];
+            v4f acc[NT][2];
+            acc[0][0] = acc[0][1] = v4f{b, b, b, b};
+            auto afrag = [&](int g, int rt) -> v4f {
+                return *reinterpret_cast<const v4f*>(htop + (rt * 16 + l15) * H + 16 * g + 4 * q);
+            };
+            contract(std::integral_constant<int, 1>{}, std::integral_constant<int, 1>{}, wp + ((size_t)dt * 64 + lane) * 4, (size_t)DT * 256, GH, afrag, acc);
+            y[jt][0] = acc[0][0];
+            y[jt][1] = acc[0][1];
+        }
+    }
+    __syncthreads();   // the h planes are free: the raw projection goes over them
+    float* ys = enc_lds;                                   // [32][Dp]
+#pragma unroll
+    for (int jt = 0; jt < 2; ++jt) {
+        const int dt = wid + 8 * jt;
+        if (dt < DT)
+#pragma unroll
+            for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+                for (int v = 0; v < 4; ++v) ys[(rt * 16 + 4 * q + v) * Dp + dt * 16 + l15] = y[jt][rt][v];
+    }
+    __syncthreads();
+    // one wave per four rows: the row's norm in a fixed order, then the store
+    for (int i = 0; i < kEncTile / 8; ++i) {
+        const int tr = wid * (kEncTile / 8) + i;
+        const long long r = (long long)blockIdx.x * kEncTile + tr;
+        if (r >= R) break;   // (uniform over the wave)
+        const float* yr = ys + tr * Dp;
+        float ss = 0.f;
+        for (int d = lane; d < D; d += kWave) ss += yr[d] * yr[d];
+        ss = wave_sum(ss);
+        const float n = sqrtf(ss);
+        float* o = p.out + (size_t)r * D;
+        for (int d = lane; d < D; d += kWave) o[d] = p.normalize ? yr[d] / n : yr[d];
+    }
+}
+
+KernelLaunchState g_encode_state[2];
+}  // namespace
+
+hipError_t launch_encoder_pack(const float* flat, int n_mels, int H, int L, int D, float* packed, hipStream_t stream) {
+    const size_t total = encoder_packed_floats(n_mels, H, L, D);
+    const unsigned blocks = (unsigned)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+    hipLaunchKernelGGL(encoder_pack_kernel, dim3(blocks), dim3(256), 0, stream, flat, n_mels, H, L, D, packed, total);
+    return hipGetLastError();
+}
+
+hipError_t launch_encode(const ProblemEncode& p, int H, hipStream_t stream) {
+    const unsigned lds = (unsigned)encoder_lds_bytes(H, p.L, p.D);
+    const unsigned tiles = (unsigned)(((long long)p.R + kEncTile - 1) / kEncTile);
+    const void* fn = H == 256 ? (const void*)encode_kernel<256> : (const void*)encode_kernel<128>;
+    const hipError_t err = prepare_kernel(g_encode_state[H == 256], fn, kEncThreads, lds, nullptr);
+    if (err != hipSuccess) return err;
+    if (H == 256) hipLaunchKernelGGL(encode_kernel<256>, dim3(tiles), dim3(kEncThreads), lds, stream, p);
+    else hipLaunchKernelGGL(encode_kernel<128>, dim3(tiles), dim3(kEncThreads), lds, stream, p);
+    return hipGetLastError();
+}
+
+int plan_string_encode(int R, int H, char* buf, size_t cap) {
+    return snprintf(buf, cap, "encode<%d>/%d", H, (int)(((long long)R + kEncTile - 1) / kEncTile));
+}
+
+}  // namespace ge2e

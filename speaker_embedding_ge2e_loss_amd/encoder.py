@@ -6,15 +6,23 @@ names (``LSTM_stack``, ``projection``) and the initialisation (xavier-normal wei
 for the LSTM, s2:18-22; the Linear keeps torch's default) follow the reference so a reference
 ``state_dict`` loads here and the other way round (s4:130 saves exactly this module's).
 
-The recurrent and projection GEMMs are library work (MIOpen / hipBLASLt through torch) and are NOT
-part of the hand-written path; what is ours is the tail: with ``normalize=False`` the module hands
+In TRAINING the recurrent and projection GEMMs are library work (MIOpen / hipBLASLt through torch) and are NOT
+part of the hand-written path; what is ours there is the tail: with ``normalize=False`` the module hands
 back the raw projection and the trainer runs the fused L2-normalise + un-permute gather
 (``functional.normalize_unperm``) in one HIP kernel instead of three torch ops.
+For INFERENCE ``embed`` / ``embed_utterances`` run the whole forward pass -- LSTM stack, projection, norm -- as one
+hand-written HIP launch (``functional.encode``, csrc/ge2e_encoder.hip); ``forward`` and ``raw`` stay torch's.
 """
 from __future__ import annotations
 
 import torch
 import torch.nn as nn
+
+
+# embed(native=None) takes the HIP kernel from this many windows on.  profiles/encoder_bench.txt (80 -> 3 x 256 -> 256,
+# T = 160): the native call takes 32-33 ms for anything up to 8192 windows (one tile of 32 per CU), torch's route 12 ms up
+# to 1024 windows, 28.9 ms at 4096 and 42.9 ms at 6144: the lines cross near 4700.
+NATIVE_MIN_ROWS = 4800
 
 
 class SpeakerEncoder(nn.Module):
@@ -46,6 +54,91 @@ class SpeakerEncoder(nn.Module):
         if not self.normalize:
             return y
         return y / torch.norm(y, dim=1).unsqueeze(1)  # s2:34
+
+
+    # ---- inference without autograd: the native forward pass (functional.encode, csrc/ge2e_encoder.hip) ------------------
+    def _shape(self):
+        lstm = self.LSTM_stack
+        return lstm.input_size, lstm.hidden_size, lstm.num_layers, self.projection.out_features
+
+    def _parameters_in_pack_order(self):
+        lstm = self.LSTM_stack
+        ps = []
+        for l in range(lstm.num_layers):
+            ps += [getattr(lstm, f"{n}_l{l}") for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
+        return ps + [self.projection.weight, self.projection.bias]
+
+    def native_supported(self) -> bool:
+        """Whether ``embed`` has a HIP kernel for this module: a plain float32 nn.LSTM stack of a supported shape on a GPU."""
+        from . import functional as GF
+        lstm = self.LSTM_stack
+        plain = lstm.bias and lstm.batch_first and not lstm.bidirectional and getattr(lstm, "proj_size", 0) == 0 \
+            and self.projection.bias is not None
+        ps = self._parameters_in_pack_order() if plain else []
+        return bool(plain) and all(p.is_cuda and p.dtype == torch.float32 for p in ps) and GF.encode_supported(*self._shape())
+
+    def packed_weights(self) -> torch.Tensor:
+        """The packed buffer ``functional.encode`` streams from, cached against the parameters' ``_version`` counters,
+        their storage and device: an optimiser step, ``load_state_dict`` or ``.to()`` repacks."""
+        from . import functional as GF
+        ps = self._parameters_in_pack_order()
+        key = tuple((p.data_ptr(), p._version, str(p.device)) for p in ps)
+        cache = getattr(self, "_packed_cache", None)
+        if cache is None or cache[0] != key:
+            with torch.no_grad():
+                flat = torch.cat([p.detach().reshape(-1) for p in ps])
+                cache = (key, GF.encoder_pack(flat, *self._shape()))
+            self._packed_cache = cache
+        return cache[1]
+
+    def embed(self, x, native=None, normalize=None):
+        """Inference without autograd: (R, T, n_mels) mel windows -> (R, D) d-vectors.  ``native=True`` is the HIP kernel
+        (one launch; a row's bits do not depend on the batch it is in) and raises where there is none; ``native=False`` is
+        torch's modules under ``no_grad``; ``native=None`` takes the kernel where ``native_supported()`` and the batch has
+        at least ``NATIVE_MIN_ROWS`` windows -- below that the library was measured faster -- and torch's route
+        otherwise.  ``normalize=None``: the module's own setting.  A callable for the loops of ``evaluation``."""
+        from . import functional as GF
+        normalize = self.normalize if normalize is None else normalize
+        ok = self.native_supported() and x.is_cuda
+        if native and not ok:
+            raise RuntimeError(f"SpeakerEncoder.embed(native=True): no HIP kernel for (n_mels, hidden, layers, dim) = "
+                               f"{self._shape()} with float32 parameters and input on a GPU")
+        if native or (native is None and ok and x.shape[0] >= NATIVE_MIN_ROWS):
+            n_mels, H, L, D = self._shape()
+            return GF.encode(self.packed_weights(), x, hidden=H, layers=L, dim=D, normalize=normalize)
+        with torch.no_grad():
+            y = self.raw(x)
+            return y / torch.norm(y, dim=1).unsqueeze(1) if normalize else y
+
+    def embed_utterances(self, mels, window: int = 160, hop: int = 80):
+        """Utterance d-vectors (len(mels), D) from whole spectrograms (F_i, n_mels): every window of ``window`` frames at
+        hops of ``hop`` is encoded -- ONE native call over the concatenated frames, the windows addressed in place -- and an
+        utterance's normalised window d-vectors are averaged and renormalised by ``enroll_accumulate`` /
+        ``enroll_finalize`` with the utterance number as the label."""
+        from . import functional as GF
+        if not self.native_supported():
+            raise RuntimeError(f"embed_utterances needs the native encoder kernel; this module {self._shape()} has none")
+        if len(mels) < 1 or window < 1 or hop < 1:
+            raise ValueError("embed_utterances needs at least one spectrogram and window, hop >= 1")
+        n_mels, H, L, D = self._shape()
+        dev = self.projection.weight.device
+        starts, labels, base = [], [], 0
+        for u, m in enumerate(mels):
+            if m.dim() != 2 or m.shape[1] != n_mels:
+                raise ValueError(f"spectrogram {u} must be (frames, {n_mels}), got {tuple(m.shape)}")
+            if m.shape[0] < window:
+                raise ValueError(f"spectrogram {u} has {m.shape[0]} frames, fewer than one window of {window}")
+            n = (m.shape[0] - window) // hop + 1
+            starts += [base + i * hop for i in range(n)]
+            labels += [u] * n
+            base += m.shape[0]
+        flat = torch.cat([torch.as_tensor(m).to(dev).float() for m in mels])
+        row_start = torch.tensor(starts, dtype=torch.int64).to(dev)
+        e = GF.encode(self.packed_weights(), flat, T=window, row_start=row_start, hidden=H, layers=L, dim=D, normalize=True)
+        sums = torch.zeros(len(mels), D, dtype=torch.float32, device=dev)
+        cnt = torch.zeros(len(mels), dtype=torch.int32, device=dev)
+        GF.enroll_accumulate(sums, cnt, e, torch.tensor(labels, dtype=torch.int32).to(dev))
+        return GF.enroll_finalize(sums, cnt)
 
 
 def get_pre_trained_embedding_model(hp, use_path_as_absolute: bool = False) -> SpeakerEncoder:

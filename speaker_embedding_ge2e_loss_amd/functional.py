@@ -1357,6 +1357,76 @@ def check_unperm(unperm: torch.Tensor, rows: int) -> None:
         raise ValueError("unperm (tensor) is not a permutation of range(rows)")
 
 
+def encode_supported(n_mels: int, hidden: int, layers: int, dim: int) -> bool:
+    """Encoder shapes ge2e_encode runs: hidden 128 or 256, 1..4 layers, up to 256 mel channels and 256 dimensions."""
+    return _lib.load().ge2e_encoder_packed_bytes(int(n_mels), int(hidden), int(layers), int(dim)) > 0
+
+
+def encoder_flat_numel(n_mels: int, hidden: int, layers: int, dim: int) -> int:
+    """Elements of the flat parameter buffer ``encoder_pack`` takes."""
+    return 4 * hidden * (n_mels + hidden + 2) + (layers - 1) * 4 * hidden * (2 * hidden + 2) + dim * hidden + dim
+
+
+def encoder_pack(flat_params: torch.Tensor, n_mels: int, hidden: int, layers: int, dim: int) -> torch.Tensor:
+    """ge2e_encoder_pack -> the packed weights ``encode`` streams from.  ``flat_params``: one float32 device vector, per
+    layer weight_ih, weight_hh, bias_ih, bias_hh in torch's layout (gate order i, f, g, o), then projection.weight and
+    projection.bias.  One launch on the current stream; run it once per set of weights."""
+    _require_cuda(flat_params, "flat_params")
+    nbytes = _lib.load().ge2e_encoder_packed_bytes(int(n_mels), int(hidden), int(layers), int(dim))
+    if nbytes == 0:
+        raise ValueError(f"encoder shape (n_mels {n_mels}, hidden {hidden}, layers {layers}, dim {dim}) has no native kernel")
+    f = flat_params.detach()
+    if f.dim() != 1 or f.dtype != torch.float32 or not f.is_contiguous() or \
+            f.numel() != encoder_flat_numel(n_mels, hidden, layers, dim):
+        raise ValueError(f"flat_params must be a contiguous float32 vector of "
+                         f"{encoder_flat_numel(n_mels, hidden, layers, dim)} elements, got {tuple(f.shape)} {f.dtype}")
+    packed = torch.empty(nbytes // 4, dtype=torch.float32, device=f.device)
+    _launch("ge2e_encoder_pack", f.device, f.data_ptr(), int(n_mels), int(hidden), int(layers), int(dim), packed.data_ptr(),
+            _stream_ptr(f))
+    return packed
+
+
+def encode(packed: torch.Tensor, mel: torch.Tensor, *, T: Optional[int] = None, row_start: Optional[torch.Tensor] = None,
+           hidden: int, layers: int, dim: int, normalize: bool = True, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ge2e_encode: mel windows to d-vectors (R, dim) float32 in one launch on the current stream, no workspace.
+    ``mel``: (R, T, n_mels); or flat (frames, n_mels) with ``row_start`` (R,) int64 on the device -- the first frame of
+    every window, windows may overlap -- and ``T``, the window length.  float64 mels are cast to float32 (s2:28).
+    ``normalize=False`` returns the raw projection (``SpeakerEncoder.raw``'s contract).  ``out``: a contiguous (R, dim)
+    float32 tensor to write into (static buffers of a captured graph)."""
+    _require_cuda(mel, "mel")
+    dev = mel.device
+    m = mel.detach()
+    if m.dtype == torch.float64:
+        m = m.float()
+    if m.dtype != torch.float32:
+        raise TypeError(f"mel must be float32 or float64, got {mel.dtype}")
+    m = m.contiguous()
+    if row_start is None:
+        if m.dim() != 3 or m.shape[0] < 1 or m.shape[1] < 1 or (T is not None and T != m.shape[1]):
+            raise ValueError(f"mel must be (R, T, n_mels) with R, T >= 1 (or flat with row_start and T), got {tuple(m.shape)}")
+        R, T, n_mels = m.shape
+        rs_ptr = None
+    else:
+        if m.dim() != 2 or T is None or T < 1 or m.shape[0] < T:
+            raise ValueError("with row_start, mel must be flat (frames, n_mels) with frames >= T, and T given")
+        if row_start.dtype != torch.int64 or row_start.dim() != 1 or row_start.device != dev or row_start.numel() < 1:
+            raise TypeError(f"row_start must be a (R,) torch.int64 tensor on {dev}")
+        row_start = row_start.contiguous()
+        R, n_mels = row_start.numel(), m.shape[1]
+        rs_ptr = row_start.data_ptr()
+    if packed.device != dev or packed.dtype != torch.float32 or not packed.is_contiguous() or \
+            packed.numel() * 4 != _lib.load().ge2e_encoder_packed_bytes(n_mels, int(hidden), int(layers), int(dim)):
+        raise ValueError(f"packed is not encoder_pack's buffer for (n_mels {n_mels}, hidden {hidden}, layers {layers}, "
+                         f"dim {dim}) on {dev}")
+    if out is None:
+        out = torch.empty(R, dim, dtype=torch.float32, device=dev)
+    elif tuple(out.shape) != (R, dim) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
+        raise TypeError(f"out must be a contiguous ({R}, {dim}) torch.float32 tensor on {dev}")
+    _launch("ge2e_encode", dev, packed.data_ptr(), m.data_ptr(), rs_ptr, R, int(T), n_mels, int(hidden), int(layers), int(dim),
+            int(bool(normalize)), out.data_ptr(), _stream_ptr(m))
+    return out
+
+
 def raw_supported(N: int, M: int, D: int) -> bool:
     """Shapes ge2e_loss_raw runs as ONE launch (the one-wave-per-batch kernel's register-only shapes)."""
     return bool(_lib.load().ge2e_raw_supported(N, M, D))
