@@ -641,6 +641,60 @@ int ge2e_encode(const float* packed, const float* mel, const long long* row_star
                 float* out /* [R][D] */, void* stream);
 int ge2e_encode_plan(int R, int T, int n_mels, int H, int L, int D, char* buf, size_t buf_bytes);
 
+/*
+ * MEL FRONT END (csrc/ge2e_melspec.hip): waveforms to the frames ge2e_encode reads -- reflect pad, overlapping frames, a
+ * window, |rfft|, a mel basis, 20 log10 and a clip (s0:29-66 with pySTFT, s0:201-219) -- in ONE launch.  float32, the mel
+ * product exact fp32 on the matrix core (v_mfma_f32_16x16x4_f32).  Supported: n_fft 256, 512, 1024 or 2048, 1 <= n_mels <=
+ * 128, any hop >= 1 (it need not divide n_fft and may exceed it), any U >= 1; everything else is GE2E_ERR_IMPL and nothing
+ * is launched.
+ *
+ * ge2e_melspec_pack, once per (window, basis).  window [n_fft] and basis [n_fft/2 + 1][n_mels], float32 on the device, any
+ * values: the kernel does not know what a Hann window or a mel scale is.  packed (ge2e_melspec_packed_bytes, 16-byte
+ * aligned; every byte is written): the window; the transform's twiddles exp(-2 pi i k / n_fft), k < n_fft, as (cos, sin),
+ * computed in double and rounded once; the basis in the MFMA's B-fragment order [column tile][K-step][lane], its n_fft/2 + 1
+ * rows zero-padded to a multiple of 4 and its n_mels columns to a multiple of 16.  One launch.  Checks, in this order:
+ * GE2E_ERR_NULL (window, basis or packed), GE2E_ERR_SHAPE (n_mels < 1), GE2E_ERR_IMPL, GE2E_ERR_ALIGN (packed not 16-byte
+ * aligned).
+ *
+ * ge2e_melspec.  Utterance u is wav[utt_start[u] .. + utt_len[u]) (int64, in samples, on the device), every sample times
+ * gain[u] (1 where gain is NULL), logically extended with zeros to P_u = utt_padded_len[u] (utt_len[u] where NULL; P_u >=
+ * utt_len[u] is the caller's guarantee): the reference's zero pad to the last partial slice without a copy.  Samples at or
+ * past utt_len[u] are never read.  The extended signal is reflect-padded by n_fft/2 on both sides (numpy's mode='reflect',
+ * the edge sample not repeated: this needs P_u > n_fft/2), frame f is samples f hop .. f hop + n_fft of that, and there are
+ * F_u = P_u / hop + 1 frames (integer division).  frame_start [U + 1] (int64, device) is the prefix sum of F_u and
+ * total_frames its last entry: host arithmetic on lengths, the caller's.  out[frame_start[u] + f][n_mels], float32:
+ *   m = |rfft(window . frame)| . basis
+ *   mode 0   m, the linear mel
+ *   mode 1   clip((20 log10(max(10^(min_level_db / 20), m)) - ref_level_db - min_level_db) / -min_level_db, 0, 1), computed
+ *            from the very bits mode 0 stores; min_level_db = -100 and ref_level_db = 16 are s0:47-50
+ * A NaN or Inf sample makes EVERY element of the frames that contain it NaN, in both modes (numpy's maximum and clip keep a
+ * NaN; nothing is clamped away), and no other frame changes by a bit.  Exactly total_frames n_mels elements are written.
+ * One launch of ceil(total_frames / 16) workgroups of 512 threads.  A workgroup owns 16 consecutive rows of out, which may
+ * belong to different utterances: each row finds its own by a binary search of frame_start.  One wave per frame gathers it
+ * (reflection and zero extension are address arithmetic), applies gain and window, and runs the real transform as an
+ * n_fft/2-point complex FFT -- radix-8 and radix-4 butterflies in registers, the points exchanged through LDS between the
+ * passes -- plus the real-input post-pass; the 16 x (n_fft/2 + 1) magnitudes in LDS then meet the packed basis, streamed
+ * from L2, on the matrix core, one 16-column tile per wave.  No workspace, no allocation, no synchronisation, everything on
+ * `stream`, grid from the arguments alone: fit for a HIP graph.  The bits of an output row depend on that frame's samples,
+ * its gain and `packed` ALONE: not on U, on the row's position in its tile, or on its neighbours.
+ * Checked on the host before anything is launched, in this order: GE2E_ERR_NULL (packed, wav, utt_start, utt_len,
+ * frame_start or out), GE2E_ERR_SHAPE (U, hop, n_mels or total_frames < 1, mode not 0 or 1, min_level_db not below 0),
+ * GE2E_ERR_IMPL (n_fft or n_mels unsupported), GE2E_ERR_ALIGN (packed or out not 16-byte aligned, wav not aligned to a float).
+ *
+ * ge2e_melspec_plan (diagnostics, no GPU): "melspec<n_fft>/tiles", the instantiation and its grid ceil(total_frames / 16),
+ * snprintf-style as ge2e_loss_plan; < 0: GE2E_ERR_SHAPE or GE2E_ERR_IMPL as the call itself.  (No part of ge2e_plan_atoms.)
+ */
+size_t ge2e_melspec_packed_bytes(int n_fft, int n_mels);   /* 0 for an unsupported shape */
+int ge2e_melspec_pack(const float* window /* [n_fft] */, const float* basis /* [n_fft/2+1][n_mels] */,
+                      int n_fft, int n_mels, float* packed, void* stream);
+int ge2e_melspec(const float* packed, const float* wav,
+                 const long long* utt_start, const long long* utt_len,      /* [U], device, in samples */
+                 const long long* utt_padded_len /* [U] or NULL */, const float* gain /* [U] or NULL */,
+                 const long long* frame_start /* [U+1], device */, int U, long long total_frames,
+                 int n_fft, int hop, int n_mels, int mode, float min_level_db, float ref_level_db,
+                 float* out /* [total_frames][n_mels] */, void* stream);
+int ge2e_melspec_plan(int U, long long total_frames, int n_fft, int hop, int n_mels, char* buf, size_t buf_bytes);
+
 /* ---- diagnostics (tests only): which kernels a call launches ---------------------------------------------------------
  * Below ge2e_resolve_impl every launcher chooses again among kernels and template instantiations.  These queries print
  * that choice -- made by the very functions the launchers switch on -- without a GPU and without launching anything:

@@ -87,6 +87,10 @@ PROTOTYPES = {
     "ge2e_encoder_pack": (C.c_int, [_fp] + [C.c_int] * 4 + [_fp, _fp]),
     "ge2e_encode": (C.c_int, [_fp, _fp, _fp] + [C.c_int] * 7 + [_fp, _fp]),
     "ge2e_encode_plan": (C.c_int, [C.c_int] * 6 + [C.c_char_p, C.c_size_t]),
+    "ge2e_melspec_packed_bytes": (C.c_size_t, [C.c_int] * 2),
+    "ge2e_melspec_pack": (C.c_int, [_fp, _fp, C.c_int, C.c_int, _fp, _fp]),
+    "ge2e_melspec": (C.c_int, [_fp] * 7 + [C.c_int, C.c_longlong] + [C.c_int] * 4 + [C.c_float, C.c_float, _fp, _fp]),
+    "ge2e_melspec_plan": (C.c_int, [C.c_int, C.c_longlong] + [C.c_int] * 3 + [C.c_char_p, C.c_size_t]),
     "ge2e_raw_supported": (C.c_int, [C.c_int] * 3),
     "ge2e_loss_fwd_bwd_raw": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, C.c_float, C.c_float,
                                         C.c_int, _fp, _fp, _fp, _fp, _fp, _fp]),
@@ -198,6 +202,11 @@ def cos_sim_plan(B: int, N: int, M: int, D: int) -> list[str]:
 def encode_plan(R: int, T: int, n_mels: int, H: int, L: int, D: int) -> list[str]:
     """... ge2e_encode would launch: ["encode<H>/tiles"]."""
     return _plan(load().ge2e_encode_plan, R, T, n_mels, H, L, D)
+
+
+def melspec_plan(U: int, total_frames: int, n_fft: int, hop: int, n_mels: int) -> list[str]:
+    """... ge2e_melspec would launch: ["melspec<n_fft>/tiles"]."""
+    return _plan(load().ge2e_melspec_plan, U, total_frames, n_fft, hop, n_mels)
 
 
 def plan_atoms() -> list[str]:

@@ -1,0 +1,177 @@
+"""The audio front end of the reference (``utils/audio_utils.py``, s0) around ``functional.melspec``: the tables the
+reference takes from scipy and librosa -- a periodic Hann window, the Slaney mel filterbank -- built here in float64, its
+partial-utterance arithmetic (``compute_partial_slices``), the per-utterance gain of ``normalize_volume``, and
+``MelFrontEnd``, which holds the packed tables per device and turns waveforms into the frames ``functional.encode`` reads.
+
+Out of scope: decoding audio files, resampling and the webrtcvad silence trimming.  The caller hands in samples at the
+model's sampling rate.
+"""
+from __future__ import annotations
+
+import math
+from typing import NamedTuple, Optional, Sequence
+
+import numpy as np
+import torch
+
+def hann_window(n_fft: int) -> torch.Tensor:
+    """The periodic Hann window scipy's ``get_window('hann', n_fft, fftbins=True)`` returns, (n_fft,) float64."""
+    k = torch.arange(n_fft, dtype=torch.float64)
+    return 0.5 - 0.5 * torch.cos(2.0 * math.pi * k / n_fft)
+
+
+def _hz_to_mel(f):
+    f = np.asarray(f, dtype=np.float64)
+    min_log_mel, logstep = 1000.0 / (200.0 / 3), np.log(6.4) / 27.0
+    return np.where(f >= 1000.0, min_log_mel + np.log(np.maximum(f, 1e-9) / 1000.0) / logstep, f / (200.0 / 3))
+
+
+def _mel_to_hz(m):
+    m = np.asarray(m, dtype=np.float64)
+    min_log_mel, logstep = 1000.0 / (200.0 / 3), np.log(6.4) / 27.0
+    return np.where(m >= min_log_mel, 1000.0 * np.exp(logstep * (m - min_log_mel)), m * (200.0 / 3))
+
+
+def mel_filterbank(sr: float, n_fft: int, n_mels: int, fmin: float = 0.0, fmax: Optional[float] = None) -> torch.Tensor:
+    """What ``librosa.filters.mel(sr, n_fft, n_mels=, fmin=, fmax=)`` returns by default, transposed to the layout
+    ``melspec_pack`` takes: (n_fft/2 + 1, n_mels) float64.  Slaney's mel scale -- linear below 1 kHz at 200/3 Hz a mel,
+    logarithmic above with step log(6.4) / 27 --, triangles between n_mels + 2 equally spaced mel points, each
+    area-normalised by 2 / (f[i+2] - f[i]).  The reference calls it with fmin 90 and fmax 7600 (s0:22-26)."""
+    fmax = sr / 2.0 if fmax is None else fmax
+    fft_f = np.linspace(0.0, sr / 2.0, n_fft // 2 + 1)
+    mel_f = _mel_to_hz(np.linspace(_hz_to_mel(fmin), _hz_to_mel(fmax), n_mels + 2))
+    fdiff = np.diff(mel_f)
+    ramps = mel_f[:, None] - fft_f[None, :]
+    lower = -ramps[:-2] / fdiff[:-1, None]
+    upper = ramps[2:] / fdiff[1:, None]
+    w = np.maximum(0.0, np.minimum(lower, upper)) * (2.0 / (mel_f[2:] - mel_f[:-2]))[:, None]
+    return torch.from_numpy(np.ascontiguousarray(w.T))
+
+
+class PartialSlices(NamedTuple):
+    mel_starts: list      # the first mel frame of every partial utterance
+    padded_length: int    # the sample count the waveform is zero-extended to: max(n_samples, the last slice's end)
+
+
+def partial_slices(n_samples: int, *, sampling_rate: int = 16000, mel_window_step: float = 10, partials_n_frames: int = 180,
+                   rate: float = 1.3, min_coverage: float = 0.75) -> PartialSlices:
+    """``compute_partial_slices`` (s0:150-199): where the partial utterances of ``partials_n_frames`` mel frames start,
+    ``rate`` of them a second, the last one dropped where it would cover less than ``min_coverage`` (never the only one).
+    As in the reference, ``samples_per_frame`` comes from ``mel_window_step`` (milliseconds) although the spectrogram's
+    hop is ``hop_length``: the mel starts index the spectrogram as they are."""
+    if not 0 < min_coverage <= 1:
+        raise ValueError("min_coverage must be in (0, 1]")
+    samples_per_frame = int(sampling_rate * mel_window_step / 1000)
+    n_frames = int(math.ceil((n_samples + 1) / samples_per_frame))
+    frame_step = int(np.round((sampling_rate / rate) / samples_per_frame))
+    if not 0 < frame_step <= partials_n_frames:
+        raise ValueError(f"rate {rate} gives a step of {frame_step} frames; it must be in 1 .. {partials_n_frames}")
+    starts = list(range(0, max(1, n_frames - partials_n_frames + frame_step + 1), frame_step))
+    last = starts[-1] * samples_per_frame
+    coverage = (n_samples - last) / (partials_n_frames * samples_per_frame)
+    if coverage < min_coverage and len(starts) > 1:
+        starts = starts[:-1]
+    stop = (starts[-1] + partials_n_frames) * samples_per_frame
+    return PartialSlices(starts, max(n_samples, stop))
+
+
+def volume_gain(wav: torch.Tensor, lengths: Optional[Sequence[int]] = None, target_dbfs: float = -30.0,
+                increase_only: bool = True) -> torch.Tensor:
+    """The factor ``normalize_volume`` (s0:94-105) multiplies every utterance by, (U,) float32 on wav's device, made with
+    torch ops (no read-back): 10^((target - dBFS) / 20) with dBFS = 20 log10(rms), and, with ``increase_only``, 1 where that
+    would lower the volume.  ``melspec(gain=...)`` applies it inside the kernel."""
+    ls = [wav.numel()] if lengths is None else [int(v) for v in lengths]
+    sq = (wav.detach().double() ** 2)
+    csum = torch.cat([sq.new_zeros(1), torch.cumsum(sq, 0)])
+    ends = torch.tensor(np.cumsum(ls), dtype=torch.int64).to(wav.device)
+    n = torch.tensor(ls, dtype=torch.float64).to(wav.device)
+    begins = ends - n.long()
+    rms = torch.sqrt((csum[ends] - csum[begins]) / n)
+    change = target_dbfs - 20.0 * torch.log10(rms)
+    gain = 10.0 ** (change / 20.0)
+    if increase_only:
+        gain = torch.where(change < 0, torch.ones_like(gain), gain)
+    return gain.float()
+
+
+class MelFrontEnd:
+    """Waveforms to mel frames at one set of audio settings.  The window and filterbank are built once in float64 and
+    packed once per device (``functional.melspec_pack``); ``frames`` is one ``functional.melspec`` call over all the
+    waveforms, ``partials`` the partial utterances of every waveform as ``get_mel_spects_from_audio`` returns them."""
+
+    def __init__(self, sampling_rate: int = 16000, n_fft: int = 1024, hop_length: int = 128, n_mels: int = 80,
+                 fmin: float = 90.0, fmax: float = 7600.0, mel_window_step: float = 10, partials_n_frames: int = 180,
+                 rate_partial_slices: float = 1.3, min_coverage: float = 0.75, target_dbfs: float = -30.0,
+                 min_level_db: float = -100.0, ref_level_db: float = 16.0):
+        self.sampling_rate, self.n_fft, self.hop_length, self.n_mels = sampling_rate, n_fft, hop_length, n_mels
+        self.mel_window_step, self.partials_n_frames = mel_window_step, partials_n_frames
+        self.rate_partial_slices, self.min_coverage, self.target_dbfs = rate_partial_slices, min_coverage, target_dbfs
+        self.min_level_db, self.ref_level_db = min_level_db, ref_level_db
+        self.window = hann_window(n_fft)
+        self.basis = mel_filterbank(sampling_rate, n_fft, n_mels, fmin, fmax)
+        self._tables = {}
+
+    @classmethod
+    def from_hp(cls, hp) -> "MelFrontEnd":
+        """From the reference's hyper-parameters (``hp.audio``, ``hp.vad``; s0:22-26 fixes fmin 90 and fmax 7600)."""
+        a, v = hp.audio, hp.vad
+        return cls(a.sampling_rate, a.n_fft, a.hop_length, a.mel_n_channels, 90.0, 7600.0, a.mel_window_step,
+                   a.partials_n_frames, v.rate_partial_slices, v.min_coverage, getattr(v, "audio_norm_target_dBFS", -30.0))
+
+    def tables(self, device):
+        """The packed tables on ``device``, made on first use."""
+        from . import functional as GF
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        t = self._tables.get(device)
+        if t is None:
+            t = self._tables[device] = GF.melspec_pack(self.window.to(device), self.basis.to(device))
+        return t
+
+    def slices(self, n_samples: int) -> PartialSlices:
+        return partial_slices(n_samples, sampling_rate=self.sampling_rate, mel_window_step=self.mel_window_step,
+                              partials_n_frames=self.partials_n_frames, rate=self.rate_partial_slices,
+                              min_coverage=self.min_coverage)
+
+    def frames(self, wavs, normalize_volume: bool = False, pad_to_partials: bool = False, mode: str = "db",
+               native: Optional[bool] = None):
+        """``(frames, frame_start)`` of ``functional.melspec`` for a list of 1-D float32 device waveforms (or one): all of
+        them in one launch.  ``normalize_volume``: the gain of ``normalize_volume(increase_only=True)``, applied in the
+        kernel.  ``pad_to_partials``: every waveform zero-extended to the end of its last partial slice, as
+        ``get_mel_spects_from_audio(partial_slices=True)`` pads it."""
+        from . import functional as GF
+        wavs = [wavs] if isinstance(wavs, torch.Tensor) else list(wavs)
+        if not wavs:
+            raise ValueError("no waveform")
+        dev = wavs[0].device
+        lengths = [int(w.numel()) for w in wavs]
+        flat = wavs[0].detach().float().contiguous() if len(wavs) == 1 else torch.cat([w.detach().float().reshape(-1) for w in wavs])
+        padded = [self.slices(n).padded_length for n in lengths] if pad_to_partials else None
+        gain = volume_gain(flat, lengths, self.target_dbfs, increase_only=True) if normalize_volume else None
+        return GF.melspec(self.tables(dev), flat, lengths, hop=self.hop_length, padded_lengths=padded, gain=gain, mode=mode,
+                          min_level_db=self.min_level_db, ref_level_db=self.ref_level_db, native=native)
+
+    def partial_rows(self, lengths, frame_start):
+        """``(row_start, owner)`` Python lists: the first row of ``frames(pad_to_partials=True)`` of every partial
+        utterance and the waveform it belongs to; a partial whose frames the spectrogram does not hold is left out, as
+        s0:59 leaves it out."""
+        rows, owner = [], []
+        for u, n in enumerate(lengths):
+            have = frame_start[u + 1] - frame_start[u]
+            for s in self.slices(n).mel_starts:
+                if s + self.partials_n_frames <= have:
+                    rows.append(frame_start[u] + s)
+                    owner.append(u)
+        return rows, owner
+
+    def partials(self, wavs, normalize_volume: bool = False, native: Optional[bool] = None):
+        """Per waveform the tensor ``get_mel_spects_from_audio(partial_slices=True)`` returns, (partials,
+        partials_n_frames, n_mels) float32: gathered copies of the frames (``SpeakerEncoder.embed_audio`` addresses them
+        in place instead)."""
+        wavs = [wavs] if isinstance(wavs, torch.Tensor) else list(wavs)
+        frames, frame_start = self.frames(wavs, normalize_volume, pad_to_partials=True, native=native)
+        rows, owner = self.partial_rows([int(w.numel()) for w in wavs], frame_start)
+        T = self.partials_n_frames
+        return [torch.stack([frames[r:r + T] for r, o in zip(rows, owner) if o == u]) if u in owner
+                else frames.new_zeros(0, T, self.n_mels) for u in range(len(wavs))]

@@ -15,6 +15,7 @@
 #include "ge2e_labeled_helpers.hpp"
 #include "ge2e_enroll.hpp"
 #include "ge2e_encoder.hpp"
+#include "ge2e_melspec.hpp"
 #include "ge2e_identify.hpp"
 #include "ge2e_snorm.hpp"
 #include "ge2e_helpers.hpp"
@@ -669,6 +670,48 @@ int ge2e_encode_plan(int R, int T, int n_mels, int H, int L, int D, char* buf, s
     if (R < 1 || T < 1 || n_mels < 1 || D < 1 || L < 1) return GE2E_ERR_SHAPE;
     if (!encoder_supported(n_mels, H, L, D)) return GE2E_ERR_IMPL;
     return plan_string_encode(R, H, buf, buf_bytes);
+}
+
+// MEL FRONT END (include/ge2e_hip.h, csrc/ge2e_melspec.hip): window, twiddles and basis packed once, then waveforms to
+// (log-)mel frames in one launch.
+size_t ge2e_melspec_packed_bytes(int n_fft, int n_mels) {
+    return melspec_supported(n_fft, n_mels) ? melspec_packed_floats(n_fft, n_mels) * sizeof(float) : 0;
+}
+
+int ge2e_melspec_pack(const float* window, const float* basis, int n_fft, int n_mels, float* packed, void* stream) {
+    if (!window || !basis || !packed) return GE2E_ERR_NULL;
+    if (n_mels < 1) return GE2E_ERR_SHAPE;
+    if (!melspec_supported(n_fft, n_mels)) return GE2E_ERR_IMPL;
+    if (!aligned16(packed)) return GE2E_ERR_ALIGN;
+    return (int)launch_melspec_pack(window, basis, n_fft, n_mels, packed, (hipStream_t)stream);
+}
+
+static int melspec_shape_check(int U, long long total_frames, int n_fft, int hop, int n_mels) {
+    if (U < 1 || hop < 1 || n_mels < 1 || total_frames < 1) return GE2E_ERR_SHAPE;
+    // (a grid of more than 2^31 - 1 tiles has no launch)
+    if (!melspec_supported(n_fft, n_mels) || (total_frames + kMelTile - 1) / kMelTile > 0x7fffffffLL) return GE2E_ERR_IMPL;
+    return GE2E_OK;
+}
+
+int ge2e_melspec(const float* packed, const float* wav, const long long* utt_start, const long long* utt_len,
+                 const long long* utt_padded_len, const float* gain, const long long* frame_start, int U,
+                 long long total_frames, int n_fft, int hop, int n_mels, int mode, float min_level_db, float ref_level_db,
+                 float* out, void* stream) {
+    if (!packed || !wav || !utt_start || !utt_len || !frame_start || !out) return GE2E_ERR_NULL;
+    if (U < 1 || hop < 1 || n_mels < 1 || total_frames < 1 || (mode != 0 && mode != 1) || !(min_level_db < 0.f))
+        return GE2E_ERR_SHAPE;
+    const int rc = melspec_shape_check(U, total_frames, n_fft, hop, n_mels);
+    if (rc != GE2E_OK) return rc;
+    if (!aligned16(packed) || !aligned16(out) || ((uintptr_t)wav & 3)) return GE2E_ERR_ALIGN;
+    const ProblemMelspec p = {packed, wav, utt_start, utt_len, utt_padded_len, gain, frame_start, out, total_frames,
+                              U, hop, n_mels, mode, (float)pow(10.0, (double)min_level_db / 20.0), min_level_db, ref_level_db};
+    return (int)launch_melspec(p, n_fft, (hipStream_t)stream);
+}
+
+int ge2e_melspec_plan(int U, long long total_frames, int n_fft, int hop, int n_mels, char* buf, size_t buf_bytes) {
+    const int rc = melspec_shape_check(U, total_frames, n_fft, hop, n_mels);
+    if (rc != GE2E_OK) return rc;
+    return plan_string_melspec(total_frames, n_fft, buf, buf_bytes);
 }
 
 // ---- diagnostics: the launch plan of a call, from the launchers' own decision functions (ge2e_plan.hpp); no GPU needed ----

@@ -230,6 +230,14 @@ __device__ __forceinline__ float wave_sums_scatter(float (&v)[K], int lane) {
     for (int m = 1; m < K4; ++m) r = l15 == m ? u[m] : r;
     return r;
 }
+// The lanes of a wave see each other's LDS stores: the wave runs in lockstep and LDS returns in order; this keeps the
+// compiler from moving an access across the point.
+__device__ __forceinline__ void wave_lds_point() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 template <int R, int RMAX, class F>
 __device__ __forceinline__ void static_for(F&& f) {
     if constexpr (R < RMAX) {

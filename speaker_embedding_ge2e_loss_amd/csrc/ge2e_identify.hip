@@ -54,14 +54,6 @@ __device__ __forceinline__ float key_score(u64 key) {   // (the empty slot: -inf
     return hi == 0u ? -INFINITY : key_to_score(hi);
 }
 
-// The lanes of a wave see each other's LDS stores: the wave runs in lockstep and LDS returns in order; this keeps the
-// compiler from moving an access across the point.
-__device__ __forceinline__ void wave_lds_point() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // key into the descending list L[0 .. k - 1] (key > L[k - 1]) -> the new last key.  One pass from the end without a branch
 // on what it reads: position i takes its upper neighbour where that one is below the key, the key where only its own old
 // value is, and keeps its value otherwise.  Four positions at a time: their reads are independent of each other, so one LDS

@@ -141,7 +141,35 @@ class SpeakerEncoder(nn.Module):
         return GF.enroll_finalize(sums, cnt)
 
 
-def get_pre_trained_embedding_model(hp, use_path_as_absolute: bool = False) -> SpeakerEncoder:
+    def embed_audio(self, wavs, front_end, normalize_volume: bool = False):
+        """Utterance d-vectors (len(wavs), D) from waveforms (1-D float32 tensors on the module's device), as the
+        reference makes them from ``get_mel_spects_from_audio(partial_slices=True)``: three launches and no copy between
+        them.  ``front_end`` (an ``audio.MelFrontEnd``) turns all the waveforms, each zero-extended to the end of its last
+        partial slice, into one flat frame buffer (``functional.melspec``); every partial utterance of
+        ``partials_n_frames`` frames is encoded where it lies (``functional.encode`` with ``row_start``); an utterance's
+        normalised partial d-vectors are averaged and renormalised by ``enroll_accumulate`` / ``enroll_finalize``."""
+        from . import functional as GF
+        if not self.native_supported():
+            raise RuntimeError(f"embed_audio needs the native encoder kernel; this module {self._shape()} has none")
+        wavs = [wavs] if isinstance(wavs, torch.Tensor) else list(wavs)
+        n_mels, H, L, D = self._shape()
+        if front_end.n_mels != n_mels:
+            raise ValueError(f"the front end makes {front_end.n_mels} mel channels, the encoder takes {n_mels}")
+        dev = self.projection.weight.device
+        frames, frame_start = front_end.frames([w.to(dev) for w in wavs], normalize_volume, pad_to_partials=True)
+        rows, owner = front_end.partial_rows([int(w.numel()) for w in wavs], frame_start)
+        if sorted(set(owner)) != list(range(len(wavs))):
+            raise ValueError("a waveform has no whole partial utterance in its spectrogram (hop_length above the slices' step)")
+        idx = torch.tensor([rows, owner], dtype=torch.int64).to(dev)
+        e = GF.encode(self.packed_weights(), frames, T=front_end.partials_n_frames, row_start=idx[0], hidden=H, layers=L,
+                      dim=D, normalize=True)
+        sums = torch.zeros(len(wavs), D, dtype=torch.float32, device=dev)
+        cnt = torch.zeros(len(wavs), dtype=torch.int32, device=dev)
+        GF.enroll_accumulate(sums, cnt, e, idx[1].to(torch.int32))
+        return GF.enroll_finalize(sums, cnt)
+
+
+def get_pre_trained_embedding_model(hp,use_path_as_absolute: bool = False) -> SpeakerEncoder:
     """The reference's loader of the same name (s2:38-67): a fresh encoder built from ``hp``, the encoder-only checkpoint
     ``hp.m_ge2e.best_model_path`` (joined with ``hp.general.project_root`` unless ``use_path_as_absolute``) loaded into
     it, eval mode, on ``hp.general.device``.  The file format is the reference's (s4:130: the module's ``state_dict``),

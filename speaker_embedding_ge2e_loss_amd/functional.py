@@ -1427,6 +1427,172 @@ def encode(packed: torch.Tensor, mel: torch.Tensor, *, T: Optional[int] = None, 
     return out
 
 
+def melspec_supported(n_fft: int, n_mels: int) -> bool:
+    """Front-end shapes ge2e_melspec runs: n_fft 256, 512, 1024 or 2048 and up to 128 mel channels."""
+    return _lib.load().ge2e_melspec_packed_bytes(int(n_fft), int(n_mels)) > 0
+
+
+class MelTables(NamedTuple):
+    """What ``melspec_pack`` returns: the window (n_fft,) and basis (n_fft/2 + 1, n_mels) as given (float32, the torch
+    route reads them) and ``packed``, ge2e_melspec_pack's buffer, or None where the shape has no native kernel."""
+    packed: Optional[torch.Tensor]
+    window: torch.Tensor
+    basis: torch.Tensor
+
+    @property
+    def n_fft(self) -> int:
+        return self.window.numel()
+
+    @property
+    def n_mels(self) -> int:
+        return self.basis.shape[1]
+
+
+class MelLayout(NamedTuple):
+    """Where the utterances of a flat waveform buffer lie and where their frames go: int64 device tensors for the kernel,
+    ``frame_start`` also as a Python list (U + 1 entries, the last one the frame total).  Pure arithmetic on lengths."""
+    utt_start: torch.Tensor
+    utt_len: torch.Tensor
+    utt_padded_len: torch.Tensor
+    frame_start_dev: torch.Tensor
+    frame_start: list
+    lengths: list
+    padded_lengths: list
+    hop: int
+
+
+def melspec_pack(window: torch.Tensor, basis: torch.Tensor) -> MelTables:
+    """ge2e_melspec_pack -> the tables ``melspec`` reads.  ``window`` (n_fft,) and ``basis`` (n_fft/2 + 1, n_mels) on the
+    device, any values (``audio.hann_window`` / ``audio.mel_filterbank`` make the reference's); cast to float32.  One
+    launch on the current stream; run it once per (window, basis).  For a shape without a kernel ``packed`` is None and
+    ``melspec`` takes its torch route."""
+    _require_cuda(window, "window")
+    w = window.detach().to(torch.float32).contiguous()
+    b = basis.detach().to(device=w.device, dtype=torch.float32).contiguous()
+    if w.dim() != 1 or b.dim() != 2 or w.numel() % 2 or b.shape[0] != w.numel() // 2 + 1 or b.shape[1] < 1:
+        raise ValueError(f"window must be (n_fft,) with n_fft even and basis (n_fft/2 + 1, n_mels), got {tuple(w.shape)} "
+                         f"and {tuple(b.shape)}")
+    n_fft, n_mels = w.numel(), b.shape[1]
+    nbytes = _lib.load().ge2e_melspec_packed_bytes(n_fft, n_mels)
+    if nbytes == 0:
+        return MelTables(None, w, b)
+    packed = torch.empty(nbytes // 4, dtype=torch.float32, device=w.device)
+    _launch("ge2e_melspec_pack", w.device, w.data_ptr(), b.data_ptr(), n_fft, n_mels, packed.data_ptr(), _stream_ptr(w))
+    return MelTables(packed, w, b)
+
+
+def melspec_layout(lengths, *, hop: int, n_fft: int, padded_lengths=None, device=None) -> MelLayout:
+    """The index tables of a ``melspec`` call: utterance u is ``lengths[u]`` samples from the sum of the lengths before
+    it, extended with zeros to ``padded_lengths[u]`` (its own length where None), and has ``padded // hop + 1`` frames.
+    ``lengths`` / ``padded_lengths``: Python lists or CPU tensors.  Build it once for a captured graph and pass it as
+    ``melspec(layout=...)``: building it uploads four small tensors."""
+    ls = [int(v) for v in (lengths.tolist() if isinstance(lengths, torch.Tensor) else lengths)]
+    if padded_lengths is None:
+        ps = list(ls)
+    else:
+        ps = [int(v) for v in (padded_lengths.tolist() if isinstance(padded_lengths, torch.Tensor) else padded_lengths)]
+    if hop < 1 or len(ls) < 1 or len(ps) != len(ls):
+        raise ValueError("melspec needs hop >= 1, at least one utterance and one padded length per utterance")
+    starts, frame_start = [], [0]
+    at = 0
+    for n, p in zip(ls, ps):
+        if n < 0 or p < n or p <= n_fft // 2:
+            raise ValueError(f"an utterance of {n} samples padded to {p}: the padded length must be at least the length "
+                             f"and more than n_fft / 2 = {n_fft // 2} (the reflection)")
+        starts.append(at)
+        at += n
+        frame_start.append(frame_start[-1] + p // hop + 1)
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    meta = torch.tensor([starts, ls, ps, frame_start[:-1]], dtype=torch.int64)
+    tail = torch.tensor([frame_start[-1]], dtype=torch.int64)
+    d = torch.cat([meta.reshape(-1), tail]).to(dev)
+    U = len(ls)
+    return MelLayout(d[:U], d[U:2 * U], d[2 * U:3 * U], d[3 * U:], frame_start, ls, ps, int(hop))
+
+
+def _melspec_torch(t: MelTables, wav, lay: MelLayout, gain, mode, min_level_db, ref_level_db, out):
+    """The same frames with torch's ops on wav's device: pad, ``unfold``, ``torch.fft.rfft``, ``matmul``."""
+    n_fft = t.n_fft
+    for u, (n, p) in enumerate(zip(lay.lengths, lay.padded_lengths)):
+        at = int(sum(lay.lengths[:u]))
+        x = wav[at:at + n]
+        if gain is not None:
+            x = x * gain[u]
+        x = torch.nn.functional.pad(x, (0, p - n))
+        x = torch.nn.functional.pad(x[None, None], (n_fft // 2, n_fft // 2), mode="reflect")[0, 0]
+        m = torch.fft.rfft(x.unfold(0, n_fft, lay.hop) * t.window, dim=1).abs().matmul(t.basis)
+        if mode == "db":
+            level = torch.full((), 10.0 ** (min_level_db / 20.0), dtype=m.dtype, device=m.device)
+            m = ((20.0 * torch.log10(torch.maximum(level, m)) - ref_level_db - min_level_db) / -min_level_db).clamp(0.0, 1.0)
+        out[lay.frame_start[u]:lay.frame_start[u + 1]] = m
+    return out
+
+
+def melspec(packed, wav: torch.Tensor, lengths=None, *, hop: int, n_fft: Optional[int] = None, n_mels: Optional[int] = None,
+            padded_lengths=None, gain: Optional[torch.Tensor] = None, mode: str = "db", min_level_db: float = -100.0,
+            ref_level_db: float = 16.0, out: Optional[torch.Tensor] = None, native: Optional[bool] = None,
+            layout: Optional[MelLayout] = None):
+    """ge2e_melspec: waveforms to mel frames in one launch on the current stream, no workspace -> ``(frames,
+    frame_start)``: ``frames`` (total_frames, n_mels) float32, the layout ``encode(..., row_start=)`` reads, and
+    ``frame_start`` a Python list of U + 1 first rows (host arithmetic on the lengths: nothing is read back).
+    ``packed``: ``melspec_pack``'s MelTables (or its raw ``packed`` tensor, with ``n_fft`` and ``n_mels``).  ``wav``: a flat
+    float32 device tensor holding the utterances back to back, ``lengths`` their sample counts (a list or CPU tensor; None:
+    ``wav`` is one utterance); ``padded_lengths``: the length each utterance is zero-extended to, without a copy;
+    ``gain`` (U,) float32 on the device: a scale per utterance (``audio.volume_gain``).  ``mode`` "db" (the reference's
+    normalised log-mel in [0, 1]) or "linear".  ``layout``: a ``melspec_layout`` built beforehand (a captured graph).
+    ``native=None`` takes the kernel where the shape has one and the torch route otherwise; ``native=True`` raises where
+    it has none; ``native=False`` is the torch route."""
+    _require_cuda(wav, "wav")
+    dev = wav.device
+    w = wav.detach()
+    if w.dim() != 1 or w.dtype != torch.float32 or not w.is_contiguous():
+        raise TypeError(f"wav must be a flat contiguous float32 tensor, got {tuple(w.shape)} {w.dtype}")
+    if mode not in ("db", "linear"):
+        raise ValueError(f"mode must be 'db' or 'linear', got {mode!r}")
+    if not min_level_db < 0:
+        raise ValueError("min_level_db must be below 0")
+    tables = packed if isinstance(packed, MelTables) else None
+    if tables is not None:
+        if (n_fft is not None and n_fft != tables.n_fft) or (n_mels is not None and n_mels != tables.n_mels):
+            raise ValueError(f"the tables are for n_fft {tables.n_fft}, n_mels {tables.n_mels}, not {n_fft}, {n_mels}")
+        n_fft, n_mels, pk = tables.n_fft, tables.n_mels, tables.packed
+    else:
+        pk = packed
+        if n_fft is None or n_mels is None:
+            raise ValueError("a raw packed tensor needs n_fft and n_mels")
+    use_native = pk is not None and melspec_supported(n_fft, n_mels) if native is None else bool(native)
+    if use_native and (pk is None or not melspec_supported(n_fft, n_mels)):
+        raise RuntimeError(f"melspec(native=True): no HIP kernel for n_fft {n_fft}, n_mels {n_mels}")
+    if not use_native and tables is None:
+        raise ValueError("the torch route needs melspec_pack's MelTables (window and basis), not a raw packed tensor")
+    if layout is None:
+        layout = melspec_layout([w.numel()] if lengths is None else lengths, hop=hop, n_fft=n_fft,
+                                padded_lengths=padded_lengths, device=dev)
+    elif layout.hop != hop or layout.utt_start.device != dev:
+        raise ValueError(f"layout was built for hop {layout.hop} on {layout.utt_start.device}")
+    if sum(layout.lengths) > w.numel():
+        raise ValueError(f"the lengths add up to {sum(layout.lengths)} samples, wav has {w.numel()}")
+    U, total = len(layout.lengths), layout.frame_start[-1]
+    if gain is not None:
+        if gain.dtype != torch.float32 or gain.device != dev or tuple(gain.shape) != (U,) or not gain.is_contiguous():
+            raise TypeError(f"gain must be a contiguous ({U},) torch.float32 tensor on {dev}")
+        gain = gain.detach()
+    if out is None:
+        out = torch.empty(total, n_mels, dtype=torch.float32, device=dev)
+    elif tuple(out.shape) != (total, n_mels) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
+        raise TypeError(f"out must be a contiguous ({total}, {n_mels}) torch.float32 tensor on {dev}")
+    if not use_native:
+        return _melspec_torch(tables, w, layout, gain, mode, min_level_db, ref_level_db, out), layout.frame_start
+    if pk.device != dev or pk.dtype != torch.float32 or not pk.is_contiguous() or \
+            pk.numel() * 4 != _lib.load().ge2e_melspec_packed_bytes(n_fft, n_mels):
+        raise ValueError(f"packed is not melspec_pack's buffer for n_fft {n_fft}, n_mels {n_mels} on {dev}")
+    _launch("ge2e_melspec", dev, pk.data_ptr(), w.data_ptr(), layout.utt_start.data_ptr(), layout.utt_len.data_ptr(),
+            layout.utt_padded_len.data_ptr(), None if gain is None else gain.data_ptr(), layout.frame_start_dev.data_ptr(),
+            U, total, n_fft, int(hop), n_mels, int(mode == "db"), float(min_level_db), float(ref_level_db), out.data_ptr(),
+            _stream_ptr(w))
+    return out, layout.frame_start
+
+
 def raw_supported(N: int, M: int, D: int) -> bool:
     """Shapes ge2e_loss_raw runs as ONE launch (the one-wave-per-batch kernel's register-only shapes)."""
     return bool(_lib.load().ge2e_raw_supported(N, M, D))
