@@ -58,14 +58,15 @@ def epilogue(mel, min_level_db=-100.0, ref_level_db=16.0):
     return np.clip((db - dt(min_level_db)) / dt(-min_level_db), dt(0.0), dt(1.0))
 
 
-def melspec_ref(x, basis, n_fft, hop, dtype=np.float64, padded_len=None, gain=1.0, window=None):
+def melspec_ref(x, basis, n_fft, hop, dtype=np.float64, padded_len=None, gain=1.0, window=None, min_level_db=-100.0,
+                ref_level_db=16.0):
     """(linear mel, normalised dB mel) of one waveform: `x` times `gain`, extended with zeros to `padded_len`; `basis`
-    (n_fft/2 + 1, n_mels)."""
+    (n_fft/2 + 1, n_mels); `window` the periodic Hann window unless given."""
     x = np.asarray(x).astype(dtype) * dtype(gain)
     if padded_len is not None and padded_len > len(x):
         x = np.pad(x, (0, padded_len - len(x)))
     mel = magnitudes(x, n_fft, hop, dtype, window) @ np.asarray(basis).astype(dtype)
-    return mel, epilogue(mel)
+    return mel, epilogue(mel, min_level_db, ref_level_db)
 
 
 def rel_err(got, ref):

@@ -15,6 +15,11 @@ reference_tones 0.83, n512_hop160_three 0.96, n256_mels13 1.18, n2048_mels128 0.
 of a single sum, not averaged over a row), hop_above_n_fft 0.90; the length edges 0.82 .. 1.21; n_mels 1 / 13 / 80 / 128:
 1.71 / 0.63 / 0.95 / 0.98; padded 0.91, gain 0.99.  dB against the float64 epilogue of the kernel's own output: at most
 1.33e-07 of the 4.77e-07 allowed.  Every bin: the worst at 0.009 of fft_bound.
+A window without symmetry (uniform in [0.1, 1), the yardstick computed with the same window), n_fft 256 / 512 / 1024 / 2048:
+0.98 / 0.92 / 0.78 / 0.90; every bin under it at n_fft 1024: the worst at 0.004 of fft_bound.
+Other dB parameters, (min_level_db, ref_level_db): every term of the 2^-21 above scales with 100 / |min_level_db|, so the
+bound is 2^-21 x 100 / |min_level_db|.  Against the float64 epilogue of the kernel's own output: (-80, 20) 0.15 of the bound,
+(-120.5, 0) 0.25, (-40, -6.5) 0.11; end to end err / err_ref 1.02, 0.97, 0.27.
 """
 import functools
 import os
@@ -79,9 +84,10 @@ def frame_starts(padded, hop):
     return fs
 
 
-def mel_abi(lib, basis, utts, *, n_fft, hop, mode, padded=None, gain=None, finite=True, min_db=-100.0, ref_db=16.0):
+def mel_abi(lib, basis, utts, *, n_fft, hop, mode, padded=None, gain=None, finite=True, min_db=-100.0, ref_db=16.0,
+            window=None):
     """ge2e_melspec through raw pointers on guarded buffers -> (total_frames, n_mels) float32 numpy.  `utts`: float32 arrays;
-    in the wav buffer every utterance is followed by GAP NaN samples."""
+    in the wav buffer every utterance is followed by GAP NaN samples.  `window`: float32, the Hann window unless given."""
     n_mels = basis.shape[1]
     lens = [len(u) for u in utts]
     padded = list(lens) if padded is None else list(padded)
@@ -97,7 +103,7 @@ def mel_abi(lib, basis, utts, *, n_fft, hop, mode, padded=None, gain=None, finit
     g = None if gain is None else torch.as_tensor(np.asarray(gain, dtype=np.float32)).to(dev())
     out = Buf((fs[-1], n_mels))
     p8 = idx.data_ptr()
-    ok(lib.ge2e_melspec(tables(basis, n_fft).packed.data_ptr(), wav.ptr, p8, p8 + 8 * U, p8 + 16 * U,
+    ok(lib.ge2e_melspec(tables(basis, n_fft, window).packed.data_ptr(), wav.ptr, p8, p8 + 8 * U, p8 + 16 * U,
                         None if g is None else g.data_ptr(), p8 + 24 * U, U, fs[-1], n_fft, hop, n_mels, mode, min_db, ref_db,
                         out.ptr, None), "ge2e_melspec")
     got = out.get("ge2e_melspec", finite=finite)
@@ -105,19 +111,19 @@ def mel_abi(lib, basis, utts, *, n_fft, hop, mode, padded=None, gain=None, finit
     return got
 
 
-def refs(basis, utts, n_fft, hop, padded=None, gain=None, dtype=np.float64):
+def refs(basis, utts, n_fft, hop, padded=None, gain=None, dtype=np.float64, window=None, min_db=-100.0, ref_db=16.0):
     padded = [None] * len(utts) if padded is None else padded
     gain = [1.0] * len(utts) if gain is None else gain
-    both = [mr.melspec_ref(u, basis, n_fft, hop, dtype, p, g) for u, p, g in zip(utts, padded, gain)]
+    both = [mr.melspec_ref(u, basis, n_fft, hop, dtype, p, g, window, min_db, ref_db) for u, p, g in zip(utts, padded, gain)]
     return np.concatenate([b[0] for b in both]), np.concatenate([b[1] for b in both])
 
 
-def check(lib, what, basis, utts, n_fft, hop, padded=None, gain=None):
+def check(lib, what, basis, utts, n_fft, hop, padded=None, gain=None, window=None):
     """Linear and dB mode of one call against float64, under the gates of the module docstring -> (linear, dB) outputs."""
-    lin64, db64 = refs(basis, utts, n_fft, hop, padded, gain)
-    lin32, db32 = refs(basis, utts, n_fft, hop, padded, gain, dtype=np.float32)
-    lin = mel_abi(lib, basis, utts, n_fft=n_fft, hop=hop, mode=0, padded=padded, gain=gain)
-    db = mel_abi(lib, basis, utts, n_fft=n_fft, hop=hop, mode=1, padded=padded, gain=gain)
+    lin64, db64 = refs(basis, utts, n_fft, hop, padded, gain, window=window)
+    lin32, db32 = refs(basis, utts, n_fft, hop, padded, gain, dtype=np.float32, window=window)
+    lin = mel_abi(lib, basis, utts, n_fft=n_fft, hop=hop, mode=0, padded=padded, gain=gain, window=window)
+    db = mel_abi(lib, basis, utts, n_fft=n_fft, hop=hop, mode=1, padded=padded, gain=gain, window=window)
     assert lin.shape == lin64.shape and db.shape == db64.shape, (what, lin.shape, lin64.shape)
     err, err_ref = mr.rel_err(lin, lin64), mr.rel_err(lin32, lin64)
     print(f"{what}: linear err {err:.3e}, err_ref {err_ref:.3e}, ratio {err / err_ref:.2f}, gate {mr.gate(err_ref):.3e}")
@@ -160,22 +166,46 @@ def fft_bound(S64, n_fft):
     return 8.0 * np.log2(n_fft) * 2.0 ** -24 * np.linalg.norm(S64, axis=1, keepdims=True)
 
 
-@pytest.mark.parametrize("n_fft", [256, 512, 1024, 2048])
-def test_every_bin_through_one_hot_bases(lib, n_fft):
+def every_bin(lib, n_fft, window=None):
     hop = n_fft // 2 + 3
     x = noise(3 * n_fft, n_fft, amp=1.0)
-    S64 = mr.magnitudes(x, n_fft, hop)
+    S64 = mr.magnitudes(x, n_fft, hop, window=window)
     K = n_fft // 2 + 1
     worst = 0.0
     for k0 in range(0, K, 128):
         n = min(128, K - k0)
         basis = np.zeros((K, n), dtype=np.float32)
         basis[k0 + np.arange(n), np.arange(n)] = 1.0
-        got = mel_abi(lib, basis, [x], n_fft=n_fft, hop=hop, mode=0)
+        got = mel_abi(lib, basis, [x], n_fft=n_fft, hop=hop, mode=0, window=window)
         diff = np.abs(got - S64[:, k0:k0 + n]) / fft_bound(S64, n_fft)
         worst = max(worst, diff.max())
         assert diff.max() <= 1.0, (n_fft, k0, np.unravel_index(diff.argmax(), diff.shape))
     print(f"n_fft {n_fft}: the worst bin is at {worst:.3f} of the bound")
+
+
+@pytest.mark.parametrize("n_fft", [256, 512, 1024, 2048])
+def test_every_bin_through_one_hot_bases(lib, n_fft):
+    every_bin(lib, n_fft)
+
+
+@functools.lru_cache(maxsize=None)
+def asymmetric_window(n_fft):
+    """A window without any symmetry (float32, as the kernel holds it): window[n] taken for window[n_fft - 1 - n], or for a
+    neighbour's, changes every bin."""
+    w = np.random.default_rng(1000 + n_fft).uniform(0.1, 1.0, n_fft).astype(np.float32)
+    w.setflags(write=False)
+    return w
+
+
+@pytest.mark.parametrize("n_fft", [256, 512, 1024, 2048])
+def test_an_asymmetric_window(lib, n_fft):
+    w = asymmetric_window(n_fft)
+    assert np.abs(w - w[::-1]).max() > 0.5 and np.abs(w[1:] - w[:0:-1]).max() > 0.5
+    check(lib, f"window n_fft {n_fft}", slaney(n_fft, 40), [noise(3 * n_fft, 30 + n_fft)], n_fft, n_fft // 4 + 1, window=w)
+
+
+def test_every_bin_under_an_asymmetric_window(lib):
+    every_bin(lib, 1024, asymmetric_window(1024))
 
 
 @pytest.mark.parametrize("n_fft", [256, 512, 1024, 2048])
@@ -230,6 +260,59 @@ def test_clip_edges(lib):
     loud = [noise(2000, 7, amp=1e4)]
     assert refs(basis, loud, 512, 160)[0].min() > 2 * 10 ** (16 / 20)          # (every mel is over the ceiling)
     assert (mel_abi(lib, basis, loud, n_fft=512, hop=160, mode=1) == 1.0).all()
+
+
+DB_PARAMS = [(-80.0, 20.0), (-120.5, 0.0), (-40.0, -6.5)]
+
+
+def db_utts():
+    return [noise(1500, 40), noise(1200, 41, amp=1e-7)]       # the second: every mel below every min_level of DB_PARAMS
+
+
+@pytest.mark.parametrize("min_db,ref_db", DB_PARAMS)
+def test_other_db_parameters(lib, min_db, ref_db):
+    """Every term of the module docstring's 2^-21 scales with 100 / |min_db| (the final rounding, at most 2^-24, is within
+    it), so that is the bound here."""
+    n_fft, hop, basis, utts = 512, 160, slaney(512, 40), db_utts()
+    bound = DB_ABS * 100.0 / abs(min_db)
+    lin64, db64 = refs(basis, utts, n_fft, hop, min_db=min_db, ref_db=ref_db)
+    _, db32 = refs(basis, utts, n_fft, hop, dtype=np.float32, min_db=min_db, ref_db=ref_db)
+    quiet = np.arange(len(db64)) >= 1500 // hop + 1
+    # what the case is there for, on the reference: the quiet utterance on the floor, the other one between the clips,
+    # and far from what the default parameters would give
+    floor = mr.epilogue(np.zeros(1), min_db, ref_db)[0]
+    assert abs(floor - max(0.0, ref_db / min_db)) < 1e-12                  # (6.5 / 40 for the last, not 0)
+    assert lin64[quiet].max() < 10.0 ** (min_db / 20.0) and (db64[quiet] == floor).all()
+    assert ((db64[~quiet] > 0) & (db64[~quiet] < 1)).mean() > 0.9
+    assert np.median(np.abs(db64 - mr.epilogue(lin64))[~quiet]) > 0.05
+    lin = mel_abi(lib, basis, utts, n_fft=n_fft, hop=hop, mode=0)
+    db = mel_abi(lib, basis, utts, n_fft=n_fft, hop=hop, mode=1, min_db=min_db, ref_db=ref_db)
+    own = np.abs(db.astype(np.float64) - mr.epilogue(lin.astype(np.float64), min_db, ref_db)).max()
+    print(f"dB ({min_db}, {ref_db}): against the float64 epilogue of the kernel's own linear output {own:.3e}, "
+          f"{own / bound:.2f} of the bound {bound:.3e}")
+    assert own <= bound, (min_db, ref_db, own)
+    err, err_ref = mr.rel_err(db, db64), mr.rel_err(db32, db64)
+    print(f"dB ({min_db}, {ref_db}): end to end err {err:.3e}, err_ref {err_ref:.3e}, gate {mr.gate(err_ref, floor=bound):.3e}")
+    assert err <= mr.gate(err_ref, floor=bound), (min_db, ref_db, err, err_ref)
+    assert np.abs(db[quiet].astype(np.float64) - floor).max() <= bound and db.min() >= 0.0 and db.max() <= 1.0
+
+
+def test_db_parameters_through_python(GF, lib):
+    from speaker_embedding_ge2e_loss_amd.audio import MelFrontEnd
+    basis, utts = slaney(512, 40), db_utts()
+    lengths = [len(u) for u in utts]
+    wav = torch.as_tensor(np.concatenate(utts)).to(dev())
+    default = mel_abi(lib, basis, utts, n_fft=512, hop=160, mode=1)
+    for min_db, ref_db in DB_PARAMS:
+        want = mel_abi(lib, basis, utts, n_fft=512, hop=160, mode=1, min_db=min_db, ref_db=ref_db)
+        got, _ = GF.melspec(tables(basis, 512), wav, lengths, hop=160, min_level_db=min_db, ref_level_db=ref_db)
+        assert same_bits(got.cpu().numpy(), want) and not same_bits(want, default)
+        # a front end built with them: the bits of functional.melspec with them, on the front end's own tables
+        fe = MelFrontEnd(16000, 512, 160, 40, 90.0, 7600.0, 10, 20, 10.0, 0.75, min_level_db=min_db, ref_level_db=ref_db)
+        got, fs = fe.frames([wav[:lengths[0]], wav[lengths[0]:]])
+        want, fs2 = GF.melspec(fe.tables(dev()), wav, lengths, hop=160, min_level_db=min_db, ref_level_db=ref_db)
+        assert fs == fs2 and torch.equal(got, want)
+        assert not torch.equal(got, GF.melspec(fe.tables(dev()), wav, lengths, hop=160)[0])
 
 
 def frames_holding(n, n_fft, hop, bad):
