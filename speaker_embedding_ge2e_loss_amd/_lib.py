@@ -1,4 +1,9 @@
-"""ctypes binding of libge2e_hip.so (include/ge2e_hip.h).  Plumbing only.
+"""ctypes binding of libge2e_hip.so, derived from include/ge2e_hip.h.  Plumbing only.
+
+The header is the one description of the C ABI: the library is compiled against it, and this module reads it -- every
+`#define GE2E_<NAME> <int>` becomes a constant at import, every `ge2e_*` declaration a ctypes prototype at the first use of
+PROTOTYPES, bind() or load() (that parse costs more than importing ctypes does).  A new entry point is declared in the header
+and nowhere here.  The parser knows the types the header uses and refuses any other.
 
 The library is loaded lazily and there is NO fallback: if the shared object is
 missing or a symbol is absent, every product entry point raises.
@@ -6,137 +11,114 @@ missing or a symbol is absent, every product entry point raises.
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import os
+import re
 
-from .build import LIB_PATH
-
-ABI_VERSION = 2
-
-VARIANT_SOFTMAX, VARIANT_CONTRAST = 0, 1
-VARIANTS = {"softmax": VARIANT_SOFTMAX, "contrast": VARIANT_CONTRAST}
-IMPL_AUTO, IMPL_GENERIC, IMPL_FUSED_F32, IMPL_FUSED_SPLIT, IMPL_TILED, IMPL_TEAM, IMPL_WAVE, IMPL_AUTO_NO_TEAM = 0, 1, 2, 3, 4, 5, 6, 7
-IMPLS = {"auto": IMPL_AUTO, "generic": IMPL_GENERIC, "fused_f32": IMPL_FUSED_F32,
-         "fused_split": IMPL_FUSED_SPLIT, "tiled": IMPL_TILED, "team": IMPL_TEAM, "wave": IMPL_WAVE,
-         # AUTO without the eight-CU team kernel: for a GPU that other streams / processes keep busy (ge2e_hip.h)
-         "auto_no_team": IMPL_AUTO_NO_TEAM}
-IMPL_NAMES = {v: k for k, v in IMPLS.items()}
-
-_fp = C.c_void_p  # device pointers travel as integers
-
-# symbol -> (restype, argtypes); mirrors include/ge2e_hip.h one to one
-PROTOTYPES = {
-    "ge2e_abi_version": (C.c_int, []),
-    "ge2e_strerror": (C.c_char_p, [C.c_int]),
-    "ge2e_resolve_impl": (C.c_int, [C.c_int] * 6),
-    "ge2e_workspace_bytes": (C.c_size_t, [C.c_int] * 6),
-    "ge2e_workspace_init": (C.c_int, [_fp, C.c_size_t, _fp]),
-    "ge2e_loss_fwd_bwd": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, C.c_float,
-                                    C.c_float, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp, _fp,
-                                    C.c_size_t, _fp]),
-    "ge2e_workspace_bytes_f64": (C.c_size_t, [C.c_int] * 5),
-    "ge2e_loss_fwd_bwd_f64": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, C.c_double, C.c_double,
-                                        C.c_int, _fp, _fp, _fp, _fp, _fp, _fp, C.c_size_t, _fp]),
-    "ge2e_workspace_bytes_ragged": (C.c_size_t, [C.c_int] * 5),
-    "ge2e_loss_fwd_bwd_ragged": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, C.c_float, C.c_float,
-                                           C.c_int, _fp, _fp, _fp, _fp, _fp, _fp, C.c_size_t, _fp]),
-    "ge2e_label_index_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
-    "ge2e_label_index": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, C.c_size_t, _fp]),
-    "ge2e_workspace_bytes_labeled": (C.c_size_t, [C.c_int] * 5),
-    "ge2e_loss_fwd_bwd_labeled": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, C.c_float, C.c_float,
-                                            C.c_int, _fp, _fp, _fp, _fp, _fp, _fp, C.c_size_t, _fp]),
-    "ge2e_label_index_masked_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
-    "ge2e_label_index_masked": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp, C.c_size_t, _fp]),
-    "ge2e_workspace_bytes_labeled_masked": (C.c_size_t, [C.c_int] * 5),
-    "ge2e_loss_fwd_bwd_labeled_masked": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, C.c_float,
-                                                   C.c_float, C.c_int, _fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_size_t, _fp]),
-    "ge2e_workspace_bytes_labeled_wide": (C.c_size_t, [C.c_int] * 5),
-    "ge2e_loss_fwd_bwd_labeled_wide": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, C.c_float,
-                                                 C.c_float, C.c_int, _fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_size_t, _fp]),
-    "ge2e_cos_sim_labeled_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
-    "ge2e_cos_sim_labeled": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _fp, C.c_int,
-                                       _fp, _fp, _fp, _fp, _fp, _fp, C.c_size_t, _fp]),
-    "ge2e_eer_counts_labeled": (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_int, C.c_int, _fp, C.c_int, _fp, _fp]),
-    "ge2e_cos_sim_labeled_bwd_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
-    "ge2e_cos_sim_labeled_bwd": (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _fp, _fp,
-                                           _fp, C.c_size_t, _fp]),
-    "ge2e_calc_loss_labeled": (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _fp, _fp, _fp]),
-    "ge2e_calc_loss_labeled_bwd": (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _fp, _fp, _fp,
-                                             _fp]),
-    "ge2e_enroll_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
-    "ge2e_enroll_accumulate": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, C.c_size_t, _fp]),
-    "ge2e_enroll_finalize": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_float, _fp, _fp]),
-    "ge2e_verify_scores": (C.c_int, [_fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _fp, C.c_int,
-                                     _fp, _fp, _fp, _fp]),
-    "ge2e_selftest_verify_form": (C.c_int, [_fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _fp,
-                                            C.c_int, _fp, _fp, _fp, _fp, C.c_int]),
-    "ge2e_identify_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
-    "ge2e_identify": (C.c_int, [_fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _fp, _fp, _fp,
-                                _fp, _fp, C.c_size_t, _fp]),
-    "ge2e_selftest_identify_workspace_bytes": (C.c_size_t, [C.c_int] * 5),
-    "ge2e_selftest_identify_slices": (C.c_int, [_fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
-                                                _fp, _fp, _fp, _fp, _fp, C.c_size_t, _fp, C.c_int]),
-    "ge2e_cohort_stats_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
-    "ge2e_cohort_stats": (C.c_int, [_fp, _fp, C.c_int, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
-                                    C.c_float, _fp, _fp, C.c_size_t, _fp]),
-    "ge2e_verify_scores_normed": (C.c_int, [_fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _fp, _fp,
-                                            _fp, C.c_int, _fp, _fp, _fp, _fp]),
-    "ge2e_selftest_cohort_stats_workspace_bytes": (C.c_size_t, [C.c_int] * 5),
-    "ge2e_selftest_cohort_stats_chunk": (C.c_int, [_fp, _fp, C.c_int, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
-                                                   C.c_float, C.c_float, _fp, _fp, C.c_size_t, _fp, C.c_int]),
-    "ge2e_encoder_packed_bytes": (C.c_size_t, [C.c_int] * 4),
-    "ge2e_encoder_pack": (C.c_int, [_fp] + [C.c_int] * 4 + [_fp, _fp]),
-    "ge2e_encode": (C.c_int, [_fp, _fp, _fp] + [C.c_int] * 7 + [_fp, _fp]),
-    "ge2e_encode_plan": (C.c_int, [C.c_int] * 6 + [C.c_char_p, C.c_size_t]),
-    "ge2e_melspec_packed_bytes": (C.c_size_t, [C.c_int] * 2),
-    "ge2e_melspec_pack": (C.c_int, [_fp, _fp, C.c_int, C.c_int, _fp, _fp]),
-    "ge2e_melspec": (C.c_int, [_fp] * 7 + [C.c_int, C.c_longlong] + [C.c_int] * 4 + [C.c_float, C.c_float, _fp, _fp]),
-    "ge2e_melspec_plan": (C.c_int, [C.c_int, C.c_longlong] + [C.c_int] * 3 + [C.c_char_p, C.c_size_t]),
-    "ge2e_raw_supported": (C.c_int, [C.c_int] * 3),
-    "ge2e_loss_fwd_bwd_raw": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, C.c_float, C.c_float,
-                                        C.c_int, _fp, _fp, _fp, _fp, _fp, _fp]),
-    "ge2e_cos_sim": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _fp,
-                               _fp, C.c_size_t, _fp]),
-    "ge2e_cos_sim_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
-    "ge2e_cos_sim_centroids": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _fp, _fp]),
-    "ge2e_calc_loss": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _fp, _fp, _fp]),
-    "ge2e_loss_plan": (C.c_int, [C.c_int] * 8 + [C.c_char_p, C.c_size_t]),
-    "ge2e_cos_sim_plan": (C.c_int, [C.c_int] * 4 + [C.c_char_p, C.c_size_t]),
-    "ge2e_plan_atoms": (C.c_int, [C.c_char_p, C.c_size_t]),
-    "ge2e_selftest_split_gemm": (C.c_int, [_fp] * 7),
-    "ge2e_selftest_wave_ops": (C.c_int, [_fp] * 3),
-    "ge2e_selftest_rows16": (C.c_int, [_fp] * 6),
-    "ge2e_selftest_team_bytes": (C.c_size_t, [C.c_int]),
-    "ge2e_selftest_team": (C.c_int, [_fp, C.c_size_t, C.c_int, C.c_int, C.c_int, _fp, _fp]),
-    "ge2e_centroids": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp]),
-    "ge2e_utterance_centroids": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp]),
-    "ge2e_centroids_bwd": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp]),
-    "ge2e_cos_sim_bwd_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
-    "ge2e_cos_sim_bwd": (C.c_int, [_fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _fp, _fp,
-                                   _fp, C.c_size_t, _fp]),
-    "ge2e_calc_loss_bwd": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _fp, _fp, _fp, _fp]),
-    "ge2e_cos_sim_rows": (C.c_int, [_fp, _fp] + [C.c_int] * 6 + [C.c_float, C.c_float, _fp, _fp]),
-    "ge2e_cos_sim_rows_bwd_workspace_bytes": (C.c_size_t, [C.c_int] * 5),
-    "ge2e_cos_sim_rows_bwd": (C.c_int, [_fp, _fp, _fp, _fp] + [C.c_int] * 6 + [C.c_float, C.c_float, _fp, _fp, _fp, C.c_size_t, _fp]),
-    "ge2e_calc_loss_rows": (C.c_int, [_fp] + [C.c_int] * 5 + [C.c_float, C.c_int, _fp, _fp, _fp]),
-    "ge2e_calc_loss_rows_bwd": (C.c_int, [_fp] + [C.c_int] * 5 + [C.c_float, C.c_int, _fp, _fp, _fp, _fp]),
-    "ge2e_normalize_unperm": (C.c_int, [_fp, _fp, C.c_int, C.c_int, _fp, _fp, _fp]),
-    "ge2e_normalize_unperm_bwd": (C.c_int, [_fp, _fp, _fp, _fp, C.c_int, C.c_int, _fp, _fp]),
-    "ge2e_eer_counts": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, _fp, C.c_int, _fp, _fp]),
-    "ge2e_scale_grads": (C.c_int, [_fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp]),
-    "ge2e_sample_batch": (C.c_int, [_fp, C.c_int, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp]),
-    "ge2e_selftest_team_fallback": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, C.c_float, C.c_float,
-                                              C.c_int, _fp, _fp, _fp, _fp, _fp, _fp, C.c_size_t, _fp]),
-    "ge2e_selftest_team_abort_midgrid": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, C.c_float, C.c_float,
-                                                   C.c_int, _fp, _fp, _fp, _fp, _fp, _fp, C.c_size_t, _fp]),
-    "ge2e_selftest_team_grid": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, C.c_float, C.c_float,
-                                          C.c_int, _fp, _fp, _fp, _fp, _fp, _fp, C.c_size_t, _fp, C.c_int]),
-}
-
-_lib = None
+from .build import INCLUDE, LIB_PATH
 
 
 class GE2ELibraryError(RuntimeError):
     pass
+
+
+_SCALARS = {"int": C.c_int, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t, "long long": C.c_longlong}
+
+
+def _ctype(decl: str, symbol: str, what: str):
+    """A return type, or a parameter with its name, as the header writes it -> the ctypes class."""
+    base, star, _ = decl.partition("*")
+    words = base.split()
+    if words[:1] == ["const"]:
+        words = words[1:]
+    if star:                                   # device pointers travel as integers
+        return C.c_char_p if words == ["char"] else C.c_void_p
+    if what != "return type":
+        words = words[:-1]                     # the parameter's name
+    try:
+        return _SCALARS[" ".join(words)]
+    except KeyError:
+        raise ValueError(f"{symbol}: {what} `{' '.join(decl.split())}` is not of a type the binding knows") from None
+
+
+def _without_comments(text: str) -> str:
+    return re.sub(r"/\*[^*]*\*+(?:[^/*][^*]*\*+)*/|//[^\n]*", " ", text)      # /* ... */ without backtracking, // ...
+
+
+def parse_macros(text: str) -> dict:
+    """GE2E_NAME -> value of every `#define GE2E_NAME <int or (-int)>` of a header."""
+    return {name: int(value) for name, value in re.findall(r"#[ \t]*define[ \t]+(GE2E_\w+)[ \t]+\(?(-?\d+)\)?[ \t]*$",
+                                                           _without_comments(text), flags=re.M)}
+
+
+def parse_prototypes(text: str) -> dict:
+    """symbol -> (restype, [argtypes]) of every declaration `<ret> ge2e_name(<params>);` of a header."""
+    text = re.sub(r'#[^\n]*|extern\s+"C"\s*\{|\}', " ", _without_comments(text))     # preprocessor lines, the C++ wrapper
+    prototypes = {}
+    for statement in text.split(";"):
+        m = re.fullmatch(r"\s*([^()]+?)\s*\b(ge2e_\w+)\s*\(([^()]*)\)\s*", statement)
+        if m is None:
+            continue
+        ret, symbol, params = m.groups()
+        params = [] if params.strip() == "void" else params.split(",")
+        prototypes[symbol] = (_ctype(ret, symbol, "return type"),
+                              [_ctype(p, symbol, f"parameter {i + 1}") for i, p in enumerate(params)])
+    named = re.findall(r"(ge2e_\w+)\s*\(", text)
+    if len(named) != len(prototypes):
+        odd = sorted(n for n in set(named) if n not in prototypes or named.count(n) > 1)
+        raise ValueError(f"{len(named)} ge2e_* declarations, {len(prototypes)} parsed; not understood or declared twice: {odd}")
+    return prototypes
+
+
+def _header() -> str:
+    path = os.path.join(INCLUDE, "ge2e_hip.h")
+    try:
+        with open(path) as f:
+            return f.read()
+    except OSError as e:
+        raise GE2ELibraryError(f"{path} not readable: the ctypes binding is derived from it") from e
+
+
+MACROS = parse_macros(_header())
+
+
+def _family(prefix: str) -> dict:
+    return {name[len(prefix):].lower(): value for name, value in MACROS.items() if name.startswith(prefix)}
+
+
+ABI_VERSION = MACROS["GE2E_ABI_VERSION"]
+VARIANTS = _family("GE2E_VARIANT_")
+# "auto_no_team": AUTO without the eight-CU team kernel, for a GPU that other streams / processes keep busy (ge2e_hip.h)
+IMPLS = _family("GE2E_IMPL_")
+IMPL_NAMES = {v: k for k, v in IMPLS.items()}
+# VARIANT_SOFTMAX, VARIANT_CONTRAST, IMPL_AUTO ... IMPL_AUTO_NO_TEAM as module names
+globals().update({name[5:]: value for name, value in MACROS.items() if name.startswith(("GE2E_VARIANT_", "GE2E_IMPL_"))})
+
+
+@functools.lru_cache(maxsize=None)
+def _prototypes() -> dict:
+    return parse_prototypes(_header())
+
+
+def __getattr__(name: str):
+    if name == "PROTOTYPES":                   # made at its first use, once
+        return _prototypes()
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
+_lib = None
+
+
+def bind(lib):
+    """Set restype and argtypes of every prototype on a ctypes.CDLL (the product library or a variant build of it)."""
+    for name, (res, args) in _prototypes().items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError as e:
+            raise GE2ELibraryError(f"{lib._name} does not export {name}") from e
+        fn.restype = res
+        fn.argtypes = args
+    return lib
 
 
 def load(path: str | None = None):
@@ -149,14 +131,7 @@ def load(path: str | None = None):
         raise GE2ELibraryError(
             f"{path} not found: the HIP extension is not built. Run "
             "`python -m speaker_embedding_ge2e_loss_amd.build` (needs hipcc); there is no CPU fallback.")
-    lib = C.CDLL(path)
-    for name, (res, args) in PROTOTYPES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as e:
-            raise GE2ELibraryError(f"{path} does not export {name}") from e
-        fn.restype = res
-        fn.argtypes = args
+    lib = bind(C.CDLL(path))
     if lib.ge2e_abi_version() != ABI_VERSION:
         raise GE2ELibraryError(f"ABI mismatch: library {lib.ge2e_abi_version()} != binding {ABI_VERSION}")
     _lib = lib

@@ -940,7 +940,7 @@ def _verify(embeddings, models, cnt, stats, labels, thresholds, need_scores, eps
 
 # ---- identification: the best k enrolled speakers of every trial row (csrc/ge2e_identify.hip) -----------------------------
 
-IDENTIFY_MAX_TOP = 32    # GE2E_IDENTIFY_MAX_TOP
+IDENTIFY_MAX_TOP = _lib.MACROS["GE2E_IDENTIFY_MAX_TOP"]
 
 
 @dataclass
@@ -983,7 +983,7 @@ def identify(embeddings: torch.Tensor, models: torch.Tensor, cnt: torch.Tensor, 
 
 # ---- score normalisation against a cohort, AS-norm (csrc/ge2e_snorm.hip) ---------------------------------------------------
 
-COHORT_MAX = 65536       # GE2E_COHORT_MAX
+COHORT_MAX = _lib.MACROS["GE2E_COHORT_MAX"]
 EPS_STD = 1e-5
 
 

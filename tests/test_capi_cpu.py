@@ -2,11 +2,12 @@
 rejects bad arguments before touching the GPU.  No compute is launched here."""
 import ctypes
 import os
+import re
 
 import pytest
 
 from capi import built_lib as lib  # noqa: F401
-from capi import header_symbols
+from capi import header_symbols, header_text
 from speaker_embedding_ge2e_loss_amd import _lib, build
 
 
@@ -18,6 +19,100 @@ def test_library_exports_every_declared_symbol(lib):
     for s in syms:
         assert hasattr(raw, s), f"{s} declared in include/ge2e_hip.h but not exported"
     assert set(syms) == set(_lib.PROTOTYPES), "ctypes binding and header disagree"
+
+
+# ---- the binding is derived from the header (_lib.parse_prototypes, _lib.parse_macros); where these tests read the header
+# itself, they do it with regexes of their own ----
+
+_TYPES_HEADER = """
+#ifdef __cplusplus
+extern "C" {
+#endif
+#define GE2E_SOME_LIMIT 48   /* a comment
+                                over two lines */
+#define GE2E_ERR_SOME (-7)
+/* ge2e_in_a_comment(int x); */
+const char* ge2e_a(void);   // ge2e_in_a_line_comment(int x);
+size_t ge2e_b(long long n, double x, char* buf, size_t k, const long long* p /* [U] or NULL */,
+              unsigned* out, float f, const char* name, void* stream);
+#ifdef __cplusplus
+}
+#endif
+"""
+
+
+def test_parser_maps_the_types_the_header_uses():
+    c = ctypes
+    assert _lib.parse_prototypes(_TYPES_HEADER) == {
+        "ge2e_a": (c.c_char_p, []),
+        "ge2e_b": (c.c_size_t, [c.c_longlong, c.c_double, c.c_char_p, c.c_size_t, c.c_void_p, c.c_void_p, c.c_float, c.c_char_p,
+                                c.c_void_p])}
+    assert _lib.parse_macros(_TYPES_HEADER) == {"GE2E_SOME_LIMIT": 48, "GE2E_ERR_SOME": -7}
+
+
+@pytest.mark.parametrize("decl", ["int ge2e_bad(short x);", "int ge2e_bad(int B, unsigned long n);", "int ge2e_bad(struct S s);",
+                                  "short ge2e_bad(int B);", "int ge2e_bad(int);",
+                                  "int ge2e_bad(int B, void (*done)(int));",          # no declaration the pattern matches
+                                  "int ge2e_a(int B);"])                              # declared twice
+def test_parser_refuses_what_it_does_not_know(decl):
+    """Never a default: an unknown scalar type, and a declaration the pattern cannot take, raise and name the symbol."""
+    with pytest.raises(ValueError, match=decl.split("(")[0].split()[-1]):
+        _lib.parse_prototypes(_TYPES_HEADER + decl)
+
+
+def test_missing_header_fails_loudly(tmp_path, monkeypatch):
+    monkeypatch.setattr(_lib, "INCLUDE", str(tmp_path))
+    with pytest.raises(_lib.GE2ELibraryError, match=os.path.join(str(tmp_path), "ge2e_hip.h")):
+        _lib._header()
+
+
+def test_constants_are_the_headers_macros(lib):
+    from speaker_embedding_ge2e_loss_amd import functional
+    macros = {name: int(value) for name, value in re.findall(r"#define\s+(GE2E_[A-Z0-9_]+)\s+\(?(-?\d+)\)?", header_text())}
+
+    def family(prefix):
+        return {name[len(prefix):].lower(): value for name, value in macros.items() if name.startswith(prefix)}
+    assert len(family("GE2E_IMPL_")) >= 8 and _lib.IMPLS == family("GE2E_IMPL_")
+    assert len(family("GE2E_VARIANT_")) >= 2 and _lib.VARIANTS == family("GE2E_VARIANT_")
+    assert _lib.IMPL_NAMES == {value: name for name, value in _lib.IMPLS.items()}
+    assert (_lib.IMPL_AUTO, _lib.IMPL_AUTO_NO_TEAM, _lib.VARIANT_CONTRAST) == \
+        (macros["GE2E_IMPL_AUTO"], macros["GE2E_IMPL_AUTO_NO_TEAM"], macros["GE2E_VARIANT_CONTRAST"])
+    assert _lib.ABI_VERSION == macros["GE2E_ABI_VERSION"] == lib.ge2e_abi_version()
+    assert functional.IDENTIFY_MAX_TOP == macros["GE2E_IDENTIFY_MAX_TOP"] == 32
+    assert functional.COHORT_MAX == macros["GE2E_COHORT_MAX"] == 65536
+    assert _lib.MACROS == macros
+    errors = family("GE2E_ERR_")
+    assert len(errors) >= 6 and all(value < 0 for value in errors.values())
+    for value in errors.values():
+        assert len(lib.ge2e_strerror(value)) > 3
+
+
+def test_wide_parameters_bind_wide():
+    """A `long long` bound as c_int, or a size_t as c_int, passes every call with small values and corrupts the arguments of
+    a large one: every by-value parameter (and return value) of those types in the header binds at full width."""
+    wide = {"long long": ctypes.c_longlong, "size_t": ctypes.c_size_t}
+    seen = {ctype: 0 for ctype in wide.values()}
+    for ret, symbol, params in re.findall(r"([\w \t*]+?)\b(ge2e_\w+)\s*\(([^()]*)\)\s*;", header_text()):
+        restype, argtypes = _lib.PROTOTYPES[symbol]
+        if ret.strip() in wide:
+            assert restype is wide[ret.strip()], symbol
+            seen[restype] += 1
+        for i, param in enumerate(params.split(",")):
+            m = re.fullmatch(r"\s*(long long|size_t)\s+\w+\s*", param)
+            if m:
+                assert argtypes[i] is wide[m.group(1)], (symbol, param)
+                seen[argtypes[i]] += 1
+    assert seen[ctypes.c_longlong] >= 2 and seen[ctypes.c_size_t] >= 40, seen      # total_frames twice; every workspace
+
+
+def test_bind_types_every_prototype_of_a_library(lib):
+    raw = _lib.bind(ctypes.CDLL(build.LIB_PATH))
+    assert len(_lib.PROTOTYPES) >= 82
+    for name, (restype, argtypes) in _lib.PROTOTYPES.items():
+        fn = getattr(raw, name)
+        assert fn.restype is restype and list(fn.argtypes) == argtypes, name
+    with pytest.raises(_lib.GE2ELibraryError, match="does not export ge2e_"):
+        _lib.bind(ctypes.CDLL(None))          # the interpreter itself: no ge2e_* symbol
 
 
 def test_abi_version_and_errors(lib):

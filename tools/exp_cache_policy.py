@@ -19,10 +19,7 @@ def run(defs, B=4096, iters=8):
     cmd = [build._hipcc(), "-O3", "-std=c++17", f"--offload-arch={build.ARCH}", "-fPIC", "-shared",
            f"-I{build.INCLUDE}", "-o", lib_path] + [f"-D{k}={v}" for k, v in defs.items()] + build.sources()
     subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL)
-    lib = C.CDLL(lib_path)
-    for name, (res, argt) in _lib.PROTOTYPES.items():
-        getattr(lib, name).restype = res
-        getattr(lib, name).argtypes = argt
+    lib = _lib.bind(C.CDLL(lib_path))
     cfg = bench.CONFIGS["cfg2"]
     N, M, D = cfg["N"], cfg["M"], cfg["D"]
     dev = torch.device("cuda:0")

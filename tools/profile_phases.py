@@ -61,10 +61,7 @@ def main():
     lib_path = os.path.join(build.PKG_DIR, args.lib)
     if not (args.no_build and os.path.exists(lib_path)):
         build.build_variant(lib_path, ["-DGE2E_PROFILE"] + os.environ.get("GE2E_EXTRA_DEFS", "").split())
-    lib = C.CDLL(lib_path)
-    for name, (res, argt) in _lib.PROTOTYPES.items():
-        getattr(lib, name).restype = res
-        getattr(lib, name).argtypes = argt
+    lib = _lib.bind(C.CDLL(lib_path))
     lib.ge2e_debug_set_prof.argtypes = [C.c_void_p]
     lib.ge2e_debug_set_prof.restype = None
 
