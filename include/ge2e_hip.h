@@ -642,6 +642,59 @@ int ge2e_encode(const float* packed, const float* mel, const long long* row_star
 int ge2e_encode_plan(int R, int T, int n_mels, int H, int L, int D, char* buf, size_t buf_bytes);
 
 /*
+ * ENCODER TRAINING (csrc/ge2e_encoder_train.hip; the forward is csrc/ge2e_encoder.hip's kernel in a second instantiation):
+ * the same encoder with gradients -- a forward that keeps what the backward needs, and the backward through time, the
+ * projection's and the norm's backward in hand-written HIP, float32, exact fp32 on the matrix core.  Shapes as
+ * ge2e_encode: H = 128 or 256, 1 <= L <= 4, 1 <= n_mels <= 256, 1 <= D <= 256, any T >= 1 and R >= 1, dense rows or
+ * row_start; everything else is GE2E_ERR_IMPL and nothing is launched.  No gradient with respect to the mels.
+ *
+ * ge2e_encode_train: ge2e_encode's arguments plus `tape` (ge2e_encode_train_tape_bytes, 16-byte aligned, the caller's).
+ * `out` has the bits ge2e_encode writes for the same inputs.  The tape holds EVERYTHING the backward reads, nothing is
+ * recomputed but tanh(c): per layer six planes [T][R][H] -- the gate activations i, f, g, o, the cell c, the hidden state h
+ * -- then the raw projection [R][D]: 4 (6 L T R H + R D) bytes, i.e. 6 L H T 4 bytes a window: 2.9 MB a window for
+ * 3 x 256 at T = 160, 24 GB at R = 8192.  Its layout is private to the two kernels.  Rows past R in the last tile write
+ * nothing.  One launch of ceil(R / 32) workgroups, as ge2e_encode.
+ *
+ * ge2e_encoder_pack_bwd, once per set of weights: flat_params (ge2e_encoder_pack's) -> packed_bwd
+ * (ge2e_encoder_packed_bwd_bytes, 16-byte aligned; every byte is written): per layer [4H][I_l + H] -- layer 0: [4H][H],
+ * weight_hh alone -- in the fragment order of d[input | h_prev] = dz W, then the projection [pad16(D)][H], zero past D.
+ *
+ * ge2e_encode_bwd: d_out [R][D], the gradient with respect to ge2e_encode_train's `out` (of y / |y| for normalize != 0:
+ * dy = (g - e (e.g)) / |y|, no epsilon; of y itself otherwise) -> d_flat_params, the gradient of every parameter in ONE flat
+ * buffer in flat_params' own layout (bias_ih and bias_hh of a layer get the same values).  Written, not accumulated; every
+ * element exactly once; nothing outside it is touched.  mel, row_start, the shape and normalize are those of the forward
+ * call that filled `tape`.  workspace (ge2e_encode_bwd_workspace_bytes, 16-byte aligned): dZ [L][T][R][4H] in torch's gate
+ * order -- the pre-activation gradients, at offset 0 --, dy [R][D], and the K-slice partials of the weight gradients; it
+ * needs no initialisation and every byte the call reads it has written itself.
+ * Launches: the recurrence, ceil(R / 16) workgroups of 512 threads (a workgroup owns 16 rows for all frames and layers,
+ * frames downwards, dc in registers, dh and dz in LDS: 4 (16 L H + 16 (4H + 4)) bytes, 128.25 KiB at H = 256, L = 4); L + 1
+ * weight-gradient GEMMs over K = R T (the projection's: K = R), each a grid of 64 x 64 output blocks times K-slices; one
+ * reduction that sums the slices in ascending order.  The slices of K pairs are min(ceil(K / 512), 32) equal parts rounded
+ * up to a multiple of 4: grids and slice counts come from the shape alone, there are no atomics, and two calls on the same
+ * inputs give the same bits.  No allocation, no synchronisation, everything on `stream`: fit for a HIP graph.
+ * A row whose d_out is zero contributes exact zeros to every dz.
+ * Checks of all of these, in this order: GE2E_ERR_NULL (any pointer but row_start and stream), GE2E_ERR_SHAPE (R, T,
+ * n_mels, D or L < 1; the pack: n_mels, D or L < 1), GE2E_ERR_IMPL, GE2E_ERR_ALIGN (any buffer not 16-byte aligned;
+ * flat_params is read four bytes at a time and may lie anywhere).  The size queries return 0 where the call would refuse.
+ *
+ * ge2e_encode_train_plan / ge2e_encode_bwd_plan (diagnostics, no GPU): "encode_train<H>/tiles" and
+ * "encode_bwd<H>/tiles,encode_wgrad/NxMxS" (L + 1 times: column blocks x row blocks x slices) ",encode_reduce/blocks",
+ * snprintf-style as ge2e_encode_plan.  (These names are no part of ge2e_plan_atoms.)
+ */
+size_t ge2e_encoder_packed_bwd_bytes(int n_mels, int H, int L, int D);   /* 0 for an unsupported shape */
+int ge2e_encoder_pack_bwd(const float* flat_params, int n_mels, int H, int L, int D, float* packed_bwd, void* stream);
+size_t ge2e_encode_train_tape_bytes(int R, int T, int n_mels, int H, int L, int D);
+int ge2e_encode_train(const float* packed, const float* mel, const long long* row_start /* [R] or NULL */,
+                      int R, int T, int n_mels, int H, int L, int D, int normalize,
+                      float* out /* [R][D] */, float* tape, void* stream);
+size_t ge2e_encode_bwd_workspace_bytes(int R, int T, int n_mels, int H, int L, int D);
+int ge2e_encode_bwd(const float* packed_bwd, const float* mel, const long long* row_start /* [R] or NULL */,
+                    int R, int T, int n_mels, int H, int L, int D, int normalize, const float* tape,
+                    const float* d_out /* [R][D] */, float* d_flat_params, void* workspace, void* stream);
+int ge2e_encode_train_plan(int R, int T, int n_mels, int H, int L, int D, char* buf, size_t buf_bytes);
+int ge2e_encode_bwd_plan(int R, int T, int n_mels, int H, int L, int D, char* buf, size_t buf_bytes);
+
+/*
  * MEL FRONT END (csrc/ge2e_melspec.hip): waveforms to the frames ge2e_encode reads -- reflect pad, overlapping frames, a
  * window, |rfft|, a mel basis, 20 log10 and a clip (s0:29-66 with pySTFT, s0:201-219) -- in ONE launch.  float32, the mel
  * product exact fp32 on the matrix core (v_mfma_f32_16x16x4_f32).  Supported: n_fft 256, 512, 1024 or 2048, 1 <= n_mels <=

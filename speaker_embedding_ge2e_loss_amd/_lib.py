@@ -179,6 +179,17 @@ def encode_plan(R: int, T: int, n_mels: int, H: int, L: int, D: int) -> list[str
     return _plan(load().ge2e_encode_plan, R, T, n_mels, H, L, D)
 
 
+def encode_train_plan(R: int, T: int, n_mels: int, H: int, L: int, D: int) -> list[str]:
+    """... ge2e_encode_train would launch: ["encode_train<H>/tiles"]."""
+    return _plan(load().ge2e_encode_train_plan, R, T, n_mels, H, L, D)
+
+
+def encode_bwd_plan(R: int, T: int, n_mels: int, H: int, L: int, D: int) -> list[str]:
+    """... ge2e_encode_bwd would launch: the recurrence "encode_bwd<H>/tiles", L + 1 "encode_wgrad/NxMxS" (column blocks x
+    row blocks x K-slices; the last is the projection's) and "encode_reduce/blocks"."""
+    return _plan(load().ge2e_encode_bwd_plan, R, T, n_mels, H, L, D)
+
+
 def melspec_plan(U: int, total_frames: int, n_fft: int, hop: int, n_mels: int) -> list[str]:
     """... ge2e_melspec would launch: ["melspec<n_fft>/tiles"]."""
     return _plan(load().ge2e_melspec_plan, U, total_frames, n_fft, hop, n_mels)

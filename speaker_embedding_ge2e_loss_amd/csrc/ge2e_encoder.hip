@@ -20,7 +20,10 @@
 //             sum of squares in a fixed order, y / sqrt(ss) (no epsilon, s2:34: a zero row gives NaN) or y itself, stored.
 // Every K chain has a fixed order and MFMA rows are independent: the bits of an output row depend on that row's frames and
 // the weights alone.  Pad rows of the last tile compute on zeros and are never stored.
+//   training  ge2e_encode_train is the SAME kernel in its kTape instantiation: the cell update also stores the gates, c and h,
+//             the epilogue the raw projection, into the caller's tape (ge2e_encoder_train.hpp) for ge2e_encode_bwd.
 #include "ge2e_encoder.hpp"
+#include "ge2e_encoder_train.hpp"
 
 #include <math.h>
 #include <stdio.h>
@@ -87,7 +90,9 @@ __global__ __launch_bounds__(256) void encoder_pack_kernel(const float* __restri
 
 __device__ __forceinline__ float enc_sigmoid(float z) { return 1.0f / (1.0f + expf(-z)); }   // finite at z = +-100 and beyond
 
-template <int H>
+// kTape: the training forward.  The same kernel, and what the backward reads goes to p.tape on the way (layout:
+// ge2e_encoder_train.hpp): the gate activations, c and h of every layer, frame and row, and the raw projection.
+template <int H, bool kTape>
 __global__ __launch_bounds__(kEncThreads) void encode_kernel(ProblemEncode p) {
     extern __shared__ __attribute__((aligned(16))) float enc_lds[];
     constexpr int UB = H / 128, NT = 4 * UB, CT = H / 4, GH = H / 16;
@@ -197,6 +202,20 @@ __global__ __launch_bounds__(kEncThreads) void encode_kernel(ProblemEncode p) {
                             const float cn = fg * c[l][ub][rt][v] + ig * gg;
                             c[l][ub][rt][v] = cn;
                             hnew[ub][rt][v] = og * tanhf(cn);
+                            if constexpr (kTape) {
+                                const long long r = (long long)blockIdx.x * kEncTile + rt * 16 + 4 * q + v;
+                                if (r < R) {   // pad rows write nothing
+                                    const size_t plane = (size_t)T * R * H;
+                                    float* tp = p.tape + (size_t)l * kEncTapePlanes * plane +
+                                                ((size_t)t * R + (size_t)r) * H + (wid * UB + ub) * 16 + l15;
+                                    tp[0] = ig;
+                                    tp[plane] = fg;
+                                    tp[2 * plane] = gg;
+                                    tp[3 * plane] = og;
+                                    tp[4 * plane] = cn;
+                                    tp[5 * plane] = hnew[ub][rt][v];
+                                }
+                            }
                         }
                 __syncthreads();   // every wave has read the layer's old h
                 float* hw = hs + (size_t)l * kEncTile * H;
@@ -258,10 +277,26 @@ __global__ __launch_bounds__(kEncThreads) void encode_kernel(ProblemEncode p) {
         const float n = sqrtf(ss);
         float* o = p.out + (size_t)r * D;
         for (int d = lane; d < D; d += kWave) o[d] = p.normalize ? yr[d] / n : yr[d];
+        if constexpr (kTape) {
+            float* ty = p.tape + (size_t)kEncTapePlanes * L * T * (size_t)R * H + (size_t)r * D;
+            for (int d = lane; d < D; d += kWave) ty[d] = yr[d];
+        }
     }
 }
 
-KernelLaunchState g_encode_state[2];
+KernelLaunchState g_encode_state[2][2];
+
+template <bool kTape>
+hipError_t launch_encode_as(const ProblemEncode& p, int H, hipStream_t stream) {
+    const unsigned lds = (unsigned)encoder_lds_bytes(H, p.L, p.D);
+    const unsigned tiles = (unsigned)(((long long)p.R + kEncTile - 1) / kEncTile);
+    const void* fn = H == 256 ? (const void*)encode_kernel<256, kTape> : (const void*)encode_kernel<128, kTape>;
+    const hipError_t err = prepare_kernel(g_encode_state[kTape][H == 256], fn, kEncThreads, lds, nullptr);
+    if (err != hipSuccess) return err;
+    if (H == 256) hipLaunchKernelGGL((encode_kernel<256, kTape>), dim3(tiles), dim3(kEncThreads), lds, stream, p);
+    else hipLaunchKernelGGL((encode_kernel<128, kTape>), dim3(tiles), dim3(kEncThreads), lds, stream, p);
+    return hipGetLastError();
+}
 }  // namespace
 
 hipError_t launch_encoder_pack(const float* flat, int n_mels, int H, int L, int D, float* packed, hipStream_t stream) {
@@ -271,19 +306,15 @@ hipError_t launch_encoder_pack(const float* flat, int n_mels, int H, int L, int 
     return hipGetLastError();
 }
 
-hipError_t launch_encode(const ProblemEncode& p, int H, hipStream_t stream) {
-    const unsigned lds = (unsigned)encoder_lds_bytes(H, p.L, p.D);
-    const unsigned tiles = (unsigned)(((long long)p.R + kEncTile - 1) / kEncTile);
-    const void* fn = H == 256 ? (const void*)encode_kernel<256> : (const void*)encode_kernel<128>;
-    const hipError_t err = prepare_kernel(g_encode_state[H == 256], fn, kEncThreads, lds, nullptr);
-    if (err != hipSuccess) return err;
-    if (H == 256) hipLaunchKernelGGL(encode_kernel<256>, dim3(tiles), dim3(kEncThreads), lds, stream, p);
-    else hipLaunchKernelGGL(encode_kernel<128>, dim3(tiles), dim3(kEncThreads), lds, stream, p);
-    return hipGetLastError();
-}
+hipError_t launch_encode(const ProblemEncode& p, int H, hipStream_t stream) { return launch_encode_as<false>(p, H, stream); }
+hipError_t launch_encode_train(const ProblemEncode& p, int H, hipStream_t stream) { return launch_encode_as<true>(p, H, stream); }
 
 int plan_string_encode(int R, int H, char* buf, size_t cap) {
     return snprintf(buf, cap, "encode<%d>/%d", H, (int)(((long long)R + kEncTile - 1) / kEncTile));
+}
+
+int plan_string_encode_train(int R, int H, char* buf, size_t cap) {
+    return snprintf(buf, cap, "encode_train<%d>/%d", H, (int)(((long long)R + kEncTile - 1) / kEncTile));
 }
 
 }  // namespace ge2e

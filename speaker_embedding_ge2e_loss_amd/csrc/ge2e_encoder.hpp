@@ -37,6 +37,7 @@ struct ProblemEncode {
     const long long* row_start;   // [R] first frame of every row, or null: row r starts at frame r T
     float* out;                   // [R][D]
     int R, T, n_mels, L, D, normalize;
+    float* tape;                  // the training forward's tape (ge2e_encoder_train.hpp), or null: inference
 };
 
 hipError_t launch_encoder_pack(const float* flat, int n_mels, int H, int L, int D, float* packed, hipStream_t stream);

@@ -6,10 +6,13 @@ names (``LSTM_stack``, ``projection``) and the initialisation (xavier-normal wei
 for the LSTM, s2:18-22; the Linear keeps torch's default) follow the reference so a reference
 ``state_dict`` loads here and the other way round (s4:130 saves exactly this module's).
 
-In TRAINING the recurrent and projection GEMMs are library work (MIOpen / hipBLASLt through torch) and are NOT
-part of the hand-written path; what is ours there is the tail: with ``normalize=False`` the module hands
-back the raw projection and the trainer runs the fused L2-normalise + un-permute gather
-(``functional.normalize_unperm``) in one HIP kernel instead of three torch ops.
+In TRAINING the recurrent and projection GEMMs are by default library work (MIOpen / hipBLASLt through torch); what is
+ours there is the tail: with ``normalize=False`` the module hands back the raw projection and the trainer runs the fused
+L2-normalise + un-permute gather (``functional.normalize_unperm``) in one HIP kernel instead of three torch
+ops.  With ``native_train=True`` the whole encoder is hand-written both ways: ``raw`` / ``forward`` go through
+``functional.encode_train`` (csrc/ge2e_encoder_train.hip) -- a forward that keeps a tape, and the LSTM backward through
+time, the projection's and the norm's backward in HIP -- and ``loss.backward()`` fills the ``.grad``s without the library.
+It is opt-in: no speed is promised below a few thousand windows, and the tape costs 6 L H T 4 bytes a window.
 For INFERENCE ``embed`` / ``embed_utterances`` run the whole forward pass -- LSTM stack, projection, norm -- as one
 hand-written HIP launch (``functional.encode``, csrc/ge2e_encoder.hip); ``forward`` and ``raw`` stay torch's.
 """
@@ -27,8 +30,9 @@ NATIVE_MIN_ROWS = 4800
 
 class SpeakerEncoder(nn.Module):
     def __init__(self, n_mels: int = 80, hidden: int = 256, layers: int = 3, embedding: int = 256,
-                 normalize: bool = True):
+                 normalize: bool = True, *, native_train: bool = False):
         super().__init__()
+        self.native_train = native_train
         self.LSTM_stack = nn.LSTM(n_mels, hidden, num_layers=layers, batch_first=True)  # s2:13-16
         for name, param in self.LSTM_stack.named_parameters():  # s2:18-22
             if "bias" in name:
@@ -45,11 +49,24 @@ class SpeakerEncoder(nn.Module):
         return cls(hp.audio.mel_n_channels, hp.m_ge2e.model_hidden_size, hp.m_ge2e.model_num_layers,
                    hp.m_ge2e.model_embedding_size, normalize=normalize).to(hp.general.device)
 
+    def _native_train_route(self, x) -> bool:
+        """native_train is set, gradients are wanted, the module has a kernel and the input is on a GPU."""
+        return self.native_train and torch.is_grad_enabled() and x.is_cuda and self.native_supported()
+
+    def _encode_train(self, x, normalize: bool):
+        from . import functional as GF
+        n_mels, H, L, D = self._shape()
+        return GF.encode_train(self._parameters_in_pack_order(), x, hidden=H, layers=L, dim=D, normalize=normalize)
+
     def raw(self, x):
+        if self._native_train_route(x):
+            return self._encode_train(x, False)
         x, _ = self.LSTM_stack(x.float())       # s2:28
         return self.projection(x[:, x.size(1) - 1].float())  # s2:30-31
 
     def forward(self, x):
+        if self.normalize and self._native_train_route(x):
+            return self._encode_train(x, True)   # the kernel does the norm, and its backward
         y = self.raw(x)
         if not self.normalize:
             return y

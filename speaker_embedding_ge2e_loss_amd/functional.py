@@ -1386,13 +1386,8 @@ def encoder_pack(flat_params: torch.Tensor, n_mels: int, hidden: int, layers: in
     return packed
 
 
-def encode(packed: torch.Tensor, mel: torch.Tensor, *, T: Optional[int] = None, row_start: Optional[torch.Tensor] = None,
-           hidden: int, layers: int, dim: int, normalize: bool = True, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """ge2e_encode: mel windows to d-vectors (R, dim) float32 in one launch on the current stream, no workspace.
-    ``mel``: (R, T, n_mels); or flat (frames, n_mels) with ``row_start`` (R,) int64 on the device -- the first frame of
-    every window, windows may overlap -- and ``T``, the window length.  float64 mels are cast to float32 (s2:28).
-    ``normalize=False`` returns the raw projection (``SpeakerEncoder.raw``'s contract).  ``out``: a contiguous (R, dim)
-    float32 tensor to write into (static buffers of a captured graph)."""
+def _encoder_rows(mel: torch.Tensor, T: Optional[int], row_start: Optional[torch.Tensor]):
+    """The mel argument of ``encode`` / ``encode_train`` -> (contiguous float32 mels, row_start or None, R, T, n_mels)."""
     _require_cuda(mel, "mel")
     dev = mel.device
     m = mel.detach()
@@ -1404,16 +1399,24 @@ def encode(packed: torch.Tensor, mel: torch.Tensor, *, T: Optional[int] = None, 
     if row_start is None:
         if m.dim() != 3 or m.shape[0] < 1 or m.shape[1] < 1 or (T is not None and T != m.shape[1]):
             raise ValueError(f"mel must be (R, T, n_mels) with R, T >= 1 (or flat with row_start and T), got {tuple(m.shape)}")
-        R, T, n_mels = m.shape
-        rs_ptr = None
-    else:
-        if m.dim() != 2 or T is None or T < 1 or m.shape[0] < T:
-            raise ValueError("with row_start, mel must be flat (frames, n_mels) with frames >= T, and T given")
-        if row_start.dtype != torch.int64 or row_start.dim() != 1 or row_start.device != dev or row_start.numel() < 1:
-            raise TypeError(f"row_start must be a (R,) torch.int64 tensor on {dev}")
-        row_start = row_start.contiguous()
-        R, n_mels = row_start.numel(), m.shape[1]
-        rs_ptr = row_start.data_ptr()
+        return m, None, m.shape[0], m.shape[1], m.shape[2]
+    if m.dim() != 2 or T is None or T < 1 or m.shape[0] < T:
+        raise ValueError("with row_start, mel must be flat (frames, n_mels) with frames >= T, and T given")
+    if row_start.dtype != torch.int64 or row_start.dim() != 1 or row_start.device != dev or row_start.numel() < 1:
+        raise TypeError(f"row_start must be a (R,) torch.int64 tensor on {dev}")
+    return m, row_start.contiguous(), row_start.numel(), int(T), m.shape[1]
+
+
+def encode(packed: torch.Tensor, mel: torch.Tensor, *, T: Optional[int] = None, row_start: Optional[torch.Tensor] = None,
+           hidden: int, layers: int, dim: int, normalize: bool = True, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ge2e_encode: mel windows to d-vectors (R, dim) float32 in one launch on the current stream, no workspace.
+    ``mel``: (R, T, n_mels); or flat (frames, n_mels) with ``row_start`` (R,) int64 on the device -- the first frame of
+    every window, windows may overlap -- and ``T``, the window length.  float64 mels are cast to float32 (s2:28).
+    ``normalize=False`` returns the raw projection (``SpeakerEncoder.raw``'s contract).  ``out``: a contiguous (R, dim)
+    float32 tensor to write into (static buffers of a captured graph)."""
+    m, row_start, R, T, n_mels = _encoder_rows(mel, T, row_start)
+    dev = m.device
+    rs_ptr = None if row_start is None else row_start.data_ptr()
     if packed.device != dev or packed.dtype != torch.float32 or not packed.is_contiguous() or \
             packed.numel() * 4 != _lib.load().ge2e_encoder_packed_bytes(n_mels, int(hidden), int(layers), int(dim)):
         raise ValueError(f"packed is not encoder_pack's buffer for (n_mels {n_mels}, hidden {hidden}, layers {layers}, "
@@ -1425,6 +1428,84 @@ def encode(packed: torch.Tensor, mel: torch.Tensor, *, T: Optional[int] = None, 
     _launch("ge2e_encode", dev, packed.data_ptr(), m.data_ptr(), rs_ptr, R, int(T), n_mels, int(hidden), int(layers), int(dim),
             int(bool(normalize)), out.data_ptr(), _stream_ptr(m))
     return out
+
+
+def encode_train_tape_bytes(R: int, T: int, n_mels: int, hidden: int, layers: int, dim: int) -> int:
+    """Bytes of the tape ``encode_train`` keeps between its forward and its backward: 4 (6 layers T R hidden + R dim) --
+    2.9 MB a window for 80 -> 3 x 256 -> 256 at T = 160.  0 for a shape without a kernel."""
+    return _lib.load().ge2e_encode_train_tape_bytes(int(R), int(T), int(n_mels), int(hidden), int(layers), int(dim))
+
+
+def encode_bwd_workspace_bytes(R: int, T: int, n_mels: int, hidden: int, layers: int, dim: int) -> int:
+    """Bytes of the workspace ``encode_train``'s backward allocates: the dZ planes (4 layers T R 4 hidden), dy and the
+    K-slice partials of the weight gradients.  0 for a shape without a kernel."""
+    return _lib.load().ge2e_encode_bwd_workspace_bytes(int(R), int(T), int(n_mels), int(hidden), int(layers), int(dim))
+
+
+class _EncodeTrainFunction(torch.autograd.Function):
+    """ge2e_encode_train / ge2e_encode_bwd as one autograd node over the parameter tensors in pack order."""
+
+    @staticmethod
+    def forward(ctx, m, row_start, shape, normalize, *params):
+        R, T, n_mels, H, L, D = shape
+        lib, dev, stream = _lib.load(), m.device, _stream_ptr(m)
+        flat = torch.cat([p.detach().reshape(-1) for p in params])
+        packed = encoder_pack(flat, n_mels, H, L, D)
+        packed_bwd = torch.empty(lib.ge2e_encoder_packed_bwd_bytes(n_mels, H, L, D) // 4, dtype=torch.float32, device=dev)
+        _launch("ge2e_encoder_pack_bwd", dev, flat.data_ptr(), n_mels, H, L, D, packed_bwd.data_ptr(), stream)
+        tape = torch.empty(lib.ge2e_encode_train_tape_bytes(*shape) // 4, dtype=torch.float32, device=dev)
+        out = torch.empty(R, D, dtype=torch.float32, device=dev)
+        rs_ptr = None if row_start is None else row_start.data_ptr()
+        _launch("ge2e_encode_train", dev, packed.data_ptr(), m.data_ptr(), rs_ptr, R, T, n_mels, H, L, D, int(normalize),
+                out.data_ptr(), tape.data_ptr(), stream)
+        ctx.save_for_backward(m, packed_bwd, tape, *([] if row_start is None else [row_start]))
+        ctx.cfg = (shape, normalize, [tuple(p.shape) for p in params])
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        shape, normalize, shapes = ctx.cfg
+        R, T, n_mels, H, L, D = shape
+        m, packed_bwd, tape, *rest = ctx.saved_tensors
+        lib, dev = _lib.load(), m.device
+        g = g.detach().to(torch.float32).contiguous()
+        d_flat = torch.empty(encoder_flat_numel(n_mels, H, L, D), dtype=torch.float32, device=dev)
+        ws = torch.empty(lib.ge2e_encode_bwd_workspace_bytes(*shape) // 4, dtype=torch.float32, device=dev)
+        _launch("ge2e_encode_bwd", dev, packed_bwd.data_ptr(), m.data_ptr(), rest[0].data_ptr() if rest else None, R, T, n_mels,
+                H, L, D, int(normalize), tape.data_ptr(), g.data_ptr(), d_flat.data_ptr(), ws.data_ptr(), _stream_ptr(m))
+        grads, off = [], 0
+        for s in shapes:                                  # the views of the flat buffer, one per parameter
+            n = 1
+            for d in s:
+                n *= d
+            grads.append(d_flat[off:off + n].view(s))
+            off += n
+        return (None, None, None, None, *grads)
+
+
+def encode_train(params, mel: torch.Tensor, *, T: Optional[int] = None, row_start: Optional[torch.Tensor] = None,
+                 hidden: int, layers: int, dim: int, normalize: bool = True) -> torch.Tensor:
+    """The encoder's forward WITH gradients, native both ways: ge2e_encode_train keeps a tape, and ``backward()`` runs
+    ge2e_encode_bwd -- the LSTM backward through time, the projection's and the norm's backward in hand-written HIP --
+    and hands every parameter its gradient as a view of one flat buffer.  ``params``: the float32 parameter tensors in
+    pack order (per layer weight_ih, weight_hh, bias_ih, bias_hh; then projection.weight, projection.bias) on ``mel``'s
+    device; they are concatenated and packed on every call.  ``mel``, ``T`` and ``row_start`` as ``encode``; the output
+    (R, dim) has ``encode``'s bits.  No gradient goes to the mels: a ``mel`` that requires grad raises.  The tape takes
+    ``encode_train_tape_bytes`` between forward and backward, the backward ``encode_bwd_workspace_bytes`` more.  Raises
+    where the shape has no kernel: there is no fallback here."""
+    if mel.requires_grad:
+        raise ValueError("encode_train produces no gradient with respect to the mels: mel must not require grad")
+    params = list(params)
+    m, row_start, R, T, n_mels = _encoder_rows(mel, T, row_start)
+    shape = (int(R), int(T), int(n_mels), int(hidden), int(layers), int(dim))
+    if not encode_supported(*shape[2:]):
+        raise ValueError(f"encoder shape (n_mels {n_mels}, hidden {hidden}, layers {layers}, dim {dim}) has no native kernel")
+    want = [(4 * hidden, n_mels if l == 0 else hidden) if k == 0 else (4 * hidden, hidden) if k == 1 else (4 * hidden,)
+            for l in range(layers) for k in range(4)] + [(dim, hidden), (dim,)]
+    if [tuple(p.shape) for p in params] != want or any(p.dtype != torch.float32 or p.device != m.device for p in params):
+        raise ValueError(f"params must be the {len(want)} float32 tensors of the encoder in pack order on {m.device}: {want}")
+    return _EncodeTrainFunction.apply(m, row_start, shape, bool(normalize), *params)
 
 
 def melspec_supported(n_fft: int, n_mels: int) -> bool:
