@@ -645,68 +645,68 @@ int ge2e_calc_loss_labeled_bwd(const float* sim, const int* col, const int* acti
 
 // ENCODER INFERENCE (include/ge2e_hip.h, csrc/ge2e_encoder.hip): the weights packed once, then mel windows to d-vectors in
 // one launch.
+// The shape-and-implementation step of every encoder entry, inference and training; the packs have no rows or frames and
+// pass R = T = 1.
+static int encoder_checks(int R, int T, int n_mels, int H, int L, int D) {
+    if (R < 1 || T < 1 || n_mels < 1 || D < 1 || L < 1) return GE2E_ERR_SHAPE;
+    return encoder_supported(n_mels, H, L, D) ? GE2E_OK : GE2E_ERR_IMPL;
+}
+// ... and all four steps of the two packs.
+static int encoder_pack_checks(const float* flat_params, const float* packed, int n_mels, int H, int L, int D) {
+    if (!flat_params || !packed) return GE2E_ERR_NULL;
+    if (const int code = encoder_checks(1, 1, n_mels, H, L, D)) return code;
+    return aligned16(packed) ? GE2E_OK : GE2E_ERR_ALIGN;
+}
+
 size_t ge2e_encoder_packed_bytes(int n_mels, int H, int L, int D) {
-    return encoder_supported(n_mels, H, L, D) ? encoder_packed_floats(n_mels, H, L, D) * sizeof(float) : 0;
+    return encoder_checks(1, 1, n_mels, H, L, D) == GE2E_OK ? encoder_packed_floats(n_mels, H, L, D) * sizeof(float) : 0;
 }
 
 int ge2e_encoder_pack(const float* flat_params, int n_mels, int H, int L, int D, float* packed, void* stream) {
-    if (!flat_params || !packed) return GE2E_ERR_NULL;
-    if (n_mels < 1 || D < 1 || L < 1) return GE2E_ERR_SHAPE;
-    if (!encoder_supported(n_mels, H, L, D)) return GE2E_ERR_IMPL;
-    if (!aligned16(packed)) return GE2E_ERR_ALIGN;
+    if (const int code = encoder_pack_checks(flat_params, packed, n_mels, H, L, D)) return code;
     return (int)launch_encoder_pack(flat_params, n_mels, H, L, D, packed, (hipStream_t)stream);
 }
 
 int ge2e_encode(const float* packed, const float* mel, const long long* row_start, int R, int T, int n_mels, int H, int L,
                 int D, int normalize, float* out, void* stream) {
     if (!packed || !mel || !out) return GE2E_ERR_NULL;
-    if (R < 1 || T < 1 || n_mels < 1 || D < 1 || L < 1) return GE2E_ERR_SHAPE;
-    if (!encoder_supported(n_mels, H, L, D)) return GE2E_ERR_IMPL;
+    if (const int code = encoder_checks(R, T, n_mels, H, L, D)) return code;
     if (!aligned16(packed) || !aligned16(mel) || !aligned16(out)) return GE2E_ERR_ALIGN;
     const ProblemEncode p = {packed, mel, row_start, out, R, T, n_mels, L, D, normalize != 0, nullptr};
     return (int)launch_encode(p, H, (hipStream_t)stream);
 }
 
 int ge2e_encode_plan(int R, int T, int n_mels, int H, int L, int D, char* buf, size_t buf_bytes) {
-    if (R < 1 || T < 1 || n_mels < 1 || D < 1 || L < 1) return GE2E_ERR_SHAPE;
-    if (!encoder_supported(n_mels, H, L, D)) return GE2E_ERR_IMPL;
+    if (const int code = encoder_checks(R, T, n_mels, H, L, D)) return code;
     return plan_string_encode(R, H, buf, buf_bytes);
 }
 
 // ENCODER TRAINING (include/ge2e_hip.h, csrc/ge2e_encoder_train.hip): the forward that leaves a tape, the transposed pack,
 // the backward through time into one flat gradient buffer.
-static int encoder_train_checks(int R, int T, int n_mels, int H, int L, int D) {
-    if (R < 1 || T < 1 || n_mels < 1 || D < 1 || L < 1) return GE2E_ERR_SHAPE;
-    return encoder_supported(n_mels, H, L, D) ? GE2E_OK : GE2E_ERR_IMPL;
-}
-
 size_t ge2e_encoder_packed_bwd_bytes(int n_mels, int H, int L, int D) {
-    return encoder_supported(n_mels, H, L, D) ? encoder_packed_bwd_floats(H, L, D) * sizeof(float) : 0;
+    return encoder_checks(1, 1, n_mels, H, L, D) == GE2E_OK ? encoder_packed_bwd_floats(H, L, D) * sizeof(float) : 0;
 }
 
 int ge2e_encoder_pack_bwd(const float* flat_params, int n_mels, int H, int L, int D, float* packed_bwd, void* stream) {
-    if (!flat_params || !packed_bwd) return GE2E_ERR_NULL;
-    if (n_mels < 1 || D < 1 || L < 1) return GE2E_ERR_SHAPE;
-    if (!encoder_supported(n_mels, H, L, D)) return GE2E_ERR_IMPL;
-    if (!aligned16(packed_bwd)) return GE2E_ERR_ALIGN;
+    if (const int code = encoder_pack_checks(flat_params, packed_bwd, n_mels, H, L, D)) return code;
     return (int)launch_encoder_pack_bwd(flat_params, n_mels, H, L, D, packed_bwd, (hipStream_t)stream);
 }
 
 size_t ge2e_encode_train_tape_bytes(int R, int T, int n_mels, int H, int L, int D) {
-    return encoder_train_checks(R, T, n_mels, H, L, D) == GE2E_OK ? encoder_tape_floats(R, T, H, L, D) * sizeof(float) : 0;
+    return encoder_checks(R, T, n_mels, H, L, D) == GE2E_OK ? encoder_tape_floats(R, T, H, L, D) * sizeof(float) : 0;
 }
 
 int ge2e_encode_train(const float* packed, const float* mel, const long long* row_start, int R, int T, int n_mels, int H, int L,
                       int D, int normalize, float* out, float* tape, void* stream) {
     if (!packed || !mel || !out || !tape) return GE2E_ERR_NULL;
-    if (const int code = encoder_train_checks(R, T, n_mels, H, L, D)) return code;
+    if (const int code = encoder_checks(R, T, n_mels, H, L, D)) return code;
     if (!aligned16(packed) || !aligned16(mel) || !aligned16(out) || !aligned16(tape)) return GE2E_ERR_ALIGN;
     const ProblemEncode p = {packed, mel, row_start, out, R, T, n_mels, L, D, normalize != 0, tape};
     return (int)launch_encode_train(p, H, (hipStream_t)stream);
 }
 
 size_t ge2e_encode_bwd_workspace_bytes(int R, int T, int n_mels, int H, int L, int D) {
-    return encoder_train_checks(R, T, n_mels, H, L, D) == GE2E_OK
+    return encoder_checks(R, T, n_mels, H, L, D) == GE2E_OK
                ? encoder_bwd_workspace(R, T, n_mels, H, L, D).total * sizeof(float) : 0;
 }
 
@@ -714,7 +714,7 @@ int ge2e_encode_bwd(const float* packed_bwd, const float* mel, const long long* 
                     int L, int D, int normalize, const float* tape, const float* d_out, float* d_flat_params, void* workspace,
                     void* stream) {
     if (!packed_bwd || !mel || !tape || !d_out || !d_flat_params || !workspace) return GE2E_ERR_NULL;
-    if (const int code = encoder_train_checks(R, T, n_mels, H, L, D)) return code;
+    if (const int code = encoder_checks(R, T, n_mels, H, L, D)) return code;
     if (!aligned16(packed_bwd) || !aligned16(mel) || !aligned16(tape) || !aligned16(d_out) || !aligned16(d_flat_params) ||
         !aligned16(workspace))
         return GE2E_ERR_ALIGN;
@@ -724,12 +724,12 @@ int ge2e_encode_bwd(const float* packed_bwd, const float* mel, const long long* 
 }
 
 int ge2e_encode_train_plan(int R, int T, int n_mels, int H, int L, int D, char* buf, size_t buf_bytes) {
-    if (const int code = encoder_train_checks(R, T, n_mels, H, L, D)) return code;
+    if (const int code = encoder_checks(R, T, n_mels, H, L, D)) return code;
     return plan_string_encode_train(R, H, buf, buf_bytes);
 }
 
 int ge2e_encode_bwd_plan(int R, int T, int n_mels, int H, int L, int D, char* buf, size_t buf_bytes) {
-    if (const int code = encoder_train_checks(R, T, n_mels, H, L, D)) return code;
+    if (const int code = encoder_checks(R, T, n_mels, H, L, D)) return code;
     return plan_string_encode_bwd(R, T, n_mels, H, L, D, buf, buf_bytes);
 }
 

@@ -12,7 +12,7 @@
 //             tile pc = (w UB + ub) 4 + gate holds the gate's columns of the 16 units of block ub of wave w, so i, f, g, o of
 //             one unit land in the same lane and register slot of four accumulators and the cell update runs in
 //             registers.  Then the 4 H biases b_ih + b_hh in the same column order.  The projection likewise:
-//             [H][pad16(D)] and pad16(D) biases, zero past D.
+//             [H][pad16(D)] and pad16(D) biases, zero past D.  (Every index map: ge2e_encoder.hpp; the K loop: enc_contract.)
 //   state     c in registers (UB x 2 x 4 per layer), h of every layer in LDS [L][32][H]; x_t and the weights come from
 //             global memory (L2) one group ahead of the MFMAs that use them.  Two barriers per layer-step: the old h of the
 //             layer is read by every wave before any wave overwrites it.
@@ -26,9 +26,9 @@
 #include "ge2e_encoder_train.hpp"
 
 #include <math.h>
-#include <stdio.h>
 
-#include "ge2e_rows_dev.hpp"
+#include "ge2e_encoder_dev.hpp"
+#include "ge2e_plan.hpp"
 
 namespace ge2e {
 
@@ -45,43 +45,34 @@ __global__ __launch_bounds__(256) void encoder_pack_kernel(const float* __restri
                                                             float* __restrict__ packed, size_t total) {
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += stride) {
-        size_t off = 0;
-        const float* src = flat;
-        float val = 0.f;
-        bool done = false;
-        for (int l = 0; l < L && !done; ++l) {
-            const int I = l ? H : n_mels, Ip = enc_pad16(I), C = 4 * H, CT = C / 16;
-            const size_t lf = enc_layer_floats(I, H);
-            if (idx < off + lf) {
-                const size_t local = idx - off, wsz = (size_t)(Ip + H) * C;
-                const float *w_ih = src, *w_hh = w_ih + (size_t)C * I, *b_ih = w_hh + (size_t)C * H, *b_hh = b_ih + C;
-                if (local < wsz) {
-                    const int i = (int)(local & 3), lane = (int)((local >> 2) & 63);
-                    const int rest = (int)(local >> 8), pc = rest % CT, g = rest / CT;
-                    const int k = 16 * g + 4 * (lane >> 4) + i, row = enc_gate_row(pc, lane & 15, H);
-                    if (k < Ip) val = k < I ? w_ih[(size_t)row * I + k] : 0.f;
-                    else val = w_hh[(size_t)row * H + (k - Ip)];
-                } else {
-                    const int b = (int)(local - wsz), row = enc_gate_row(b >> 4, b & 15, H);
-                    val = b_ih[row] + b_hh[row];
-                }
-                done = true;
-            }
-            off += lf;
-            src += (size_t)C * (I + H + 2);
-        }
-        if (!done) {
-            const int Dp = enc_pad16(D), DT = Dp / 16;
-            const size_t local = idx - off, wsz = (size_t)H * Dp;
-            const float *wp = src, *bp = src + (size_t)D * H;
+        int l = 0;
+        while (l < L && idx >= enc_pack_layer(l + 1, n_mels, H)) ++l;
+        const size_t local = idx - enc_pack_layer(l, n_mels, H);
+        float val;
+        if (l < L) {
+            const EncFlatLayer f = enc_flat_layer(l, n_mels, H);
+            const int I = f.I, Ip = enc_pad16(I), C = 4 * H;
+            const size_t wsz = (size_t)(Ip + H) * C;
             if (local < wsz) {
-                const int i = (int)(local & 3), lane = (int)((local >> 2) & 63);
-                const int rest = (int)(local >> 8), dt = rest % DT, g = rest / DT;
-                const int k = 16 * g + 4 * (lane >> 4) + i, d = dt * 16 + (lane & 15);
-                val = d < D ? wp[(size_t)d * H + k] : 0.f;
+                const EncFragIdx e = enc_frag_decode(local, C / 16);
+                const int k = e.k, row = enc_gate_row(e.tile, e.l15, H);
+                if (k < Ip) val = k < I ? flat[f.w_ih + (size_t)row * I + k] : 0.f;
+                else val = flat[f.w_hh + (size_t)row * H + (k - Ip)];
+            } else {
+                const int b = (int)(local - wsz), row = enc_gate_row(b >> 4, b & 15, H);
+                val = flat[f.b_ih + row] + flat[f.b_hh + row];
+            }
+        } else {
+            const EncFlatProj f = enc_flat_proj(n_mels, H, L, D);
+            const int Dp = enc_pad16(D);
+            const size_t wsz = (size_t)H * Dp;
+            if (local < wsz) {
+                const EncFragIdx e = enc_frag_decode(local, Dp / 16);
+                const int d = e.tile * 16 + e.l15;
+                val = d < D ? flat[f.w + (size_t)d * H + e.k] : 0.f;
             } else {
                 const int d = (int)(local - wsz);
-                val = d < D ? bp[d] : 0.f;
+                val = d < D ? flat[f.b + d] : 0.f;
             }
         }
         packed[idx] = val;
@@ -124,53 +115,13 @@ __global__ __launch_bounds__(kEncThreads) void encode_kernel(ProblemEncode p) {
         for (int ub = 0; ub < UB; ++ub) c[l][ub][0] = c[l][ub][1] = zero4;
     __syncthreads();
 
-    // The wave's column tiles against both row halves over G groups of 16 k, in NCG chunks of TPC tiles per group.  `bw`:
-    // the lane's slot of the wave's first tile in group 0 (tiles 256 floats apart, groups `gstride`); `afrag(g, rt)`: the
-    // lane's four activations.  The weights of the next chunk and the activations of the next group are fetched before
-    // the MFMAs of the current chunk.
-    auto contract = [&](auto tpc_c, auto ncg_c, const float* bw, size_t gstride, int G, auto&& afrag, v4f (&acc)[NT][2]) {
-        constexpr int TPC = decltype(tpc_c)::value, NCG = decltype(ncg_c)::value;
-        v4f bn[TPC], an[2];
-#pragma unroll
-        for (int j = 0; j < TPC; ++j) bn[j] = *reinterpret_cast<const v4f*>(bw + (size_t)j * 256);
-        an[0] = afrag(0, 0);
-        an[1] = afrag(0, 1);
-#pragma clang loop unroll(disable)
-        for (int g = 0; g < G; ++g) {
-            const v4f ac[2] = {an[0], an[1]};
-            const bool more = g + 1 < G;
-            if (more) {
-                an[0] = afrag(g + 1, 0);
-                an[1] = afrag(g + 1, 1);
-            }
-            static_for<0, NCG>([&](auto uc) {
-                constexpr int u = decltype(uc)::value;
-                v4f bc[TPC];
-#pragma unroll
-                for (int j = 0; j < TPC; ++j) bc[j] = bn[j];
-                if (u + 1 < NCG || more) {
-                    const float* nb = u + 1 < NCG ? bw + (size_t)g * gstride + (size_t)(u + 1) * TPC * 256
-                                                  : bw + (size_t)(g + 1) * gstride;
-#pragma unroll
-                    for (int j = 0; j < TPC; ++j) bn[j] = *reinterpret_cast<const v4f*>(nb + (size_t)j * 256);
-                }
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int j = 0; j < TPC; ++j) {
-                        acc[u * TPC + j][0] = mfma_f32(ac[0][i], bc[j][i], acc[u * TPC + j][0]);
-                        acc[u * TPC + j][1] = mfma_f32(ac[1][i], bc[j][i], acc[u * TPC + j][1]);
-                    }
-            });
-        }
-    };
-
+    const EncTape tape = enc_tape(R, T, H, L);
     for (int t = 0; t < T; ++t) {
-        const float* wl = p.packed;
         static_for<0, kEncMaxLayers>([&](auto lc) {
             constexpr int l = decltype(lc)::value;
             if (l < L) {
                 const int Gin = l == 0 ? G0 : GH, G = Gin + GH;
+                const float* wl = p.packed + enc_pack_layer(l, n_mels, H);
                 const float* bias = wl + (size_t)G * 16 * 4 * H;
                 v4f acc[NT][2];
 #pragma unroll
@@ -187,8 +138,7 @@ __global__ __launch_bounds__(kEncThreads) void encode_kernel(ProblemEncode p) {
                     }
                     return *reinterpret_cast<const v4f*>(hown + (rt * 16 + l15) * H + 16 * (g - Gin) + 4 * q);
                 };
-                contract(std::integral_constant<int, 4>{}, std::integral_constant<int, UB>{}, wl + ((size_t)wid * NT * 64 + lane) * 4, (size_t)CT * 256, G,
-                         afrag, acc);
+                enc_contract<2, 4, UB>(wl + enc_frag_slot(0, CT, wid * NT, lane), enc_frag_slot(1, CT, 0, 0), G, afrag, acc);
                 // the cell update, in registers: the lane holds i, f, g, o of unit l15 of block ub for the rows 4 q + v
                 v4f hnew[UB][2];
 #pragma unroll
@@ -205,15 +155,13 @@ __global__ __launch_bounds__(kEncThreads) void encode_kernel(ProblemEncode p) {
                             if constexpr (kTape) {
                                 const long long r = (long long)blockIdx.x * kEncTile + rt * 16 + 4 * q + v;
                                 if (r < R) {   // pad rows write nothing
-                                    const size_t plane = (size_t)T * R * H;
-                                    float* tp = p.tape + (size_t)l * kEncTapePlanes * plane +
-                                                ((size_t)t * R + (size_t)r) * H + (wid * UB + ub) * 16 + l15;
-                                    tp[0] = ig;
-                                    tp[plane] = fg;
-                                    tp[2 * plane] = gg;
-                                    tp[3 * plane] = og;
-                                    tp[4 * plane] = cn;
-                                    tp[5 * plane] = hnew[ub][rt][v];
+                                    float* tp = p.tape + enc_tape_at(tape, l, EncTape::I, t, r, (wid * UB + ub) * 16 + l15);
+                                    tp[enc_tape_step(tape, EncTape::I, 0)] = ig;
+                                    tp[enc_tape_step(tape, EncTape::F, 0)] = fg;
+                                    tp[enc_tape_step(tape, EncTape::G, 0)] = gg;
+                                    tp[enc_tape_step(tape, EncTape::O, 0)] = og;
+                                    tp[enc_tape_step(tape, EncTape::C, 0)] = cn;
+                                    tp[enc_tape_step(tape, EncTape::Hid, 0)] = hnew[ub][rt][v];
                                 }
                             }
                         }
@@ -227,13 +175,12 @@ __global__ __launch_bounds__(kEncThreads) void encode_kernel(ProblemEncode p) {
                         for (int v = 0; v < 4; ++v)
                             hw[(rt * 16 + 4 * q + v) * H + (wid * UB + ub) * 16 + l15] = hnew[ub][rt][v];
                 __syncthreads();   // ... and the new one is there for the layer above and for the next step
-                wl = bias + 4 * H;
             }
         });
     }
 
     // projection of the top layer's h: column tiles wid and wid + 8 of pad16(D) / 16
-    const float* wp = p.packed + enc_layer_floats(n_mels, H) + (size_t)(L - 1) * enc_layer_floats(H, H);
+    const float* wp = p.packed + enc_pack_layer(L, n_mels, H);
     const float* pbias = wp + (size_t)H * Dp;
     const float* htop = hs + (size_t)(L - 1) * kEncTile * H;
     v4f y[2][2];
@@ -243,12 +190,12 @@ __global__ __launch_bounds__(kEncThreads) void encode_kernel(ProblemEncode p) {
         y[jt][0] = y[jt][1] = zero4;
         if (dt < DT) {   // (uniform over the wave)
             const float b = pbias[dt * 16 + l15];
-            v4f acc[NT][2];
+            v4f acc[1][2];
             acc[0][0] = acc[0][1] = v4f{b, b, b, b};
             auto afrag = [&](int g, int rt) -> v4f {
                 return *reinterpret_cast<const v4f*>(htop + (rt * 16 + l15) * H + 16 * g + 4 * q);
             };
-            contract(std::integral_constant<int, 1>{}, std::integral_constant<int, 1>{}, wp + ((size_t)dt * 64 + lane) * 4, (size_t)DT * 256, GH, afrag, acc);
+            enc_contract<2, 1, 1>(wp + enc_frag_slot(0, DT, dt, lane), enc_frag_slot(1, DT, 0, 0), GH, afrag, acc);
             y[jt][0] = acc[0][0];
             y[jt][1] = acc[0][1];
         }
@@ -278,7 +225,7 @@ __global__ __launch_bounds__(kEncThreads) void encode_kernel(ProblemEncode p) {
         float* o = p.out + (size_t)r * D;
         for (int d = lane; d < D; d += kWave) o[d] = p.normalize ? yr[d] / n : yr[d];
         if constexpr (kTape) {
-            float* ty = p.tape + (size_t)kEncTapePlanes * L * T * (size_t)R * H + (size_t)r * D;
+            float* ty = p.tape + enc_tape_y(tape) + (size_t)r * D;
             for (int d = lane; d < D; d += kWave) ty[d] = yr[d];
         }
     }
@@ -288,33 +235,26 @@ KernelLaunchState g_encode_state[2][2];
 
 template <bool kTape>
 hipError_t launch_encode_as(const ProblemEncode& p, int H, hipStream_t stream) {
-    const unsigned lds = (unsigned)encoder_lds_bytes(H, p.L, p.D);
-    const unsigned tiles = (unsigned)(((long long)p.R + kEncTile - 1) / kEncTile);
-    const void* fn = H == 256 ? (const void*)encode_kernel<256, kTape> : (const void*)encode_kernel<128, kTape>;
-    const hipError_t err = prepare_kernel(g_encode_state[kTape][H == 256], fn, kEncThreads, lds, nullptr);
-    if (err != hipSuccess) return err;
-    if (H == 256) hipLaunchKernelGGL((encode_kernel<256, kTape>), dim3(tiles), dim3(kEncThreads), lds, stream, p);
-    else hipLaunchKernelGGL((encode_kernel<128, kTape>), dim3(tiles), dim3(kEncThreads), lds, stream, p);
-    return hipGetLastError();
+    return launch_for_h(H, encode_kernel<128, kTape>, encode_kernel<256, kTape>, g_encode_state[kTape],
+                        (unsigned)enc_tiles(p.R, kEncTile), (unsigned)encoder_lds_bytes(H, p.L, p.D), p, stream);
 }
 }  // namespace
 
 hipError_t launch_encoder_pack(const float* flat, int n_mels, int H, int L, int D, float* packed, hipStream_t stream) {
     const size_t total = encoder_packed_floats(n_mels, H, L, D);
-    const unsigned blocks = (unsigned)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-    hipLaunchKernelGGL(encoder_pack_kernel, dim3(blocks), dim3(256), 0, stream, flat, n_mels, H, L, D, packed, total);
+    hipLaunchKernelGGL(encoder_pack_kernel, dim3(reduce_blocks(total)), dim3(256), 0, stream, flat, n_mels, H, L, D, packed, total);
     return hipGetLastError();
 }
 
 hipError_t launch_encode(const ProblemEncode& p, int H, hipStream_t stream) { return launch_encode_as<false>(p, H, stream); }
 hipError_t launch_encode_train(const ProblemEncode& p, int H, hipStream_t stream) { return launch_encode_as<true>(p, H, stream); }
 
-int plan_string_encode(int R, int H, char* buf, size_t cap) {
-    return snprintf(buf, cap, "encode<%d>/%d", H, (int)(((long long)R + kEncTile - 1) / kEncTile));
+static int plan_string_tiles(const char* kernel, int R, int H, char* buf, size_t cap) {
+    Out o{buf, cap};
+    o.add("%s<%d>/%d", kernel, H, enc_tiles(R, kEncTile));
+    return o.done();
 }
-
-int plan_string_encode_train(int R, int H, char* buf, size_t cap) {
-    return snprintf(buf, cap, "encode_train<%d>/%d", H, (int)(((long long)R + kEncTile - 1) / kEncTile));
-}
+int plan_string_encode(int R, int H, char* buf, size_t cap) { return plan_string_tiles("encode", R, H, buf, cap); }
+int plan_string_encode_train(int R, int H, char* buf, size_t cap) { return plan_string_tiles("encode_train", R, H, buf, cap); }
 
 }  // namespace ge2e

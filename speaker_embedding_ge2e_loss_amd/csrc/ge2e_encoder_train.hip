@@ -18,14 +18,15 @@
 //               workspace, one flat-buffer image per slice.
 //   reduce      encode_reduce_kernel: every element of the flat gradient buffer is the sum of its slices in ascending
 //               order, written once (bias_hh reads bias_ih's partials).  No atomics: the same bits on every call.
+// Index maps: ge2e_encoder_train.hpp (tape, backward pack), ge2e_encoder.hpp (flat buffer, fragments); the K loop: enc_contract.
 // Pad rows of the last tile: dy = 0 and every saved value reads as 0, so their dz are exact zeros in LDS and nothing of
 // them is stored.  A row whose upstream gradient is zero has dy = 0, dh = 0 and dc = 0: exact zeros in every dz.
 #include "ge2e_encoder_train.hpp"
 
 #include <math.h>
-#include <stdio.h>
 
-#include "ge2e_rows_dev.hpp"
+#include "ge2e_encoder_dev.hpp"
+#include "ge2e_plan.hpp"
 
 namespace ge2e {
 
@@ -35,33 +36,17 @@ __global__ __launch_bounds__(256) void encoder_pack_bwd_kernel(const float* __re
                                                                 float* __restrict__ packed, size_t total) {
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += stride) {
-        size_t off = 0;
-        const float* src = flat;
-        float val = 0.f;
-        bool done = false;
-        for (int l = 0; l < L && !done; ++l) {
-            const int I = l ? H : n_mels, C = l ? 2 * H : H, CT = C / 16;
-            const size_t lf = enc_bwd_layer_floats(l, H);
-            if (idx < off + lf) {
-                const size_t local = idx - off;
-                const float *w_ih = src, *w_hh = w_ih + (size_t)4 * H * I;
-                const int i = (int)(local & 3), lane = (int)((local >> 2) & 63);
-                const int rest = (int)(local >> 8), ct = rest % CT, g = rest / CT;
-                const int k = 16 * g + 4 * (lane >> 4) + i, col = ct * 16 + (lane & 15);
-                if (l == 0) val = w_hh[(size_t)k * H + col];
-                else val = col < H ? w_ih[(size_t)k * H + col] : w_hh[(size_t)k * H + (col - H)];
-                done = true;
-            }
-            off += lf;
-            src += (size_t)4 * H * (I + H + 2);
-        }
-        if (!done) {
-            const int CT = H / 16;
-            const size_t local = idx - off;
-            const int i = (int)(local & 3), lane = (int)((local >> 2) & 63);
-            const int rest = (int)(local >> 8), ct = rest % CT, g = rest / CT;
-            const int k = 16 * g + 4 * (lane >> 4) + i, col = ct * 16 + (lane & 15);
-            val = k < D ? src[(size_t)k * H + col] : 0.f;
+        int l = 0;
+        while (l < L && idx >= enc_bwd_pack_layer(l + 1, H)) ++l;
+        const EncFragIdx e = enc_frag_decode(idx - enc_bwd_pack_layer(l, H), (l == 0 || l == L ? H : 2 * H) / 16);
+        const int k = e.k, col = e.tile * 16 + e.l15;
+        float val;
+        if (l < L) {
+            const EncFlatLayer f = enc_flat_layer(l, n_mels, H);
+            if (l == 0) val = flat[f.w_hh + (size_t)k * H + col];
+            else val = col < H ? flat[f.w_ih + (size_t)k * H + col] : flat[f.w_hh + (size_t)k * H + (col - H)];
+        } else {
+            val = k < D ? flat[enc_flat_proj(n_mels, H, L, D).w + (size_t)k * H + col] : 0.f;
         }
         packed[idx] = val;
     }
@@ -77,7 +62,8 @@ __global__ __launch_bounds__(kEncThreads) void encode_bwd_kernel(ProblemEncodeBw
     const int L = p.L, T = p.T, D = p.D, R = p.R;
     const int Dp = enc_pad16(D), YS = Dp + kEncBwdPad;
     const long long r0 = (long long)blockIdx.x * kEncBwdTile;
-    const size_t RH = (size_t)R * H, plane = (size_t)T * RH;
+    const size_t RH = (size_t)R * H;
+    const EncTape tape = enc_tape(R, T, H, L);
     const v4f zero4 = {0.f, 0.f, 0.f, 0.f};
     float* dh = bwd_lds;                                   // [L][16][H]
     float* dzs = bwd_lds + (size_t)L * kEncBwdTile * H;    // [16][ZS]; before the first step dy [16][YS]
@@ -85,7 +71,7 @@ __global__ __launch_bounds__(kEncThreads) void encode_bwd_kernel(ProblemEncodeBw
     for (int i = threadIdx.x; i < L * kEncBwdTile * H; i += kEncThreads) dh[i] = 0.f;
 
     // the norm's backward, one wave per two rows: dy into LDS (zero past D and for pad rows) and into the workspace
-    const float* ytape = p.tape + (size_t)kEncTapePlanes * L * plane;
+    const float* ytape = p.tape + enc_tape_y(tape);
     for (int i = 0; i < kEncBwdTile / 8; ++i) {
         const int tr = wid * (kEncBwdTile / 8) + i;
         const long long r = r0 + tr;
@@ -117,26 +103,17 @@ __global__ __launch_bounds__(kEncThreads) void encode_bwd_kernel(ProblemEncodeBw
 
     // the projection's backward: dh of the top layer at the last frame = dy Wp, K = pad16(D)
     {
-        size_t poff = 0;
-        for (int l = 0; l < L; ++l) poff += enc_bwd_layer_floats(l, H);
-        const float* wp = p.packed_bwd + poff;
-        v4f acc[UB];
+        const float* wp = p.packed_bwd + enc_bwd_pack_layer(L, H);
+        v4f acc[UB][1];
 #pragma unroll
-        for (int ub = 0; ub < UB; ++ub) acc[ub] = zero4;
-        for (int g = 0; g < Dp / 16; ++g) {
-            const v4f a = *reinterpret_cast<const v4f*>(dzs + l15 * YS + 16 * g + 4 * q);
-#pragma unroll
-            for (int ub = 0; ub < UB; ++ub) {
-                const v4f b = *reinterpret_cast<const v4f*>(wp + (((size_t)g * (H / 16) + wid * UB + ub) * 64 + lane) * 4);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) acc[ub] = mfma_f32(a[i], b[i], acc[ub]);
-            }
-        }
+        for (int ub = 0; ub < UB; ++ub) acc[ub][0] = zero4;
+        auto afrag = [&](int g, int) -> v4f { return *reinterpret_cast<const v4f*>(dzs + l15 * YS + 16 * g + 4 * q); };
+        enc_contract<1, UB, 1>(wp + enc_frag_slot(0, H / 16, wid * UB, lane), enc_frag_slot(1, H / 16, 0, 0), Dp / 16, afrag, acc);
         float* top = dh + (size_t)(L - 1) * kEncBwdTile * H;
 #pragma unroll
         for (int ub = 0; ub < UB; ++ub)
 #pragma unroll
-            for (int v = 0; v < 4; ++v) top[(4 * q + v) * H + (wid * UB + ub) * 16 + l15] = acc[ub][v];
+            for (int v = 0; v < 4; ++v) top[(4 * q + v) * H + (wid * UB + ub) * 16 + l15] = acc[ub][0][v];
     }
     __syncthreads();   // dy has been read, the top plane is there
 
@@ -152,7 +129,7 @@ __global__ __launch_bounds__(kEncThreads) void encode_bwd_kernel(ProblemEncodeBw
             if (l < L) {
                 float* dhl = dh + (size_t)l * kEncBwdTile * H;
                 // ---- dz of the lane's cells from dh, dc and the tape ----
-                const float* tl = p.tape + (size_t)l * kEncTapePlanes * plane + (size_t)t * RH;
+                const float* tl = p.tape + enc_tape_at(tape, l, EncTape::I, t, 0, 0);   // (uniform: the layer's frame t)
                 float* dzl = p.dz + ((size_t)l * T + t) * RH * 4;
 #pragma unroll
                 for (int ub = 0; ub < UB; ++ub)
@@ -163,9 +140,10 @@ __global__ __launch_bounds__(kEncThreads) void encode_bwd_kernel(ProblemEncodeBw
                         float dzi = 0.f, dzf = 0.f, dzg = 0.f, dzo = 0.f;
                         if (r < R) {
                             const float dhv = dhl[tr * H + u];
-                            const float* tp = tl + (size_t)r * H + u;
-                            const float ig = tp[0], fg = tp[plane], gg = tp[2 * plane], og = tp[3 * plane];
-                            const float cn = tp[4 * plane], cprev = t > 0 ? (tp + 4 * plane)[-(ptrdiff_t)RH] : 0.f;
+                            const float* tp = tl + enc_tape_at(tape, 0, EncTape::I, 0, r, u);
+                            auto saved = [&](int plane, int frames) { return tp[enc_tape_step(tape, plane, frames)]; };
+                            const float ig = saved(EncTape::I, 0), fg = saved(EncTape::F, 0), gg = saved(EncTape::G, 0);
+                            const float og = saved(EncTape::O, 0), cn = saved(EncTape::C, 0), cprev = t > 0 ? saved(EncTape::C, -1) : 0.f;
                             const float tc = tanhf(cn);
                             const float dcv = dc[l][ub][v] + dhv * og * (1.0f - tc * tc);
                             dzi = dcv * gg * (ig * (1.0f - ig));
@@ -188,9 +166,7 @@ __global__ __launch_bounds__(kEncThreads) void encode_bwd_kernel(ProblemEncodeBw
                 __syncthreads();   // the dz plane is whole; every lane has read its dh
                 // ---- d[input | h_prev] = dz W: column tiles wid NTB .. of C / 16, the input half first ----
                 constexpr int C = l ? 2 * H : H, CT = C / 16, NTB = CT / 8;
-                size_t woff = 0;
-                for (int k = 0; k < l; ++k) woff += enc_bwd_layer_floats(k, H);
-                const float* wl = p.packed_bwd + woff + ((size_t)wid * NTB * 64 + lane) * 4;
+                const float* wl = p.packed_bwd + enc_bwd_pack_layer(l, H) + enc_frag_slot(0, CT, wid * NTB, lane);
                 float* dst[NTB];
                 v4f acc[NTB];
 #pragma unroll
@@ -202,9 +178,12 @@ __global__ __launch_bounds__(kEncThreads) void encode_bwd_kernel(ProblemEncodeBw
                     for (int v = 0; v < 4; ++v) acc[j][v] = input ? dst[j][(4 * q + v) * H] : 0.f;
                 }
                 const float* arow = dzs + l15 * ZS + 4 * q;
+                // This site keeps its own K loop, enc_contract's for one row half and one chunk: through the shared function
+                // the training step measured 0.6 .. 0.8 ms (1.2 %) above the parent's in two sets
+                // (profiles/encoder_refactor_ab.txt, 5a).  The same order for every accumulator: g ascending, i = 0 .. 3.
                 v4f an = *reinterpret_cast<const v4f*>(arow), bn[NTB];
 #pragma unroll
-                for (int j = 0; j < NTB; ++j) bn[j] = *reinterpret_cast<const v4f*>(wl + (size_t)j * 256);
+                for (int j = 0; j < NTB; ++j) bn[j] = *reinterpret_cast<const v4f*>(wl + (size_t)j * kEncFragTile);
 #pragma clang loop unroll(disable)
                 for (int g = 0; g < G; ++g) {
                     const v4f ac = an;
@@ -214,8 +193,7 @@ __global__ __launch_bounds__(kEncThreads) void encode_bwd_kernel(ProblemEncodeBw
                     if (g + 1 < G) {
                         an = *reinterpret_cast<const v4f*>(arow + 16 * (g + 1));
 #pragma unroll
-                        for (int j = 0; j < NTB; ++j)
-                            bn[j] = *reinterpret_cast<const v4f*>(wl + (size_t)(g + 1) * CT * 256 + (size_t)j * 256);
+                        for (int j = 0; j < NTB; ++j) bn[j] = *reinterpret_cast<const v4f*>(wl + enc_frag_slot(g + 1, CT, j, 0));
                     }
 #pragma unroll
                     for (int i = 0; i < 4; ++i)
@@ -298,16 +276,15 @@ __global__ __launch_bounds__(256) void encode_reduce_kernel(const float* __restr
                                                              float* __restrict__ d_flat) {
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += stride) {
-        size_t off = 0, src = idx;
+        size_t src = idx;
         int S = s_proj;
         for (int l = 0; l < L; ++l) {
-            const size_t lf = (size_t)4 * H * ((l ? H : n_mels) + H + 2);
-            if (idx < off + lf) {
+            const EncFlatLayer f = enc_flat_layer(l, n_mels, H);
+            if (idx < f.end) {
                 S = s_lstm;
-                if (idx >= off + lf - (size_t)4 * H) src = idx - (size_t)4 * H;   // bias_hh = bias_ih
+                if (idx >= f.b_hh) src = idx - (f.b_hh - f.b_ih);   // bias_hh = bias_ih
                 break;
             }
-            off += lf;
         }
         float sum = partial[src];
         for (int s = 1; s < S; ++s) sum += partial[(size_t)s * pstride + src];
@@ -318,10 +295,8 @@ __global__ __launch_bounds__(256) void encode_reduce_kernel(const float* __restr
 KernelLaunchState g_encode_bwd_state[2];
 
 dim3 wgrad_grid(int M, int N, long long K) {
-    return dim3((unsigned)((N + kWgradBlock - 1) / kWgradBlock), (unsigned)((M + kWgradBlock - 1) / kWgradBlock),
-                (unsigned)wgrad_slices(K));
+    return dim3((unsigned)enc_tiles(N, kWgradBlock), (unsigned)enc_tiles(M, kWgradBlock), (unsigned)wgrad_slices(K));
 }
-unsigned reduce_blocks(size_t total) { return (unsigned)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096); }
 }  // namespace
 
 hipError_t launch_encoder_pack_bwd(const float* flat, int n_mels, int H, int L, int D, float* packed, hipStream_t stream) {
@@ -336,55 +311,50 @@ hipError_t launch_encode_bwd(const ProblemEncodeBwd& p0, int H, hipStream_t stre
     const EncBwdWorkspace ws = encoder_bwd_workspace(p.R, p.T, p.n_mels, H, p.L, p.D);
     p.dz = p.ws + ws.dz;
     p.dy = p.ws + ws.dy;
-    const unsigned lds = (unsigned)encoder_bwd_lds_bytes(H, p.L);
-    const unsigned tiles = (unsigned)(((long long)p.R + kEncBwdTile - 1) / kEncBwdTile);
-    const void* fn = H == 256 ? (const void*)encode_bwd_kernel<256> : (const void*)encode_bwd_kernel<128>;
-    hipError_t err = prepare_kernel(g_encode_bwd_state[H == 256], fn, kEncThreads, lds, nullptr);
+    hipError_t err = launch_for_h(H, encode_bwd_kernel<128>, encode_bwd_kernel<256>, g_encode_bwd_state,
+                                  (unsigned)enc_tiles(p.R, kEncBwdTile), (unsigned)encoder_bwd_lds_bytes(H, p.L), p, stream);
     if (err != hipSuccess) return err;
-    if (H == 256) hipLaunchKernelGGL(encode_bwd_kernel<256>, dim3(tiles), dim3(kEncThreads), lds, stream, p);
-    else hipLaunchKernelGGL(encode_bwd_kernel<128>, dim3(tiles), dim3(kEncThreads), lds, stream, p);
-    if ((err = hipGetLastError()) != hipSuccess) return err;
 
     const long long K = (long long)p.R * p.T;
-    const size_t RH = (size_t)p.R * H, plane = (size_t)p.T * RH, total = encoder_flat_floats(p.n_mels, H, p.L, p.D);
+    const EncTape tape = enc_tape(p.R, p.T, H, p.L);
+    const size_t total = encoder_flat_floats(p.n_mels, H, p.L, p.D);
     WgradJob j{};
     j.row_start = p.row_start;
     j.partial = p.ws + ws.partial;
     j.pstride = enc_round64(total);
     j.R = p.R;
     j.T = p.T;
-    size_t off = 0;
     for (int l = 0; l < p.L; ++l) {
-        const int I = l ? H : p.n_mels;
-        j.A = p.dz + (size_t)l * plane * 4;
+        const EncFlatLayer f = enc_flat_layer(l, p.n_mels, H);
+        j.A = p.dz + (size_t)l * K * 4 * H;
         j.lda = j.M = 4 * H;
         j.K = K;
         j.slice_len = wgrad_slice_len(K);
         j.mel_part = l == 0;
-        j.B0 = l ? p.tape + ((size_t)(l - 1) * kEncTapePlanes + 5) * plane : p.mel;
-        j.ldb0 = j.N0 = I;
-        j.B1 = p.tape + ((size_t)l * kEncTapePlanes + 5) * plane;
+        j.B0 = l ? p.tape + enc_tape_at(tape, l - 1, EncTape::Hid, 0, 0, 0) : p.mel;
+        j.ldb0 = j.N0 = f.I;
+        j.B1 = p.tape + enc_tape_at(tape, l, EncTape::Hid, 0, 0, 0);
         j.N1 = H;
         j.shift = p.R;
-        j.out0 = off;
-        j.out1 = off + (size_t)4 * H * I;
-        j.outb = j.out1 + (size_t)4 * H * H;
-        hipLaunchKernelGGL(encode_wgrad_kernel, wgrad_grid(j.M, I + H, K), dim3(kWgradThreads), 0, stream, j);
+        j.out0 = f.w_ih;
+        j.out1 = f.w_hh;
+        j.outb = f.b_ih;
+        hipLaunchKernelGGL(encode_wgrad_kernel, wgrad_grid(j.M, f.I + H, K), dim3(kWgradThreads), 0, stream, j);
         if ((err = hipGetLastError()) != hipSuccess) return err;
-        off = j.outb + (size_t)8 * H;
     }
+    const EncFlatProj f = enc_flat_proj(p.n_mels, H, p.L, p.D);
     j.A = p.dy;
     j.lda = j.M = p.D;
     j.K = p.R;
     j.slice_len = wgrad_slice_len(p.R);
     j.mel_part = 0;
-    j.B0 = p.tape + ((size_t)(p.L - 1) * kEncTapePlanes + 5) * plane + (size_t)(p.T - 1) * RH;
+    j.B0 = p.tape + enc_tape_at(tape, p.L - 1, EncTape::Hid, p.T - 1, 0, 0);
     j.ldb0 = j.N0 = H;
     j.B1 = nullptr;
     j.N1 = 0;
     j.shift = 0;
-    j.out0 = j.out1 = off;
-    j.outb = off + (size_t)p.D * H;
+    j.out0 = j.out1 = f.w;
+    j.outb = f.b;
     hipLaunchKernelGGL(encode_wgrad_kernel, wgrad_grid(p.D, H, p.R), dim3(kWgradThreads), 0, stream, j);
     if ((err = hipGetLastError()) != hipSuccess) return err;
     hipLaunchKernelGGL(encode_reduce_kernel, dim3(reduce_blocks(total)), dim3(256), 0, stream, (const float*)j.partial, j.pstride,
@@ -394,14 +364,14 @@ hipError_t launch_encode_bwd(const ProblemEncodeBwd& p0, int H, hipStream_t stre
 
 int plan_string_encode_bwd(int R, int T, int n_mels, int H, int L, int D, char* buf, size_t cap) {
     const long long K = (long long)R * T;
-    int n = snprintf(buf, cap, "encode_bwd<%d>/%d", H, (int)(((long long)R + kEncBwdTile - 1) / kEncBwdTile));
+    Out o{buf, cap};
+    o.add("encode_bwd<%d>/%d", H, enc_tiles(R, kEncBwdTile));
     for (int l = 0; l <= L; ++l) {
         const dim3 g = l < L ? wgrad_grid(4 * H, (l ? H : n_mels) + H, K) : wgrad_grid(D, H, R);
-        n += snprintf((size_t)n < cap ? buf + n : nullptr, (size_t)n < cap ? cap - n : 0, ",encode_wgrad/%ux%ux%u", g.x, g.y, g.z);
+        o.add("encode_wgrad/%ux%ux%u", g.x, g.y, g.z);
     }
-    n += snprintf((size_t)n < cap ? buf + n : nullptr, (size_t)n < cap ? cap - n : 0, ",encode_reduce/%u",
-                  reduce_blocks(encoder_flat_floats(n_mels, H, L, D)));
-    return n;
+    o.add("encode_reduce/%u", reduce_blocks(encoder_flat_floats(n_mels, H, L, D)));
+    return o.done();
 }
 
 }  // namespace ge2e

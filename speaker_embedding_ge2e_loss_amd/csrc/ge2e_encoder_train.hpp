@@ -3,7 +3,7 @@
 //
 //   tape       what the backward reads, ALL of it stored (nothing is recomputed but tanh(c_t)): six planes per layer --
 //              the gate activations i, f, g, o, the cell c and the hidden state h -- each [T][R][H], then the raw
-//              projection y [R][D]:  float index (((l 6 + plane) T + t) R + r) H + u, y at 6 L T R H + r D + d.
+//              projection y [R][D]; EncTape below is the index map, the only one.
 //              6 L H T 4 bytes a window (+ 4 D): 2.9 MB at 3 x 256, T = 160, i.e. 24 GB at R = 8192.  h [T R][H] of a
 //              layer is one contiguous matrix over k = t R + r: the weight-gradient GEMM's B operand as it lies.
 //   bwd pack   per layer the matrix [4 H][C] (C = 2 H: weight_ih | weight_hh; layer 0: C = H, weight_hh alone -- no
@@ -19,22 +19,34 @@ namespace ge2e {
 
 constexpr int kEncBwdTile = 16;          // rows (windows) of a workgroup of the backward recurrence
 constexpr int kEncBwdPad = 4;            // floats between the rows of the dz plane in LDS: b128 reads of 16 rows miss each other
-constexpr int kEncTapePlanes = 6;        // i, f, g, o, c, h
 constexpr int kWgradThreads = 256;       // four waves: an output block of 64 x 64, wave w owns rows 16 w .. 16 w + 15
 constexpr int kWgradBlock = 64;
 constexpr int kWgradSliceMin = 512;      // k = (t, r) pairs of a slice while there are at most kWgradMaxSlices of them
 constexpr int kWgradMaxSlices = 32;
 
-inline size_t encoder_tape_floats(long long R, int T, int H, int L, int D) {
-    return (size_t)kEncTapePlanes * L * T * (size_t)R * H + (size_t)R * D;
+// The tape as the kernels and the launcher address it: plane stride T R H, a frame R H, planes named.  c_{t-1} is
+// plane C at t - 1: a kernel addresses one element with enc_tape_at and its neighbours in other planes and frames with
+// enc_tape_step from there (one 64-bit address per element, the steps uniform over the workgroup).
+struct EncTape {
+    enum Plane { I, F, G, O, C, Hid, kPlanes };
+    size_t plane;
+    int R, H, L;
+};
+__host__ __device__ inline EncTape enc_tape(long long R, int T, int H, int L) { return {(size_t)T * (size_t)R * H, (int)R, H, L}; }
+__host__ __device__ inline size_t enc_tape_at(const EncTape& v, int l, int plane, long long t, long long r, int u) {
+    return ((size_t)l * EncTape::kPlanes + plane) * v.plane + ((size_t)t * v.R + (size_t)r) * v.H + u;
 }
-// A layer's block of the backward pack, in floats, and the whole of it.
+__host__ __device__ inline ptrdiff_t enc_tape_step(const EncTape& v, int planes, int frames) {
+    return planes * (ptrdiff_t)v.plane + frames * ((ptrdiff_t)v.R * v.H);
+}
+__host__ __device__ inline size_t enc_tape_y(const EncTape& v) { return (size_t)EncTape::kPlanes * v.L * v.plane; }   // y [R][D]
+inline size_t encoder_tape_floats(long long R, int T, int H, int L, int D) { return enc_tape_y(enc_tape(R, T, H, L)) + (size_t)R * D; }
+// A layer's block of the backward pack, in floats; where layer l starts (l = L: the projection); the whole of it.
 __host__ __device__ inline size_t enc_bwd_layer_floats(int l, int H) { return (size_t)4 * H * (l ? 2 * H : H); }
-inline size_t encoder_packed_bwd_floats(int H, int L, int D) {
-    size_t n = (size_t)enc_pad16(D) * H;
-    for (int l = 0; l < L; ++l) n += enc_bwd_layer_floats(l, H);
-    return n;
+__host__ __device__ inline size_t enc_bwd_pack_layer(int l, int H) {
+    return l ? enc_bwd_layer_floats(0, H) + (size_t)(l - 1) * enc_bwd_layer_floats(1, H) : 0;
 }
+inline size_t encoder_packed_bwd_floats(int H, int L, int D) { return enc_bwd_pack_layer(L, H) + (size_t)enc_pad16(D) * H; }
 // LDS of the backward recurrence: the dh planes [L][16][H] and the dz plane [16][4 H + 4] (the projection's dy
 // [16][pad16(D) + 4] lies in it before the first step).  H = 256, L = 4: 64 KiB + 64.25 KiB of the CU's 160.
 inline size_t encoder_bwd_lds_bytes(int H, int L) {

@@ -5,34 +5,11 @@
 //   team<NCH,MR,RBT,softmax|contrast>   team_fwd<NCH,MR,RBT,softmax|contrast>
 //   tiled_prep<RM,NP>   tiled_sim<C>   tiled_simrows<C3,softmax|contrast,N256|Nany>   tiled_rows<W>   tiled_gc<C1|C2>
 //   tiled_gc<C3>/S (S = gc_split: the row pieces differ per split)   tiled_spk   tiled_ge<C>   tiled_reduce   tiled_cos
-#include <stdarg.h>
-#include <stdio.h>
-
 #include "../../include/ge2e_hip.h"
 #include "ge2e_plan.hpp"
 
 namespace ge2e {
 namespace {
-
-// snprintf-style accumulation into a caller's buffer: writes what fits, counts everything
-struct Out {
-    char* buf;
-    size_t cap;
-    int len = 0;
-    void add(const char* fmt, ...) __attribute__((format(printf, 2, 3))) {
-        char atom[64];
-        va_list ap;
-        va_start(ap, fmt);
-        const int n = vsnprintf(atom, sizeof atom, fmt, ap);
-        va_end(ap);
-        for (int i = -(len > 0); i < n; ++i, ++len)         // (a comma in front of every name but the first)
-            if (buf && (size_t)len + 1 < cap) buf[len] = i < 0 ? ',' : atom[i];
-    }
-    int done() {
-        if (buf && cap > 0) buf[(size_t)len < cap ? (size_t)len : cap - 1] = '\0';
-        return len;
-    }
-};
 
 const char* var_name(bool contrast) { return contrast ? "contrast" : "softmax"; }
 

@@ -3,9 +3,32 @@
 // switches on the plan it returns, and the plan queries of include/ge2e_hip.h (ge2e_plan.hip) print the same plan
 // without a GPU.  Device-dependent values -- grid sizes, occupancy -- are no part of a plan.
 #pragma once
+#include <stdarg.h>
 #include <stddef.h>
+#include <stdio.h>
 
 namespace ge2e {
+
+// snprintf-style accumulation of a plan into a caller's buffer: writes what fits, counts everything.  (Hidden: the
+// variadic member is never inlined and would be an exported symbol of the library otherwise.)
+struct __attribute__((visibility("hidden"))) Out {
+    char* buf;
+    size_t cap;
+    int len = 0;
+    void add(const char* fmt, ...) __attribute__((format(printf, 2, 3))) {
+        char atom[64];
+        va_list ap;
+        va_start(ap, fmt);
+        const int n = vsnprintf(atom, sizeof atom, fmt, ap);
+        va_end(ap);
+        for (int i = -(len > 0); i < n; ++i, ++len)         // (a comma in front of every name but the first)
+            if (buf && (size_t)len + 1 < cap) buf[len] = i < 0 ? ',' : atom[i];
+    }
+    int done() {
+        if (buf && cap > 0) buf[(size_t)len < cap ? (size_t)len : cap - 1] = '\0';
+        return len;
+    }
+};
 
 // tile configurations of the tiled contractions (ge2e_tiled.hip: C1 = 128 x 128, C2 = 256 x 256 fed from registers,
 // C3 = 256 x 256 fed by LDS-DMA); 0 = that kernel does not run

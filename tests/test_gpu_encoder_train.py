@@ -36,6 +36,7 @@ import encoder_grad_ref as gref
 import encoder_ref as enc
 from capi import GF, lib, ok  # noqa: F401
 from guarded import Buf, Workspace, dev, same_bits
+from speaker_embedding_ge2e_loss_amd import functional
 
 pytestmark = pytest.mark.gpu
 
@@ -91,7 +92,6 @@ def reference(name, normalize, zero_rows=None):
 
 def device_packs(lib, ps, shape):
     _, _, n_mels, H, L, D = shape
-    from speaker_embedding_ge2e_loss_amd import functional
     flat = torch.as_tensor(enc.flat(ps)).to(dev())
     packed = functional.encoder_pack(flat, n_mels, H, L, D)
     packed_bwd = Buf((lib.ge2e_encoder_packed_bwd_bytes(n_mels, H, L, D) // 4,))
@@ -118,7 +118,7 @@ def run_abi(lib, ps, x, g, shape, normalize, row_start=None):
     res = dict(out=out.get("ge2e_encode", finite=False), out_train=out_train.get("ge2e_encode_train", finite=False))
     for key, pattern in (("flat", 0xFF), ("flat_again", 0x7F)):
         ws.fill(pattern)
-        flat = Buf((GF_flat_numel(n_mels, H, L, D),))
+        flat = Buf((functional.encoder_flat_numel(n_mels, H, L, D),))
         ok(lib.ge2e_encode_bwd(packed_bwd.ptr, mel.ptr, rs_ptr, R, T, n_mels, H, L, D, int(normalize), tape.ptr, gbuf.ptr,
                                flat.ptr, ws.ptr, None), "ge2e_encode_bwd")
         res[key] = flat.get("ge2e_encode_bwd", finite=False)
@@ -127,10 +127,6 @@ def run_abi(lib, ps, x, g, shape, normalize, row_start=None):
     for b in (mel, gbuf, tape, packed_bwd, out, out_train):
         assert b.guards_intact()
     return res
-
-
-def GF_flat_numel(n_mels, H, L, D):
-    return 4 * H * (n_mels + H + 2) + (L - 1) * 4 * H * (2 * H + 2) + D * H + D
 
 
 @functools.lru_cache(maxsize=None)
@@ -179,6 +175,26 @@ def test_dz_planes_against_float64(lib):
         for l, want in enumerate(ref["dzs"]):
             got = dz[l].transpose(1, 0, 2)                   # (R, T, 4H)
             assert gref.rel_err(got, want) <= 1e-4, (name, l)
+
+
+@pytest.mark.parametrize("shape", ec.PACK_SHAPES + ((12, 128, 4, 17),))
+def test_pack_bwd_on_its_own(lib, shape):
+    """Whatever the order inside a tile (the gradient tests prove that): the backward pack holds weight_hh of layer 0,
+    weight_ih and weight_hh of every layer above and the projection weight, each value once -- no bias, no weight_ih of
+    layer 0 -- and +0.0 in the projection's rows past D."""
+    n_mels, H, L, D = shape
+    ps, _ = ec.integer_params(*shape)
+    kept = [ps[4 * l + i] for l in range(L) for i in (0, 1) if (l, i) != (0, 0)] + [ps[-2]]
+    expected = np.sort(np.concatenate([w.ravel() for w in kept]))
+    n_pad = ((D + 15) // 16 * 16 - D) * H
+    assert lib.ge2e_encoder_packed_bwd_bytes(*shape) == 4 * (expected.size + n_pad)
+    flat = Buf((functional.encoder_flat_numel(*shape),), data=enc.flat(ps))      # a read past either end is a NaN
+    packed = Buf((expected.size + n_pad,))                                       # NaN poison: every byte is written
+    ok(lib.ge2e_encoder_pack_bwd(flat.ptr, n_mels, H, L, D, packed.ptr, None), "ge2e_encoder_pack_bwd")
+    got = packed.get("ge2e_encoder_pack_bwd")
+    assert flat.guards_intact() and packed.guards_intact()
+    assert np.array_equal(np.sort(got[got != 0]), expected)
+    assert int((got.view(np.uint32) == 0).sum()) == n_pad
 
 
 def test_windows_addressed_in_place(lib):
@@ -328,7 +344,7 @@ def test_forward_and_backward_in_one_captured_graph(lib):
     out = torch.empty(R, D, device=dev())
     tape = torch.empty(lib.ge2e_encode_train_tape_bytes(*shape) // 4, device=dev())
     ws = torch.empty(lib.ge2e_encode_bwd_workspace_bytes(*shape) // 4, device=dev())
-    flat = torch.empty(GF_flat_numel(n_mels, H, L, D), device=dev())
+    flat = torch.empty(functional.encoder_flat_numel(n_mels, H, L, D), device=dev())
 
     def both():
         s = torch.cuda.current_stream().cuda_stream

@@ -4,7 +4,7 @@ bit for bit on one GPU:
     GE2E_HIP_LIB=$PWD/speaker_embedding_ge2e_loss_amd/libge2e_hip_parent.so python tools/output_digest.py > a.txt
     python tools/output_digest.py > b.txt && diff a.txt b.txt
 
-(tools/build_rev.sh builds the other revision's library.)  Five sections:
+(tools/build_rev.sh builds the other revision's library.)  Six sections:
 
   1. the fp32 matrix-core implementations: loss | per | dE | dw | db per (implementation, shape, variant), with and
      without the gradient.  A pair the library refuses prints SKIP.
@@ -42,6 +42,13 @@ bit for bit on one GPU:
        (48, 272, 2, 264)  gc<C3>/1, 192 tiles     (65, 272, 2, 264)  gc<C3>/2, 520 tiles: a walk of more than one round
        (32, 528, 2, 264)  gc<C3>/4, 768 tiles     (25, 800, 3, 264)  gc<C3>/8, 1600 tiles; ge<C3> walks 500
      ge2e_cos_sim on its matrix-core route (prep, sim<C1>, tiled_cos) at (1, 16, 3, 64), (2, 65, 3, 128), (1, 300, 3, 768).
+  6. the encoder through the C ABI, one line per buffer: the forward pack, the backward pack, ge2e_encode's out (normalised
+     and raw), ge2e_encode_train's out | tape, ge2e_encode_bwd's d_flat | dZ [L][T][R][4H] | dY [R][D] -- the exact ranges:
+     the workspace's round-to-64 gaps and unused slice partials are never written.  Shapes (R, T, n_mels, H, L, D):
+       (33, 2, 40, 128, 2, 64)  both tile heights with pad rows     (17, 5, 20, 256, 4, 24)  H = 256, four layers
+       (3, 2, 13, 128, 1, 37)   n_mels no multiple of 4: the scalar-load arm; D padding
+       (73, 7, 12, 128, 1, 16)  one K-slice of the weight gradient  (33, 32, 12, 128, 1, 16)  three K-slices
+       (33, 2, 40, 128, 2, 64) again through row_start: windows one frame apart, overlapping
 
 Exit status 1 if one of the fp32 matrix-core implementations appears in no line, or if the plan of a line of section 5 is
 not the one its table claims.
@@ -56,6 +63,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 import bounds_cases as bc  # noqa: E402
+import encoder_ref as enc  # noqa: E402
 from oracle import ge2e_oracle as orc  # noqa: E402
 from speaker_embedding_ge2e_loss_amd import _lib  # noqa: E402
 from speaker_embedding_ge2e_loss_amd import functional as GF  # noqa: E402
@@ -101,6 +109,9 @@ TILED_PLAN_CASES = [c for c in bc.PLAN_CASES if c[1] == "tiled"]
 TILED_COS_CASES = [((1, 16, 3, 64), ["tiled_prep<10,1>", "tiled_sim<C1>", "tiled_cos"]),
                    ((2, 65, 3, 128), ["tiled_prep<10,1>", "tiled_sim<C1>", "tiled_cos"]),
                    ((1, 300, 3, 768), ["tiled_prep<10,3>", "tiled_sim<C1>", "tiled_cos"])]
+# section 6: ((R, T, n_mels, H, L, D), windows through row_start)
+ENCODER_CASES = [((33, 2, 40, 128, 2, 64), False), ((17, 5, 20, 256, 4, 24), False), ((3, 2, 13, 128, 1, 37), False),
+                 ((73, 7, 12, 128, 1, 16), False), ((33, 32, 12, 128, 1, 16), False), ((33, 2, 40, 128, 2, 64), True)]
 
 
 def digest(o, names=("loss", "per", "dE", "dw", "db")):
@@ -336,6 +347,44 @@ def tiled_section(dev, w, b):
     return wrong
 
 
+def encoder_section(dev):
+    lib = _lib.load()
+    for shape, windows in ENCODER_CASES:
+        R, T, n_mels, H, L, D = shape
+        tag = f"encoder {shape}" + (" row_start" if windows else "")
+        rng = np.random.default_rng(sum(shape) + windows)
+        flat = torch.as_tensor(enc.flat(enc.random_params(n_mels, H, L, D, seed=sum(shape))), device=dev)
+        frames = R + T - 1 if windows else R * T                  # windows: row r starts at frame r
+        mel = torch.as_tensor(rng.uniform(0.0, 0.96, (frames, n_mels)).astype(np.float32), device=dev)
+        rs = torch.arange(R, dtype=torch.int64, device=dev) if windows else None
+        rs_ptr = rs.data_ptr() if windows else None
+        g = torch.as_tensor(rng.standard_normal((R, D)).astype(np.float32), device=dev)
+
+        def floats(nbytes):
+            return torch.full((nbytes // 4,), float("nan"), device=dev)
+        packed = floats(lib.ge2e_encoder_packed_bytes(n_mels, H, L, D))
+        packed_bwd = floats(lib.ge2e_encoder_packed_bwd_bytes(n_mels, H, L, D))
+        tape, ws = floats(lib.ge2e_encode_train_tape_bytes(*shape)), floats(lib.ge2e_encode_bwd_workspace_bytes(*shape))
+        out, d_flat = floats(4 * R * D), floats(4 * flat.numel())
+        with torch.cuda.device(dev):
+            _lib.check(lib.ge2e_encoder_pack(flat.data_ptr(), n_mels, H, L, D, packed.data_ptr(), None), "ge2e_encoder_pack")
+            line(f"{tag} pack", packed)
+            _lib.check(lib.ge2e_encoder_pack_bwd(flat.data_ptr(), n_mels, H, L, D, packed_bwd.data_ptr(), None), "ge2e_encoder_pack_bwd")
+            line(f"{tag} pack_bwd", packed_bwd)
+            for normalize in (1, 0):
+                _lib.check(lib.ge2e_encode(packed.data_ptr(), mel.data_ptr(), rs_ptr, R, T, n_mels, H, L, D, normalize,
+                                           out.data_ptr(), None), "ge2e_encode")
+                line(f"{tag} encode {'normalised' if normalize else 'raw'}", out)
+            _lib.check(lib.ge2e_encode_train(packed.data_ptr(), mel.data_ptr(), rs_ptr, R, T, n_mels, H, L, D, 1, out.data_ptr(),
+                                             tape.data_ptr(), None), "ge2e_encode_train")
+            line(f"{tag} encode_train", out, tape)
+            _lib.check(lib.ge2e_encode_bwd(packed_bwd.data_ptr(), mel.data_ptr(), rs_ptr, R, T, n_mels, H, L, D, 1, tape.data_ptr(),
+                                           g.data_ptr(), d_flat.data_ptr(), ws.data_ptr(), None), "ge2e_encode_bwd")
+            n_dz = L * T * R * 4 * H
+            dy = (n_dz + 63) // 64 * 64                           # offsets in the workspace are rounded up to 64 floats
+            line(f"{tag} encode_bwd", d_flat, ws[:n_dz], ws[dy:dy + R * D])
+
+
 def main():
     dev = torch.device("cuda:0")
     w, b = torch.tensor(7.5, device=dev), torch.tensor(-2.0, device=dev)
@@ -344,6 +393,7 @@ def main():
     bank_section(dev)
     index_section(dev)
     wrong = tiled_section(dev, w, b)
+    encoder_section(dev)
     if missing:
         print("no line for:", " ".join(missing))
     for tag in wrong:
