@@ -748,6 +748,67 @@ int ge2e_melspec(const float* packed, const float* wav,
                  float* out /* [total_frames][n_mels] */, void* stream);
 int ge2e_melspec_plan(int U, long long total_frames, int n_fft, int hop, int n_mels, char* buf, size_t buf_bytes);
 
+/*
+ * RESAMPLING AND GAIN (csrc/ge2e_resample.hip): the stage in front of ge2e_melspec -- recordings at another rate to the
+ * model's (the reference's librosa.resample, utils/audio_utils.py:83-85) in ONE launch, and the per-utterance gain of its
+ * normalize_volume (s0:94-105) in two.  float32 in and out.
+ *
+ * The definition.  Rates sr_in -> sr_out with g = gcd: L = sr_out / g (up), M = sr_in / g (down); a bank taps[L][W] with
+ * W = 2 lead + 1, float32 on the device, ANY values: the kernel does not know what a Kaiser window is
+ * (audio.resample_bank makes the project's).  Utterance u is x = wav[in_start[u] .. + in_len[u]) (int64, in samples, on
+ * the device), taken as zero outside its own extent; samples outside it are never read.  It has
+ * n_out = (in_len L + M - 1) div M outputs; output n, with t = n M in 64-bit, i0 = t div L and p = t mod L, is
+ *     y[n] = sum_{k=0}^{W-1} taps[p][k] x[i0 + lead - k]
+ * Supported: 1 <= L <= 640, 1 <= M <= 640, odd W <= 1025 ({8000, 11025, 22050, 24000, 32000, 44100, 48000, 96000} -> 16000
+ * under both presets of audio.resample_bank); everything else is GE2E_ERR_IMPL and nothing is launched.
+ *
+ * ge2e_resample_pack, once per bank.  packed (ge2e_resample_packed_bytes, 16-byte aligned; every byte is written):
+ * [W][pad4(L)] floats, packed[k][q] = taps[(q M) mod L][k] -- the phases in the order consecutive outputs meet them -- and
+ * zero in the pad columns.  One launch.  Checks, in this order: GE2E_ERR_NULL (taps or packed), GE2E_ERR_SHAPE (L or M < 1,
+ * lead < 0), GE2E_ERR_IMPL, GE2E_ERR_ALIGN (packed not 16-byte aligned).
+ *
+ * ge2e_resample.  out[out_start[u] + n], n < out_start[u + 1] - out_start[u]; out_start [U + 1] (int64, device) is the
+ * prefix sum of n_out and total_out its last entry: host arithmetic on the lengths, the caller's, as frame_start is for
+ * ge2e_melspec.  An utterance of length 0 has no outputs and is legal among others.  Exactly total_out elements are written.
+ * One launch of floor(total_out / tile) + U workgroups of 256 threads, no workspace, no allocation, no synchronisation,
+ * everything on `stream`, grid from the arguments alone: fit for a HIP graph.  A workgroup owns `tile` consecutive outputs of
+ * ONE utterance (it finds the utterance by a bisection of out_start) and stages their input span in LDS, the zeros of the
+ * extent filled in there; the bank is read from L2.  Accumulation order: one fp32 accumulator per output, started at -0,
+ * acc = fma(taps[p][k], x[i0 + lead - k], acc) for k = 0, 1, ..., W - 1 in this order, the zeros outside the extent included.
+ * So the bits of y[n] depend on that utterance's samples, on n and on `packed` ALONE: not on U, on the utterance's place in
+ * the buffer or on the output's place in its tile.  A NaN sample makes exactly the outputs whose window
+ * [i0 + lead - W + 1, i0 + lead] holds it NaN.
+ * Checked on the host before anything is launched, in this order: GE2E_ERR_NULL (packed, wav, in_start, in_len, out_start or
+ * out), GE2E_ERR_SHAPE (U, L, M or total_out < 1, lead < 0), GE2E_ERR_IMPL (the shape, or more than 2^31 - 1 workgroups),
+ * GE2E_ERR_ALIGN (packed or out not 16-byte aligned, wav not aligned to a float).
+ *
+ * ge2e_resample_plan (diagnostics, no GPU): "resample<lds,R>/tile/grid" -- the instantiation (R outputs a thread, their
+ * samples staged in LDS; "global": a span too long for LDS, read from global memory), the outputs of a tile and the grid --
+ * snprintf-style as ge2e_melspec_plan; < 0: GE2E_ERR_SHAPE or GE2E_ERR_IMPL as the call itself.  (No part of ge2e_plan_atoms.)
+ *
+ * ge2e_volume_gain.  gain_out[u] (float32, device) for utterance u = wav[utt_start[u] .. + utt_len[u]):
+ *     S = sum x^2, rms = sqrt(S / utt_len), change = target_dbfs - 20 log10(rms), gain = 10^(change / 20),
+ * and with increase_only != 0 gain = 1 where change < 0; all in double, rounded once to float32.  A silent utterance gives
+ * +inf and a length of 0 NaN, as audio.volume_gain does.  S has a fixed order: tiles of 2048 samples counted from the
+ * utterance's start; tile j belongs to slice j mod 128; thread t of a slice's 256 adds the squares of samples
+ * 2048 j + t + 256 i, i = 0 .. 7, tile after tile in index order; the 256 sums are added by a butterfly over each wave of 64,
+ * then the four waves in order; a second launch adds the utterance's 128 slices in index order.  No atomics: the same bits
+ * on every call, and the gain of an utterance does not depend on the others.  Two launches, grid from U alone.  workspace:
+ * ge2e_volume_gain_workspace_bytes(total_samples, U) bytes (0 for U < 1 or total_samples < 0), 16-byte aligned; its
+ * contents need not be kept.  Checks, in this order: GE2E_ERR_NULL (wav, utt_start, utt_len, gain_out or workspace),
+ * GE2E_ERR_SHAPE (U < 1), GE2E_ERR_ALIGN (workspace not 16-byte aligned, wav or gain_out not aligned to a float).
+ */
+size_t ge2e_resample_packed_bytes(int L, int M, int W);   /* 0 for an unsupported shape */
+int ge2e_resample_pack(const float* taps /* [L][2 lead + 1] */, int L, int M, int lead, float* packed, void* stream);
+int ge2e_resample(const float* packed, const float* wav,
+                  const long long* in_start, const long long* in_len,       /* [U], device, in samples */
+                  const long long* out_start /* [U+1], device */, int U, long long total_out,
+                  int L, int M, int lead, float* out /* [total_out] */, void* stream);
+int ge2e_resample_plan(int U, long long total_out, int L, int M, int lead, char* buf, size_t buf_bytes);
+size_t ge2e_volume_gain_workspace_bytes(long long total_samples, int U);
+int ge2e_volume_gain(const float* wav, const long long* utt_start, const long long* utt_len /* [U], device */, int U,
+                     float target_dbfs, int increase_only, float* gain_out /* [U] */, void* workspace, void* stream);
+
 /* ---- diagnostics (tests only): which kernels a call launches ---------------------------------------------------------
  * Below ge2e_resolve_impl every launcher chooses again among kernels and template instantiations.  These queries print
  * that choice -- made by the very functions the launchers switch on -- without a GPU and without launching anything:

@@ -195,6 +195,11 @@ def melspec_plan(U: int, total_frames: int, n_fft: int, hop: int, n_mels: int) -
     return _plan(load().ge2e_melspec_plan, U, total_frames, n_fft, hop, n_mels)
 
 
+def resample_plan(U: int, total_out: int, L: int, M: int, lead: int) -> list[str]:
+    """... ge2e_resample would launch: ["resample<lds,R>/tile/grid"] ("global": the samples are not staged in LDS)."""
+    return _plan(load().ge2e_resample_plan, U, total_out, L, M, lead)
+
+
 def plan_atoms() -> list[str]:
     """Every kernel name the two queries can return."""
     return _plan(load().ge2e_plan_atoms)

@@ -3,8 +3,11 @@ reference takes from scipy and librosa -- a periodic Hann window, the Slaney mel
 partial-utterance arithmetic (``compute_partial_slices``), the per-utterance gain of ``normalize_volume``, and
 ``MelFrontEnd``, which holds the packed tables per device and turns waveforms into the frames ``functional.encode`` reads.
 
-Out of scope: decoding audio files, resampling and the webrtcvad silence trimming.  The caller hands in samples at the
-model's sampling rate.
+A recording at another rate is resampled on the device first (``resample_bank``, ``functional.resample``: the reference's
+``librosa.resample`` step, with the project's own exact-phase Kaiser-windowed sinc), and its gain then comes from
+``functional.volume_gain``.
+
+Out of scope: decoding audio files and the webrtcvad silence trimming.  The caller hands in samples and their rate.
 """
 from __future__ import annotations
 
@@ -94,10 +97,66 @@ def volume_gain(wav: torch.Tensor, lengths: Optional[Sequence[int]] = None, targ
     return gain.float()
 
 
+class ResampleBank(NamedTuple):
+    up: int               # L = sr_out / gcd
+    down: int             # M = sr_in / gcd
+    lead: int             # taps either side of the centre: the width of a phase is 2 lead + 1
+    taps: torch.Tensor    # (up, 2 lead + 1) float64
+
+
+# (zero crossings, roll-off, Kaiser beta): the constants resampy publishes for its filters of the same names
+RESAMPLE_PRESETS = {"kaiser_best": (64, 0.9475937167399596, 14.769656459379492),
+                    "kaiser_fast": (16, 0.85, 8.555504641634386)}
+
+
+def resample_bank(sr_in: int, sr_out: int, filter="kaiser_best") -> ResampleBank:
+    """The polyphase bank of a Kaiser-windowed sinc for ``sr_in -> sr_out``, in float64 (``functional.resample_pack`` rounds
+    it once to float32).  With g = gcd, L = sr_out / g, M = sr_in / g, s = min(1, L / M), Z zero crossings,
+    lead = ceil(Z / s) and u = (k - lead + p / L) s:
+        taps[p][k] = s rolloff sinc(rolloff u) I0(beta sqrt(1 - (u / Z)^2)) / I0(beta)   for |u| < Z, else 0
+    so that output n, with i0 = n M div L and p = n M mod L, is sum_k taps[p][k] x[i0 + lead - k].  ``filter``:
+    "kaiser_best", "kaiser_fast" or ``(zeros, rolloff, beta)``.  Every phase is exact: no table interpolation."""
+    sr_in, sr_out = int(sr_in), int(sr_out)
+    if sr_in < 1 or sr_out < 1:
+        raise ValueError("the rates must be positive")
+    if isinstance(filter, str):
+        if filter not in RESAMPLE_PRESETS:
+            raise ValueError(f"filter must be one of {sorted(RESAMPLE_PRESETS)} or (zeros, rolloff, beta), got {filter!r}")
+        filter = RESAMPLE_PRESETS[filter]
+    Z, rolloff, beta = filter
+    if not (Z > 0 and 0 < rolloff <= 1 and beta >= 0):
+        raise ValueError("(zeros, rolloff, beta) needs zeros > 0, 0 < rolloff <= 1 and beta >= 0")
+    g = math.gcd(sr_in, sr_out)
+    L, M = sr_out // g, sr_in // g
+    if L >= M:
+        s, lead = 1.0, int(math.ceil(Z))
+    else:
+        s = L / M
+        lead = -((-Z * M) // L) if isinstance(Z, int) else int(math.ceil(Z * M / L))
+    k = np.arange(2 * lead + 1, dtype=np.float64)[None, :]
+    p = np.arange(L, dtype=np.float64)[:, None]
+    u = (k - lead + p / L) * s
+    inside = np.abs(u) < Z
+    window = np.i0(beta * np.sqrt(np.where(inside, 1.0 - (u / Z) ** 2, 0.0))) / np.i0(beta)
+    taps = np.where(inside, s * rolloff * np.sinc(rolloff * u) * window, 0.0)
+    return ResampleBank(L, M, lead, torch.from_numpy(np.ascontiguousarray(taps)))
+
+
+def resampled_length(n: int, up: int, down: int) -> int:
+    """The samples ``n`` samples become: ceil(n up / down), as librosa sizes its output."""
+    return (int(n) * int(up) + int(down) - 1) // int(down)
+
+
 class MelFrontEnd:
     """Waveforms to mel frames at one set of audio settings.  The window and filterbank are built once in float64 and
     packed once per device (``functional.melspec_pack``); ``frames`` is one ``functional.melspec`` call over all the
-    waveforms, ``partials`` the partial utterances of every waveform as ``get_mel_spects_from_audio`` returns them."""
+    waveforms, ``partials`` the partial utterances of every waveform as ``get_mel_spects_from_audio`` returns them.
+
+    ``source_rate``: the rate of the waveforms handed in where it is not ``sampling_rate``.  They are then resampled on the
+    device in one launch (``functional.resample`` with ``resample_bank(source_rate, sampling_rate, resample_filter)``,
+    packed once per (rate, filter, device)), the partial-slice arithmetic runs on the resampled lengths and the gain of
+    ``normalize_volume`` comes from ``functional.volume_gain`` on the resampled signal.  One rate for all the waveforms of
+    a call: a different rate per waveform is not built (call once per rate)."""
 
     def __init__(self, sampling_rate: int = 16000, n_fft: int = 1024, hop_length: int = 128, n_mels: int = 80,
                  fmin: float = 90.0, fmax: float = 7600.0, mel_window_step: float = 10, partials_n_frames: int = 180,
@@ -110,6 +169,7 @@ class MelFrontEnd:
         self.window = hann_window(n_fft)
         self.basis = mel_filterbank(sampling_rate, n_fft, n_mels, fmin, fmax)
         self._tables = {}
+        self._resamplers = {}
 
     @classmethod
     def from_hp(cls, hp) -> "MelFrontEnd":
@@ -134,12 +194,37 @@ class MelFrontEnd:
                               partials_n_frames=self.partials_n_frames, rate=self.rate_partial_slices,
                               min_coverage=self.min_coverage)
 
+    def _resampling(self, source_rate) -> bool:
+        return source_rate is not None and int(source_rate) != int(self.sampling_rate)
+
+    def resampler(self, source_rate: int, device, resample_filter="kaiser_best"):
+        """``functional.resample_pack`` of ``resample_bank(source_rate, sampling_rate, resample_filter)`` on ``device``,
+        made on first use and kept per (rate, filter, device)."""
+        from . import functional as GF
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        key = (int(source_rate), resample_filter if isinstance(resample_filter, str) else tuple(resample_filter), device)
+        t = self._resamplers.get(key)
+        if t is None:
+            bank = resample_bank(source_rate, self.sampling_rate, resample_filter)
+            t = self._resamplers[key] = GF.resample_pack(bank.taps.to(device), bank.up, bank.down, bank.lead)
+        return t
+
+    def resampled_lengths(self, lengths, source_rate=None) -> list:
+        """The lengths ``frames`` works with: ``lengths`` themselves, or what ``source_rate`` makes of them."""
+        if not self._resampling(source_rate):
+            return [int(n) for n in lengths]
+        g = math.gcd(int(source_rate), int(self.sampling_rate))
+        return [resampled_length(n, self.sampling_rate // g, int(source_rate) // g) for n in lengths]
+
     def frames(self, wavs, normalize_volume: bool = False, pad_to_partials: bool = False, mode: str = "db",
-               native: Optional[bool] = None):
+               native: Optional[bool] = None, source_rate: Optional[int] = None, resample_filter="kaiser_best"):
         """``(frames, frame_start)`` of ``functional.melspec`` for a list of 1-D float32 device waveforms (or one): all of
         them in one launch.  ``normalize_volume``: the gain of ``normalize_volume(increase_only=True)``, applied in the
         kernel.  ``pad_to_partials``: every waveform zero-extended to the end of its last partial slice, as
-        ``get_mel_spects_from_audio(partial_slices=True)`` pads it."""
+        ``get_mel_spects_from_audio(partial_slices=True)`` pads it.  ``source_rate`` / ``resample_filter``: the rate of
+        the waveforms where it is not ``sampling_rate`` (see the class; None: they are at the model's rate)."""
         from . import functional as GF
         wavs = [wavs] if isinstance(wavs, torch.Tensor) else list(wavs)
         if not wavs:
@@ -147,16 +232,25 @@ class MelFrontEnd:
         dev = wavs[0].device
         lengths = [int(w.numel()) for w in wavs]
         flat = wavs[0].detach().float().contiguous() if len(wavs) == 1 else torch.cat([w.detach().float().reshape(-1) for w in wavs])
+        gain = None
+        if self._resampling(source_rate):
+            flat, lengths = GF.resample(self.resampler(source_rate, dev, resample_filter), flat, lengths, native=native)
+            if normalize_volume:
+                gain = GF.volume_gain(flat, lengths, self.target_dbfs, increase_only=True, native=native)
+        elif normalize_volume:
+            gain = volume_gain(flat, lengths, self.target_dbfs, increase_only=True)
         padded = [self.slices(n).padded_length for n in lengths] if pad_to_partials else None
-        gain = volume_gain(flat, lengths, self.target_dbfs, increase_only=True) if normalize_volume else None
         return GF.melspec(self.tables(dev), flat, lengths, hop=self.hop_length, padded_lengths=padded, gain=gain, mode=mode,
                           min_level_db=self.min_level_db, ref_level_db=self.ref_level_db, native=native)
 
-    def partial_rows(self, lengths, frame_start):
+    def partial_rows(self, lengths, frame_start, source_rate: Optional[int] = None, resample_filter=None):
         """``(row_start, owner)`` Python lists: the first row of ``frames(pad_to_partials=True)`` of every partial
         utterance and the waveform it belongs to; a partial whose frames the spectrogram does not hold is left out, as
-        s0:59 leaves it out."""
+        s0:59 leaves it out.  ``lengths``: the waveforms' own, at ``source_rate`` where that is given.
+        ``resample_filter`` is accepted so that the three methods take the same arguments and is ignored: the rows
+        depend on the lengths alone, which no filter changes."""
         rows, owner = [], []
+        lengths = self.resampled_lengths(lengths, source_rate)
         for u, n in enumerate(lengths):
             have = frame_start[u + 1] - frame_start[u]
             for s in self.slices(n).mel_starts:
@@ -165,13 +259,15 @@ class MelFrontEnd:
                     owner.append(u)
         return rows, owner
 
-    def partials(self, wavs, normalize_volume: bool = False, native: Optional[bool] = None):
+    def partials(self, wavs, normalize_volume: bool = False, native: Optional[bool] = None,
+                 source_rate: Optional[int] = None, resample_filter="kaiser_best"):
         """Per waveform the tensor ``get_mel_spects_from_audio(partial_slices=True)`` returns, (partials,
         partials_n_frames, n_mels) float32: gathered copies of the frames (``SpeakerEncoder.embed_audio`` addresses them
-        in place instead)."""
+        in place instead).  ``source_rate`` / ``resample_filter`` as ``frames``."""
         wavs = [wavs] if isinstance(wavs, torch.Tensor) else list(wavs)
-        frames, frame_start = self.frames(wavs, normalize_volume, pad_to_partials=True, native=native)
-        rows, owner = self.partial_rows([int(w.numel()) for w in wavs], frame_start)
+        frames, frame_start = self.frames(wavs, normalize_volume, pad_to_partials=True, native=native,
+                                          source_rate=source_rate, resample_filter=resample_filter)
+        rows, owner = self.partial_rows([int(w.numel()) for w in wavs], frame_start, source_rate)
         T = self.partials_n_frames
         return [torch.stack([frames[r:r + T] for r, o in zip(rows, owner) if o == u]) if u in owner
                 else frames.new_zeros(0, T, self.n_mels) for u in range(len(wavs))]

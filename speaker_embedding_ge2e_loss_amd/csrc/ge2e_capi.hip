@@ -17,6 +17,7 @@
 #include "ge2e_encoder.hpp"
 #include "ge2e_encoder_train.hpp"
 #include "ge2e_melspec.hpp"
+#include "ge2e_resample.hpp"
 #include "ge2e_identify.hpp"
 #include "ge2e_snorm.hpp"
 #include "ge2e_helpers.hpp"
@@ -773,6 +774,60 @@ int ge2e_melspec_plan(int U, long long total_frames, int n_fft, int hop, int n_m
     const int rc = melspec_shape_check(U, total_frames, n_fft, hop, n_mels);
     if (rc != GE2E_OK) return rc;
     return plan_string_melspec(total_frames, n_fft, buf, buf_bytes);
+}
+
+// RESAMPLING AND GAIN (include/ge2e_hip.h, csrc/ge2e_resample.hip): the bank packed once per (rates, filter), then recordings
+// to the model's rate in one launch; the per-utterance gain of normalize_volume in two.
+size_t ge2e_resample_packed_bytes(int L, int M, int W) {
+    return resample_supported(L, M, W) ? resample_packed_floats(L, W) * sizeof(float) : 0;
+}
+
+int ge2e_resample_pack(const float* taps, int L, int M, int lead, float* packed, void* stream) {
+    if (!taps || !packed) return GE2E_ERR_NULL;
+    if (L < 1 || M < 1 || lead < 0) return GE2E_ERR_SHAPE;
+    if (!resample_supported(L, M, 2LL * lead + 1)) return GE2E_ERR_IMPL;
+    if (!aligned16(packed)) return GE2E_ERR_ALIGN;
+    return (int)launch_resample_pack(taps, L, M, 2 * lead + 1, packed, (hipStream_t)stream);
+}
+
+static int resample_shape_check(int U, long long total_out, int L, int M, int lead) {
+    if (U < 1 || L < 1 || M < 1 || total_out < 1 || lead < 0) return GE2E_ERR_SHAPE;
+    if (!resample_supported(L, M, 2LL * lead + 1)) return GE2E_ERR_IMPL;
+    // (a grid of more than 2^31 - 1 tiles has no launch)
+    if (resample_grid(total_out, U, resample_plan(L, M, 2 * lead + 1).tile) > 0x7fffffffLL) return GE2E_ERR_IMPL;
+    return GE2E_OK;
+}
+
+int ge2e_resample(const float* packed, const float* wav, const long long* in_start, const long long* in_len,
+                  const long long* out_start, int U, long long total_out, int L, int M, int lead, float* out, void* stream) {
+    if (!packed || !wav || !in_start || !in_len || !out_start || !out) return GE2E_ERR_NULL;
+    const int rc = resample_shape_check(U, total_out, L, M, lead);
+    if (rc != GE2E_OK) return rc;
+    if (!aligned16(packed) || !aligned16(out) || ((uintptr_t)wav & 3)) return GE2E_ERR_ALIGN;
+    const int W = 2 * lead + 1;
+    const ResamplePlan plan = resample_plan(L, M, W);
+    const ProblemResample p = {packed, wav, in_start, in_len, out_start, out, U, L, M, lead, W, resample_lpad(L), plan.B,
+                               plan.tile, plan.span};
+    return (int)launch_resample(p, plan, resample_grid(total_out, U, plan.tile), (hipStream_t)stream);
+}
+
+int ge2e_resample_plan(int U, long long total_out, int L, int M, int lead, char* buf, size_t buf_bytes) {
+    const int rc = resample_shape_check(U, total_out, L, M, lead);
+    if (rc != GE2E_OK) return rc;
+    return plan_string_resample(total_out, U, L, M, 2 * lead + 1, buf, buf_bytes);
+}
+
+size_t ge2e_volume_gain_workspace_bytes(long long total_samples, int U) {
+    return (total_samples < 0 || U < 1) ? 0 : volume_gain_workspace_bytes(U);
+}
+
+int ge2e_volume_gain(const float* wav, const long long* utt_start, const long long* utt_len, int U, float target_dbfs,
+                     int increase_only, float* gain_out, void* workspace, void* stream) {
+    if (!wav || !utt_start || !utt_len || !gain_out || !workspace) return GE2E_ERR_NULL;
+    if (U < 1) return GE2E_ERR_SHAPE;
+    if (!aligned16(workspace) || ((uintptr_t)wav & 3) || ((uintptr_t)gain_out & 3)) return GE2E_ERR_ALIGN;
+    return (int)launch_volume_gain(wav, utt_start, utt_len, U, (double)target_dbfs, increase_only != 0, gain_out,
+                                   (double*)workspace, (hipStream_t)stream);
 }
 
 // ---- diagnostics: the launch plan of a call, from the launchers' own decision functions (ge2e_plan.hpp); no GPU needed ----

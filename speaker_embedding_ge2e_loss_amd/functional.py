@@ -1674,6 +1674,211 @@ def melspec(packed, wav: torch.Tensor, lengths=None, *, hop: int, n_fft: Optiona
     return out, layout.frame_start
 
 
+def resample_supported(up: int, down: int, width: int) -> bool:
+    """Banks ge2e_resample runs: up and down in 1 .. 640 and an odd width (taps a phase) of at most 1025."""
+    return _lib.load().ge2e_resample_packed_bytes(int(up), int(down), int(width)) > 0
+
+
+class ResampleTables(NamedTuple):
+    """What ``resample_pack`` returns: the bank (up, 2 lead + 1) as given (float32, the torch route reads it), the ratio and
+    ``packed``, ge2e_resample_pack's buffer, or None where the shape has no native kernel."""
+    packed: Optional[torch.Tensor]
+    taps: torch.Tensor
+    up: int
+    down: int
+    lead: int
+    weight: torch.Tensor     # the torch route's conv1d weight (up, 1, width + (up - 1) down // up)
+
+    @property
+    def width(self) -> int:
+        return self.taps.shape[1]
+
+
+class ResampleLayout(NamedTuple):
+    """Where the utterances of a flat waveform buffer lie and where their resampled samples go: int64 device tensors for the
+    kernel, ``out_start`` also as a Python list (U + 1 entries, the last one the total).  Pure arithmetic on lengths."""
+    in_start: torch.Tensor
+    in_len: torch.Tensor
+    out_start_dev: torch.Tensor
+    out_start: list
+    lengths: list
+    out_lengths: list
+    up: int
+    down: int
+
+
+def _resample_conv_weight(taps: torch.Tensor, up: int, down: int) -> torch.Tensor:
+    """The torch route's conv1d weight (up, 1, width + (up - 1) down // up): channel c = n mod up has phase (c down) mod up
+    and starts (c down) div up samples further on; conv1d correlates, so the taps are reversed."""
+    c = torch.arange(up, device=taps.device)
+    width = taps.shape[1]
+    weight = taps.new_zeros(up, width + (up - 1) * down // up)
+    weight.scatter_(1, ((c * down) // up)[:, None] + torch.arange(width, device=taps.device)[None, :],
+                    taps[(c * down) % up].flip(1))
+    return weight[:, None, :]
+
+
+def resample_pack(taps: torch.Tensor, up: int, down: int, lead: int) -> ResampleTables:
+    """ge2e_resample_pack -> the tables ``resample`` reads.  ``taps`` (up, 2 lead + 1) on the device, any values
+    (``audio.resample_bank`` makes the project's Kaiser-windowed sinc); cast to float32.  One launch on the current stream;
+    run it once per bank.  For a shape without a kernel ``packed`` is None and ``resample`` takes its torch route."""
+    _require_cuda(taps, "taps")
+    t = taps.detach().to(torch.float32).contiguous()
+    up, down, lead = int(up), int(down), int(lead)
+    if up < 1 or down < 1 or lead < 0 or tuple(t.shape) != (up, 2 * lead + 1):
+        raise ValueError(f"taps must be (up, 2 lead + 1) = ({up}, {2 * lead + 1}) with up, down >= 1 and lead >= 0, got "
+                         f"{tuple(t.shape)}")
+    width, weight = 2 * lead + 1, _resample_conv_weight(t, up, down)
+    nbytes = _lib.load().ge2e_resample_packed_bytes(up, down, width)
+    if nbytes == 0:
+        return ResampleTables(None, t, up, down, lead, weight)
+    packed = torch.empty(nbytes // 4, dtype=torch.float32, device=t.device)
+    _launch("ge2e_resample_pack", t.device, t.data_ptr(), up, down, lead, packed.data_ptr(), _stream_ptr(t))
+    return ResampleTables(packed, t, up, down, lead, weight)
+
+
+def resample_layout(lengths, up: int, down: int, device=None) -> ResampleLayout:
+    """The index tables of a ``resample`` call: utterance u is ``lengths[u]`` samples from the sum of the lengths before it
+    and becomes ``ceil(lengths[u] up / down)`` samples from the sum of those before it.  ``lengths``: a Python list or CPU
+    tensor.  Build it once for a captured graph and pass it as ``resample(layout=...)``: building it is host arithmetic and
+    one small upload."""
+    ls = [int(v) for v in (lengths.tolist() if isinstance(lengths, torch.Tensor) else lengths)]
+    up, down = int(up), int(down)
+    if up < 1 or down < 1 or len(ls) < 1 or min(ls) < 0:
+        raise ValueError("resample needs up, down >= 1 and at least one utterance, none of a negative length")
+    starts, out_start = [], [0]
+    at = 0
+    for n in ls:
+        starts.append(at)
+        at += n
+        out_start.append(out_start[-1] + (n * up + down - 1) // down)
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    d = torch.tensor(starts + ls + out_start, dtype=torch.int64).to(dev)
+    U = len(ls)
+    return ResampleLayout(d[:U], d[U:2 * U], d[2 * U:], out_start, ls, [b - a for a, b in zip(out_start, out_start[1:])],
+                          up, down)
+
+
+def _resample_torch(t: ResampleTables, wav, lay: ResampleLayout, out):
+    """The same samples with torch's ops on wav's device, what a caller without the kernel would write: per utterance a
+    ``conv1d`` with ``up`` output channels of ``width`` taps at stride ``down`` over the zero-padded utterance; output n is
+    channel n mod up at position n div up."""
+    L, M, lead, W = t.up, t.down, t.lead, t.width
+    shift, weight = (L - 1) * M // L, t.weight
+    at = 0
+    for u, (n, n_out) in enumerate(zip(lay.lengths, lay.out_lengths)):
+        if n_out:
+            q = (n_out + L - 1) // L                      # positions: outputs n = c + L j, j < q
+            right = max(0, (q - 1) * M + shift + lead + 1 - n)
+            x = torch.nn.functional.pad(wav[at:at + n], (W - 1 - lead, right))
+            y = torch.nn.functional.conv1d(x[None, None], weight, stride=M)[0, :, :q]
+            out[lay.out_start[u]:lay.out_start[u + 1]] = y.t().reshape(-1)[:n_out]
+        at += n
+    return out
+
+
+def resample(tables: ResampleTables, wav: torch.Tensor, lengths=None, *, out: Optional[torch.Tensor] = None,
+             native: Optional[bool] = None, layout: Optional[ResampleLayout] = None):
+    """ge2e_resample: waveforms at one rate to another in one launch on the current stream, no workspace -> ``(flat,
+    out_lengths)``: ``flat`` float32, the resampled utterances back to back, and ``out_lengths`` a Python list of their
+    sample counts, ceil(length up / down) (host arithmetic: nothing is read back).  ``tables``: ``resample_pack``'s.
+    ``wav``: a flat float32 device tensor holding the utterances back to back, ``lengths`` their sample counts (a list or
+    CPU tensor; None: ``wav`` is one utterance); every utterance is taken as zero outside its own extent.  ``layout``: a
+    ``resample_layout`` built beforehand (a captured graph).  ``native=None`` takes the kernel where the shape has one and
+    the torch route otherwise; ``native=True`` raises where it has none; ``native=False`` is the torch route (a strided
+    ``conv1d``).  No change-over between the two: at every size measured the kernel is the faster one
+    (profiles/resample_bench.txt)."""
+    _require_cuda(wav, "wav")
+    dev = wav.device
+    w = wav.detach()
+    if w.dim() != 1 or w.dtype != torch.float32 or not w.is_contiguous():
+        raise TypeError(f"wav must be a flat contiguous float32 tensor, got {tuple(w.shape)} {w.dtype}")
+    if not isinstance(tables, ResampleTables):
+        raise TypeError("tables must be resample_pack's ResampleTables")
+    use_native = tables.packed is not None if native is None else bool(native)
+    if use_native and tables.packed is None:
+        raise RuntimeError(f"resample(native=True): no HIP kernel for up {tables.up}, down {tables.down}, width {tables.width}")
+    if layout is None:
+        layout = resample_layout([w.numel()] if lengths is None else lengths, tables.up, tables.down, device=dev)
+    elif (layout.up, layout.down) != (tables.up, tables.down) or layout.in_start.device != dev:
+        raise ValueError(f"layout was built for {layout.up} / {layout.down} on {layout.in_start.device}")
+    if sum(layout.lengths) > w.numel():
+        raise ValueError(f"the lengths add up to {sum(layout.lengths)} samples, wav has {w.numel()}")
+    U, total = len(layout.lengths), layout.out_start[-1]
+    if out is None:
+        out = torch.empty(total, dtype=torch.float32, device=dev)
+    elif tuple(out.shape) != (total,) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
+        raise TypeError(f"out must be a contiguous ({total},) torch.float32 tensor on {dev}")
+    if total == 0:
+        return out, layout.out_lengths
+    if not use_native:
+        return _resample_torch(tables, w, layout, out), layout.out_lengths
+    pk = tables.packed
+    if pk.device != dev:
+        raise ValueError(f"the tables are on {pk.device}, wav on {dev}")
+    _launch("ge2e_resample", dev, pk.data_ptr(), w.data_ptr(), layout.in_start.data_ptr(), layout.in_len.data_ptr(),
+            layout.out_start_dev.data_ptr(), U, total, tables.up, tables.down, tables.lead, out.data_ptr(), _stream_ptr(w))
+    return out, layout.out_lengths
+
+
+def volume_gain(wav: torch.Tensor, lengths=None, target_dbfs: float = -30.0, increase_only: bool = True,
+                native: Optional[bool] = None, *, layout=None, out: Optional[torch.Tensor] = None,
+                workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ge2e_volume_gain: the factor ``normalize_volume`` multiplies every utterance by, (U,) float32 on wav's device, in two
+    launches on the current stream: the sum of squares per utterance in float64 in a fixed order, without the float64
+    copies of the whole buffer ``audio.volume_gain`` makes.  ``wav`` flat float32, ``lengths`` as ``resample`` (None: one
+    utterance).  ``native=False``: ``audio.volume_gain``, the torch route; None and True: the kernel (it has no unsupported
+    shape).  ``layout`` (a ``resample_layout`` or ``melspec_layout`` of the utterances in ``wav``: its starts and lengths
+    on the device are used), ``out`` (U,) and ``workspace`` (``volume_gain_workspace``) make the call allocation-free for a
+    captured graph."""
+    if native is not None and not native:
+        from .audio import volume_gain as torch_route
+        return torch_route(wav, lengths, target_dbfs, increase_only)
+    _require_cuda(wav, "wav")
+    dev = wav.device
+    w = wav.detach()
+    if w.dim() != 1 or w.dtype != torch.float32 or not w.is_contiguous():
+        raise TypeError(f"wav must be a flat contiguous float32 tensor, got {tuple(w.shape)} {w.dtype}")
+    if layout is None:
+        ls = [w.numel()] if lengths is None else [int(v) for v in (lengths.tolist() if isinstance(lengths, torch.Tensor) else lengths)]
+        if len(ls) < 1 or min(ls) < 0 or sum(ls) > w.numel():
+            raise ValueError(f"lengths {ls[:4]}... must be non-negative and add up to at most wav's {w.numel()} samples")
+        starts = [0]
+        for n in ls[:-1]:
+            starts.append(starts[-1] + n)
+        d = torch.tensor(starts + ls, dtype=torch.int64).to(dev)
+        U = len(ls)
+        start_dev, len_dev = d[:U], d[U:]
+    else:
+        if isinstance(layout, ResampleLayout):
+            start_dev, len_dev = layout.in_start, layout.in_len
+        elif isinstance(layout, MelLayout):
+            start_dev, len_dev = layout.utt_start, layout.utt_len
+        else:
+            raise TypeError("layout must be a resample_layout or a melspec_layout")
+        U = len(layout.lengths)
+        if start_dev.device != dev or sum(layout.lengths) > w.numel():
+            raise ValueError(f"layout is on {start_dev.device} for {sum(layout.lengths)} samples; wav has {w.numel()} on {dev}")
+    if out is None:
+        out = torch.empty(U, dtype=torch.float32, device=dev)
+    elif tuple(out.shape) != (U,) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
+        raise TypeError(f"out must be a contiguous ({U},) torch.float32 tensor on {dev}")
+    if workspace is None:
+        workspace = volume_gain_workspace(w.numel(), U, dev)
+    elif workspace.device != dev or workspace.dtype != torch.float64 or not workspace.is_contiguous() or \
+            workspace.numel() * 8 < _lib.load().ge2e_volume_gain_workspace_bytes(w.numel(), U):
+        raise TypeError(f"workspace must be volume_gain_workspace({w.numel()}, {U}) on {dev}")
+    _launch("ge2e_volume_gain", dev, w.data_ptr(), start_dev.data_ptr(), len_dev.data_ptr(), U, float(target_dbfs),
+            int(bool(increase_only)), out.data_ptr(), workspace.data_ptr(), _stream_ptr(w))
+    return out
+
+
+def volume_gain_workspace(total_samples: int, U: int, device) -> torch.Tensor:
+    """A float64 tensor of ge2e_volume_gain_workspace_bytes for ``volume_gain(workspace=...)``."""
+    return torch.empty(_lib.load().ge2e_volume_gain_workspace_bytes(int(total_samples), int(U)) // 8, dtype=torch.float64,
+                       device=device)
+
+
 def raw_supported(N: int, M: int, D: int) -> bool:
     """Shapes ge2e_loss_raw runs as ONE launch (the one-wave-per-batch kernel's register-only shapes)."""
     return bool(_lib.load().ge2e_raw_supported(N, M, D))
