@@ -809,6 +809,75 @@ size_t ge2e_volume_gain_workspace_bytes(long long total_samples, int U);
 int ge2e_volume_gain(const float* wav, const long long* utt_start, const long long* utt_len /* [U], device */, int U,
                      float target_dbfs, int increase_only, float* gain_out /* [U] */, void* workspace, void* stream);
 
+/*
+ * SILENCE TRIMMING (csrc/ge2e_vad.hip): the reference's trim_long_silences (utils/audio_utils.py:107-148), which runs between
+ * normalize_volume and the spectrogram.  Everything there that is the reference's own code is reproduced exactly -- window
+ * arithmetic, int16 quantisation, moving average, rounding, dilation, selection of samples; the per-window voice decision,
+ * which the reference takes from webrtcvad, is the PROJECT'S OWN detector (below), all in integers.  A caller who has flags
+ * from elsewhere passes them to ge2e_vad_mask in place of ge2e_vad_flags' and gets the reference's trimming of them.
+ *
+ * The definition.  Utterance u is wav[utt_start[u] .. + utt_len[u]) (int64, in samples, on the device), float32.  With S
+ * samples a window (vad_window_length * sampling_rate div 1000; 480 for the reference) it has W_u = utt_len[u] div S windows;
+ * the utt_len[u] mod S samples left over are dropped (s0:118) and never read.  win_start [U + 1] (int64, device) is the prefix
+ * sum of W_u and total_windows its last entry: host arithmetic on lengths, the caller's, as frame_start is for ge2e_melspec.
+ * gain [U] (float32, device) may be NULL, which means 1.
+ *   quantise  q = sat16(rint(fl32(fl32(x * gain[u]) * 32767.0f))) (s0:121 in numpy's float32 arithmetic: two roundings, no
+ *             fused multiply-add), rint to nearest, halves to even; NaN gives 0; values past the int16 range saturate (the
+ *             reference's astype(np.int16) wraps there: the one deliberate departure).
+ *   energy    e = S sum(q^2) - (sum q)^2 over the window's S samples, in int64: S^2 times the variance (DC does not count),
+ *             exact, independent of the order of summation, at most 2^54 for S <= 4096.
+ *   flag      floor[w] = min e[v] over |v - w| <= floor_span, v in the same utterance;
+ *             flag[w] = (e[w] >= min_energy) and (e[w] * 256 > floor[w] * ratio_q8), compared exactly (128-bit products).
+ *   mask      m[w] = 2 sum(flag[w - (A - 1) div 2 .. w + A div 2]) > A, A = avg_width, flags outside the utterance zero: the
+ *             reference's moving_average and np.round (a mean of exactly 0.5 rounds to 0: the `>`);
+ *             keep[i] = any m[i - (n - 1) div 2 .. i + n div 2], n = max_silence + 1: scipy's binary_dilation with np.ones(n).
+ *   outputs   dst[w] (int32): the rank of window w among its utterance's kept windows, or -1; out_len[u] = S kept_u (int64).
+ *   trim      kept window w of utterance u goes, bits unchanged, to out[out_start[u] + S dst[w] ..]; no arithmetic touches
+ *             the samples.  The gain stays a separate factor (ge2e_melspec applies it): select(x) g == select(x g).
+ * Supported: 2 <= S <= 4096, 0 <= floor_span <= 1024, avg_width and max_silence + 1 in 1 .. 64, total_windows < 2^31;
+ * everything else is GE2E_ERR_IMPL and nothing is launched.  total_windows = 0 is legal and launches nothing.
+ *
+ * ge2e_vad_flags: two launches.  flags [total_windows] uint8 (0 / 1).  workspace: ge2e_vad_workspace_bytes(total_windows, U)
+ * bytes (the int64 energies; 0 for total_windows < 0 or U < 1), 16-byte aligned; it holds e[w] afterwards.  Launch 1 reads
+ * every sample once: 16 (S >= 64; S below: 128) consecutive windows a workgroup of 256 threads, 64 (8) lanes a window reading
+ * consecutive words, integer sums added by a butterfly.  Launch 2: 256 consecutive windows a workgroup, their energies and
+ * floor_span either side staged in LDS, one thread per window.  A window finds its utterance by a bisection of win_start.
+ * Checks, in this order: GE2E_ERR_NULL (wav, utt_start, utt_len, win_start or flags), GE2E_ERR_SHAPE (U or S < 1,
+ * total_windows, floor_span, ratio_q8 or min_energy < 0), GE2E_ERR_IMPL, GE2E_ERR_WORKSPACE (NULL or not 16-byte aligned),
+ * GE2E_ERR_ALIGN (wav or gain not aligned to a float).
+ *
+ * ge2e_vad_mask: one launch of U workgroups of 1024 threads.  A workgroup walks its utterance in chunks of 4096 windows
+ * with the count of kept windows carried from chunk to chunk; integers only, no atomics: the result does not depend on the
+ * chunk.  Checks: GE2E_ERR_NULL (flags, win_start, dst or out_len), GE2E_ERR_SHAPE (U, S or avg_width < 1, total_windows
+ * or max_silence < 0), GE2E_ERR_IMPL, GE2E_ERR_ALIGN (dst not aligned to an int, out_len not to 8 bytes).
+ *
+ * ge2e_vad_trim: one launch over the input windows, tiled as launch 1 of ge2e_vad_flags.  A dropped window is not read; a
+ * kept one moves in 16-byte pieces where its source and destination are both 16-byte aligned and word by word otherwise.
+ * out_start [U] (int64, device) is the caller's: the utterances' own starts for an in-slot form without a read-back, or a
+ * dense prefix once out_len is known.  out must not overlap wav.  Exactly sum(out_len) elements are written.  Checks:
+ * GE2E_ERR_NULL (wav, utt_start, win_start, dst, out_start or out), GE2E_ERR_SHAPE (U or S < 1, total_windows < 0),
+ * GE2E_ERR_IMPL, GE2E_ERR_ALIGN (wav or out not aligned to a float, dst not to an int).
+ *
+ * Every entry: no allocation, no synchronisation, everything on `stream`, grid from the arguments alone: fit for a HIP graph.
+ *
+ * ge2e_vad_plan (diagnostics, no GPU): "vad_energy<G>/T/grid,vad_flag/256/grid,vad_mask/4096/U,vad_trim<G>/T/grid" -- G lanes
+ * a window and T windows a workgroup, the mask kernel's chunk, the grids -- snprintf-style as ge2e_resample_plan; < 0:
+ * GE2E_ERR_SHAPE or GE2E_ERR_IMPL as the calls themselves; total_windows = 0: the empty string.  (No part of ge2e_plan_atoms.)
+ */
+size_t ge2e_vad_workspace_bytes(long long total_windows, int U);
+int ge2e_vad_flags(const float* wav, const long long* utt_start, const long long* utt_len /* [U], device, in samples */,
+                   const float* gain /* [U] or NULL */, const long long* win_start /* [U+1], device */, int U,
+                   long long total_windows, int S, int floor_span, long long ratio_q8, long long min_energy,
+                   unsigned char* flags /* [total_windows] */, void* workspace, void* stream);
+int ge2e_vad_mask(const unsigned char* flags /* [total_windows] */, const long long* win_start /* [U+1], device */, int U,
+                  long long total_windows, int S, int avg_width, int max_silence, int* dst /* [total_windows] */,
+                  long long* out_len /* [U] */, void* stream);
+int ge2e_vad_trim(const float* wav, const long long* utt_start /* [U], device */, const long long* win_start /* [U+1] */,
+                  const int* dst /* [total_windows] */, const long long* out_start /* [U], device */, int U,
+                  long long total_windows, int S, float* out, void* stream);
+int ge2e_vad_plan(int U, long long total_windows, int S, int floor_span, int avg_width, int max_silence, char* buf,
+                  size_t buf_bytes);
+
 /* ---- diagnostics (tests only): which kernels a call launches ---------------------------------------------------------
  * Below ge2e_resolve_impl every launcher chooses again among kernels and template instantiations.  These queries print
  * that choice -- made by the very functions the launchers switch on -- without a GPU and without launching anything:

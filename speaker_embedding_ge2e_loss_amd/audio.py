@@ -7,7 +7,13 @@ A recording at another rate is resampled on the device first (``resample_bank``,
 ``librosa.resample`` step, with the project's own exact-phase Kaiser-windowed sinc), and its gain then comes from
 ``functional.volume_gain``.
 
-Out of scope: decoding audio files and the webrtcvad silence trimming.  The caller hands in samples and their rate.
+The reference's ``trim_long_silences`` runs on the device too (``trim_silences=True``; ``functional.trim_silences``): its
+window arithmetic, int16 quantisation, moving average, rounding, dilation and selection of samples are reproduced exactly.
+The per-window voice decision, which the reference takes from webrtcvad, is the project's own integer detector and NOT
+webrtcvad's (webrtcvad is no part of this project): a caller who wants the reference's trimming to the sample passes
+webrtcvad's flags -- or any detector's -- as ``voice_flags=``.
+
+Out of scope: decoding audio files.  The caller hands in samples and their rate.
 """
 from __future__ import annotations
 
@@ -156,12 +162,24 @@ class MelFrontEnd:
     device in one launch (``functional.resample`` with ``resample_bank(source_rate, sampling_rate, resample_filter)``,
     packed once per (rate, filter, device)), the partial-slice arithmetic runs on the resampled lengths and the gain of
     ``normalize_volume`` comes from ``functional.volume_gain`` on the resampled signal.  One rate for all the waveforms of
-    a call: a different rate per waveform is not built (call once per rate)."""
+    a call: a different rate per waveform is not built (call once per rate).
+
+    ``trim_silences`` / ``voice_flags``: the reference's ``trim_long_silences`` between the gain and the spectrogram
+    (``functional.trim_silences`` with this front end's ``vad_*`` settings).  The order is the reference's: resample, gain
+    of the untrimmed signal, trim, spectrogram of the trimmed lengths.  The built-in voice flags are the project's own
+    detector (``vad_floor_span``, ``vad_ratio_db``, ``vad_min_level_dbfs``), not webrtcvad's; ``voice_flags`` hands in
+    others, one per window of ``vad_window_length`` ms, utterance after utterance (passing it implies the trimming).  It
+    costs one read-back of the kept lengths per call."""
 
     def __init__(self, sampling_rate: int = 16000, n_fft: int = 1024, hop_length: int = 128, n_mels: int = 80,
                  fmin: float = 90.0, fmax: float = 7600.0, mel_window_step: float = 10, partials_n_frames: int = 180,
                  rate_partial_slices: float = 1.3, min_coverage: float = 0.75, target_dbfs: float = -30.0,
-                 min_level_db: float = -100.0, ref_level_db: float = 16.0):
+                 min_level_db: float = -100.0, ref_level_db: float = 16.0, vad_window_length: int = 30,
+                 vad_moving_average_width: int = 8, vad_max_silence_length: int = 6, vad_floor_span: int = 100,
+                 vad_ratio_db: float = 9.0, vad_min_level_dbfs: float = -60.0):
+        self.vad_window_length, self.vad_moving_average_width = vad_window_length, vad_moving_average_width
+        self.vad_max_silence_length, self.vad_floor_span = vad_max_silence_length, vad_floor_span
+        self.vad_ratio_db, self.vad_min_level_dbfs = vad_ratio_db, vad_min_level_dbfs
         self.sampling_rate, self.n_fft, self.hop_length, self.n_mels = sampling_rate, n_fft, hop_length, n_mels
         self.mel_window_step, self.partials_n_frames = mel_window_step, partials_n_frames
         self.rate_partial_slices, self.min_coverage, self.target_dbfs = rate_partial_slices, min_coverage, target_dbfs
@@ -176,7 +194,12 @@ class MelFrontEnd:
         """From the reference's hyper-parameters (``hp.audio``, ``hp.vad``; s0:22-26 fixes fmin 90 and fmax 7600)."""
         a, v = hp.audio, hp.vad
         return cls(a.sampling_rate, a.n_fft, a.hop_length, a.mel_n_channels, 90.0, 7600.0, a.mel_window_step,
-                   a.partials_n_frames, v.rate_partial_slices, v.min_coverage, getattr(v, "audio_norm_target_dBFS", -30.0))
+                   a.partials_n_frames, v.rate_partial_slices, v.min_coverage, getattr(v, "audio_norm_target_dBFS", -30.0),
+                   vad_window_length=getattr(v, "vad_window_length", 30),
+                   vad_moving_average_width=getattr(v, "vad_moving_average_width", 8),
+                   vad_max_silence_length=getattr(v, "vad_max_silence_length", 6),
+                   vad_floor_span=getattr(v, "vad_floor_span", 100), vad_ratio_db=getattr(v, "vad_ratio_db", 9.0),
+                   vad_min_level_dbfs=getattr(v, "vad_min_level_dbfs", -60.0))
 
     def tables(self, device):
         """The packed tables on ``device``, made on first use."""
@@ -218,13 +241,19 @@ class MelFrontEnd:
         g = math.gcd(int(source_rate), int(self.sampling_rate))
         return [resampled_length(n, self.sampling_rate // g, int(source_rate) // g) for n in lengths]
 
-    def frames(self, wavs, normalize_volume: bool = False, pad_to_partials: bool = False, mode: str = "db",
-               native: Optional[bool] = None, source_rate: Optional[int] = None, resample_filter="kaiser_best"):
-        """``(frames, frame_start)`` of ``functional.melspec`` for a list of 1-D float32 device waveforms (or one): all of
-        them in one launch.  ``normalize_volume``: the gain of ``normalize_volume(increase_only=True)``, applied in the
-        kernel.  ``pad_to_partials``: every waveform zero-extended to the end of its last partial slice, as
-        ``get_mel_spects_from_audio(partial_slices=True)`` pads it.  ``source_rate`` / ``resample_filter``: the rate of
-        the waveforms where it is not ``sampling_rate`` (see the class; None: they are at the model's rate)."""
+    @property
+    def vad_window(self) -> int:
+        """Samples of a voice-detection window: ``vad_window_length * sampling_rate // 1000`` (s0:115)."""
+        return (int(self.vad_window_length) * int(self.sampling_rate)) // 1000
+
+    def preprocess(self, wavs, normalize_volume: bool = False, native: Optional[bool] = None,
+                   source_rate: Optional[int] = None, resample_filter="kaiser_best", trim_silences: bool = False,
+                   voice_flags=None):
+        """A batch's ``get_audio_as_np_array``: ``(flat, lengths, gain)`` -- the waveforms back to back at the model's rate,
+        their sample counts (a Python list) and the per-utterance gain on the device (None without ``normalize_volume``),
+        which stays a separate factor that ``spectrogram`` hands to the kernel.  In the reference's order: resample
+        (``source_rate``), gain of the untrimmed signal, ``trim_long_silences`` (``trim_silences`` or ``voice_flags``; the
+        lengths are then the trimmed ones, read back from the device once)."""
         from . import functional as GF
         wavs = [wavs] if isinstance(wavs, torch.Tensor) else list(wavs)
         if not wavs:
@@ -239,16 +268,49 @@ class MelFrontEnd:
                 gain = GF.volume_gain(flat, lengths, self.target_dbfs, increase_only=True, native=native)
         elif normalize_volume:
             gain = volume_gain(flat, lengths, self.target_dbfs, increase_only=True)
+        if trim_silences or voice_flags is not None:
+            flat, lengths = GF.trim_silences(flat, lengths, gain=gain, voice_flags=voice_flags, window=self.vad_window,
+                                             floor_span=self.vad_floor_span, ratio_db=self.vad_ratio_db,
+                                             min_level_dbfs=self.vad_min_level_dbfs, avg_width=self.vad_moving_average_width,
+                                             max_silence=self.vad_max_silence_length, native=native)
+        return flat, lengths, gain
+
+    def spectrogram(self, flat, lengths, gain=None, pad_to_partials: bool = False, mode: str = "db",
+                    native: Optional[bool] = None):
+        """``(frames, frame_start)`` of ``functional.melspec`` for what ``preprocess`` returned."""
+        from . import functional as GF
+        if not pad_to_partials:
+            for u, n in enumerate(lengths):
+                if n <= self.n_fft // 2:
+                    raise ValueError(f"utterance {u} has {n} samples (after any silence trimming): the spectrogram's "
+                                     f"reflection needs more than n_fft / 2 = {self.n_fft // 2}; pad_to_partials extends it")
+        if flat.numel() == 0:
+            flat = flat.new_zeros(1)          # every utterance trimmed to nothing: the kernel wants an address, reads nothing
         padded = [self.slices(n).padded_length for n in lengths] if pad_to_partials else None
-        return GF.melspec(self.tables(dev), flat, lengths, hop=self.hop_length, padded_lengths=padded, gain=gain, mode=mode,
-                          min_level_db=self.min_level_db, ref_level_db=self.ref_level_db, native=native)
+        return GF.melspec(self.tables(flat.device), flat, lengths, hop=self.hop_length, padded_lengths=padded, gain=gain,
+                          mode=mode, min_level_db=self.min_level_db, ref_level_db=self.ref_level_db, native=native)
+
+    def frames(self, wavs, normalize_volume: bool = False, pad_to_partials: bool = False, mode: str = "db",
+               native: Optional[bool] = None, source_rate: Optional[int] = None, resample_filter="kaiser_best",
+               trim_silences: bool = False, voice_flags=None):
+        """``(frames, frame_start)`` of ``functional.melspec`` for a list of 1-D float32 device waveforms (or one): all of
+        them in one launch.  ``normalize_volume``: the gain of ``normalize_volume(increase_only=True)``, applied in the
+        kernel.  ``pad_to_partials``: every waveform zero-extended to the end of its last partial slice, as
+        ``get_mel_spects_from_audio(partial_slices=True)`` pads it.  ``source_rate`` / ``resample_filter``: the rate of
+        the waveforms where it is not ``sampling_rate`` (see the class; None: they are at the model's rate).
+        ``trim_silences`` / ``voice_flags``: the reference's silence trimming first (see the class); an utterance trimmed
+        to ``n_fft / 2`` samples or fewer raises a ValueError unless ``pad_to_partials`` extends it."""
+        flat, lengths, gain = self.preprocess(wavs, normalize_volume, native, source_rate, resample_filter, trim_silences,
+                                              voice_flags)
+        return self.spectrogram(flat, lengths, gain, pad_to_partials, mode, native)
 
     def partial_rows(self, lengths, frame_start, source_rate: Optional[int] = None, resample_filter=None):
         """``(row_start, owner)`` Python lists: the first row of ``frames(pad_to_partials=True)`` of every partial
         utterance and the waveform it belongs to; a partial whose frames the spectrogram does not hold is left out, as
         s0:59 leaves it out.  ``lengths``: the waveforms' own, at ``source_rate`` where that is given.
         ``resample_filter`` is accepted so that the three methods take the same arguments and is ignored: the rows
-        depend on the lengths alone, which no filter changes."""
+        depend on the lengths alone, which no filter changes.  After silence trimming the lengths are ``preprocess``'s
+        (already at the model's rate: no ``source_rate`` then)."""
         rows, owner = [], []
         lengths = self.resampled_lengths(lengths, source_rate)
         for u, n in enumerate(lengths):
@@ -260,14 +322,17 @@ class MelFrontEnd:
         return rows, owner
 
     def partials(self, wavs, normalize_volume: bool = False, native: Optional[bool] = None,
-                 source_rate: Optional[int] = None, resample_filter="kaiser_best"):
+                 source_rate: Optional[int] = None, resample_filter="kaiser_best", trim_silences: bool = False,
+                 voice_flags=None):
         """Per waveform the tensor ``get_mel_spects_from_audio(partial_slices=True)`` returns, (partials,
         partials_n_frames, n_mels) float32: gathered copies of the frames (``SpeakerEncoder.embed_audio`` addresses them
-        in place instead).  ``source_rate`` / ``resample_filter`` as ``frames``."""
+        in place instead).  ``source_rate`` / ``resample_filter`` / ``trim_silences`` / ``voice_flags`` as ``frames``; an
+        utterance trimmed to nothing yields one partial of silence, as the reference does."""
         wavs = [wavs] if isinstance(wavs, torch.Tensor) else list(wavs)
-        frames, frame_start = self.frames(wavs, normalize_volume, pad_to_partials=True, native=native,
-                                          source_rate=source_rate, resample_filter=resample_filter)
-        rows, owner = self.partial_rows([int(w.numel()) for w in wavs], frame_start, source_rate)
+        flat, lengths, gain = self.preprocess(wavs, normalize_volume, native, source_rate, resample_filter, trim_silences,
+                                              voice_flags)
+        frames, frame_start = self.spectrogram(flat, lengths, gain, pad_to_partials=True, native=native)
+        rows, owner = self.partial_rows(lengths, frame_start)
         T = self.partials_n_frames
         return [torch.stack([frames[r:r + T] for r, o in zip(rows, owner) if o == u]) if u in owner
                 else frames.new_zeros(0, T, self.n_mels) for u in range(len(wavs))]

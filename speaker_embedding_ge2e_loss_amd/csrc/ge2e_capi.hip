@@ -18,6 +18,7 @@
 #include "ge2e_encoder_train.hpp"
 #include "ge2e_melspec.hpp"
 #include "ge2e_resample.hpp"
+#include "ge2e_vad.hpp"
 #include "ge2e_identify.hpp"
 #include "ge2e_snorm.hpp"
 #include "ge2e_helpers.hpp"
@@ -828,6 +829,73 @@ int ge2e_volume_gain(const float* wav, const long long* utt_start, const long lo
     if (!aligned16(workspace) || ((uintptr_t)wav & 3) || ((uintptr_t)gain_out & 3)) return GE2E_ERR_ALIGN;
     return (int)launch_volume_gain(wav, utt_start, utt_len, U, (double)target_dbfs, increase_only != 0, gain_out,
                                    (double*)workspace, (hipStream_t)stream);
+}
+
+// SILENCE TRIMMING (include/ge2e_hip.h, csrc/ge2e_vad.hip): window energies and voice flags in two launches, the mask and the
+// ranks of the kept windows in one, the compaction in one.
+size_t ge2e_vad_workspace_bytes(long long total_windows, int U) {
+    return (total_windows < 0 || U < 1) ? 0 : vad_workspace_bytes(total_windows);
+}
+
+// the window, the window count and the grids every entry shares: SHAPE before IMPL
+static int vad_shape_check(int U, long long total_windows, int S) {
+    if (U < 1 || S < 1 || total_windows < 0) return GE2E_ERR_SHAPE;
+    if (!vad_window_supported(S) || total_windows > 0x7fffffffLL) return GE2E_ERR_IMPL;
+    return GE2E_OK;
+}
+
+static int vad_mask_check(int avg_width, int max_silence) {
+    if (avg_width < 1 || max_silence < 0) return GE2E_ERR_SHAPE;
+    return (avg_width > kVadMaxWidth || max_silence + 1 > kVadMaxWidth) ? GE2E_ERR_IMPL : GE2E_OK;
+}
+
+int ge2e_vad_flags(const float* wav, const long long* utt_start, const long long* utt_len, const float* gain,
+                   const long long* win_start, int U, long long total_windows, int S, int floor_span, long long ratio_q8,
+                   long long min_energy, unsigned char* flags, void* workspace, void* stream) {
+    if (!wav || !utt_start || !utt_len || !win_start || !flags) return GE2E_ERR_NULL;
+    if (floor_span < 0 || ratio_q8 < 0 || min_energy < 0) return GE2E_ERR_SHAPE;
+    const int rc = vad_shape_check(U, total_windows, S);
+    if (rc != GE2E_OK) return rc;
+    if (floor_span > kVadMaxSpan) return GE2E_ERR_IMPL;
+    if (!workspace || !aligned16(workspace)) return GE2E_ERR_WORKSPACE;
+    if (((uintptr_t)wav & 3) || ((uintptr_t)gain & 3)) return GE2E_ERR_ALIGN;
+    if (total_windows == 0) return GE2E_OK;
+    const ProblemVad p = {wav, utt_start, gain, win_start, U, S, total_windows};
+    return (int)launch_vad_flags(p, floor_span, (unsigned long long)ratio_q8, min_energy, flags, (long long*)workspace,
+                                 (hipStream_t)stream);
+}
+
+int ge2e_vad_mask(const unsigned char* flags, const long long* win_start, int U, long long total_windows, int S, int avg_width,
+                  int max_silence, int* dst, long long* out_len, void* stream) {
+    if (!flags || !win_start || !dst || !out_len) return GE2E_ERR_NULL;
+    if (vad_mask_check(avg_width, max_silence) == GE2E_ERR_SHAPE) return GE2E_ERR_SHAPE;
+    int rc = vad_shape_check(U, total_windows, S);
+    if (rc == GE2E_OK) rc = vad_mask_check(avg_width, max_silence);
+    if (rc != GE2E_OK) return rc;
+    if (((uintptr_t)dst & 3) || ((uintptr_t)out_len & 7)) return GE2E_ERR_ALIGN;
+    // (an utterance without windows still gets its out_len = 0: the launch is per utterance)
+    return (int)launch_vad_mask(flags, win_start, U, S, avg_width, max_silence, dst, out_len, (hipStream_t)stream);
+}
+
+int ge2e_vad_trim(const float* wav, const long long* utt_start, const long long* win_start, const int* dst,
+                  const long long* out_start, int U, long long total_windows, int S, float* out, void* stream) {
+    if (!wav || !utt_start || !win_start || !dst || !out_start || !out) return GE2E_ERR_NULL;
+    const int rc = vad_shape_check(U, total_windows, S);
+    if (rc != GE2E_OK) return rc;
+    if (((uintptr_t)wav & 3) || ((uintptr_t)out & 3) || ((uintptr_t)dst & 3)) return GE2E_ERR_ALIGN;
+    if (total_windows == 0) return GE2E_OK;
+    const ProblemVad p = {wav, utt_start, nullptr, win_start, U, S, total_windows};
+    return (int)launch_vad_trim(p, dst, out_start, out, (hipStream_t)stream);
+}
+
+int ge2e_vad_plan(int U, long long total_windows, int S, int floor_span, int avg_width, int max_silence, char* buf,
+                  size_t buf_bytes) {
+    if (floor_span < 0 || vad_mask_check(avg_width, max_silence) == GE2E_ERR_SHAPE) return GE2E_ERR_SHAPE;
+    int rc = vad_shape_check(U, total_windows, S);
+    if (rc == GE2E_OK && floor_span > kVadMaxSpan) rc = GE2E_ERR_IMPL;
+    if (rc == GE2E_OK) rc = vad_mask_check(avg_width, max_silence);
+    if (rc != GE2E_OK) return rc;
+    return plan_string_vad(total_windows, U, S, buf, buf_bytes);
 }
 
 // ---- diagnostics: the launch plan of a call, from the launchers' own decision functions (ge2e_plan.hpp); no GPU needed ----

@@ -159,7 +159,7 @@ class SpeakerEncoder(nn.Module):
 
 
     def embed_audio(self, wavs, front_end, normalize_volume: bool = False, source_rate=None,
-                    resample_filter="kaiser_best"):
+                    resample_filter="kaiser_best", trim_silences: bool = False, voice_flags=None):
         """Utterance d-vectors (len(wavs), D) from waveforms (1-D float32 tensors on the module's device), as the
         reference makes them from ``get_mel_spects_from_audio(partial_slices=True)``: three launches and no copy between
         them.  ``front_end`` (an ``audio.MelFrontEnd``) turns all the waveforms, each zero-extended to the end of its last
@@ -168,7 +168,11 @@ class SpeakerEncoder(nn.Module):
         normalised partial d-vectors are averaged and renormalised by ``enroll_accumulate`` / ``enroll_finalize``.
         ``source_rate``: the rate of the waveforms where it is not the front end's ``sampling_rate``; they are then
         resampled on the device first (one more launch, ``functional.resample`` with ``resample_filter``; see
-        ``audio.MelFrontEnd``).  One rate for all the waveforms of a call."""
+        ``audio.MelFrontEnd``).  One rate for all the waveforms of a call.  ``trim_silences`` / ``voice_flags``: the
+        reference's ``trim_long_silences`` between the gain and the spectrogram (``functional.trim_silences``: four more
+        launches and one read-back of the kept lengths; the built-in voice flags are the project's own detector, not
+        webrtcvad's -- pass other flags as ``voice_flags``).  An utterance trimmed to nothing gives the d-vector of one
+        partial of silence, as the reference does."""
         from . import functional as GF
         if not self.native_supported():
             raise RuntimeError(f"embed_audio needs the native encoder kernel; this module {self._shape()} has none")
@@ -177,9 +181,11 @@ class SpeakerEncoder(nn.Module):
         if front_end.n_mels != n_mels:
             raise ValueError(f"the front end makes {front_end.n_mels} mel channels, the encoder takes {n_mels}")
         dev = self.projection.weight.device
-        frames, frame_start = front_end.frames([w.to(dev) for w in wavs], normalize_volume, pad_to_partials=True,
-                                               source_rate=source_rate, resample_filter=resample_filter)
-        rows, owner = front_end.partial_rows([int(w.numel()) for w in wavs], frame_start, source_rate)
+        flat, lengths, gain = front_end.preprocess([w.to(dev) for w in wavs], normalize_volume, source_rate=source_rate,
+                                                   resample_filter=resample_filter, trim_silences=trim_silences,
+                                                   voice_flags=voice_flags)
+        frames, frame_start = front_end.spectrogram(flat, lengths, gain, pad_to_partials=True)
+        rows, owner = front_end.partial_rows(lengths, frame_start)
         if sorted(set(owner)) != list(range(len(wavs))):
             raise ValueError("a waveform has no whole partial utterance in its spectrogram (hop_length above the slices' step)")
         idx = torch.tensor([rows, owner], dtype=torch.int64).to(dev)

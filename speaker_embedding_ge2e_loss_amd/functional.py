@@ -1879,6 +1879,281 @@ def volume_gain_workspace(total_samples: int, U: int, device) -> torch.Tensor:
                        device=device)
 
 
+VAD_DEFAULTS = dict(floor_span=100, ratio_db=9.0, min_level_dbfs=-60.0)     # the built-in detector's parameters
+# vad_mask(native=None) takes the torch route for an utterance of more windows than this (41 min at 30 ms a window): the mask
+# kernel walks an utterance in one workgroup, 12 us a chunk of 4096 windows, and torch's dozen launches cost about 0.28 ms at
+# any size measured; at 30 chunks it is 0.39 ms against 0.29 ms (profiles/vad_bench.txt).  The other stages have no change-over.
+VAD_MASK_TORCH_FROM = 20 * 4096
+
+
+class VadLayout(NamedTuple):
+    """Where the utterances of a flat waveform buffer lie and which windows of ``window`` samples they have: int64 device
+    tensors for the kernels, ``win_start`` also as a Python list (U + 1 entries, the last one the total).  Pure arithmetic on
+    lengths."""
+    utt_start: torch.Tensor
+    utt_len: torch.Tensor
+    win_start_dev: torch.Tensor
+    win_start: list
+    lengths: list
+    window: int
+
+    @property
+    def total_windows(self) -> int:
+        return self.win_start[-1]
+
+
+def vad_supported(window: int, floor_span: int = 0, avg_width: int = 1, max_silence: int = 0) -> bool:
+    """Parameters the silence-trimming kernels run: a window of 2 .. 4096 samples, ``floor_span`` up to 1024 windows,
+    ``avg_width`` and ``max_silence + 1`` up to 64."""
+    return 2 <= int(window) <= 4096 and 0 <= int(floor_span) <= 1024 and 1 <= int(avg_width) <= 64 and 0 <= int(max_silence) <= 63
+
+
+def vad_layout(lengths, window: int, device=None) -> VadLayout:
+    """The index tables of the silence-trimming calls: utterance u is ``lengths[u]`` samples from the sum of the lengths
+    before it and has ``lengths[u] // window`` windows.  ``lengths``: a Python list or CPU tensor.  Host arithmetic and one
+    small upload; build it once for a captured graph."""
+    ls = [int(v) for v in (lengths.tolist() if isinstance(lengths, torch.Tensor) else lengths)]
+    window = int(window)
+    if window < 1 or len(ls) < 1 or min(ls) < 0:
+        raise ValueError("the window must be at least 1 sample and there must be an utterance, none of a negative length")
+    starts, win_start = [], [0]
+    at = 0
+    for n in ls:
+        starts.append(at)
+        at += n
+        win_start.append(win_start[-1] + n // window)
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    d = torch.tensor(starts + ls + win_start, dtype=torch.int64).to(dev)
+    U = len(ls)
+    return VadLayout(d[:U], d[U:2 * U], d[2 * U:], win_start, ls, window)
+
+
+def vad_detector_params(window: int, ratio_db: float, min_level_dbfs: float):
+    """``(ratio_q8, min_energy)``: the integers ge2e_vad_flags compares with, from the detector's decibels."""
+    return (int(round(10.0 ** (ratio_db / 10.0) * 256)),
+            int(round(window * window * (32767.0 * 10.0 ** (min_level_dbfs / 20.0)) ** 2)))
+
+
+def _vad_check_wav(wav: torch.Tensor, layout: VadLayout) -> torch.Tensor:
+    w = wav.detach()
+    if w.dim() != 1 or w.dtype != torch.float32 or not w.is_contiguous():
+        raise TypeError(f"wav must be a flat contiguous float32 tensor, got {tuple(w.shape)} {w.dtype}")
+    if layout.utt_start.device != w.device or sum(layout.lengths) > w.numel():
+        raise ValueError(f"layout is on {layout.utt_start.device} for {sum(layout.lengths)} samples; wav has {w.numel()} on "
+                         f"{w.device}")
+    return w
+
+
+def _vad_window_index(lay: VadLayout):
+    """Per window, on the device: the utterance it belongs to, its index there and its first sample."""
+    counts = lay.win_start_dev[1:] - lay.win_start_dev[:-1]
+    owner = torch.repeat_interleave(torch.arange(len(lay.lengths), device=counts.device), counts,
+                                    output_size=lay.total_windows)
+    local = torch.arange(lay.total_windows, device=counts.device) - lay.win_start_dev[owner]
+    return owner, local, lay.utt_start[owner] + local * lay.window
+
+
+def _vad_padded(values: torch.Tensor, lay: VadLayout, owner, local, fill):
+    """(U, the longest utterance's windows): every utterance's per-window values in a row of its own, ``fill`` behind."""
+    width = max(b - a for a, b in zip(lay.win_start, lay.win_start[1:]))
+    m = torch.full((len(lay.lengths), width), fill, dtype=values.dtype, device=values.device)
+    m[owner, local] = values
+    return m
+
+
+def _vad_window_sum(x: torch.Tensor, left: int, right: int) -> torch.Tensor:
+    """Along the rows of x: the sum over [i - left, i + right], zeros outside."""
+    c = torch.cumsum(torch.nn.functional.pad(x, (left + 1, right)), dim=1)
+    return c[:, left + right + 1:] - c[:, :x.shape[1]]
+
+
+def _vad_window_min(x: torch.Tensor, span: int, big: int) -> torch.Tensor:
+    """Along the rows of x: the minimum over [i - span, i + span], ``big`` outside; log2(span) ``minimum`` passes."""
+    K = 2 * span + 1
+    m = torch.nn.functional.pad(x, (span, span), value=big)
+    n, width = x.shape[1], 1
+    while 2 * width <= K:
+        m = torch.minimum(m[:, :-width], m[:, width:])
+        width *= 2
+    return torch.minimum(m[:, :n], m[:, K - width:K - width + n])
+
+
+def _vad_flags_torch(w, lay: VadLayout, gain, span: int, ratio_q8: int, min_energy: int) -> torch.Tensor:
+    """The same flags with torch's ops on wav's device, what a caller without the kernels would write: the windows as rows
+    of an ``unfold`` view, the sums in int64, the sliding minimum by doubling, the 128-bit comparison as a division."""
+    S = lay.window
+    owner, local, first = _vad_window_index(lay)
+    x = w.unfold(0, S, 1)[first]
+    if gain is not None:
+        x = x * gain[owner][:, None]
+    r = torch.round(x * 32767.0)
+    q = torch.nan_to_num(r, nan=0.0, posinf=32767.0, neginf=-32768.0).clamp(-32768.0, 32767.0).long()
+    e = S * (q * q).sum(1) - q.sum(1) ** 2
+    big = 1 << 62
+    fl = _vad_window_min(_vad_padded(e, lay, owner, local, big), span, big)[owner, local]
+    left = e * 256
+    # left > fl * ratio without the product: fl <= (left - 1) // ratio
+    above = (left > 0) & (fl <= torch.div(left - 1, max(ratio_q8, 1), rounding_mode="floor")) if ratio_q8 > 0 else left > 0
+    return ((e >= min_energy) & above).to(torch.uint8)
+
+
+def vad_flags(wav: torch.Tensor, lengths=None, gain: Optional[torch.Tensor] = None, *, window: int,
+              floor_span: int = VAD_DEFAULTS["floor_span"], ratio_db: float = VAD_DEFAULTS["ratio_db"],
+              min_level_dbfs: float = VAD_DEFAULTS["min_level_dbfs"], layout: Optional[VadLayout] = None,
+              native: Optional[bool] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ge2e_vad_flags: one voice flag per window of ``window`` samples, (total_windows,) uint8 on wav's device, in two
+    launches on the current stream.  This is the PROJECT'S OWN detector, not webrtcvad's: with the int16 value q of every
+    sample (``round(x * gain * 32767)``, saturating) and e = S sum(q^2) - (sum q)^2 (S^2 times the window's variance), a
+    window is voiced when its level is at least ``min_level_dbfs`` and more than ``ratio_db`` above the quietest window
+    within ``floor_span`` windows of it in the same utterance.  All in integers: the kernel, the torch route
+    (``native=False``) and ``tests/vad_ref.py`` agree to the bit.  ``wav`` flat float32, ``lengths`` as ``resample`` (None:
+    one utterance), ``gain`` (U,) float32 on the device or None, ``layout`` a ``vad_layout`` built beforehand.
+    ``native=None`` takes the kernels where they support the parameters (``vad_supported``) and the torch route otherwise;
+    ``native=True`` raises there."""
+    _require_cuda(wav, "wav")
+    dev = wav.device
+    if layout is None:
+        layout = vad_layout([wav.numel()] if lengths is None else lengths, window, device=dev)
+    elif layout.window != int(window):
+        raise ValueError(f"layout was built for a window of {layout.window} samples, not {window}")
+    w = _vad_check_wav(wav, layout)
+    U, total, S = len(layout.lengths), layout.total_windows, layout.window
+    if gain is not None:
+        if gain.dtype != torch.float32 or gain.device != dev or tuple(gain.shape) != (U,) or not gain.is_contiguous():
+            raise TypeError(f"gain must be a contiguous ({U},) torch.float32 tensor on {dev}")
+        gain = gain.detach()
+    floor_span = int(floor_span)
+    if floor_span < 0:
+        raise ValueError("floor_span must not be negative")
+    supported = vad_supported(S, floor_span)
+    use_native = supported if native is None else bool(native)
+    if use_native and not supported:
+        raise RuntimeError(f"vad_flags(native=True): no HIP kernel for window {S}, floor_span {floor_span}")
+    ratio_q8, min_energy = vad_detector_params(S, ratio_db, min_level_dbfs)
+    if total == 0:
+        return torch.empty(0, dtype=torch.uint8, device=dev)
+    if not use_native:
+        return _vad_flags_torch(w, layout, gain, floor_span, ratio_q8, min_energy)
+    need = _lib.load().ge2e_vad_workspace_bytes(total, U)
+    if workspace is None:
+        workspace = torch.empty(need // 8, dtype=torch.int64, device=dev)
+    elif workspace.device != dev or workspace.dtype != torch.int64 or not workspace.is_contiguous() or workspace.numel() * 8 < need:
+        raise TypeError(f"workspace must be a contiguous torch.int64 tensor of {need // 8} elements on {dev}")
+    flags = torch.empty(total, dtype=torch.uint8, device=dev)
+    _launch("ge2e_vad_flags", dev, w.data_ptr(), layout.utt_start.data_ptr(), layout.utt_len.data_ptr(),
+            None if gain is None else gain.data_ptr(), layout.win_start_dev.data_ptr(), U, total, S, floor_span, ratio_q8,
+            min_energy, flags.data_ptr(), workspace.data_ptr(), _stream_ptr(w))
+    return flags
+
+
+def _vad_mask_torch(flags, lay: VadLayout, avg_width: int, max_silence: int):
+    owner, local, _ = _vad_window_index(lay)
+    A, n = avg_width, max_silence + 1
+    f = _vad_padded((flags != 0).long(), lay, owner, local, 0)
+    valid = _vad_padded(torch.ones_like(owner), lay, owner, local, 0)
+    m = ((2 * _vad_window_sum(f, (A - 1) // 2, A // 2) > A) & (valid > 0)).long()
+    keep = (_vad_window_sum(m, (n - 1) // 2, n // 2) > 0) & (valid > 0)
+    rank = torch.cumsum(keep.long(), dim=1) - 1
+    dst = torch.where(keep, rank, torch.full_like(rank, -1))[owner, local].to(torch.int32)
+    return dst, keep.long().sum(1) * lay.window
+
+
+def vad_mask(flags: torch.Tensor, layout: VadLayout, avg_width: int = 8, max_silence: int = 6, native: Optional[bool] = None):
+    """ge2e_vad_mask: the reference's smoothing and dilation of the voice flags (its ``moving_average`` of width
+    ``avg_width`` rounded half to even, scipy's ``binary_dilation`` with ``max_silence + 1`` ones) and the compaction's
+    index, in one launch -> ``(dst, out_len_dev)``: ``dst`` (total_windows,) int32, the rank of a window among its
+    utterance's kept windows or -1, and ``out_len_dev`` (U,) int64 on the device, the samples every utterance keeps.
+    ``flags`` (total_windows,) uint8 or bool on the device: ``vad_flags``' or anyone's (webrtcvad's, a neural detector's),
+    non-zero meaning voiced.  ``native`` as ``vad_flags``, with one change-over by size: ``native=None`` takes the torch
+    route where an utterance has more than ``VAD_MASK_TORCH_FROM`` windows (the kernel walks an utterance in one
+    workgroup; profiles/vad_bench.txt)."""
+    _require_cuda(flags, "flags")
+    dev = flags.device
+    U, total = len(layout.lengths), layout.total_windows
+    f = flags.detach()
+    if f.dtype == torch.bool:
+        f = f.to(torch.uint8)
+    if f.dtype != torch.uint8 or tuple(f.shape) != (total,) or not f.is_contiguous() or layout.utt_start.device != dev:
+        raise TypeError(f"flags must be a contiguous ({total},) uint8 or bool tensor on {layout.utt_start.device}")
+    avg_width, max_silence = int(avg_width), int(max_silence)
+    if avg_width < 1 or max_silence < 0:
+        raise ValueError("avg_width must be at least 1 and max_silence at least 0")
+    supported = vad_supported(layout.window, 0, avg_width, max_silence)
+    longest = max(b - a for a, b in zip(layout.win_start, layout.win_start[1:]))
+    use_native = (supported and longest <= VAD_MASK_TORCH_FROM) if native is None else bool(native)
+    if use_native and not supported:
+        raise RuntimeError(f"vad_mask(native=True): no HIP kernel for window {layout.window}, avg_width {avg_width}, "
+                           f"max_silence {max_silence}")
+    if total == 0:
+        return torch.empty(0, dtype=torch.int32, device=dev), torch.zeros(U, dtype=torch.int64, device=dev)
+    if not use_native:
+        return _vad_mask_torch(f, layout, avg_width, max_silence)
+    dst = torch.empty(total, dtype=torch.int32, device=dev)
+    out_len = torch.empty(U, dtype=torch.int64, device=dev)
+    _launch("ge2e_vad_mask", dev, f.data_ptr(), layout.win_start_dev.data_ptr(), U, total, layout.window, avg_width,
+            max_silence, dst.data_ptr(), out_len.data_ptr(), _stream_ptr(f))
+    return dst, out_len
+
+
+def trim_silences(wav: torch.Tensor, lengths=None, *, gain: Optional[torch.Tensor] = None, voice_flags=None, window: int,
+                  floor_span: int = VAD_DEFAULTS["floor_span"], ratio_db: float = VAD_DEFAULTS["ratio_db"],
+                  min_level_dbfs: float = VAD_DEFAULTS["min_level_dbfs"], avg_width: int = 8, max_silence: int = 6,
+                  layout: Optional[VadLayout] = None, native: Optional[bool] = None):
+    """The reference's ``trim_long_silences`` on the device -> ``(flat, out_lengths)`` as ``resample`` returns them:
+    ``flat`` float32, the trimmed utterances back to back, and ``out_lengths`` a Python list of their sample counts.
+    Every utterance is cut to whole windows of ``window`` samples (``vad_window_length * sampling_rate // 1000``), the
+    windows get voice flags, the flags are smoothed and dilated (``vad_mask``) and the samples of the kept windows are
+    copied, bits unchanged (``ge2e_vad_trim``).  ``gain`` (U,) scales the samples for the detector only, as the reference
+    trims the normalised signal; the samples returned are wav's own, and the caller goes on passing ``gain`` to ``melspec``.
+    ``voice_flags``: flags from elsewhere, (total_windows,) non-zero for voiced, utterance after utterance
+    (``vad_layout(...).win_start`` says where); None: ``vad_flags``, the project's own detector -- NOT webrtcvad's, which
+    the reference uses: pass webrtcvad's flags here to get the reference's trimming.
+
+    ONE synchronisation: between the mask and the trim launch the U kept lengths (int64) are read back, because what comes
+    next -- ``melspec``'s frame layout, the partial slices -- is host arithmetic on lengths.  Four launches otherwise (three
+    with ``voice_flags``).  ``native=None`` takes the kernels where they support the parameters and torch ops otherwise
+    (``unfold``, ``cumsum``, indexing: the same flags and the same bits).  Measured (profiles/vad_bench.txt) the kernels are
+    the faster route at every size but one: the mask of a single utterance of more than ``VAD_MASK_TORCH_FROM`` windows
+    (41 minutes), which ``native=None`` therefore leaves to torch's ops (``vad_mask``); the results are the same bits."""
+    _require_cuda(wav, "wav")
+    dev = wav.device
+    if layout is None:
+        layout = vad_layout([wav.numel()] if lengths is None else lengths, window, device=dev)
+    elif layout.window != int(window):
+        raise ValueError(f"layout was built for a window of {layout.window} samples, not {window}")
+    w = _vad_check_wav(wav, layout)
+    U, total, S = len(layout.lengths), layout.total_windows, layout.window
+    if total == 0:
+        return torch.empty(0, dtype=torch.float32, device=dev), [0] * U
+    supported = vad_supported(S, floor_span if voice_flags is None else 0, avg_width, max_silence)
+    use_native = supported if native is None else bool(native)
+    if use_native and not supported:
+        raise RuntimeError(f"trim_silences(native=True): no HIP kernel for window {S}, floor_span {floor_span}, avg_width "
+                           f"{avg_width}, max_silence {max_silence}")
+    if voice_flags is None:
+        flags = vad_flags(w, gain=gain, window=S, floor_span=floor_span, ratio_db=ratio_db, min_level_dbfs=min_level_dbfs,
+                          layout=layout, native=use_native)
+    else:
+        flags = (torch.as_tensor(voice_flags).reshape(-1) != 0).to(device=dev, dtype=torch.uint8)
+        if flags.numel() != total:
+            raise ValueError(f"voice_flags has {flags.numel()} entries; the utterances have {total} windows of {S} samples")
+    dst, out_len = vad_mask(flags, layout, avg_width, max_silence, native=None if native is None else use_native)
+    out_lengths = [int(v) for v in out_len.tolist()]           # the one read-back
+    out = torch.empty(sum(out_lengths), dtype=torch.float32, device=dev)
+    if out.numel() == 0:
+        return out, out_lengths
+    if not use_native:
+        _, _, first = _vad_window_index(layout)
+        return w.unfold(0, S, 1)[first[dst >= 0]].reshape(-1), out_lengths
+    starts = [0]
+    for n in out_lengths[:-1]:
+        starts.append(starts[-1] + n)
+    out_start = torch.tensor(starts, dtype=torch.int64).to(dev)
+    _launch("ge2e_vad_trim", dev, w.data_ptr(), layout.utt_start.data_ptr(), layout.win_start_dev.data_ptr(), dst.data_ptr(),
+            out_start.data_ptr(), U, total, S, out.data_ptr(), _stream_ptr(w))
+    return out, out_lengths
+
+
 def raw_supported(N: int, M: int, D: int) -> bool:
     """Shapes ge2e_loss_raw runs as ONE launch (the one-wave-per-batch kernel's register-only shapes)."""
     return bool(_lib.load().ge2e_raw_supported(N, M, D))
