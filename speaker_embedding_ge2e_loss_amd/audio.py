@@ -204,9 +204,7 @@ class MelFrontEnd:
     def tables(self, device):
         """The packed tables on ``device``, made on first use."""
         from . import functional as GF
-        device = torch.device(device)
-        if device.type == "cuda" and device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
+        device = GF._resolve_device(device)
         t = self._tables.get(device)
         if t is None:
             t = self._tables[device] = GF.melspec_pack(self.window.to(device), self.basis.to(device))
@@ -224,9 +222,7 @@ class MelFrontEnd:
         """``functional.resample_pack`` of ``resample_bank(source_rate, sampling_rate, resample_filter)`` on ``device``,
         made on first use and kept per (rate, filter, device)."""
         from . import functional as GF
-        device = torch.device(device)
-        if device.type == "cuda" and device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
+        device = GF._resolve_device(device)
         key = (int(source_rate), resample_filter if isinstance(resample_filter, str) else tuple(resample_filter), device)
         t = self._resamplers.get(key)
         if t is None:

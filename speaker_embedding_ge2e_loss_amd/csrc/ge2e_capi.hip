@@ -64,6 +64,9 @@ bool workspace_ok(const void* workspace, size_t workspace_bytes, size_t need, ui
 
 // The kernels move 16 bytes per lane to and from E / dE.  (A null pointer -- no dE -- is aligned.)
 bool aligned16(const void* p) { return !((uintptr_t)p & 15); }
+// The audio entries read and write single words: float32 and int32 (aligned4), int64 (aligned8).
+bool aligned4(const void* p) { return !((uintptr_t)p & 3); }
+bool aligned8(const void* p) { return !((uintptr_t)p & 7); }
 
 // The checks of every loss entry point behind its NULL rule, in the order that is part of the ABI: shape, variant,
 // [implementation], workspace, alignment of E and dE; GE2E_OK (0) when all hold.  `shape_good` is the entry's own shape
@@ -765,7 +768,7 @@ int ge2e_melspec(const float* packed, const float* wav, const long long* utt_sta
         return GE2E_ERR_SHAPE;
     const int rc = melspec_shape_check(U, total_frames, n_fft, hop, n_mels);
     if (rc != GE2E_OK) return rc;
-    if (!aligned16(packed) || !aligned16(out) || ((uintptr_t)wav & 3)) return GE2E_ERR_ALIGN;
+    if (!aligned16(packed) || !aligned16(out) || !aligned4(wav)) return GE2E_ERR_ALIGN;
     const ProblemMelspec p = {packed, wav, utt_start, utt_len, utt_padded_len, gain, frame_start, out, total_frames,
                               U, hop, n_mels, mode, (float)pow(10.0, (double)min_level_db / 20.0), min_level_db, ref_level_db};
     return (int)launch_melspec(p, n_fft, (hipStream_t)stream);
@@ -804,7 +807,7 @@ int ge2e_resample(const float* packed, const float* wav, const long long* in_sta
     if (!packed || !wav || !in_start || !in_len || !out_start || !out) return GE2E_ERR_NULL;
     const int rc = resample_shape_check(U, total_out, L, M, lead);
     if (rc != GE2E_OK) return rc;
-    if (!aligned16(packed) || !aligned16(out) || ((uintptr_t)wav & 3)) return GE2E_ERR_ALIGN;
+    if (!aligned16(packed) || !aligned16(out) || !aligned4(wav)) return GE2E_ERR_ALIGN;
     const int W = 2 * lead + 1;
     const ResamplePlan plan = resample_plan(L, M, W);
     const ProblemResample p = {packed, wav, in_start, in_len, out_start, out, U, L, M, lead, W, resample_lpad(L), plan.B,
@@ -826,7 +829,7 @@ int ge2e_volume_gain(const float* wav, const long long* utt_start, const long lo
                      int increase_only, float* gain_out, void* workspace, void* stream) {
     if (!wav || !utt_start || !utt_len || !gain_out || !workspace) return GE2E_ERR_NULL;
     if (U < 1) return GE2E_ERR_SHAPE;
-    if (!aligned16(workspace) || ((uintptr_t)wav & 3) || ((uintptr_t)gain_out & 3)) return GE2E_ERR_ALIGN;
+    if (!aligned16(workspace) || !aligned4(wav) || !aligned4(gain_out)) return GE2E_ERR_ALIGN;
     return (int)launch_volume_gain(wav, utt_start, utt_len, U, (double)target_dbfs, increase_only != 0, gain_out,
                                    (double*)workspace, (hipStream_t)stream);
 }
@@ -858,7 +861,7 @@ int ge2e_vad_flags(const float* wav, const long long* utt_start, const long long
     if (rc != GE2E_OK) return rc;
     if (floor_span > kVadMaxSpan) return GE2E_ERR_IMPL;
     if (!workspace || !aligned16(workspace)) return GE2E_ERR_WORKSPACE;
-    if (((uintptr_t)wav & 3) || ((uintptr_t)gain & 3)) return GE2E_ERR_ALIGN;
+    if (!aligned4(wav) || !aligned4(gain)) return GE2E_ERR_ALIGN;
     if (total_windows == 0) return GE2E_OK;
     const ProblemVad p = {wav, utt_start, gain, win_start, U, S, total_windows};
     return (int)launch_vad_flags(p, floor_span, (unsigned long long)ratio_q8, min_energy, flags, (long long*)workspace,
@@ -872,7 +875,7 @@ int ge2e_vad_mask(const unsigned char* flags, const long long* win_start, int U,
     int rc = vad_shape_check(U, total_windows, S);
     if (rc == GE2E_OK) rc = vad_mask_check(avg_width, max_silence);
     if (rc != GE2E_OK) return rc;
-    if (((uintptr_t)dst & 3) || ((uintptr_t)out_len & 7)) return GE2E_ERR_ALIGN;
+    if (!aligned4(dst) || !aligned8(out_len)) return GE2E_ERR_ALIGN;
     // (an utterance without windows still gets its out_len = 0: the launch is per utterance)
     return (int)launch_vad_mask(flags, win_start, U, S, avg_width, max_silence, dst, out_len, (hipStream_t)stream);
 }
@@ -882,7 +885,7 @@ int ge2e_vad_trim(const float* wav, const long long* utt_start, const long long*
     if (!wav || !utt_start || !win_start || !dst || !out_start || !out) return GE2E_ERR_NULL;
     const int rc = vad_shape_check(U, total_windows, S);
     if (rc != GE2E_OK) return rc;
-    if (((uintptr_t)wav & 3) || ((uintptr_t)out & 3) || ((uintptr_t)dst & 3)) return GE2E_ERR_ALIGN;
+    if (!aligned4(wav) || !aligned4(out) || !aligned4(dst)) return GE2E_ERR_ALIGN;
     if (total_windows == 0) return GE2E_OK;
     const ProblemVad p = {wav, utt_start, nullptr, win_start, U, S, total_windows};
     return (int)launch_vad_trim(p, dst, out_start, out, (hipStream_t)stream);

@@ -245,6 +245,20 @@ __device__ __forceinline__ void static_for(F&& f) {
         static_for<R + 1, RMAX>(f);
     }
 }
+// Which owner holds position x of a ragged layout (the utterance of a frame, a window or a block; the speaker of a row): the
+// last index in [0, n) whose key is not above x, by bisection.  key(i) is non-decreasing in i; equal keys resolve to the
+// last one, so empty owners, which share their start with the next one, are passed over; n >= 1.  Where every key is
+// above x the answer is 0: the caller's keys start at or below every x it asks about.
+template <class X, class Key>
+__device__ __forceinline__ int last_not_above(int n, X x, Key&& key) {
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (key(mid) <= x) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
 template <int LANE>
 __device__ __forceinline__ float lane_put(float vec, float uniform) {   // vec[LANE] = uniform (a wave-uniform value)
     const int u = __builtin_amdgcn_readfirstlane(__float_as_int(uniform));
@@ -424,6 +438,14 @@ inline hipError_t prepare_kernel(KernelLaunchState& st, const void* fn, int thre
     }
     if (blocks_per_cu) *blocks_per_cu = nb;
     return hipSuccess;
+}
+// Host side: the launch of a grid-stride kernel over `total` >= 1 elements (the table packers).  `kernel` takes `args...`
+// and then the count as a size_t; one thread per element, 256 a workgroup, the kernel's launch bound.  Returns the
+// launch's error.
+template <class Kernel, class... Args>
+hipError_t launch_per_element(Kernel kernel, size_t total, hipStream_t stream, Args... args) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, args..., total);
+    return hipGetLastError();
 }
 
 }  // namespace ge2e

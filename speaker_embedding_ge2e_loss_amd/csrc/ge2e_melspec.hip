@@ -1,7 +1,8 @@
 // ge2e_melspec_pack / ge2e_melspec: the mel front end (s0:29-66, 201-219: reflect pad, overlapping frames, periodic Hann
 // window, |rfft|, the mel basis, 20 log10 and the clip), waveforms to frames of [total_frames][n_mels] in ONE launch.
-//   tile      one 512-thread workgroup owns 16 consecutive rows (frames) of out; a row finds its utterance by a binary
-//             search of frame_start.  Wave w transforms rows w and w + 8, then owns column tile w of the mel product.
+//   tile      one 512-thread workgroup owns 16 consecutive rows (frames) of out; a row finds its utterance in frame_start
+//             (last_not_above, ge2e_common.hpp).  Wave w transforms rows w and w + 8, then owns column tile w of the mel
+//             product.
 //   gather    sample n of frame f of an utterance is x[reflect(f hop + n - n_fft / 2)] of the signal extended with zeros to
 //             its padded length; reflection, extension and the utterance's offset are address arithmetic, and a sample at
 //             or past utt_len is never read.  (x gain) window[n], two samples as one complex point.
@@ -122,22 +123,19 @@ __global__ __launch_bounds__(kMelThreads) void melspec_kernel(ProblemMelspec p) 
         const int trow = wid + fr * kMelWaves;
         const long long row = (long long)blockIdx.x * kMelTile + trow;
         const bool valid = row < p.total_frames;
-        // the row's utterance: the last u with frame_start[u] <= row
         long long pos0 = 0, len = 0, P = 1;
         const float* x = p.wav;
         float gain = 1.f;
         if (valid) {
-            int lo = 0, hi = p.U - 1;
-            while (lo < hi) {
-                const int mid = (lo + hi + 1) >> 1;
-                if (p.frame_start[mid] <= row) lo = mid;
-                else hi = mid - 1;
-            }
-            len = p.utt_len[lo];
-            P = p.utt_padded_len ? p.utt_padded_len[lo] : len;
-            x = p.wav + p.utt_start[lo];
-            gain = p.gain ? p.gain[lo] : 1.f;
-            pos0 = (row - p.frame_start[lo]) * (long long)p.hop - NFFT / 2;
+            // the row's utterance: the last u with frame_start[u] <= row (the pointer by value: with p captured by
+            // reference hipcc allocates and vectorises the transform of <256> and <512> differently;
+            // profiles/audio_front_end_refactor_ab.txt, section 3)
+            const int u = last_not_above(p.U, row, [fs = p.frame_start](int i) { return fs[i]; });
+            len = p.utt_len[u];
+            P = p.utt_padded_len ? p.utt_padded_len[u] : len;
+            x = p.wav + p.utt_start[u];
+            gain = p.gain ? p.gain[u] : 1.f;
+            pos0 = (row - p.frame_start[u]) * (long long)p.hop - NFFT / 2;
         }
         bool bad = false;
         // sample n of the frame, times gain and window; never reads at or past utt_len (or before 0, whatever P is)
@@ -255,10 +253,8 @@ KernelLaunchState g_melspec_state[4];
 }  // namespace
 
 hipError_t launch_melspec_pack(const float* window, const float* basis, int n_fft, int n_mels, float* packed, hipStream_t stream) {
-    const size_t total = melspec_packed_floats(n_fft, n_mels);
-    const unsigned blocks = (unsigned)((total + 255) / 256);
-    hipLaunchKernelGGL(melspec_pack_kernel, dim3(blocks), dim3(256), 0, stream, window, basis, n_fft, n_mels, packed, total);
-    return hipGetLastError();
+    return launch_per_element(melspec_pack_kernel, melspec_packed_floats(n_fft, n_mels), stream, window, basis, n_fft, n_mels,
+                              packed);
 }
 
 template <int NFFT>

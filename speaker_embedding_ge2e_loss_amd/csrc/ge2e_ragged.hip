@@ -122,14 +122,7 @@ __global__ __launch_bounds__(256) void ge2e_ragged_kernel(ProblemRagged p, size_
 
         // ---- phase 0: row -> speaker; speaker sums, counts and unit centroids ------------
         // the largest j in [0, N) with off[j] <= r: the speaker of row r under the contract, some speaker without it
-        for (int r = threadIdx.x; r < R; r += blockDim.x) {
-            int lo = 0, hi = N - 1;
-            while (lo < hi) {
-                const int mid = (lo + hi + 1) >> 1;
-                if (off_at(mid) <= r) lo = mid; else hi = mid - 1;
-            }
-            SPK[r] = lo;
-        }
+        for (int r = threadIdx.x; r < R; r += blockDim.x) SPK[r] = last_not_above(N, r, off_at);
         for (int j = wid; j < N; j += NW) {
             const int r0 = off_at(j), r1 = off_at(j + 1);
             const float fm = (float)(r1 - r0);

@@ -49,17 +49,12 @@ __global__ __launch_bounds__(kResampleThreads) void resample_kernel(ProblemResam
     extern __shared__ __attribute__((aligned(16))) float res_lds[];
     // the block's utterance: the last u whose first block, out_start[u] / tile + u, is not past this one
     const long long blk = blockIdx.x;
-    int lo = 0, hi = p.U - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (p.out_start[mid] / p.tile + mid <= blk) lo = mid;
-        else hi = mid - 1;
-    }
-    const long long o0 = p.out_start[lo], n_out = p.out_start[lo + 1] - o0;
-    const long long lt = blk - (o0 / p.tile + lo);          // the tile of the utterance
+    const int u = last_not_above(p.U, blk, [&](int i) { return p.out_start[i] / p.tile + i; });
+    const long long o0 = p.out_start[u], n_out = p.out_start[u + 1] - o0;
+    const long long lt = blk - (o0 / p.tile + u);           // the tile of the utterance
     if (lt < 0 || lt * p.tile >= n_out) return;             // (uniform over the workgroup)
-    const long long len = p.in_len[lo];
-    const float* __restrict__ x = p.wav + p.in_start[lo];
+    const long long len = p.in_len[u];
+    const float* __restrict__ x = p.wav + p.in_start[u];
     const long long t0 = lt * p.tile;
     // output t0 has i0 = t0 M / L exactly (L divides the tile); local word j of the span is sample span_lo + j
     const long long span_lo = lt * ((long long)p.B * R * p.M) + p.lead - (p.W - 1);
@@ -147,10 +142,7 @@ hipError_t launch_resample_r(const ProblemResample& p, long long grid, hipStream
 }  // namespace
 
 hipError_t launch_resample_pack(const float* taps, int L, int M, int W, float* packed, hipStream_t stream) {
-    const size_t total = resample_packed_floats(L, W);
-    const unsigned blocks = (unsigned)((total + 255) / 256);
-    hipLaunchKernelGGL(resample_pack_kernel, dim3(blocks), dim3(256), 0, stream, taps, L, M, W, resample_lpad(L), packed, total);
-    return hipGetLastError();
+    return launch_per_element(resample_pack_kernel, resample_packed_floats(L, W), stream, taps, L, M, W, resample_lpad(L), packed);
 }
 
 hipError_t launch_resample(const ProblemResample& p, const ResamplePlan& plan, long long grid, hipStream_t stream) {

@@ -43,7 +43,7 @@ inline ResamplePlan resample_plan(int L, int M, int W) {
     return {false, 4, B, L * B * 4, 0};
 }
 // Workgroups of a call: utterance u owns blocks out_start[u] / tile + u up to that of u + 1 (at least its ceil(n_out / tile)
-// tiles: the numbers grow strictly, so a block finds its utterance by bisection); floor(total_out / tile) + U in all.
+// tiles: the numbers grow strictly, so a block finds its utterance with last_not_above); floor(total_out / tile) + U in all.
 inline long long resample_grid(long long total_out, int U, int tile) { return total_out / tile + U; }
 
 struct ProblemResample {

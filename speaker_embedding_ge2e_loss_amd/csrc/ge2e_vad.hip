@@ -14,8 +14,8 @@
 // windows a thread, an exclusive scan over the workgroup (shuffles in the wave, the 16 wave totals through LDS).
 // TRIM.  Tiled as ENERGY.  A window with dst < 0 is skipped before any of its samples is touched; a kept one is copied as
 // bits, 16 bytes a lane where source and destination are both 16-byte aligned, a word a lane otherwise.
-// A window finds its utterance by a bisection of win_start: the last u with win_start[u] <= w (empty utterances among them
-// share their start with the next one and are passed over).
+// A window finds its utterance in win_start: the last u with win_start[u] <= w (last_not_above, ge2e_common.hpp: empty
+// utterances among them share their start with the next one and are passed over).
 #include "ge2e_vad.hpp"
 
 #include <stdint.h>
@@ -26,13 +26,26 @@ namespace ge2e {
 namespace {
 
 __device__ __forceinline__ int vad_utterance(const long long* __restrict__ win_start, int U, long long w) {
-    int lo = 0, hi = U - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (win_start[mid] <= w) lo = mid;
-        else hi = mid - 1;
+    return last_not_above(U, w, [&](int u) { return win_start[u]; });
+}
+
+// The walk of ENERGY and TRIM over the workgroup's tile: group g of G lanes takes its kVadWindowsPerGroup windows in turn.
+// A window w whose rank(w) is negative is left before its utterance is looked up; body(w, u, x, lane, rank(w)) gets the
+// others: window w of utterance u, whose S samples start at x.  p is taken, and captured by the bodies, by value: its fields
+// are scalars read once, which no store of a body can be taken to change.
+template <int G, class Rank, class Body>
+__device__ __forceinline__ void vad_walk(const ProblemVad p, Rank&& rank, Body&& body) {
+    constexpr int kTile = kVadThreads / G * kVadWindowsPerGroup;
+    const int g = threadIdx.x / G, lane = threadIdx.x % G;
+    const long long w0 = (long long)blockIdx.x * kTile + g * kVadWindowsPerGroup;
+    for (int i = 0; i < kVadWindowsPerGroup; ++i) {
+        const long long w = w0 + i;
+        if (w >= p.total_windows) break;                    // (uniform over the group)
+        const int r = rank(w);
+        if (r < 0) continue;
+        const int u = vad_utterance(p.win_start, p.U, w);
+        body(w, u, p.wav + p.utt_start[u] + (w - p.win_start[u]) * p.S, lane, r);
     }
-    return lo;
 }
 
 // numpy's np.round(x * g * 32767) in float32 -- two roundings, no fma -- then int16 with saturation; NaN -> 0
@@ -44,14 +57,7 @@ __device__ __forceinline__ int vad_quantise(float x, float g) {
 
 template <int G>
 __global__ __launch_bounds__(kVadThreads) void vad_energy_kernel(ProblemVad p, long long* __restrict__ energy) {
-    constexpr int kTile = kVadThreads / G * kVadWindowsPerGroup;
-    const int g = threadIdx.x / G, lane = threadIdx.x % G;
-    const long long w0 = (long long)blockIdx.x * kTile + g * kVadWindowsPerGroup;
-    for (int i = 0; i < kVadWindowsPerGroup; ++i) {
-        const long long w = w0 + i;
-        if (w >= p.total_windows) break;                    // (uniform over the group)
-        const int u = vad_utterance(p.win_start, p.U, w);
-        const float* __restrict__ x = p.wav + p.utt_start[u] + (w - p.win_start[u]) * p.S;
+    vad_walk<G>(p, [](long long) { return 0; }, [=](long long w, int u, const float* __restrict__ x, int lane, int) {
         const float gain = p.gain ? p.gain[u] : 1.0f;
         int s = 0;
         long long sq = 0;
@@ -67,7 +73,7 @@ __global__ __launch_bounds__(kVadThreads) void vad_energy_kernel(ProblemVad p, l
             sq += __shfl_xor(sq, o);
         }
         if (lane == 0) energy[w] = (long long)p.S * sq - (long long)s * s;
-    }
+    });
 }
 
 __global__ __launch_bounds__(kVadThreads) void vad_flag_kernel(const long long* __restrict__ energy,
@@ -161,16 +167,9 @@ template <int G>
 __global__ __launch_bounds__(kVadThreads) void vad_trim_kernel(ProblemVad p, const int* __restrict__ dst,
                                                                 const long long* __restrict__ out_start,
                                                                 float* __restrict__ out) {
-    constexpr int kTile = kVadThreads / G * kVadWindowsPerGroup;
-    const int g = threadIdx.x / G, lane = threadIdx.x % G;
-    const long long w0 = (long long)blockIdx.x * kTile + g * kVadWindowsPerGroup;
-    for (int i = 0; i < kVadWindowsPerGroup; ++i) {
-        const long long w = w0 + i;
-        if (w >= p.total_windows) break;
-        const int d = dst[w];
-        if (d < 0) continue;                                 // dropped: not a sample of it is read
-        const int u = vad_utterance(p.win_start, p.U, w);
-        const unsigned* __restrict__ from = (const unsigned*)(p.wav + p.utt_start[u] + (w - p.win_start[u]) * p.S);
+    // a window with dst < 0 is dropped: not a sample of it is read
+    vad_walk<G>(p, [=](long long w) { return dst[w]; }, [=](long long, int u, const float* __restrict__ x, int lane, int d) {
+        const unsigned* __restrict__ from = (const unsigned*)x;
         unsigned* __restrict__ to = (unsigned*)(out + out_start[u] + (long long)p.S * d);
         int done = 0;
         if ((((uintptr_t)from | (uintptr_t)to) & 15) == 0) {
@@ -179,20 +178,15 @@ __global__ __launch_bounds__(kVadThreads) void vad_trim_kernel(ProblemVad p, con
             done = quads << 2;
         }
         for (int j = done + lane; j < p.S; j += G) to[j] = from[j];
-    }
+    });
 }
 
-template <int G>
-hipError_t launch_energy_g(const ProblemVad& p, long long* energy, hipStream_t stream) {
+// ENERGY and TRIM have one tiling: the instantiation for the window's lane group over vad_tile(S) windows a workgroup.
+template <class... Args>
+hipError_t launch_walk(void (*k64)(ProblemVad, Args...), void (*k8)(ProblemVad, Args...), const ProblemVad& p,
+                       hipStream_t stream, Args... args) {
     const long long grid = vad_grid(p.total_windows, vad_tile(p.S));
-    hipLaunchKernelGGL((vad_energy_kernel<G>), dim3((unsigned)grid), dim3(kVadThreads), 0, stream, p, energy);
-    return hipGetLastError();
-}
-
-template <int G>
-hipError_t launch_trim_g(const ProblemVad& p, const int* dst, const long long* out_start, float* out, hipStream_t stream) {
-    const long long grid = vad_grid(p.total_windows, vad_tile(p.S));
-    hipLaunchKernelGGL((vad_trim_kernel<G>), dim3((unsigned)grid), dim3(kVadThreads), 0, stream, p, dst, out_start, out);
+    hipLaunchKernelGGL(vad_group(p.S) == 64 ? k64 : k8, dim3((unsigned)grid), dim3(kVadThreads), 0, stream, p, args...);
     return hipGetLastError();
 }
 
@@ -200,7 +194,7 @@ hipError_t launch_trim_g(const ProblemVad& p, const int* dst, const long long* o
 
 hipError_t launch_vad_flags(const ProblemVad& p, int floor_span, unsigned long long ratio_q8, long long min_energy,
                             unsigned char* flags, long long* energy, hipStream_t stream) {
-    const hipError_t err = vad_group(p.S) == 64 ? launch_energy_g<64>(p, energy, stream) : launch_energy_g<8>(p, energy, stream);
+    const hipError_t err = launch_walk(vad_energy_kernel<64>, vad_energy_kernel<8>, p, stream, energy);
     if (err != hipSuccess) return err;
     hipLaunchKernelGGL(vad_flag_kernel, dim3((unsigned)vad_grid(p.total_windows, kVadFlagTile)), dim3(kVadThreads), 0, stream,
                        energy, p.win_start, p.U, p.total_windows, floor_span, ratio_q8, min_energy, flags);
@@ -215,8 +209,7 @@ hipError_t launch_vad_mask(const unsigned char* flags, const long long* win_star
 }
 
 hipError_t launch_vad_trim(const ProblemVad& p, const int* dst, const long long* out_start, float* out, hipStream_t stream) {
-    return vad_group(p.S) == 64 ? launch_trim_g<64>(p, dst, out_start, out, stream)
-                                : launch_trim_g<8>(p, dst, out_start, out, stream);
+    return launch_walk(vad_trim_kernel<64>, vad_trim_kernel<8>, p, stream, dst, out_start, out);
 }
 
 int plan_string_vad(long long total_windows, int U, int S, char* buf, size_t cap) {

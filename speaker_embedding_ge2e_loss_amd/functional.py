@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import functools
 from dataclasses import dataclass
+from itertools import accumulate
 from typing import NamedTuple, Optional
 
 import torch
@@ -1513,6 +1514,86 @@ def melspec_supported(n_fft: int, n_mels: int) -> bool:
     return _lib.load().ge2e_melspec_packed_bytes(int(n_fft), int(n_mels)) > 0
 
 
+# ---- what the audio stages (melspec, resample, volume_gain, vad_*, trim_silences) share: the layout and the call prologue ----
+def _resolve_device(device=None) -> torch.device:
+    """``device`` as a torch.device; None, and "cuda" without an index, are the current device."""
+    dev = torch.device("cuda" if device is None else device)
+    return torch.device("cuda", torch.cuda.current_device()) if dev.type == "cuda" and dev.index is None else dev
+
+
+def _int_list(values) -> list:
+    return [int(v) for v in (values.tolist() if isinstance(values, torch.Tensor) else values)]
+
+
+def _utterance_tables(ls: list, counts: list, device, *extra):
+    """The tables of an audio layout.  ``ls``: the utterances' sample counts, back to back in the flat buffer; ``counts``:
+    how many units (frames, output samples, windows) each has; ``extra``: further per-utterance rows.  Returns ``(unit_start,
+    rows)``: the running starts of the units as a Python list of U + 1 entries, the last one the total, and int64 views of
+    ONE upload to ``device``: the utterances' starts, their lengths, every extra row, then the U + 1 unit starts.
+    ``counts=None``: no units -- ``unit_start`` is None and the rows are the starts and the lengths alone.  Python ints
+    until the upload: a length past 2^32 stays exact."""
+    if len(ls) < 1 or min(ls) < 0:
+        raise ValueError("there must be at least one utterance, none of a negative length")
+    starts = list(accumulate(ls, initial=0))
+    unit_start = None if counts is None else list(accumulate(counts, initial=0))
+    rows = [starts[:-1], ls, *extra] + ([] if counts is None else [unit_start])
+    d = torch.tensor(sum(rows, []), dtype=torch.int64).to(_resolve_device(device))
+    return unit_start, d.split([len(row) for row in rows])
+
+
+def _utterances(layout):
+    """``(starts, lengths, ls)`` of a MelLayout, ResampleLayout or VadLayout: where its utterances lie in the flat buffer,
+    int64 on the device, and the lengths as the Python list.  Every layout type has the two tensors as its first fields."""
+    if not isinstance(layout, (MelLayout, ResampleLayout, VadLayout)):
+        raise TypeError("layout must be a melspec_layout, a resample_layout or a vad_layout")
+    return layout[0], layout[1], layout.lengths
+
+
+def _flat_wav(wav: torch.Tensor) -> torch.Tensor:
+    w = wav.detach()
+    if w.dim() != 1 or w.dtype != torch.float32 or not w.is_contiguous():
+        raise TypeError(f"wav must be a flat contiguous float32 tensor, got {tuple(w.shape)} {w.dtype}")
+    return w
+
+
+def _check_fits(starts: torch.Tensor, ls: list, w: torch.Tensor) -> None:
+    """Utterances of ``ls`` samples, their starts in ``starts``, lie inside ``w`` on w's device."""
+    if starts.device != w.device or sum(ls) > w.numel():
+        raise ValueError(f"the utterances add up to {sum(ls)} samples with their starts on {starts.device}; wav has "
+                         f"{w.numel()} on {w.device}")
+
+
+def _check_gain(gain: Optional[torch.Tensor], U: int, dev) -> Optional[torch.Tensor]:
+    if gain is None:
+        return None
+    if gain.dtype != torch.float32 or gain.device != dev or tuple(gain.shape) != (U,) or not gain.is_contiguous():
+        raise TypeError(f"gain must be a contiguous ({U},) torch.float32 tensor on {dev}")
+    return gain.detach()
+
+
+def _out_tensor(out: Optional[torch.Tensor], shape: tuple, dev) -> torch.Tensor:
+    """``out`` where it is the contiguous float32 tensor of ``shape`` on ``dev``, a new one where it is None."""
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=dev)
+    if tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
+        raise TypeError(f"out must be a contiguous {shape} torch.float32 tensor on {dev}")
+    return out
+
+
+def _use_native(native: Optional[bool], supported: bool, name: str, what, default: Optional[bool] = None) -> bool:
+    """The route of an audio entry: ``native=None`` takes ``default`` (the kernel wherever there is one, where None),
+    ``native=True`` raises where there is none; ``what()`` names the parameters without a kernel."""
+    use = (supported if default is None else default) if native is None else bool(native)
+    if use and not supported:
+        raise RuntimeError(f"{name}(native=True): no HIP kernel for {what()}")
+    return use
+
+
+def _utterance_views(w: torch.Tensor, layout) -> list:
+    """The utterances of the flat buffer as views, in the layout's order (the torch routes)."""
+    return [w[a:a + n] for a, n in zip(accumulate(layout.lengths, initial=0), layout.lengths)]
+
+
 class MelTables(NamedTuple):
     """What ``melspec_pack`` returns: the window (n_fft,) and basis (n_fft/2 + 1, n_mels) as given (float32, the torch
     route reads them) and ``packed``, ge2e_melspec_pack's buffer, or None where the shape has no native kernel."""
@@ -1567,39 +1648,25 @@ def melspec_layout(lengths, *, hop: int, n_fft: int, padded_lengths=None, device
     it, extended with zeros to ``padded_lengths[u]`` (its own length where None), and has ``padded // hop + 1`` frames.
     ``lengths`` / ``padded_lengths``: Python lists or CPU tensors.  Build it once for a captured graph and pass it as
     ``melspec(layout=...)``: building it uploads four small tensors."""
-    ls = [int(v) for v in (lengths.tolist() if isinstance(lengths, torch.Tensor) else lengths)]
-    if padded_lengths is None:
-        ps = list(ls)
-    else:
-        ps = [int(v) for v in (padded_lengths.tolist() if isinstance(padded_lengths, torch.Tensor) else padded_lengths)]
+    ls = _int_list(lengths)
+    ps = list(ls) if padded_lengths is None else _int_list(padded_lengths)
     if hop < 1 or len(ls) < 1 or len(ps) != len(ls):
         raise ValueError("melspec needs hop >= 1, at least one utterance and one padded length per utterance")
-    starts, frame_start = [], [0]
-    at = 0
     for n, p in zip(ls, ps):
         if n < 0 or p < n or p <= n_fft // 2:
             raise ValueError(f"an utterance of {n} samples padded to {p}: the padded length must be at least the length "
                              f"and more than n_fft / 2 = {n_fft // 2} (the reflection)")
-        starts.append(at)
-        at += n
-        frame_start.append(frame_start[-1] + p // hop + 1)
-    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    meta = torch.tensor([starts, ls, ps, frame_start[:-1]], dtype=torch.int64)
-    tail = torch.tensor([frame_start[-1]], dtype=torch.int64)
-    d = torch.cat([meta.reshape(-1), tail]).to(dev)
-    U = len(ls)
-    return MelLayout(d[:U], d[U:2 * U], d[2 * U:3 * U], d[3 * U:], frame_start, ls, ps, int(hop))
+    frame_start, rows = _utterance_tables(ls, [p // hop + 1 for p in ps], device, ps)
+    return MelLayout(*rows, frame_start, ls, ps, int(hop))
 
 
 def _melspec_torch(t: MelTables, wav, lay: MelLayout, gain, mode, min_level_db, ref_level_db, out):
     """The same frames with torch's ops on wav's device: pad, ``unfold``, ``torch.fft.rfft``, ``matmul``."""
     n_fft = t.n_fft
-    for u, (n, p) in enumerate(zip(lay.lengths, lay.padded_lengths)):
-        at = int(sum(lay.lengths[:u]))
-        x = wav[at:at + n]
+    for u, x in enumerate(_utterance_views(wav, lay)):
         if gain is not None:
             x = x * gain[u]
-        x = torch.nn.functional.pad(x, (0, p - n))
+        x = torch.nn.functional.pad(x, (0, lay.padded_lengths[u] - lay.lengths[u]))
         x = torch.nn.functional.pad(x[None, None], (n_fft // 2, n_fft // 2), mode="reflect")[0, 0]
         m = torch.fft.rfft(x.unfold(0, n_fft, lay.hop) * t.window, dim=1).abs().matmul(t.basis)
         if mode == "db":
@@ -1625,9 +1692,7 @@ def melspec(packed, wav: torch.Tensor, lengths=None, *, hop: int, n_fft: Optiona
     it has none; ``native=False`` is the torch route."""
     _require_cuda(wav, "wav")
     dev = wav.device
-    w = wav.detach()
-    if w.dim() != 1 or w.dtype != torch.float32 or not w.is_contiguous():
-        raise TypeError(f"wav must be a flat contiguous float32 tensor, got {tuple(w.shape)} {w.dtype}")
+    w = _flat_wav(wav)
     if mode not in ("db", "linear"):
         raise ValueError(f"mode must be 'db' or 'linear', got {mode!r}")
     if not min_level_db < 0:
@@ -1641,9 +1706,9 @@ def melspec(packed, wav: torch.Tensor, lengths=None, *, hop: int, n_fft: Optiona
         pk = packed
         if n_fft is None or n_mels is None:
             raise ValueError("a raw packed tensor needs n_fft and n_mels")
-    use_native = pk is not None and melspec_supported(n_fft, n_mels) if native is None else bool(native)
-    if use_native and (pk is None or not melspec_supported(n_fft, n_mels)):
-        raise RuntimeError(f"melspec(native=True): no HIP kernel for n_fft {n_fft}, n_mels {n_mels}")
+    # (native=False does not ask the library whether the shape has a kernel)
+    supported = (native is None or bool(native)) and pk is not None and melspec_supported(n_fft, n_mels)
+    use_native = _use_native(native, supported, "melspec", lambda: f"n_fft {n_fft}, n_mels {n_mels}")
     if not use_native and tables is None:
         raise ValueError("the torch route needs melspec_pack's MelTables (window and basis), not a raw packed tensor")
     if layout is None:
@@ -1651,17 +1716,10 @@ def melspec(packed, wav: torch.Tensor, lengths=None, *, hop: int, n_fft: Optiona
                                 padded_lengths=padded_lengths, device=dev)
     elif layout.hop != hop or layout.utt_start.device != dev:
         raise ValueError(f"layout was built for hop {layout.hop} on {layout.utt_start.device}")
-    if sum(layout.lengths) > w.numel():
-        raise ValueError(f"the lengths add up to {sum(layout.lengths)} samples, wav has {w.numel()}")
+    _check_fits(layout.utt_start, layout.lengths, w)
     U, total = len(layout.lengths), layout.frame_start[-1]
-    if gain is not None:
-        if gain.dtype != torch.float32 or gain.device != dev or tuple(gain.shape) != (U,) or not gain.is_contiguous():
-            raise TypeError(f"gain must be a contiguous ({U},) torch.float32 tensor on {dev}")
-        gain = gain.detach()
-    if out is None:
-        out = torch.empty(total, n_mels, dtype=torch.float32, device=dev)
-    elif tuple(out.shape) != (total, n_mels) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
-        raise TypeError(f"out must be a contiguous ({total}, {n_mels}) torch.float32 tensor on {dev}")
+    gain = _check_gain(gain, U, dev)
+    out = _out_tensor(out, (total, n_mels), dev)
     if not use_native:
         return _melspec_torch(tables, w, layout, gain, mode, min_level_db, ref_level_db, out), layout.frame_start
     if pk.device != dev or pk.dtype != torch.float32 or not pk.is_contiguous() or \
@@ -1742,21 +1800,12 @@ def resample_layout(lengths, up: int, down: int, device=None) -> ResampleLayout:
     and becomes ``ceil(lengths[u] up / down)`` samples from the sum of those before it.  ``lengths``: a Python list or CPU
     tensor.  Build it once for a captured graph and pass it as ``resample(layout=...)``: building it is host arithmetic and
     one small upload."""
-    ls = [int(v) for v in (lengths.tolist() if isinstance(lengths, torch.Tensor) else lengths)]
-    up, down = int(up), int(down)
-    if up < 1 or down < 1 or len(ls) < 1 or min(ls) < 0:
-        raise ValueError("resample needs up, down >= 1 and at least one utterance, none of a negative length")
-    starts, out_start = [], [0]
-    at = 0
-    for n in ls:
-        starts.append(at)
-        at += n
-        out_start.append(out_start[-1] + (n * up + down - 1) // down)
-    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    d = torch.tensor(starts + ls + out_start, dtype=torch.int64).to(dev)
-    U = len(ls)
-    return ResampleLayout(d[:U], d[U:2 * U], d[2 * U:], out_start, ls, [b - a for a, b in zip(out_start, out_start[1:])],
-                          up, down)
+    ls, up, down = _int_list(lengths), int(up), int(down)
+    if up < 1 or down < 1:
+        raise ValueError("resample needs up, down >= 1")
+    out_lengths = [(n * up + down - 1) // down for n in ls]
+    out_start, rows = _utterance_tables(ls, out_lengths, device)
+    return ResampleLayout(*rows, out_start, ls, out_lengths, up, down)
 
 
 def _resample_torch(t: ResampleTables, wav, lay: ResampleLayout, out):
@@ -1765,15 +1814,13 @@ def _resample_torch(t: ResampleTables, wav, lay: ResampleLayout, out):
     channel n mod up at position n div up."""
     L, M, lead, W = t.up, t.down, t.lead, t.width
     shift, weight = (L - 1) * M // L, t.weight
-    at = 0
-    for u, (n, n_out) in enumerate(zip(lay.lengths, lay.out_lengths)):
+    for u, (x, n, n_out) in enumerate(zip(_utterance_views(wav, lay), lay.lengths, lay.out_lengths)):
         if n_out:
             q = (n_out + L - 1) // L                      # positions: outputs n = c + L j, j < q
             right = max(0, (q - 1) * M + shift + lead + 1 - n)
-            x = torch.nn.functional.pad(wav[at:at + n], (W - 1 - lead, right))
+            x = torch.nn.functional.pad(x, (W - 1 - lead, right))
             y = torch.nn.functional.conv1d(x[None, None], weight, stride=M)[0, :, :q]
             out[lay.out_start[u]:lay.out_start[u + 1]] = y.t().reshape(-1)[:n_out]
-        at += n
     return out
 
 
@@ -1790,25 +1837,18 @@ def resample(tables: ResampleTables, wav: torch.Tensor, lengths=None, *, out: Op
     (profiles/resample_bench.txt)."""
     _require_cuda(wav, "wav")
     dev = wav.device
-    w = wav.detach()
-    if w.dim() != 1 or w.dtype != torch.float32 or not w.is_contiguous():
-        raise TypeError(f"wav must be a flat contiguous float32 tensor, got {tuple(w.shape)} {w.dtype}")
+    w = _flat_wav(wav)
     if not isinstance(tables, ResampleTables):
         raise TypeError("tables must be resample_pack's ResampleTables")
-    use_native = tables.packed is not None if native is None else bool(native)
-    if use_native and tables.packed is None:
-        raise RuntimeError(f"resample(native=True): no HIP kernel for up {tables.up}, down {tables.down}, width {tables.width}")
+    use_native = _use_native(native, tables.packed is not None, "resample",
+                             lambda: f"up {tables.up}, down {tables.down}, width {tables.width}")
     if layout is None:
         layout = resample_layout([w.numel()] if lengths is None else lengths, tables.up, tables.down, device=dev)
     elif (layout.up, layout.down) != (tables.up, tables.down) or layout.in_start.device != dev:
         raise ValueError(f"layout was built for {layout.up} / {layout.down} on {layout.in_start.device}")
-    if sum(layout.lengths) > w.numel():
-        raise ValueError(f"the lengths add up to {sum(layout.lengths)} samples, wav has {w.numel()}")
+    _check_fits(layout.in_start, layout.lengths, w)
     U, total = len(layout.lengths), layout.out_start[-1]
-    if out is None:
-        out = torch.empty(total, dtype=torch.float32, device=dev)
-    elif tuple(out.shape) != (total,) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
-        raise TypeError(f"out must be a contiguous ({total},) torch.float32 tensor on {dev}")
+    out = _out_tensor(out, (total,), dev)
     if total == 0:
         return out, layout.out_lengths
     if not use_native:
@@ -1828,41 +1868,23 @@ def volume_gain(wav: torch.Tensor, lengths=None, target_dbfs: float = -30.0, inc
     launches on the current stream: the sum of squares per utterance in float64 in a fixed order, without the float64
     copies of the whole buffer ``audio.volume_gain`` makes.  ``wav`` flat float32, ``lengths`` as ``resample`` (None: one
     utterance).  ``native=False``: ``audio.volume_gain``, the torch route; None and True: the kernel (it has no unsupported
-    shape).  ``layout`` (a ``resample_layout`` or ``melspec_layout`` of the utterances in ``wav``: its starts and lengths
-    on the device are used), ``out`` (U,) and ``workspace`` (``volume_gain_workspace``) make the call allocation-free for a
-    captured graph."""
+    shape).  ``layout`` (a ``melspec_layout``, ``resample_layout`` or ``vad_layout`` of the utterances in ``wav``: its
+    starts and lengths on the device are used), ``out`` (U,) and ``workspace`` (``volume_gain_workspace``) make the call
+    allocation-free for a captured graph."""
     if native is not None and not native:
         from .audio import volume_gain as torch_route
         return torch_route(wav, lengths, target_dbfs, increase_only)
     _require_cuda(wav, "wav")
     dev = wav.device
-    w = wav.detach()
-    if w.dim() != 1 or w.dtype != torch.float32 or not w.is_contiguous():
-        raise TypeError(f"wav must be a flat contiguous float32 tensor, got {tuple(w.shape)} {w.dtype}")
+    w = _flat_wav(wav)
     if layout is None:
-        ls = [w.numel()] if lengths is None else [int(v) for v in (lengths.tolist() if isinstance(lengths, torch.Tensor) else lengths)]
-        if len(ls) < 1 or min(ls) < 0 or sum(ls) > w.numel():
-            raise ValueError(f"lengths {ls[:4]}... must be non-negative and add up to at most wav's {w.numel()} samples")
-        starts = [0]
-        for n in ls[:-1]:
-            starts.append(starts[-1] + n)
-        d = torch.tensor(starts + ls, dtype=torch.int64).to(dev)
-        U = len(ls)
-        start_dev, len_dev = d[:U], d[U:]
+        ls = [w.numel()] if lengths is None else _int_list(lengths)
+        _, (start_dev, len_dev) = _utterance_tables(ls, None, dev)
     else:
-        if isinstance(layout, ResampleLayout):
-            start_dev, len_dev = layout.in_start, layout.in_len
-        elif isinstance(layout, MelLayout):
-            start_dev, len_dev = layout.utt_start, layout.utt_len
-        else:
-            raise TypeError("layout must be a resample_layout or a melspec_layout")
-        U = len(layout.lengths)
-        if start_dev.device != dev or sum(layout.lengths) > w.numel():
-            raise ValueError(f"layout is on {start_dev.device} for {sum(layout.lengths)} samples; wav has {w.numel()} on {dev}")
-    if out is None:
-        out = torch.empty(U, dtype=torch.float32, device=dev)
-    elif tuple(out.shape) != (U,) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
-        raise TypeError(f"out must be a contiguous ({U},) torch.float32 tensor on {dev}")
+        start_dev, len_dev, ls = _utterances(layout)
+    _check_fits(start_dev, ls, w)
+    U = len(ls)
+    out = _out_tensor(out, (U,), dev)
     if workspace is None:
         workspace = volume_gain_workspace(w.numel(), U, dev)
     elif workspace.device != dev or workspace.dtype != torch.float64 or not workspace.is_contiguous() or \
@@ -1912,20 +1934,11 @@ def vad_layout(lengths, window: int, device=None) -> VadLayout:
     """The index tables of the silence-trimming calls: utterance u is ``lengths[u]`` samples from the sum of the lengths
     before it and has ``lengths[u] // window`` windows.  ``lengths``: a Python list or CPU tensor.  Host arithmetic and one
     small upload; build it once for a captured graph."""
-    ls = [int(v) for v in (lengths.tolist() if isinstance(lengths, torch.Tensor) else lengths)]
-    window = int(window)
-    if window < 1 or len(ls) < 1 or min(ls) < 0:
-        raise ValueError("the window must be at least 1 sample and there must be an utterance, none of a negative length")
-    starts, win_start = [], [0]
-    at = 0
-    for n in ls:
-        starts.append(at)
-        at += n
-        win_start.append(win_start[-1] + n // window)
-    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    d = torch.tensor(starts + ls + win_start, dtype=torch.int64).to(dev)
-    U = len(ls)
-    return VadLayout(d[:U], d[U:2 * U], d[2 * U:], win_start, ls, window)
+    ls, window = _int_list(lengths), int(window)
+    if window < 1:
+        raise ValueError("the window must be at least 1 sample")
+    win_start, rows = _utterance_tables(ls, [n // window for n in ls], device)
+    return VadLayout(*rows, win_start, ls, window)
 
 
 def vad_detector_params(window: int, ratio_db: float, min_level_dbfs: float):
@@ -1934,14 +1947,15 @@ def vad_detector_params(window: int, ratio_db: float, min_level_dbfs: float):
             int(round(window * window * (32767.0 * 10.0 ** (min_level_dbfs / 20.0)) ** 2)))
 
 
-def _vad_check_wav(wav: torch.Tensor, layout: VadLayout) -> torch.Tensor:
-    w = wav.detach()
-    if w.dim() != 1 or w.dtype != torch.float32 or not w.is_contiguous():
-        raise TypeError(f"wav must be a flat contiguous float32 tensor, got {tuple(w.shape)} {w.dtype}")
-    if layout.utt_start.device != w.device or sum(layout.lengths) > w.numel():
-        raise ValueError(f"layout is on {layout.utt_start.device} for {sum(layout.lengths)} samples; wav has {w.numel()} on "
-                         f"{w.device}")
-    return w
+def _vad_prologue(wav: torch.Tensor, lengths, window: int, layout: Optional[VadLayout]):
+    """``(w, layout)`` of ``vad_flags`` and ``trim_silences``: the call's layout, built where None, and the checked wav."""
+    if layout is None:
+        layout = vad_layout([wav.numel()] if lengths is None else lengths, window, device=wav.device)
+    elif layout.window != int(window):
+        raise ValueError(f"layout was built for a window of {layout.window} samples, not {window}")
+    w = _flat_wav(wav)
+    _check_fits(layout.utt_start, layout.lengths, w)
+    return w, layout
 
 
 def _vad_window_index(lay: VadLayout):
@@ -2012,23 +2026,13 @@ def vad_flags(wav: torch.Tensor, lengths=None, gain: Optional[torch.Tensor] = No
     ``native=True`` raises there."""
     _require_cuda(wav, "wav")
     dev = wav.device
-    if layout is None:
-        layout = vad_layout([wav.numel()] if lengths is None else lengths, window, device=dev)
-    elif layout.window != int(window):
-        raise ValueError(f"layout was built for a window of {layout.window} samples, not {window}")
-    w = _vad_check_wav(wav, layout)
+    w, layout = _vad_prologue(wav, lengths, window, layout)
     U, total, S = len(layout.lengths), layout.total_windows, layout.window
-    if gain is not None:
-        if gain.dtype != torch.float32 or gain.device != dev or tuple(gain.shape) != (U,) or not gain.is_contiguous():
-            raise TypeError(f"gain must be a contiguous ({U},) torch.float32 tensor on {dev}")
-        gain = gain.detach()
+    gain = _check_gain(gain, U, dev)
     floor_span = int(floor_span)
     if floor_span < 0:
         raise ValueError("floor_span must not be negative")
-    supported = vad_supported(S, floor_span)
-    use_native = supported if native is None else bool(native)
-    if use_native and not supported:
-        raise RuntimeError(f"vad_flags(native=True): no HIP kernel for window {S}, floor_span {floor_span}")
+    use_native = _use_native(native, vad_supported(S, floor_span), "vad_flags", lambda: f"window {S}, floor_span {floor_span}")
     ratio_q8, min_energy = vad_detector_params(S, ratio_db, min_level_dbfs)
     if total == 0:
         return torch.empty(0, dtype=torch.uint8, device=dev)
@@ -2080,10 +2084,8 @@ def vad_mask(flags: torch.Tensor, layout: VadLayout, avg_width: int = 8, max_sil
         raise ValueError("avg_width must be at least 1 and max_silence at least 0")
     supported = vad_supported(layout.window, 0, avg_width, max_silence)
     longest = max(b - a for a, b in zip(layout.win_start, layout.win_start[1:]))
-    use_native = (supported and longest <= VAD_MASK_TORCH_FROM) if native is None else bool(native)
-    if use_native and not supported:
-        raise RuntimeError(f"vad_mask(native=True): no HIP kernel for window {layout.window}, avg_width {avg_width}, "
-                           f"max_silence {max_silence}")
+    use_native = _use_native(native, supported, "vad_mask", lambda: f"window {layout.window}, avg_width {avg_width}, "
+                             f"max_silence {max_silence}", default=supported and longest <= VAD_MASK_TORCH_FROM)
     if total == 0:
         return torch.empty(0, dtype=torch.int32, device=dev), torch.zeros(U, dtype=torch.int64, device=dev)
     if not use_native:
@@ -2117,19 +2119,13 @@ def trim_silences(wav: torch.Tensor, lengths=None, *, gain: Optional[torch.Tenso
     (41 minutes), which ``native=None`` therefore leaves to torch's ops (``vad_mask``); the results are the same bits."""
     _require_cuda(wav, "wav")
     dev = wav.device
-    if layout is None:
-        layout = vad_layout([wav.numel()] if lengths is None else lengths, window, device=dev)
-    elif layout.window != int(window):
-        raise ValueError(f"layout was built for a window of {layout.window} samples, not {window}")
-    w = _vad_check_wav(wav, layout)
+    w, layout = _vad_prologue(wav, lengths, window, layout)
     U, total, S = len(layout.lengths), layout.total_windows, layout.window
     if total == 0:
         return torch.empty(0, dtype=torch.float32, device=dev), [0] * U
-    supported = vad_supported(S, floor_span if voice_flags is None else 0, avg_width, max_silence)
-    use_native = supported if native is None else bool(native)
-    if use_native and not supported:
-        raise RuntimeError(f"trim_silences(native=True): no HIP kernel for window {S}, floor_span {floor_span}, avg_width "
-                           f"{avg_width}, max_silence {max_silence}")
+    use_native = _use_native(native, vad_supported(S, floor_span if voice_flags is None else 0, avg_width, max_silence),
+                             "trim_silences", lambda: f"window {S}, floor_span {floor_span}, avg_width {avg_width}, "
+                             f"max_silence {max_silence}")
     if voice_flags is None:
         flags = vad_flags(w, gain=gain, window=S, floor_span=floor_span, ratio_db=ratio_db, min_level_dbfs=min_level_dbfs,
                           layout=layout, native=use_native)
@@ -2145,10 +2141,7 @@ def trim_silences(wav: torch.Tensor, lengths=None, *, gain: Optional[torch.Tenso
     if not use_native:
         _, _, first = _vad_window_index(layout)
         return w.unfold(0, S, 1)[first[dst >= 0]].reshape(-1), out_lengths
-    starts = [0]
-    for n in out_lengths[:-1]:
-        starts.append(starts[-1] + n)
-    out_start = torch.tensor(starts, dtype=torch.int64).to(dev)
+    out_start = torch.tensor(list(accumulate(out_lengths[:-1], initial=0)), dtype=torch.int64).to(dev)
     _launch("ge2e_vad_trim", dev, w.data_ptr(), layout.utt_start.data_ptr(), layout.win_start_dev.data_ptr(), dst.data_ptr(),
             out_start.data_ptr(), U, total, S, out.data_ptr(), _stream_ptr(w))
     return out, out_lengths

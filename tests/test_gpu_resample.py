@@ -217,6 +217,23 @@ def test_rows_do_not_depend_on_their_batch_and_calls_repeat(lib):
         assert all(same_bits(g, h) for g, h in zip(batch, again))
 
 
+@pytest.mark.parametrize("L,M", [(160, 441), (1, 3), (2, 1)])
+def test_empty_utterances_first_in_a_run_and_last_but_one(lib, L, M):
+    """Empty utterances own one block each and share their out_start with the next utterance: first, in a run of two and
+    last but one.  A block must find its own utterance whatever stands around it: every utterance of the batched call is
+    held to resample_ref by the oracle's bound (a float64 oracle: the bound, not equality, is its comparison) and equals,
+    to the bit, the same entry on that utterance alone."""
+    lead, taps = bank32(L, M, "kaiser_fast")
+    lens = [0, 5, 0, 0, 900, 0, 1]
+    utts = [noise(n, 50 + i, amp=1.0) for i, n in enumerate(lens)]
+    got = res_abi(lib, taps, L, M, lead, utts)
+    assert [len(g) for g in got] == [rr.out_length(n, L, M) for n in lens]
+    for i, (g, u) in enumerate(zip(got, utts)):
+        within_bound((L, M, i), g, u, taps, L, M, lead)
+        if len(u):
+            assert same_bits(g, res_abi(lib, taps, L, M, lead, [u])[0]), i
+
+
 # ---- the instantiations the shapes above do not reach -------------------------------------------------------------------------
 # The ratios above run resample<lds,8> and, at (160, 441), resample<lds,2>.  (L, M, lead) for the other three: four outputs a
 # thread (96 kHz -> 16 kHz under kaiser_best has this shape: W 769), one output a thread, and a span LDS does not hold, read

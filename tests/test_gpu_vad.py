@@ -318,6 +318,48 @@ def test_determinism_and_independence_of_the_batch(lib):
     assert at == len(first[4])
 
 
+@pytest.mark.parametrize("S,lens,gains", [(480, [1000, 0, 479, 480, 961], [1.0, 2.0, 0.5, 0.25, 1.5]),
+                                          (30, [0, 4000, 0, 95, 0], None)])
+def test_empty_utterances_first_in_runs_and_near_the_end(lib, S, lens, gains):
+    """Utterances without a window share their win_start with the next one: first, in a run, between two others and last.
+    A window must find the LAST utterance that starts at or before it.  Every stage equals vad_ref to the bit, utterance by
+    utterance, and equals the same calls on each non-empty utterance alone; the mask and the trim run twice, on the
+    detector's flags and with every window voiced (width 1, no dilation), so that the trim looks up every window."""
+    utts = [signal(n, 90 + i, S) for i, n in enumerate(lens)]
+    span, ratio, floor_energy = 3, vr.ratio_q8(3.0), vr.min_energy(S, -50.0)
+
+    def stages(b):
+        flags, energies = b.flags(lib, span, ratio, floor_energy)
+        out = [flags, energies[:b.total]]
+        for f, A, silence in ((flags, 3, 2), (np.ones(b.total, np.uint8), 1, 0)):
+            dst, out_len = b.mask(lib, f, A, silence)
+            out += [dst, out_len, b.trim(lib, dst, out_len.tolist())[0]]
+        return out
+
+    b = Batch(utts, S, gains=gains)
+    got = stages(b)
+    want_flags = np.concatenate(b.ref_flags(span, ratio, floor_energy))
+    assert np.array_equal(got[0], want_flags) and np.array_equal(got[1], np.concatenate(b.ref_energies()))
+    for k, f, A, silence in ((2, want_flags, 3, 2), (5, np.ones(b.total, np.uint8), 1, 0)):
+        dst, kept, keeps = b.ref_mask(f, A, silence)
+        assert np.array_equal(got[k], dst) and got[k + 1].tolist() == kept
+        assert np.array_equal(got[k + 2], np.concatenate(b.ref_trim(keeps)).view(np.uint32))
+    assert got[6].tolist() == [w * S for w in b.windows] and b.total > 0
+    at = {4: 0, 7: 0}
+    for u, x in enumerate(utts):
+        if len(x) == 0:
+            continue
+        alone = stages(Batch([x], S, offset=u % 2, gains=None if gains is None else [gains[u]]))
+        a, e = b.win_start[u], b.win_start[u + 1]
+        for k in (0, 1, 2, 5):
+            assert np.array_equal(alone[k], got[k][a:e]), (u, k)
+        for k in (4, 7):
+            n = int(got[k - 1][u])
+            assert alone[k - 1][0] == n and np.array_equal(alone[k], got[k][at[k]:at[k] + n]), (u, k)
+            at[k] += n
+    assert at == {4: len(got[4]), 7: len(got[7])}
+
+
 # ---- functional and the pipeline ---------------------------------------------------------------------------------------------
 def host_trim(wavs, S, gains=None, A=8, silence=6, **detector):
     return [vr.trim_silences(w, S, 1.0 if gains is None else gains[u], A, silence, **detector)[0] for u, w in enumerate(wavs)]

@@ -174,6 +174,28 @@ def test_layout_and_lengths_against_the_ceil_formula():
     assert fe.resampled_lengths([123], None) == [123] and fe.resampled_lengths([123], 16000) == [123]
 
 
+def test_volume_gain_reads_any_layout_through_one_accessor():
+    """The three layout types hand out the same utterance starts and lengths (what volume_gain's kernel reads, whichever
+    layout it is given); the torch route of volume_gain takes ``lengths`` and ignores a layout, so with each of them it
+    returns audio.volume_gain's values."""
+    from speaker_embedding_ge2e_loss_amd import functional as GF
+    lengths = [700, 300, 1500, 260]
+    layouts = [GF.melspec_layout(lengths, hop=160, n_fft=512, device="cpu"), GF.resample_layout(lengths, 160, 441, device="cpu"),
+               GF.vad_layout(lengths, 480, device="cpu")]
+    wav = torch.as_tensor(0.05 * np.random.default_rng(3).standard_normal(sum(lengths)).astype(np.float32))
+    want = audio.volume_gain(wav, lengths)
+    for lay in layouts:
+        starts, lens, ls = GF._utterances(lay)
+        assert starts.tolist() == [0, 700, 1000, 2500] and lens.tolist() == lengths == ls
+        assert starts.dtype == lens.dtype == torch.int64 and starts.device == lens.device == torch.device("cpu")
+        GF._check_fits(starts, ls, wav)
+        assert torch.equal(GF.volume_gain(wav, lengths, native=False, layout=lay), want)
+        with pytest.raises(ValueError):
+            GF._check_fits(starts, ls, wav[:-1])
+    with pytest.raises(TypeError):
+        GF._utterances((layouts[0][0], layouts[0][1]))
+
+
 @pytest.mark.parametrize("name", ["kaiser_best", "kaiser_fast"])
 def test_the_bank_is_the_formula_and_its_phases_sum_to_one(name):
     worst = 0.0

@@ -4,7 +4,7 @@ bit for bit on one GPU:
     GE2E_HIP_LIB=$PWD/speaker_embedding_ge2e_loss_amd/libge2e_hip_parent.so python tools/output_digest.py > a.txt
     python tools/output_digest.py > b.txt && diff a.txt b.txt
 
-(tools/build_rev.sh builds the other revision's library.)  Six sections:
+(tools/build_rev.sh builds the other revision's library.)  Seven sections:
 
   1. the fp32 matrix-core implementations: loss | per | dE | dw | db per (implementation, shape, variant), with and
      without the gradient.  A pair the library refuses prints SKIP.
@@ -49,6 +49,17 @@ bit for bit on one GPU:
        (3, 2, 13, 128, 1, 37)   n_mels no multiple of 4: the scalar-load arm; D padding
        (73, 7, 12, 128, 1, 16)  one K-slice of the weight gradient  (33, 32, 12, 128, 1, 16)  three K-slices
        (33, 2, 40, 128, 2, 64) again through row_start: windows one frame apart, overlapping
+  7. the audio front end through ``functional``, every call once with native=True and once with native=False, one line per
+     call over its tensors and its Python lists (frame_start, out_lengths), seeded inputs:
+       melspec at n_fft 512, hop 160, 40 mels, lengths [2500, 6500, 300] padded to [3200, 6500, 300], with a gain, both
+       modes: 64 frames, four tiles, utterance boundaries inside tiles
+       resample at (up, down) = (160, 441), (1, 3), (2, 1), banks audio.resample_bank(..., "kaiser_fast"), lengths
+       [0, 5, 0, 0, 900, 0, 1]: empty utterances first, in a run and last but one; volume_gain on the resampled output,
+       once with a layout and once with lengths
+       vad_flags, vad_mask and trim_silences: a window of 480 at lengths [1000, 0, 479, 480, 961] with a gain; a window
+       of 30 at [0, 4000, 0, 95, 0]; and that one again with voice_flags handed in
+       MelFrontEnd.frames on waveforms of 0.3 s, 0.5 s and 0.31 s at 44100 Hz, source_rate=44100, normalize_volume,
+       trim_silences, pad_to_partials
 
 Exit status 1 if one of the fp32 matrix-core implementations appears in no line, or if the plan of a line of section 5 is
 not the one its table claims.
@@ -385,6 +396,63 @@ def encoder_section(dev):
             line(f"{tag} encode_bwd", d_flat, ws[:n_dz], ws[dy:dy + R * D])
 
 
+RESAMPLE_RATIOS = [(160, 441), (1, 3), (2, 1)]
+RESAMPLE_LENGTHS = [0, 5, 0, 0, 900, 0, 1]
+VAD_CASES = [(480, [1000, 0, 479, 480, 961], [1.0, 2.0, 0.5, 0.25, 1.5]), (30, [0, 4000, 0, 95, 0], None)]
+VAD_DETECTOR = dict(floor_span=5, ratio_db=3.0, min_level_dbfs=-50.0)
+VAD_MASK = dict(avg_width=3, max_silence=2)
+
+
+def bursts(n, seed, period, dev):
+    """Noise that is loud (0.1) for `period` samples and quiet (0.0003) for the next, and so on."""
+    x = np.random.default_rng(seed).standard_normal(n) * np.where((np.arange(n) // period) % 2 == 0, 0.1, 0.0003)
+    return torch.as_tensor(x.astype(np.float32), device=dev)
+
+
+def audio_section(dev):
+    from speaker_embedding_ge2e_loss_amd import audio
+
+    def both(tag, call):
+        for native in (True, False):
+            out = call(native)
+            out = out if isinstance(out, tuple) else (out,)
+            line(f"{tag} native={native}", *[t if isinstance(t, torch.Tensor) else torch.tensor(t, dtype=torch.int64) for t in out])
+
+    lengths, padded = [2500, 6500, 300], [3200, 6500, 300]
+    tables = GF.melspec_pack(audio.hann_window(512).to(dev), audio.mel_filterbank(16000, 512, 40).to(dev))
+    line("melspec_pack 512 40", tables.packed)
+    wav, gain = bursts(sum(lengths), 1, 800, dev), torch.tensor([1.0, 0.5, 2.0], device=dev)
+    for mode in ("db", "linear"):
+        both(f"melspec {mode}", lambda native: GF.melspec(tables, wav, lengths, hop=160, padded_lengths=padded, gain=gain,
+                                                         mode=mode, native=native))
+    wav = bursts(sum(RESAMPLE_LENGTHS), 2, 100, dev)
+    for up, down in RESAMPLE_RATIOS:
+        bank = audio.resample_bank(down, up, "kaiser_fast")
+        t = GF.resample_pack(bank.taps.to(dev), bank.up, bank.down, bank.lead)
+        line(f"resample_pack {up}/{down}", t.packed)
+        both(f"resample {up}/{down}", lambda native: GF.resample(t, wav, RESAMPLE_LENGTHS, native=native))
+        out, out_lengths = GF.resample(t, wav, RESAMPLE_LENGTHS)
+        lay = GF.resample_layout(out_lengths, 1, 1, device=dev)
+        both(f"volume_gain {up}/{down} layout", lambda native: GF.volume_gain(out, out_lengths, native=native, layout=lay))
+        both(f"volume_gain {up}/{down} lengths", lambda native: GF.volume_gain(out, out_lengths, native=native))
+    for S, ls, gains in VAD_CASES:
+        wav = bursts(sum(ls), S, 3 * S, dev)
+        g = None if gains is None else torch.tensor(gains, device=dev)
+        lay = GF.vad_layout(ls, S, device=dev)
+        both(f"vad_flags {S}", lambda native: GF.vad_flags(wav, ls, g, window=S, native=native, **VAD_DETECTOR))
+        flags = GF.vad_flags(wav, ls, g, window=S, **VAD_DETECTOR)
+        both(f"vad_mask {S}", lambda native: GF.vad_mask(flags, lay, native=native, **VAD_MASK))
+        both(f"trim_silences {S}", lambda native: GF.trim_silences(wav, ls, gain=g, window=S, native=native, **VAD_DETECTOR,
+                                                                    **VAD_MASK))
+    handed = (np.random.default_rng(7).random(lay.total_windows) < 0.4).astype(np.uint8)
+    both(f"trim_silences {S} voice_flags", lambda native: GF.trim_silences(wav, ls, voice_flags=handed, window=S, native=native,
+                                                                           **VAD_MASK))
+    fe = audio.MelFrontEnd()
+    wavs = [bursts(int(sec * 44100), 10 + i, 4410, dev) for i, sec in enumerate((0.3, 0.5, 0.31))]
+    both("MelFrontEnd.frames", lambda native: fe.frames(wavs, normalize_volume=True, pad_to_partials=True, native=native,
+                                                        source_rate=44100, trim_silences=True))
+
+
 def main():
     dev = torch.device("cuda:0")
     w, b = torch.tensor(7.5, device=dev), torch.tensor(-2.0, device=dev)
@@ -394,6 +462,7 @@ def main():
     index_section(dev)
     wrong = tiled_section(dev, w, b)
     encoder_section(dev)
+    audio_section(dev)
     if missing:
         print("no line for:", " ".join(missing))
     for tag in wrong:
