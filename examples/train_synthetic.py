@@ -4,13 +4,15 @@ speakers, with every hot piece on the GPU.  One process per GPU:
     python examples/train_synthetic.py                       # one GPU
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 examples/train_synthetic.py
     python examples/train_synthetic.py --native-encoder      # the encoder's forward AND backward in hand-written HIP
+    python examples/train_synthetic.py --native-step         # both gradient clips and SGD as one call of two HIP launches
 
 s1 (loader)  -> data.SpectrogramStore + GE2EBatchSampler   (resident arrays, one gather-and-cast launch per batch)
 s2 (encoder) -> encoder.SpeakerEncoder(normalize=False)     (LSTM + Linear through torch; the tail is fused below.
                                                               --native-encoder: native_train=True, functional.encode_train
                                                               with its LSTM backward through time, no nn.LSTM backward)
 s3 (loss)    -> GE2ELoss                                     (one HIP launch: loss + every gradient)
-s4 (trainer) -> trainer.DPTrainer(fused_tail=True)           (perm / un-perm, clips, SGD, flat-bucket RCCL all-reduce)
+s4 (trainer) -> trainer.DPTrainer(fused_tail=True)           (perm / un-perm, clips, SGD, flat-bucket RCCL all-reduce.
+                                                              --native-step: native_step=True, optim.ClipSGD over the bucket)
 s5 (EER)     -> evaluation.calculate_ERR                     (HIP cosines + threshold-sweep counts)
 """
 import os
@@ -30,6 +32,7 @@ from speaker_embedding_ge2e_loss_amd.trainer import DPTrainer  # noqa: E402
 
 def main():
     native = "--native-encoder" in sys.argv[1:]
+    native_step = "--native-step" in sys.argv[1:]
     rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
     dev = torch.device("cuda", int(os.environ.get("LOCAL_RANK", 0)))
     torch.cuda.set_device(dev)
@@ -48,7 +51,7 @@ def main():
     torch.manual_seed(0)
     hp = HParams(device=dev)
     encoder = SpeakerEncoder(F, 256, 3, 256, normalize=False, native_train=native).to(dev)   # the reference's sizes (strings/constants.py)
-    trainer = DPTrainer(encoder, GE2ELoss(hp), lr=0.05, seed=rank, fused_tail=True)
+    trainer = DPTrainer(encoder, GE2ELoss(hp), lr=0.05, seed=rank, fused_tail=True, native_step=native_step)
 
     gen = torch.Generator().manual_seed(rank)
     for epoch in range(3):

@@ -878,6 +878,65 @@ int ge2e_vad_trim(const float* wav, const long long* utt_start /* [U], device */
 int ge2e_vad_plan(int U, long long total_windows, int S, int floor_span, int avg_width, int max_silence, char* buf,
                   size_t buf_bytes);
 
+/*
+ * OPTIMIZER STEP (csrc/ge2e_optim.hip): the training step's last statements (s4:201-203) -- torch.nn.utils.clip_grad_norm_
+ * once per parameter group, then torch.optim.SGD.step -- over a flat gradient bucket in TWO launches, whatever the number
+ * of tensors.  Fixed-order sums, no atomics: the same bits on every call.
+ *
+ * The tables (device memory, the caller's; functional.sgd_layout builds them).  A SEGMENT is one parameter tensor:
+ * seg[s] = (address of its first element, its element offset in grad (and in momentum), numel >= 1, group g in [0, G)),
+ * four int64; segments are SORTED BY GROUP.  A CHUNK is at most GE2E_SGD_CHUNK consecutive elements of one segment;
+ * chunk_start [S + 1] (int32) is the prefix sum of ceil(numel / GE2E_SGD_CHUNK) and C its last entry.  hyper [G][4]
+ * (float32) holds lr, max_norm, weight_decay, momentum of each group and is read by the launches themselves: a new
+ * learning rate is a device write, and a captured launch stays valid.  The addresses in seg are raw: a parameter whose
+ * storage moved needs a new table (functional.sgd_clip_step compares data_ptr() on every call; nothing else can notice).
+ *
+ * The definition, all in float32 with every operation rounded on its own (no fused multiply-add):
+ *   partial[c] = sum over chunk c of fl(fl(g grad_scale)^2); thread t of 256 adds its elements in index order -- single
+ *                elements up to the first 16-byte boundary of the gradient, then 16-byte pieces t, t + 256, ..., then at
+ *                most 3 single elements -- then a butterfly over each wave of 64, then (w0 + w1) + (w2 + w3).
+ *   norm[g]    = sqrtf(sum of the group's partials): thread t adds partial[b + t], partial[b + t + 256], ... of the group's
+ *                chunk range in that order, then the same two trees.  EVERY workgroup of launch 2 does this for every
+ *                group, with the same code, and holds the same bits.
+ *   coef[g]    = c > 1 ? 1 : c with c = max_norm[g] / (norm[g] + 1e-6f): clip_grad_norm_'s formula; a NaN norm gives a NaN
+ *                coef (torch.clamp passes it on), an infinite norm 0.
+ *   g1 = g grad_scale;  g2 = g1 coef[group]                  (what clip_grad_norm_ leaves in .grad)
+ *   g3 = weight_decay != 0 ? g2 + weight_decay p : g2         (SGD's weight decay, after the clip)
+ *   m' = momentum != 0 ? momentum m + g3 : g3                 (the buffer starts as zeros, which is torch's "buf = g" at the
+ *                                                              first step; dampening 0, no Nesterov)
+ *   p' = p - lr[group] m'
+ * Stores: p' to the parameter; m' to momentum[offset ..] where momentum is not NULL (also in a group whose momentum is 0,
+ * whose m is not read); g2 to grad, or +0 with GE2E_SGD_FLAG_ZERO_GRAD; stats[g] = (norm, coef) where stats is not NULL.
+ * GE2E_SGD_FLAG_SKIP_NONFINITE: if the norm of ANY group is not finite, no parameter and no momentum element is written
+ * (they keep their bits), grad is written as above, and *skipped is incremented by one workgroup (a plain read and
+ * write on the stream; *skipped is the caller's to zero).
+ * A segment whose parameter, gradient and momentum addresses are congruent mod 16 moves in 16-byte pieces behind the
+ * boundary; any other a word at a time.  Any 4-byte boundary is legal; nothing outside [0, numel) of a segment is touched.
+ * A group without segments is legal (norm 0, coef 1 or max_norm / 1e-6f).
+ *
+ * workspace: ge2e_sgd_clip_workspace_bytes(C) = 4 C rounded up to 256 bytes (0 for C < 1), 256-byte aligned; it holds the
+ * partials afterwards.  No allocation, no synchronisation, everything on `stream`, grids from C alone: fit for a HIP graph.
+ * Checked on the host before anything is launched, in this order: GE2E_ERR_NULL (seg, chunk_start, grad or hyper;
+ * GE2E_SGD_FLAG_SKIP_NONFINITE without skipped), GE2E_ERR_SHAPE (S, C or G < 1, C < S, G > GE2E_SGD_MAX_GROUPS, a flag bit
+ * that is not defined), GE2E_ERR_WORKSPACE (NULL, too small, or not 256-byte aligned), GE2E_ERR_ALIGN (grad, momentum or
+ * another float32 / int32 buffer not 4-byte aligned, seg not 8-byte aligned).
+ *
+ * ge2e_sgd_clip_plan (diagnostics, no GPU): "sgd_sqsum/4096/C,sgd_update<mom>/4096/C" -- the chunk and the grid of either
+ * launch; <plain> without a momentum buffer -- snprintf-style as ge2e_vad_plan; < 0: GE2E_ERR_SHAPE as the call itself.
+ * (No part of ge2e_plan_atoms.)
+ */
+#define GE2E_SGD_MAX_GROUPS 8
+#define GE2E_SGD_CHUNK 4096
+#define GE2E_SGD_FLAG_ZERO_GRAD 1
+#define GE2E_SGD_FLAG_SKIP_NONFINITE 2
+size_t ge2e_sgd_clip_workspace_bytes(int C);                     /* 0 for C < 1 */
+int ge2e_sgd_clip_step(const long long* seg /* [S][4] device: address, grad offset, numel, group */,
+                       const int* chunk_start /* [S+1] device */, int S, int C, int G,
+                       float* grad, float* momentum /* or NULL */, const float* hyper /* [G][4] device */,
+                       float grad_scale, int flags, float* stats /* [G][2] or NULL */, int* skipped /* or NULL */,
+                       void* workspace, size_t workspace_bytes, void* stream);
+int ge2e_sgd_clip_plan(int S, int C, int G, int has_momentum, int flags, char* buf, size_t buf_bytes);
+
 /* ---- diagnostics (tests only): which kernels a call launches ---------------------------------------------------------
  * Below ge2e_resolve_impl every launcher chooses again among kernels and template instantiations.  These queries print
  * that choice -- made by the very functions the launchers switch on -- without a GPU and without launching anything:

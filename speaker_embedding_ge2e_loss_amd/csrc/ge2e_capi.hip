@@ -19,6 +19,7 @@
 #include "ge2e_melspec.hpp"
 #include "ge2e_resample.hpp"
 #include "ge2e_vad.hpp"
+#include "ge2e_optim.hpp"
 #include "ge2e_identify.hpp"
 #include "ge2e_snorm.hpp"
 #include "ge2e_helpers.hpp"
@@ -899,6 +900,37 @@ int ge2e_vad_plan(int U, long long total_windows, int S, int floor_span, int avg
     if (rc == GE2E_OK) rc = vad_mask_check(avg_width, max_silence);
     if (rc != GE2E_OK) return rc;
     return plan_string_vad(total_windows, U, S, buf, buf_bytes);
+}
+
+// OPTIMIZER STEP (include/ge2e_hip.h, csrc/ge2e_optim.hip): both gradient clips and SGD over the flat bucket in two launches.
+static_assert(kSgdMaxGroups == GE2E_SGD_MAX_GROUPS && kSgdChunk == GE2E_SGD_CHUNK && kSgdFlagZeroGrad == GE2E_SGD_FLAG_ZERO_GRAD &&
+                  kSgdFlagSkipNonfinite == GE2E_SGD_FLAG_SKIP_NONFINITE, "the header's constants are the kernels'");
+size_t ge2e_sgd_clip_workspace_bytes(int C) { return C < 1 ? 0 : sgd_workspace_bytes(C); }
+
+static int sgd_shape_check(int S, int C, int G, int flags) {
+    if (S < 1 || C < 1 || G < 1 || C < S || G > kSgdMaxGroups) return GE2E_ERR_SHAPE;
+    return (flags & ~(kSgdFlagZeroGrad | kSgdFlagSkipNonfinite)) ? GE2E_ERR_SHAPE : GE2E_OK;
+}
+
+int ge2e_sgd_clip_step(const long long* seg, const int* chunk_start, int S, int C, int G, float* grad, float* momentum,
+                       const float* hyper, float grad_scale, int flags, float* stats, int* skipped, void* workspace,
+                       size_t workspace_bytes, void* stream) {
+    if (!seg || !chunk_start || !grad || !hyper) return GE2E_ERR_NULL;
+    if ((flags & kSgdFlagSkipNonfinite) && !skipped) return GE2E_ERR_NULL;
+    const int rc = sgd_shape_check(S, C, G, flags);
+    if (rc != GE2E_OK) return rc;
+    if (!workspace_ok(workspace, workspace_bytes, sgd_workspace_bytes(C))) return GE2E_ERR_WORKSPACE;
+    if (!aligned8(seg) || !aligned4(chunk_start) || !aligned4(grad) || !aligned4(momentum) || !aligned4(hyper) ||
+        !aligned4(stats) || !aligned4(skipped))
+        return GE2E_ERR_ALIGN;
+    const ProblemSgd p = {seg, chunk_start, S, C, G, grad, momentum, hyper, grad_scale, flags, stats, skipped, (float*)workspace};
+    return (int)launch_sgd_clip_step(p, (hipStream_t)stream);
+}
+
+int ge2e_sgd_clip_plan(int S, int C, int G, int has_momentum, int flags, char* buf, size_t buf_bytes) {
+    const int rc = sgd_shape_check(S, C, G, flags);
+    if (rc != GE2E_OK) return rc;
+    return plan_string_sgd(C, has_momentum != 0, buf, buf_bytes);
 }
 
 // ---- diagnostics: the launch plan of a call, from the launchers' own decision functions (ge2e_plan.hpp); no GPU needed ----

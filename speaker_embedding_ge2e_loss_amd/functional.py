@@ -2147,6 +2147,139 @@ def trim_silences(wav: torch.Tensor, lengths=None, *, gain: Optional[torch.Tenso
     return out, out_lengths
 
 
+SGD_CHUNK = _lib.MACROS["GE2E_SGD_CHUNK"]
+SGD_MAX_GROUPS = _lib.MACROS["GE2E_SGD_MAX_GROUPS"]
+
+
+class SgdLayout:
+    """The tables of ``sgd_clip_step`` for a list of parameter groups (include/ge2e_hip.h, OPTIMIZER STEP): ``seg`` (S, 4)
+    int64 -- address, offset in the flat gradient, numel, group of every tensor, sorted by group -- and ``chunk_start``
+    (S + 1,) int32 on the tensors' device, with ``S``, ``C`` (chunks = workgroups of either launch) and ``G``.
+
+    THE ADDRESSES ARE RAW.  The kernels write through ``seg`` whatever lives there now; a tensor whose storage was replaced
+    (``p.data = ...``, ``module.to(...)``, ``load_state_dict(assign=True)``) leaves a stale address behind.  The ONLY defence
+    is ``refresh()``: it compares every tensor's current ``data_ptr()`` with the table's and uploads the table again, in
+    place, when one moved.  ``sgd_clip_step`` calls it on every call.  A caller who launches from the tables directly, or
+    replays a captured graph, has to keep the storages alive and where they are -- or call ``refresh()`` before the replay:
+    the table is rewritten in place, so a captured launch reads the new addresses.
+
+    On CUDA the layout also owns what the call reuses from one step to the next: the workspace, the ``stats`` the call
+    returns, and the counter of skipped steps."""
+
+    def __init__(self, tensors, groups, offsets, G: int, device: torch.device):
+        self.tensors, self.groups, self.offsets, self.G, self.device = tensors, groups, offsets, G, device
+        self.S = len(tensors)
+        self.extent = max(o + t.numel() for o, t in zip(offsets, tensors))      # elements of the flat gradient it reaches
+        counts = [-(-t.numel() // SGD_CHUNK) for t in tensors]
+        self.chunk_start_host = list(accumulate(counts, initial=0))
+        self.C = self.chunk_start_host[-1]
+        self.chunk_start = torch.tensor(self.chunk_start_host, dtype=torch.int32).to(device)
+        self.ptrs = [t.data_ptr() for t in tensors]
+        self.seg = self._table().to(device)
+        self.workspace = self.stats = self.skipped = None
+        if device.type == "cuda":
+            with _on_device(device):
+                need = int(_lib.load().ge2e_sgd_clip_workspace_bytes(self.C))
+            self.workspace = alloc_workspace(need, device, init=False)
+            self.stats = torch.zeros(G, 2, dtype=torch.float32, device=device)
+            self.skipped = torch.zeros(1, dtype=torch.int32, device=device)
+
+    def _table(self) -> torch.Tensor:
+        return torch.tensor([[a, o, t.numel(), g] for a, o, t, g in zip(self.ptrs, self.offsets, self.tensors, self.groups)],
+                            dtype=torch.int64)
+
+    def refresh(self) -> bool:
+        """Upload the table again if a tensor's storage moved; True if it did."""
+        ptrs = [t.data_ptr() for t in self.tensors]
+        if ptrs == self.ptrs:
+            return False
+        if self.device.type == "cuda" and _capturing is not None and _capturing():
+            raise RuntimeError("a parameter's storage moved while the stream is being captured: refresh the layout before")
+        self.ptrs = ptrs
+        self.seg.copy_(self._table())
+        return True
+
+
+def sgd_layout(groups, flat_grad_offsets) -> SgdLayout:
+    """The tables of ``sgd_clip_step``.  ``groups``: up to 8 lists of tensors (the parameter groups: one gradient norm, one
+    ``hyper`` row each); ``flat_grad_offsets``: lists of the same lengths, the element offset of each tensor's gradient in
+    the flat gradient (and in the momentum buffer).  Every tensor must be float32, contiguous and on one device, and appear
+    once; an empty tensor has nothing to update and is left out.  Works on CPU tensors too (the tables, for inspection; the
+    call itself needs the GPU).  Host arithmetic and two small uploads: build it once.  See ``SgdLayout`` on stale
+    addresses."""
+    groups = [list(g) for g in groups]
+    offsets = [_int_list(o) for o in flat_grad_offsets]
+    if not 1 <= len(groups) <= SGD_MAX_GROUPS:
+        raise ValueError(f"1 .. {SGD_MAX_GROUPS} parameter groups, got {len(groups)}")
+    if len(offsets) != len(groups) or any(len(o) != len(g) for o, g in zip(offsets, groups)):
+        raise ValueError("flat_grad_offsets must name one offset per tensor, group by group")
+    tensors, owner, offs, seen, dev = [], [], [], set(), None
+    for gi, (g, o) in enumerate(zip(groups, offsets)):
+        for t, off in zip(g, o):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+                raise TypeError(f"group {gi}: float32 tensors only, got {getattr(t, 'dtype', type(t))}")
+            if id(t) in seen:
+                raise ValueError(f"group {gi}: a tensor appears twice (it would be updated twice)")
+            seen.add(id(t))
+            if dev is None:
+                dev = t.device
+            if t.device != dev:
+                raise ValueError(f"group {gi}: every tensor on one device (got {t.device} beside {dev})")
+            if not t.is_contiguous():
+                raise ValueError(f"group {gi}: a parameter that is not contiguous has no flat range to update")
+            if off < 0:
+                raise ValueError(f"group {gi}: negative offset {off}")
+            if t.numel() == 0:
+                continue
+            tensors.append(t)
+            owner.append(gi)
+            offs.append(off)
+    if not tensors:
+        raise ValueError("nothing to update: no tensor with elements")
+    return SgdLayout(tensors, owner, offs, len(groups), dev)
+
+
+def sgd_clip_step(layout: SgdLayout, grad: torch.Tensor, hyper: torch.Tensor, momentum: Optional[torch.Tensor] = None,
+                  grad_scale: float = 1.0, zero_grad: bool = False, skip_nonfinite: bool = False):
+    """``clip_grad_norm_`` per group, then ``torch.optim.SGD.step``, for every tensor of ``layout`` in two HIP launches
+    (ge2e_sgd_clip_step; the arithmetic, operation by operation, is in include/ge2e_hip.h).  ``grad``: the flat float32
+    gradient the layout's offsets index; it is left holding the clipped gradients, or zeros with ``zero_grad``.  ``hyper``
+    (G, 4) float32 on the device: ``lr, max_norm, weight_decay, momentum`` per group, read by the launches -- write a new
+    learning rate into it and the next call (or replay) uses it.  ``momentum``: the momentum buffer, shaped as ``grad``
+    (zeros before the first step), or None.  ``grad_scale`` multiplies every gradient before the norm (1 / world size).
+    ``skip_nonfinite``: a step in which any group's norm is inf or NaN leaves parameters and momentum untouched and counts.
+
+    Returns ``stats`` (G, 2) -- the norm before the clip and the coefficient applied, per group -- and with
+    ``skip_nonfinite`` ``(stats, skipped)``, the int32 count of skipped steps so far.  Both belong to the layout and are
+    overwritten by the next call; nothing is allocated and nothing waits for the device.  The layout is refreshed first
+    (``SgdLayout.refresh``): the only defence against a parameter whose storage moved."""
+    _require_cuda(grad, "grad")
+    dev = grad.device
+    if layout.device != dev:
+        raise RuntimeError(f"the layout's tensors are on {layout.device}, grad on {dev}")
+    need = layout.extent
+    for name, t in (("grad", grad), ("momentum", momentum)):
+        if t is None:
+            continue
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev or t.numel() < need:
+            raise ValueError(f"{name} must be a contiguous float32 tensor of at least {need} elements on {dev}")
+    if hyper.dtype != torch.float32 or hyper.device != dev or not hyper.is_contiguous() or tuple(hyper.shape) != (layout.G, 4):
+        raise ValueError(f"hyper must be a contiguous float32 ({layout.G}, 4) tensor on {dev}")
+    layout.refresh()
+    flags = (_lib.MACROS["GE2E_SGD_FLAG_ZERO_GRAD"] if zero_grad else 0) | \
+        (_lib.MACROS["GE2E_SGD_FLAG_SKIP_NONFINITE"] if skip_nonfinite else 0)
+    _launch("ge2e_sgd_clip_step", dev, layout.seg.data_ptr(), layout.chunk_start.data_ptr(), layout.S, layout.C, layout.G,
+            grad.data_ptr(), _ptr(momentum), hyper.data_ptr(), float(grad_scale), flags, layout.stats.data_ptr(),
+            layout.skipped.data_ptr() if skip_nonfinite else None, layout.workspace.data_ptr(), layout.workspace.numel(),
+            _stream_ptr(grad))
+    return (layout.stats, layout.skipped) if skip_nonfinite else layout.stats
+
+
+def sgd_clip_plan(layout: SgdLayout, has_momentum: bool = False) -> list:
+    """Diagnostics: the two launches of ``sgd_clip_step`` for this layout, ``["sgd_sqsum/4096/C", "sgd_update<mom>/4096/C"]``."""
+    return _lib._plan(_lib.load().ge2e_sgd_clip_plan, layout.S, layout.C, layout.G, int(has_momentum), 0)
+
+
 def raw_supported(N: int, M: int, D: int) -> bool:
     """Shapes ge2e_loss_raw runs as ONE launch (the one-wave-per-batch kernel's register-only shapes)."""
     return bool(_lib.load().ge2e_raw_supported(N, M, D))

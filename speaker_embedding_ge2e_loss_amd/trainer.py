@@ -29,11 +29,15 @@ class DPTrainer:
     def __init__(self, model: torch.nn.Module, loss_module: torch.nn.Module, lr: float = 0.05,
                  clip_model: float = 3.0, clip_loss: float = 1.0,
                  process_group: Optional["dist.ProcessGroup"] = None, seed: Optional[int] = None,
-                 fused_tail: bool = False, shared_device: bool = False):
+                 fused_tail: bool = False, shared_device: bool = False, native_step: bool = False):
         # fused_tail: the encoder returns its raw projection (SpeakerEncoder(normalize=False)) and the
         # L2-normalise + un-permute + (N,M,D) layout run as one HIP kernel instead of
         # norm / divide / index_select / contiguous
         self.fused_tail = fused_tail
+        # native_step: the mean over ranks, both gradient clips and the SGD update (s4:201-203 and the div_ before them) run as
+        # ONE call of two HIP launches over the flat bucket (optim.ClipSGD) instead of torch's twenty-odd small ones; the
+        # optimizer is then a ClipSGD whose param_groups carry lr as before.  Off by default.
+        self.native_step = bool(native_step)
         self.model = model
         self.ge2e_loss = loss_module
         # shared_device: other streams or processes keep CUs of this GPU busy while the loss runs (communication overlapped
@@ -73,6 +77,14 @@ class DPTrainer:
             self._views.append(self.flat_grad[off:off + n].view(p.shape))
             off += n
         self._bind_grads()
+        if self.native_step:
+            if not (dev.type == "cuda" and dt == torch.float32):
+                raise ValueError(f"native_step=True runs HIP kernels on the parameters: they must be float32 on a GPU "
+                                 f"(got {dt} on {dev}); there is no CPU path")
+            from .optim import ClipSGD
+            # the reference's settings: no momentum, no weight decay, one threshold per group; same groups, same bucket
+            self.optimizer = ClipSGD([{"params": list(g["params"])} for g in self.optimizer.param_groups], lr=lr,
+                                     max_norm=(clip_model, clip_loss), flat_grad=self.flat_grad, grad_scale=1.0 / self.world)
         if self.world > 1:  # start from identical weights (rank 0's)
             for p in self._params:
                 dist.broadcast(p.data, src=0, group=self.pg)
@@ -133,7 +145,11 @@ class DPTrainer:
         loss.backward()             # s4:200
         if self.world > 1:
             dist.all_reduce(self.flat_grad, op=dist.ReduceOp.SUM, group=self.pg)
-            self.flat_grad.div_(self.world)  # mean over ranks: keeps lr and the clip thresholds meaningful
+            if not self.native_step:
+                self.flat_grad.div_(self.world)  # mean over ranks: keeps lr and the clip thresholds meaningful
+        if self.native_step:        # the mean, s4:201-203 in one call; .grad holds the clipped gradients afterwards, as below
+            self.optimizer.step()
+            return loss.detach()
         torch.nn.utils.clip_grad_norm_(self.model.parameters(), self.clip_model)      # s4:201
         torch.nn.utils.clip_grad_norm_(self.ge2e_loss.parameters(), self.clip_loss)   # s4:202
         self.optimizer.step()       # s4:203
@@ -240,7 +256,7 @@ class TrainEmbedModel:
     reference's schedule read from ``hp.m_ge2e`` (epochs, checkpoint interval, best-weights rule); under
     ``torch.distributed`` every rank trains on its own batches and the gradients are averaged in one bucket per step."""
 
-    def __init__(self, hp, variant: str = "softmax", fused_tail: bool = False):
+    def __init__(self, hp, variant: str = "softmax", fused_tail: bool = False, native_step: bool = False):
         import os
         from .encoder import SpeakerEncoder
         from .loss import GE2ELoss
@@ -254,7 +270,7 @@ class TrainEmbedModel:
             print(f"Pre-trained model loaded {self._restore}")
         self.ge2e_loss = GE2ELoss(hp, variant=variant)                                       # s4:33
         self.lr = hp.m_ge2e.lr                                                               # s4:41
-        self.trainer = DPTrainer(self.model, self.ge2e_loss, lr=self.lr, fused_tail=fused_tail)
+        self.trainer = DPTrainer(self.model, self.ge2e_loss, lr=self.lr, fused_tail=fused_tail, native_step=native_step)
         self.optimizer = self.trainer.optimizer                                              # s4:35-42
         self.train_loader, self.test_loader = get_train_test_data_loader(hp)                 # s4:45
         self.checkpoint_dir = None
